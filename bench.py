@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- Mrays/s of the fused trace+plot hot path on the built-in scene.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 without a launcher: bench.py starts its own ranks)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (N > 1 without a launcher: bench.py starts its own ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what the headline does not need, at N = 1:
+config.others (the other BASELINE configs and the App), roofline.executed_live (rocprofv3 passes) and cpu_baseline.
 
 One "step" = `--launches-per-step` (2) fused TraceUnit::render + PlotUnit::plot launches of `--batches-per-launch`
 (1024) batches of 524,288 camera paths each (trace_unit.rs:67) on the built-in demo scene (app.rs:166-363), then the
@@ -431,6 +434,17 @@ def measure_app(R, fused, threads, device, batches=8192, depth=64):
             "batches_per_s": st["paths"] / BATCH / st["seconds"], "workers": threads, "depth": depth, "seconds": st["seconds"]}
 
 
+def dump_outputs(out_dir, gather, W, H, paths, rays):
+    """--dump-outputs: what the timed path hands its caller after its last step -- the GatherUnit's accumulated XYZ image
+    (float32, H x W x 3: 24.9 MB at 1920x1080, the largest config) -- and the device-counted paths and segments of the timed steps
+    (float64).  The same arguments give the same paths, seeds and streams; the splat sums with float atomics, so two runs of one
+    build agree to rounding, the counts exactly."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "xyz.npy"), gather.tristimulus_buffer.reshape(H, W, 3))
+    np.save(os.path.join(out_dir, "counts.npy"), np.array([paths, rays], dtype=np.float64))
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: start the N ranks ourselves (the same environment contract
     torch.distributed.run sets up), relay rank 0's JSON line."""
@@ -533,10 +547,16 @@ def main():
     ap.add_argument("--batches-per-launch", type=int, default=1024)
     ap.add_argument("--fetch", default="lds", choices=["lds", "global"])
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-others", action="store_true", help="skip the short runs of the other BASELINE configs (config.others)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the timed steps also run config.others, roofline.executed_live and cpu_baseline (each can be "
+                         "left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what they computed to DIR/xyz.npy (rank 0's accumulated XYZ image) and "
+                         "DIR/counts.npy (paths and segments of the timed steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-others", action="store_true", help="with --full: skip the short runs of the other BASELINE configs (config.others)")
     ap.add_argument("--no-live-counters", action="store_true",
-                    help="skip roofline.executed_live (bench.py re-running itself under rocprofv3 --pmc after the timed region, N = 1 only)")
+                    help="with --full: skip roofline.executed_live (bench.py re-running itself under rocprofv3 --pmc after the timed region)")
     ap.add_argument("--total-paths", type=int, default=0,
                     help="strong scaling (SURVEY 8e): the paths of ONE STEP for the whole job, split evenly over the ranks "
                          "(rounded down to launches-per-step x 64 per rank); default 0 = weak scaling, the per-GPU work is fixed")
@@ -699,6 +719,8 @@ def main():
     p1, s1, ms1 = trace.stats()
     rays, paths, kernel_ms = s1 - s0, p1 - p0, ms1 - ms0
     elapsed, (total_rays, total_paths) = D.aggregate(t1 - t0, [rays, paths])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gather, W, H, total_paths, total_rays)
     # the exchange, per step: device time of the ncclReduce calls on this rank's plot stream (rl_plot_unit_exchange_stats),
     # or host time of the staged sums; MAX over ranks (a collective ends when its slowest rank does)
     if comm is not None:
@@ -789,7 +811,7 @@ def main():
                          "kernel": "rl_trace_kernel", "kernel_ms_per_launch": launch_ms, "rays_per_launch": rays_per_launch,
                          "algorithmic_flops_per_ray": f_seg,
                          "executed": executed,
-                         "executed_live": None,   # filled in below (N = 1, rocprofv3 on the box): the same figures counted in this run
+                         "executed_live": None,   # filled in below (--full, N = 1, rocprofv3 on the box): the same figures counted in this run
                          "traffic": traffic,
                          "hbm": ({"achieved": traffic / (launch_ms * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
                                   "frac": traffic / (launch_ms * 1e-3) / 8e12} if traffic else None),
@@ -801,11 +823,12 @@ def main():
                                  "occupancy (issue_ceiling.kernel_vs_plain_stream), a fifth wave per SIMD gains 0.4-1.7 % (profiles/r06_fifth_wave.txt): what is left "
                                  "is fewer vector instructions per ray.  DESIGN.md 4.1"},
         }
-        if world == 1 and not args.no_others:
+        full = world == 1 and args.full
+        if full and not args.no_others:
             out["config"]["others"] = [measure(R, c, f, rank, 6, 64, 1, args.seed, device) for c, f in OTHERS]
             workers = max(1, min(usable_cores(), 4))
             out["config"]["others"] += [measure_app(R, fused, workers, device) for fused in (False, True)]
-        if world == 1 and not args.no_live_counters and not os.environ.get("RL_BENCH_LIVE_CHILD"):
+        if full and not args.no_live_counters and not os.environ.get("RL_BENCH_LIVE_CHILD"):
             live = executed_live(args, executed)
             out["roofline"]["executed_live"] = live
             if not live.get("skipped"):   # counted in THIS run: the live counters lead, the committed profile is the cross-check
@@ -815,7 +838,7 @@ def main():
                 rf["achieved"] = rf["frac"] * PEAK_VALU_TLANEOPS
                 rf["frac_source"] = "executed_live (rocprofv3 --pmc passes of this run)"
                 rf["issue_ceiling"] = issue_ceiling(live)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(R, objs, cam, W, H)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -241,7 +241,7 @@ def test_bench_line_counts_its_own_counters_when_rocprofv3_is_on_the_box():
     if not (shutil.which("rocprofv3") or os.path.exists("/opt/rocm/bin/rocprofv3")):
         pytest.skip("no rocprofv3")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--launches-per-step", "1", "--batches-per-launch", "64",
-           "--no-cpu-baseline", "--no-others"]
+           "--full", "--no-cpu-baseline", "--no-others"]
     out = subprocess.run(cmd, capture_output=True, timeout=600, check=True).stdout.decode()
     line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     live = line["roofline"]["executed_live"]
@@ -261,6 +261,26 @@ def test_bench_line_counts_its_own_counters_when_rocprofv3_is_on_the_box():
     assert abs(rf["achieved"] / rf["peak"] - rf["frac"]) < 1e-9 and rf["unit"] == "Tlane-op/s"
     assert rf["algorithmic"]["frac"] == rf["frac_algorithmic"] and "SPEED-UP" in rf["algorithmic"]["is"]
     assert 0.5 < rf["issue_ceiling"]["kernel_vs_plain_stream"] < 1.3
+
+
+def test_plain_bench_run_times_its_steps_and_dumps_what_they_computed(tmp_path):
+    """Without --full the line carries the headline only; --dump-outputs writes the accumulated XYZ image and the device's counts
+    of the timed steps, and the same arguments give the same counts and the same image up to the atomics' summation order."""
+    dumps = []
+    for run in range(2):
+        out_dir = tmp_path / ("run%d" % run)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--launches-per-step", "1",
+               "--batches-per-launch", "4", "--config", "demo-720p", "--dump-outputs", str(out_dir)]
+        out = subprocess.run(cmd, capture_output=True, timeout=600, check=True).stdout.decode()
+        line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 2 and abs(line["ms_per_step"] - line["timed_region_s"] * 1e3 / 2) < 1e-6
+        assert "others" not in line["config"] and "cpu_baseline" not in line and line["roofline"]["executed_live"] is None
+        counts, xyz = np.load(out_dir / "counts.npy"), np.load(out_dir / "xyz.npy")
+        assert counts.dtype == np.float64 and counts[0] == 2 * 4 * 524288 and counts[1] / counts[0] == line["segments_per_path"]
+        assert xyz.dtype == np.float32 and xyz.shape == (720, 1280, 3) and np.isfinite(xyz).all() and xyz.sum() > 0
+        dumps.append((counts, xyz))
+    assert (dumps[0][0] == dumps[1][0]).all()
+    assert np.allclose(dumps[0][1], dumps[1][1], rtol=1e-4, atol=1e-6 * float(dumps[0][1].max()))
 
 
 def test_bench_with_more_ranks_than_gpus_falls_back_instead_of_hanging(R):

@@ -5,7 +5,7 @@
 set -u
 N=${N:-2}
 PARITY=${PARITY:-}
-BENCH_ARGS=${BENCH_ARGS:---steps 4 --warmup 1 --no-cpu-baseline --no-live-counters}
+BENCH_ARGS=${BENCH_ARGS:---steps 4 --warmup 1 --full --no-cpu-baseline --no-live-counters}
 mkdir -p gpurun_out/ab
 for a in $PARITY; do
   RL_LIBRARY=$PWD/robigo_luculenta_amd/librl_alt_$a.so timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_independent.py -x -q -m gpu -k "bit_exact or matrix or independent or random_scenes" 2>&1 | tail -1 | sed "s/^/$a: /"

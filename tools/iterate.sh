@@ -10,7 +10,7 @@ timeout 600 python -m pytest tests/test_gpu_parity.py tests/test_independent.py 
 tail -3 $OUT/pytest.txt
 for s in demo glass replicated; do timeout 120 python tools/kernel_stats.py 64 $s; done > $OUT/kernel_stats.txt 2>&1
 cat $OUT/kernel_stats.txt
-timeout 300 python bench.py --steps 4 --warmup 1 --no-cpu-baseline ${2:+--no-others} > $OUT/bench.json 2> $OUT/bench.err
+timeout 300 python bench.py --steps 4 --warmup 1 --full --no-cpu-baseline ${2:+--no-others} > $OUT/bench.json 2> $OUT/bench.err
 python - <<PY
 import json
 d = json.load(open("$OUT/bench.json"))
