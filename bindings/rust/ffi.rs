@@ -18,6 +18,11 @@ use std::os::raw::{c_char, c_double, c_float, c_int};
     pub fov_over_pi: f32, pub focal_factor: f32, pub depth_of_field: f32, pub chromatic_abberation: f32,
 }
 #[repr(C)] pub struct RlSceneDesc { pub n_objects: u32, pub objects: *const RlObjectDesc, pub camera: RlCameraDesc }
+// Scene::intersect as a batched query (rl_scene_intersect*): ray.rs:19-33 without wavelength and probability, intersection.rs:20-32
+#[repr(C)] #[derive(Copy, Clone)] pub struct RlRay { pub origin: RlVector3, pub t_max: f32, pub direction: RlVector3, pub reserved: u32 } // 32 bytes
+#[repr(C)] #[derive(Copy, Clone)] pub struct RlIntersection { pub position: RlVector3, pub normal: RlVector3, pub tangent: RlVector3, pub distance: f32 } // 40 bytes
+#[repr(C)] #[derive(Copy, Clone)] pub struct RlRayHit { pub isect: RlIntersection, pub object: u32, pub reserved: u32 } // 48 bytes
+pub const RL_OBJECT_NONE: u32 = 0xffff_ffff;
 
 pub const RL_TASK_MAX_UNITS: usize = 256;
 pub const RL_COMM_ID_BYTES: usize = 128;
@@ -52,6 +57,9 @@ extern "C" {
                               camera: *mut RlCameraDesc) -> c_int;
     pub fn rl_scene_create(desc: *const RlSceneDesc, device: c_int, out: *mut *mut RlScene) -> c_int;
     pub fn rl_scene_destroy(scene: *mut RlScene) -> c_int;
+    pub fn rl_scene_intersect(scene: *const RlScene, primitive_fetch: c_int, rays: *const RlRay, n_rays: u32, hits: *mut RlRayHit) -> c_int;
+    pub fn rl_scene_intersect_device(scene: *const RlScene, primitive_fetch: c_int, device_rays: *const RlRay, n_rays: u32,
+                                     device_hits: *mut RlRayHit) -> c_int;
 
     pub fn rl_trace_unit_create(device: c_int, id: u32, w: u32, h: u32, n_photons: u32, out: *mut *mut RlTraceUnit) -> c_int;
     pub fn rl_trace_unit_destroy(u: *mut RlTraceUnit) -> c_int;

@@ -147,6 +147,47 @@ int rl_scene_desc_load(const char* path, RlObjectDesc* objects, uint32_t cap, ui
 int rl_scene_create(const RlSceneDesc* desc, int device, RlScene** out);
 int rl_scene_destroy(RlScene* scene);
 
+/* Ray (ray.rs:19-33) as a query: wavelength and probability do not affect Scene::intersect and are left out. */
+typedef struct RlRay {
+    RlVector3 origin;
+    float t_max;         /* only hits with distance < t_max count (and < 1e12, scene.rs:43); INFINITY = Scene::intersect */
+    RlVector3 direction; /* used as given, not normalised (the reference's glass rays are not normalised either) */
+    uint32_t reserved;   /* ignored */
+} RlRay;                 /* 32 bytes */
+
+typedef struct RlIntersection { /* intersection.rs:20-32 */
+    RlVector3 position, normal, tangent;
+    float distance;
+} RlIntersection;               /* 40 bytes */
+
+#define RL_OBJECT_NONE 0xffffffffu
+
+typedef struct RlRayHit {
+    RlIntersection isect; /* all zero on a miss */
+    uint32_t object;      /* index into RlSceneDesc::objects; RL_OBJECT_NONE on a miss */
+    uint32_t reserved;    /* written 0 */
+} RlRayHit;               /* 48 bytes */
+
+/* Scene::intersect (scene.rs:39-60) for a batch of rays, on the scene's device: hits[i] is bit for bit what the
+ * reference returns for rays[i] -- the nearest object (on equal distances the first one, scene.rs:51), the hit's
+ * position, normal, tangent (normalise(cross((0,1,0), normal)) on spheres, geometry.rs:248-251; zero on every other
+ * surface) and distance -- restricted to distance < t_max: a hit at exactly t_max, and any hit for a t_max that is NaN,
+ * zero or negative, is a miss.  primitive_fetch (RL_FETCH_LDS / RL_FETCH_GLOBAL) has the meaning it has for
+ * rl_trace_unit_set_fetch.  n_rays == 0 does nothing; NULL pointers with n_rays > 0, a NULL scene or an unknown fetch
+ * mode are RL_E_INVALID.  Both calls return when the hits are written.
+ *   rl_scene_intersect:        host arrays, staged through device buffers in chunks (any n_rays).
+ *   rl_scene_intersect_device: device pointers on the scene's device (e.g. torch tensors); no host round trip.
+ * Safe from several host threads at once on one scene.  Ordering against renders: a query kernel cannot share a CU with
+ * a resident trace kernel, so a call made while an open launch runs on the device (a blocking render in flight, or one
+ * begun with rl_trace_unit_render_begin / _fused_begin and not yet ended) waits until that launch drains.  An open launch
+ * ends by itself once every call appended to it is complete and no new one arrived for its grace period (~150 us): it
+ * does NOT wait for rl_trace_unit_render_end, so a query between _begin and _end completes, and the render is not
+ * disturbed (its photons are those it computes alone).  While other threads keep appending render calls to the launch,
+ * the query waits for as long as they do. */
+int rl_scene_intersect(const RlScene* scene, int primitive_fetch, const RlRay* rays, uint32_t n_rays, RlRayHit* hits);
+int rl_scene_intersect_device(const RlScene* scene, int primitive_fetch, const RlRay* device_rays, uint32_t n_rays,
+                              RlRayHit* device_hits);
+
 /* ---- TraceUnit (trace_unit.rs:51-168) ------------------------------------------------------ */
 
 /* TraceUnit::new(id, width, height) (trace_unit.rs:64-77); n_photons is the batch size the

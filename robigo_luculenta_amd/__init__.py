@@ -8,12 +8,16 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (RlAppConfig, RlAppStats, RlCameraDesc, RlError, RlMappedPhoton, RlObjectDesc, RlSceneDesc, RlTask, RlVector3, check, lib,
-                   RL_TASK_MAX_UNITS)
+from ._lib import (RlAppConfig, RlAppStats, RlCameraDesc, RlError, RlIntersection, RlMappedPhoton, RlObjectDesc, RlRay, RlRayHit, RlSceneDesc,
+                   RlTask, RlVector3, check, lib, RL_OBJECT_NONE, RL_TASK_MAX_UNITS)
 
 PHOTON_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("probability", "<f4"), ("wavelength", "<f4")])
 OBJECT_DTYPE = np.dtype([("surface_kind", "<u4"), ("material_kind", "<u4"), ("v0", "<f4", 3), ("v1", "<f4", 3),
                          ("f", "<f4", 4), ("m", "<f4", 3)])
+# Scene.intersect's records: RlRay (32 bytes) and RlRayHit (48 bytes) of include/robigo_luculenta.h
+RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("t_max", "<f4"), ("direction", "<f4", 3), ("reserved", "<u4")])
+HIT_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("tangent", "<f4", 3), ("distance", "<f4"), ("object", "<u4"),
+                      ("reserved", "<u4")])
 NUMBER_OF_PHOTONS = 1024 * 512  # trace_unit.rs:67
 
 SCENE_DEMO, SCENE_GLASS_STRESS = 0, 1
@@ -108,6 +112,31 @@ class Scene(_Handle):
     def builtin(cls, which=SCENE_DEMO, param=0, device=0):
         objs, cam = builtin_scene_desc(which, param)
         return cls(objs, cam, device)
+
+    def intersect(self, origins, directions, t_max=np.inf, fetch=FETCH_LDS):
+        """Scene::intersect (scene.rs:39-60) for n rays on the scene's device (rl_scene_intersect).  origins, directions: (n, 3)
+        float32; t_max: a scalar or n values (only hits with distance < t_max count).  Returns an (n,) HIT_DTYPE array: object
+        (RL_OBJECT_NONE on a miss), distance, position, normal, tangent."""
+        origins = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        directions = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        if len(origins) != len(directions):
+            raise ValueError("origins and directions differ in length")
+        rays = np.zeros(len(origins), dtype=RAY_DTYPE)
+        rays["origin"] = origins
+        rays["direction"] = directions
+        rays["t_max"] = np.broadcast_to(np.asarray(t_max, dtype=np.float32), (len(rays),))
+        hits = np.empty(len(rays), dtype=HIT_DTYPE)
+        check(lib.rl_scene_intersect(self._h, fetch, rays.ctypes.data_as(C.c_void_p), len(rays), hits.ctypes.data_as(C.c_void_p)))
+        return hits
+
+    def intersect_device(self, rays, hits, fetch=FETCH_LDS):
+        """rl_scene_intersect_device: `rays` and `hits` are device buffers on the scene's device with data_ptr() (e.g. torch
+        tensors) holding n RAY_DTYPE records and room for n HIT_DTYPE records; n is taken from the sizes in bytes."""
+        n_bytes = lambda t: t.numel() * t.element_size()
+        n = n_bytes(rays) // RAY_DTYPE.itemsize
+        if n_bytes(rays) != n * RAY_DTYPE.itemsize or n_bytes(hits) < n * HIT_DTYPE.itemsize:
+            raise ValueError("rays must hold whole 32-byte records and hits room for as many 48-byte ones")
+        check(lib.rl_scene_intersect_device(self._h, fetch, C.c_void_p(rays.data_ptr()), n, C.c_void_p(hits.data_ptr())))
 
 
 class TraceUnit(_Handle):
@@ -405,6 +434,14 @@ def variant_launches():
     bits for the variants that stage the scene's tables only."""
     out = (C.c_uint64 * 24)()
     check(lib.rl_debug_variant_launches(out))
+    return list(out)
+
+
+def query_launches():
+    """rl_debug_query_launches: launches per instantiation of the query kernel (Scene.intersect*) since the library was loaded;
+    index = 2 * stage + 1 * prisms with a second bound, stage 0: nothing staged in LDS, 1: the scene's tables, 2: the whole scene."""
+    out = (C.c_uint64 * 6)()
+    check(lib.rl_debug_query_launches(out))
     return list(out)
 
 

@@ -42,6 +42,21 @@ class RlSceneDesc(C.Structure):
     _fields_ = [("n_objects", C.c_uint32), ("objects", C.c_void_p), ("camera", RlCameraDesc)]
 
 
+class RlRay(C.Structure):
+    _fields_ = [("origin", RlVector3), ("t_max", C.c_float), ("direction", RlVector3), ("reserved", C.c_uint32)]
+
+
+class RlIntersection(C.Structure):
+    _fields_ = [("position", RlVector3), ("normal", RlVector3), ("tangent", RlVector3), ("distance", C.c_float)]
+
+
+class RlRayHit(C.Structure):
+    _fields_ = [("isect", RlIntersection), ("object", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+RL_OBJECT_NONE = 0xffffffff
+
+
 class RlTask(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("unit", C.c_uint32), ("n_units", C.c_uint32),
                 ("units", C.c_uint32 * RL_TASK_MAX_UNITS)]
@@ -77,6 +92,8 @@ SIGNATURES = {
     "rl_scene_desc_load": (_i, [C.c_char_p, _vp, _u32, C.POINTER(_u32), C.POINTER(RlCameraDesc)]),
     "rl_scene_create": (_i, [C.POINTER(RlSceneDesc), _i, _pp]),
     "rl_scene_destroy": (_i, [_vp]),
+    "rl_scene_intersect": (_i, [_vp, _i, _vp, _u32, _vp]),
+    "rl_scene_intersect_device": (_i, [_vp, _i, _vp, _u32, _vp]),
     "rl_trace_unit_create": (_i, [_i, _u32, _u32, _u32, _u32, _pp]),
     "rl_trace_unit_destroy": (_i, [_vp]),
     "rl_trace_unit_set_fetch": (_i, [_vp, _i]),
@@ -135,6 +152,7 @@ DEBUG_SIGNATURES = {
     "rl_debug_app_rank_plan": (_i, [_i, _vp, _u32, _vp, _vp, _vp, C.POINTER(_u32)]),
     "rl_debug_batch_histogram": (_i, [_i, _vp]),
     "rl_debug_variant_launches": (_i, [_vp]),
+    "rl_debug_query_launches": (_i, [_vp]),
     "rl_debug_prism_probe": (_i, [_vp, _u32, _vp, _u32, _vp]),
     "rl_debug_prism_count": (_i, [_vp, C.POINTER(_u32)]),
 }

@@ -40,6 +40,7 @@
 #include "../../include/robigo_luculenta.h"
 #include "../../include/robigo_luculenta_debug.h"
 #include "rl_kernels.hip.h"
+#include "rl_query.hip.h"
 #include "rl_scene.h"
 
 namespace {
@@ -300,6 +301,102 @@ int launch_trace(RlTraceUnit* u, const RlScene* scene, RlMappedPhoton* photons, 
     return RL_OK;
 }
 
+// ---- scene queries (rl_scene_intersect*, rl_query.hip.h) ----------------------------------------------------------
+typedef void (*QueryKernel)(const RlF4*, RlSceneLayout, const RlRay*, RlRayHit*, uint32_t);
+std::atomic<uint64_t> g_query_launches[6]; // rl_debug_query_launches: launches per instantiation since the library was loaded
+// Index = 2 * stage + cylinders.
+QueryKernel query_kernel_variant(int stage, bool cyl) {
+    const int index = 2 * stage + (cyl ? 1 : 0);
+    g_query_launches[index].fetch_add(1, std::memory_order_relaxed);
+    static const QueryKernel table[6] = {
+        rl_query_kernel<RL_STAGE_NONE, false>,   rl_query_kernel<RL_STAGE_NONE, true>, rl_query_kernel<RL_STAGE_TABLES, false>,
+        rl_query_kernel<RL_STAGE_TABLES, true>, rl_query_kernel<RL_STAGE_ALL, false>, rl_query_kernel<RL_STAGE_ALL, true>,
+    };
+    return table[index];
+}
+
+// What a query call runs on: a stream of its own and, for the host path, device buffers of RL_QUERY_CHUNK rays and hits.
+// Each device keeps the contexts of finished calls for the next ones, so concurrent callers never share a stream or a buffer
+// and a steady caller allocates nothing.
+#define RL_QUERY_CHUNK (1u << 20)
+struct QueryCtx {
+    hipStream_t stream = nullptr;
+    RlRay* rays = nullptr;    // host path only (allocated on first use)
+    RlRayHit* hits = nullptr;
+};
+struct DeviceQueries {
+    std::mutex lock;
+    std::vector<QueryCtx*> idle;
+    int per_cu[6] = {}; // resident workgroups per CU of each variant, for the dynamic LDS size last seen (0: not set up)
+    size_t dyn[6] = {};
+};
+DeviceQueries* queries_of(int device) {
+    static DeviceQueries all[64];
+    return &all[device >= 0 && device < 64 ? device : 0];
+}
+int query_ctx_acquire(int device, QueryCtx** out) { // device current
+    DeviceQueries* d = queries_of(device);
+    {
+        std::lock_guard<std::mutex> guard(d->lock);
+        if (!d->idle.empty()) {
+            *out = d->idle.back();
+            d->idle.pop_back();
+            return RL_OK;
+        }
+    }
+    QueryCtx* q = new (std::nothrow) QueryCtx();
+    if (!q) return fail(RL_E_INVALID, "out of host memory");
+    const hipError_t e = hipStreamCreateWithFlags(&q->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+        delete q;
+        return fail(RL_E_HIP, std::string("query stream: ") + hipGetErrorString(e));
+    }
+    *out = q;
+    return RL_OK;
+}
+void query_ctx_release(int device, QueryCtx* q) {
+    DeviceQueries* d = queries_of(device);
+    std::lock_guard<std::mutex> guard(d->lock);
+    d->idle.push_back(q);
+}
+
+// One launch of the query kernel on q's stream for rays [0, n) of device arrays (n > 0).
+int launch_query(const RlScene* scene, int fetch, int cu_count, QueryCtx* q, const RlRay* rays, RlRayHit* hits, uint32_t n) {
+    const size_t scratch_bytes = (RL_TRACE_BLOCK / 64) * sizeof(RlWaveScratch) + ring_t_bytes(scene);
+    size_t blob_bytes = 0;
+    const int stage = stage_of(scene, fetch, scratch_bytes, &blob_bytes);
+    const bool cyl = scene->lay.prism_cylinders != 0u;
+    const int index = 2 * stage + (cyl ? 1 : 0);
+    auto kernel = query_kernel_variant(stage, cyl);
+    const size_t dyn = scratch_bytes + blob_bytes;
+    DeviceQueries* d = queries_of(scene->device);
+    int per_cu = 0;
+    {
+        std::lock_guard<std::mutex> guard(d->lock);
+        if (d->per_cu[index] == 0 || d->dyn[index] != dyn) {
+            RL_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            int k = 1;
+            RL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, kernel, RL_TRACE_BLOCK, dyn));
+            d->per_cu[index] = k < 1 ? 1 : k;
+            d->dyn[index] = dyn;
+        }
+        per_cu = d->per_cu[index];
+    }
+    uint64_t blocks = (uint64_t)cu_count * (uint64_t)per_cu;
+    const uint64_t needed = ((uint64_t)n + RL_TRACE_BLOCK - 1) / RL_TRACE_BLOCK;
+    if (blocks > needed) blocks = needed;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(RL_TRACE_BLOCK), dyn, q->stream, scene->blob, scene->lay, rays, hits, n);
+    RL_HIP(hipGetLastError());
+    return RL_OK;
+}
+
+int query_check(const RlScene* scene, int fetch, const void* rays, uint32_t n_rays, const void* hits) {
+    if (fetch != RL_FETCH_LDS && fetch != RL_FETCH_GLOBAL) return fail(RL_E_INVALID, "unknown fetch mode");
+    if (n_rays > 0 && (!rays || !hits)) return fail(RL_E_INVALID, "null ray or hit buffer");
+    if (!scene) return fail(RL_E_INVALID, "null scene");
+    return RL_OK;
+}
+
 unsigned grid_for(uint64_t work_items, int cu_count) {
     uint64_t blocks = (work_items + RL_BLOCK - 1) / RL_BLOCK;
     const uint64_t cap = (uint64_t)cu_count * 8;
@@ -512,6 +609,64 @@ int rl_scene_destroy(RlScene* scene) {
     (void)sessions_quiesce(scene->device); // an open launch may still be reading the blob
     (void)hipFree(scene->blob);
     delete scene;
+    return RL_OK;
+}
+
+int rl_scene_intersect(const RlScene* scene, int primitive_fetch, const RlRay* rays, uint32_t n_rays, RlRayHit* hits) {
+    int rc = query_check(scene, primitive_fetch, rays, n_rays, hits);
+    if (rc != RL_OK || n_rays == 0) return rc;
+    if ((rc = use_device(scene->device)) != RL_OK) return rc;
+    int cus = 256;
+    if ((rc = cu_count_of(scene->device, &cus)) != RL_OK) return rc;
+    QueryCtx* q = nullptr;
+    if ((rc = query_ctx_acquire(scene->device, &q)) != RL_OK) return rc;
+    auto run = [&]() -> int {
+        if (!q->rays) RL_HIP(hipMalloc((void**)&q->rays, (size_t)RL_QUERY_CHUNK * sizeof(RlRay)));
+        if (!q->hits) RL_HIP(hipMalloc((void**)&q->hits, (size_t)RL_QUERY_CHUNK * sizeof(RlRayHit)));
+        for (uint32_t first = 0; first < n_rays;) {
+            const uint32_t n = n_rays - first < RL_QUERY_CHUNK ? n_rays - first : RL_QUERY_CHUNK;
+            RL_HIP(hipMemcpyAsync(q->rays, rays + first, (size_t)n * sizeof(RlRay), hipMemcpyHostToDevice, q->stream));
+            const int r = launch_query(scene, primitive_fetch, cus, q, q->rays, q->hits, n);
+            if (r != RL_OK) return r;
+            RL_HIP(hipMemcpyAsync(hits + first, q->hits, (size_t)n * sizeof(RlRayHit), hipMemcpyDeviceToHost, q->stream));
+            RL_HIP(hipStreamSynchronize(q->stream));
+            first += n;
+        }
+        return RL_OK;
+    };
+    rc = run();
+    if (rc != RL_OK) (void)hipStreamSynchronize(q->stream); // (nothing of this call may still run when its buffers are handed on)
+    query_ctx_release(scene->device, q);
+    return rc;
+}
+
+int rl_scene_intersect_device(const RlScene* scene, int primitive_fetch, const RlRay* device_rays, uint32_t n_rays, RlRayHit* device_hits) {
+    int rc = query_check(scene, primitive_fetch, device_rays, n_rays, device_hits);
+    if (rc != RL_OK || n_rays == 0) return rc;
+    if ((rc = use_device(scene->device)) != RL_OK) return rc;
+    // Both arrays must be memory the scene's device can address: a pageable host pointer here would fault the device.  Accepted:
+    // device memory of the scene's device, managed memory, and pinned host memory mapped at the same address.  (The runtime reports
+    // pageable host memory as hipMemoryTypeUnregistered, or fails.)
+    for (const void* p : {(const void*)device_rays, (const void*)device_hits}) {
+        hipPointerAttribute_t attr;
+        std::memset(&attr, 0, sizeof attr);
+        if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+            (void)hipGetLastError();
+            attr.type = hipMemoryTypeUnregistered;
+        }
+        const bool ok = (attr.type == hipMemoryTypeDevice && attr.device == scene->device) || attr.type == hipMemoryTypeManaged ||
+                        (attr.type == hipMemoryTypeHost && attr.devicePointer == p);
+        if (!ok) return fail(RL_E_INVALID, "rl_scene_intersect_device: a buffer is not device memory of the scene's device (host arrays: rl_scene_intersect)");
+    }
+    int cus = 256;
+    if ((rc = cu_count_of(scene->device, &cus)) != RL_OK) return rc;
+    QueryCtx* q = nullptr;
+    if ((rc = query_ctx_acquire(scene->device, &q)) != RL_OK) return rc;
+    rc = launch_query(scene, primitive_fetch, cus, q, device_rays, device_hits, n_rays);
+    const hipError_t e = hipStreamSynchronize(q->stream);
+    query_ctx_release(scene->device, q);
+    if (rc != RL_OK) return rc;
+    RL_HIP(e);
     return RL_OK;
 }
 
@@ -1715,6 +1870,12 @@ int rl_debug_batch_histogram(int device, uint64_t* out) {
 int rl_debug_variant_launches(uint64_t* out) {
     if (!out) return fail(RL_E_INVALID, "null argument");
     for (int k = 0; k < 24; ++k) out[k] = g_variant_launches[k].load(std::memory_order_relaxed);
+    return RL_OK;
+}
+
+int rl_debug_query_launches(uint64_t* out) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    for (int k = 0; k < 6; ++k) out[k] = g_query_launches[k].load(std::memory_order_relaxed);
     return RL_OK;
 }
 
