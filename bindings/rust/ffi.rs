@@ -24,6 +24,7 @@ use std::os::raw::{c_char, c_double, c_float, c_int};
 #[repr(C)] #[derive(Copy, Clone)] pub struct RlRayHit { pub isect: RlIntersection, pub object: u32, pub reserved: u32 } // 48 bytes
 pub const RL_OBJECT_NONE: u32 = 0xffff_ffff;
 
+pub const RL_MAX_PIXELS: usize = 2147483647;
 pub const RL_TASK_MAX_UNITS: usize = 256;
 pub const RL_COMM_ID_BYTES: usize = 128;
 #[repr(C)] #[derive(Copy, Clone)] pub struct RlTask {            // enum Task by value, task_scheduler.rs:26-41

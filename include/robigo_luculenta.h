@@ -188,6 +188,12 @@ int rl_scene_intersect(const RlScene* scene, int primitive_fetch, const RlRay* r
 int rl_scene_intersect_device(const RlScene* scene, int primitive_fetch, const RlRay* device_rays, uint32_t n_rays,
                               RlRayHit* device_hits);
 
+/* Largest image the units and rl_app_run accept: width * height <= RL_MAX_PIXELS = 2^31 - 1.  The kernels index
+ * pixels in 32 bits: the splat's `py * width + px` is an int, the tonemap's pixel count and grid-stride index are
+ * uint32_t.  rl_trace_unit_create, rl_plot_unit_create, rl_gather_unit_create, rl_tonemap_unit_create and rl_app_run
+ * return RL_E_INVALID with a message naming the limit for a larger image, before they touch a device. */
+#define RL_MAX_PIXELS 2147483647
+
 /* ---- TraceUnit (trace_unit.rs:51-168) ------------------------------------------------------ */
 
 /* TraceUnit::new(id, width, height) (trace_unit.rs:64-77); n_photons is the batch size the

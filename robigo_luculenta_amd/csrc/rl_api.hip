@@ -67,6 +67,13 @@ namespace {
             return fail(RL_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_));                       \
     } while (0)
 
+// RL_MAX_PIXELS (robigo_luculenta.h): checked before use_device, like the zero-size check.
+int check_image_size(const char* unit, uint32_t width, uint32_t height) {
+    if ((uint64_t)width * height <= RL_MAX_PIXELS) return RL_OK;
+    return fail(RL_E_INVALID, std::string(unit) + ": " + std::to_string(width) + " x " + std::to_string(height) +
+                                  " pixels exceed RL_MAX_PIXELS = 2^31 - 1 (the kernels index pixels in 32 bits)");
+}
+
 int use_device(int device) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(RL_E_NO_DEVICE, "no HIP device is visible");
@@ -677,7 +684,9 @@ int rl_trace_unit_create(int device, uint32_t id, uint32_t width, uint32_t heigh
     if (!out) return fail(RL_E_INVALID, "null output handle");
     *out = nullptr;
     if (width == 0 || height == 0 || n_photons == 0) return fail(RL_E_INVALID, "zero-sized trace unit");
-    int rc = use_device(device);
+    int rc = check_image_size("trace unit", width, height);
+    if (rc != RL_OK) return rc;
+    rc = use_device(device);
     if (rc != RL_OK) return rc;
     RlTraceUnit* u = new (std::nothrow) RlTraceUnit();
     if (!u) return fail(RL_E_INVALID, "out of host memory");
@@ -1235,7 +1244,9 @@ int rl_plot_unit_create(int device, uint32_t id, uint32_t width, uint32_t height
     if (!out) return fail(RL_E_INVALID, "null output handle");
     *out = nullptr;
     if (width == 0 || height == 0) return fail(RL_E_INVALID, "zero-sized plot unit");
-    int rc = use_device(device);
+    int rc = check_image_size("plot unit", width, height);
+    if (rc != RL_OK) return rc;
+    rc = use_device(device);
     if (rc != RL_OK) return rc;
     RlPlotUnit* u = new (std::nothrow) RlPlotUnit();
     if (!u) return fail(RL_E_INVALID, "out of host memory");
@@ -1370,7 +1381,9 @@ int rl_gather_unit_create(int device, uint32_t width, uint32_t height, RlGatherU
     if (!out) return fail(RL_E_INVALID, "null output handle");
     *out = nullptr;
     if (width == 0 || height == 0) return fail(RL_E_INVALID, "zero-sized gather unit");
-    int rc = use_device(device);
+    int rc = check_image_size("gather unit", width, height);
+    if (rc != RL_OK) return rc;
+    rc = use_device(device);
     if (rc != RL_OK) return rc;
     RlGatherUnit* u = new (std::nothrow) RlGatherUnit();
     if (!u) return fail(RL_E_INVALID, "out of host memory");
@@ -1488,7 +1501,9 @@ int rl_tonemap_unit_create(int device, uint32_t width, uint32_t height, RlTonema
     if (!out) return fail(RL_E_INVALID, "null output handle");
     *out = nullptr;
     if (width == 0 || height == 0) return fail(RL_E_INVALID, "zero-sized tonemap unit");
-    int rc = use_device(device);
+    int rc = check_image_size("tonemap unit", width, height);
+    if (rc != RL_OK) return rc;
+    rc = use_device(device);
     if (rc != RL_OK) return rc;
     RlTonemapUnit* u = new (std::nothrow) RlTonemapUnit();
     if (!u) return fail(RL_E_INVALID, "out of host memory");

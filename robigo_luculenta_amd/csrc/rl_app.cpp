@@ -463,6 +463,11 @@ extern "C" int rl_app_run(const RlAppConfig* config, RlAppStats* stats, uint8_t*
         rl_internal_set_last_error("rl_app_run: null config, zero-sized image or zero workers");
         return RL_E_INVALID;
     }
+    if ((uint64_t)config->width * config->height > RL_MAX_PIXELS) {
+        rl_internal_set_last_error("rl_app_run: " + std::to_string(config->width) + " x " + std::to_string(config->height) +
+                                   " pixels exceed RL_MAX_PIXELS = 2^31 - 1 (the kernels index pixels in 32 bits)");
+        return RL_E_INVALID;
+    }
     if (config->concurrency * 3 > RL_TASK_MAX_UNITS) {
         rl_internal_set_last_error("rl_app_run: concurrency " + std::to_string(config->concurrency) + " needs " +
                                    std::to_string(config->concurrency * 3) + " trace units, more than RL_TASK_MAX_UNITS = " +

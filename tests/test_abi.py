@@ -255,3 +255,28 @@ def test_diagnostics_live_in_their_own_header_outside_the_boundary():
         assert hasattr(_lib.lib, s), "library does not export %s" % s
     assert not [s for s in declared_symbols() if s.startswith("rl_debug_")]
     assert "rl_debug_" not in open(os.path.join(ROOT, "bindings", "rust", "ffi.rs")).read()
+
+
+def test_images_beyond_32_bit_pixel_indices_are_refused_before_any_device_work():
+    """The kernels index pixels in 32 bits (the splat's int `py * width + px`, the tonemap's uint32_t pixel count and
+    grid-stride index), so width * height > RL_MAX_PIXELS = 2^31 - 1 is RL_E_INVALID at creation, checked before the
+    device is touched: nothing is allocated, with or without a GPU.  46341^2 is the first square past the limit,
+    65536 x 32768 = 2^31 the first product."""
+    header = open(os.path.join(ROOT, "include", "robigo_luculenta.h")).read()
+    assert re.search(r"#define RL_MAX_PIXELS 2147483647\b", header)
+    ctors = {"trace": lambda w, h: R.TraceUnit(0, w, h, n_photons=64), "plot": lambda w, h: R.PlotUnit(0, w, h),
+             "gather": lambda w, h: R.GatherUnit(w, h), "tonemap": lambda w, h: R.TonemapUnit(w, h),
+             "app_run": _app_run_without_an_image}
+    for w, h in [(46341, 46341), (65536, 32768), (32768, 65536), (0xFFFFFFFF, 0xFFFFFFFF), (0x80000000, 1)]:
+        for name, ctor in ctors.items():
+            with pytest.raises(R.RlError) as e:
+                ctor(w, h)
+            assert e.value.code == -1, (name, w, h, str(e.value))
+            assert "RL_MAX_PIXELS" in str(e.value), (name, w, h, str(e.value))
+
+
+def _app_run_without_an_image(w, h):
+    """rl_app_run with no output image (R.app_run would allocate the w x h one first)."""
+    cfg = _lib.RlAppConfig()
+    cfg.width, cfg.height, cfg.concurrency, cfg.max_batches = w, h, 1, 1
+    R.check(_lib.lib.rl_app_run(C.byref(cfg), C.byref(_lib.RlAppStats()), None))

@@ -10,6 +10,7 @@ import sys
 import numpy as np
 import pytest
 
+import _image_cases as IC
 import _oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -61,9 +62,13 @@ def test_plot_unit_add_upload_and_async_ordering(R):
     t1.render_async(scene, seed=4, stream=1, first_path_index=0)
     a.plot([t0])
     b.plot([t1])
-    want = [O.plot(W, H, oscene.render(W, H, 4, s, 0, N, threads=4)[0]) for s in (0, 1)]
+    ph = [oscene.render(W, H, 4, s, 0, N, threads=4)[0] for s in (0, 1)]
+    want = [O.plot(W, H, p) for p in ph]
     xa, xb = a.tristimulus_buffer, b.tristimulus_buffer
     assert np.allclose(xa, want[0], rtol=2e-5, atol=1e-7) and np.allclose(xb, want[1], rtol=2e-5, atol=1e-7)
+    for got, photons, w in zip((xa, xb), ph, want):  # per pixel: within (k_p - 1) 2^-24 S_p of the exact sum (tests/_image_cases.py)
+        _, k, s, exact = IC.splat(W, H, photons)
+        assert not len(IC.splat_violations(got, w, k, s, exact)[0])
     a.add(b)                                            # rl_plot_unit_add: dst += src on one device
     assert a.tristimulus_buffer.tobytes() == (xa + xb).tobytes() and b.tristimulus_buffer.tobytes() == xb.tobytes()
     # unit re-use right after an asynchronous plot: the next render must wait for the plot that reads mapped_photons

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import _image_cases as IC
 import _oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -305,12 +306,18 @@ def test_plot_fused_and_unfused_match_oracle(demo):
     scale = np.abs(want).max()
     assert np.abs(got - want).max() <= 2e-6 * scale + 1e-6 * np.abs(want).max()
     assert np.allclose(got, want, rtol=2e-5, atol=1e-6 * scale)
+    # per pixel: within (k_p - 1) 2^-24 S_p of the exact sum of the pixel's k_p terms (the oracle's bits for k_p <= 2), so that a
+    # dim pixel cannot hide under a tolerance scaled by the image's maximum (tests/_image_cases.py)
+    img, k, s, exact = IC.splat(W, H, photons)
+    assert IC.same_bits(img, want)
+    assert not len(IC.splat_violations(got, want, k, s, exact)[0])
     # fused: same photons splatted straight from the trace kernel
     p2 = R.PlotUnit(1, W, H)
     t.render_fused(scene, p2, N, seed=1, stream=0, first_path_index=0)
     t.sync()
     got2 = p2.tristimulus_buffer
     assert np.allclose(got2, want, rtol=2e-5, atol=1e-6 * scale)
+    assert not len(IC.splat_violations(got2, want, k, s, exact)[0])
     # clear
     p2.clear()
     assert not p2.tristimulus_buffer.any()
