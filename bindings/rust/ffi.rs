@@ -23,6 +23,17 @@ use std::os::raw::{c_char, c_double, c_float, c_int};
 #[repr(C)] #[derive(Copy, Clone)] pub struct RlIntersection { pub position: RlVector3, pub normal: RlVector3, pub tangent: RlVector3, pub distance: f32 } // 40 bytes
 #[repr(C)] #[derive(Copy, Clone)] pub struct RlRayHit { pub isect: RlIntersection, pub object: u32, pub reserved: u32 } // 48 bytes
 pub const RL_OBJECT_NONE: u32 = 0xffff_ffff;
+// TraceUnit::render_ray on caller-supplied rays (rl_scene_camera_rays*, rl_scene_render_rays*)
+#[repr(C)] #[derive(Copy, Clone)] pub struct RlSpectralRay { pub origin: RlVector3, pub wavelength: f32, pub direction: RlVector3, pub reserved: u32 } // 32 bytes
+#[repr(C)] #[derive(Copy, Clone)] pub struct RlCameraSample { pub ray: RlSpectralRay, pub x: f32, pub y: f32, pub reserved0: u32, pub reserved1: u32 } // 48 bytes
+#[repr(C)] #[derive(Copy, Clone)] pub struct RlPathResult { pub value: f32, pub segments: u32, pub object: u32, pub end: u32 } // 16 bytes
+pub const RL_PATH_END_VOID: u32 = 0;
+pub const RL_PATH_END_EMITTER: u32 = 1;
+pub const RL_PATH_END_ROULETTE: u32 = 2;
+pub const RL_PATH_END_LIMIT: u32 = 3;
+pub const RL_PATH_END_INVALID: u32 = 4;
+pub const RL_PATH_MAX_SEGMENTS: u32 = 4096;
+pub const RL_PATH_MAX_SEGMENTS_CAP: u32 = 65536;
 
 pub const RL_MAX_PIXELS: usize = 2147483647;
 pub const RL_TASK_MAX_UNITS: usize = 256;
@@ -61,6 +72,15 @@ extern "C" {
     pub fn rl_scene_intersect(scene: *const RlScene, primitive_fetch: c_int, rays: *const RlRay, n_rays: u32, hits: *mut RlRayHit) -> c_int;
     pub fn rl_scene_intersect_device(scene: *const RlScene, primitive_fetch: c_int, device_rays: *const RlRay, n_rays: u32,
                                      device_hits: *mut RlRayHit) -> c_int;
+    pub fn rl_scene_camera_rays(scene: *const RlScene, width: u32, height: u32, seed: u64, stream: u32, first_path_index: u64, n: u32,
+                                samples: *mut RlCameraSample) -> c_int;
+    pub fn rl_scene_camera_rays_device(scene: *const RlScene, width: u32, height: u32, seed: u64, stream: u32, first_path_index: u64,
+                                       n: u32, device_samples: *mut RlCameraSample) -> c_int;
+    pub fn rl_scene_render_rays(scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32, first_path_index: u64,
+                                max_segments: u32, rays: *const RlSpectralRay, n_rays: u32, results: *mut RlPathResult) -> c_int;
+    pub fn rl_scene_render_rays_device(scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32, first_path_index: u64,
+                                       max_segments: u32, device_rays: *const RlSpectralRay, n_rays: u32,
+                                       device_results: *mut RlPathResult) -> c_int;
 
     pub fn rl_trace_unit_create(device: c_int, id: u32, w: u32, h: u32, n_photons: u32, out: *mut *mut RlTraceUnit) -> c_int;
     pub fn rl_trace_unit_destroy(u: *mut RlTraceUnit) -> c_int;

@@ -188,6 +188,84 @@ int rl_scene_intersect(const RlScene* scene, int primitive_fetch, const RlRay* r
 int rl_scene_intersect_device(const RlScene* scene, int primitive_fetch, const RlRay* device_rays, uint32_t n_rays,
                               RlRayHit* device_hits);
 
+/* ---- TraceUnit::render_ray as a batched call: caller-supplied spectral rays ----------------- */
+
+/* Ray (ray.rs:19-33) with its wavelength; the probability is folded into the path's intensity, which starts at 1. */
+typedef struct RlSpectralRay {
+    RlVector3 origin;
+    float wavelength;    /* nm */
+    RlVector3 direction; /* used as given, not normalised (like RlRay) */
+    uint32_t reserved;   /* ignored */
+} RlSpectralRay;         /* 32 bytes */
+
+typedef struct RlCameraSample {
+    RlSpectralRay ray;          /* the camera ray of the path: make_camera + Camera::get_ray (trace_unit.rs:136-158) */
+    float x, y;                 /* screen position: RlMappedPhoton x, y of the same path */
+    uint32_t reserved0, reserved1; /* written 0 */
+} RlCameraSample;               /* 48 bytes */
+
+enum RlPathEnd {
+    RL_PATH_END_VOID = 0,     /* the path left the scene (trace_unit.rs:94) */
+    RL_PATH_END_EMITTER = 1,  /* it hit a light: value = intensity * get_intensity(wavelength) (trace_unit.rs:99-101) */
+    RL_PATH_END_ROULETTE = 2, /* Russian roulette ended it after a bounce (trace_unit.rs:122-125) */
+    RL_PATH_END_LIMIT = 3,    /* it used max_segments segments without ending: value 0 (not in the reference) */
+    RL_PATH_END_INVALID = 4   /* its wavelength is not finite: value 0, no segment (not in the reference) */
+};
+
+typedef struct RlPathResult {
+    float value;       /* render_ray's return value (trace_unit.rs:81-132); 0 for every end but RL_PATH_END_EMITTER */
+    uint32_t segments; /* Scene::intersect calls the path made */
+    uint32_t object;   /* the emitter the path ended on; RL_OBJECT_NONE for any other end */
+    uint32_t end;      /* enum RlPathEnd */
+} RlPathResult;        /* 16 bytes */
+
+#define RL_PATH_MAX_SEGMENTS 4096     /* max_segments = 0 */
+#define RL_PATH_MAX_SEGMENTS_CAP 65536 /* the largest max_segments accepted */
+
+/* rl_scene_camera_rays: the camera half of a path.  samples[i] is what path first_path_index + i of RNG stream `stream` under
+ * `seed` draws from blocks 0 and 1 (rl_rng.h) for a width x height image, turned into a ray: its wavelength, its screen position
+ * x, y and the camera ray (rl_trace_unit_render's camera for a trace unit of that size).  width or height 0, or
+ * width * height > RL_MAX_PIXELS, is RL_E_INVALID.
+ *
+ * rl_scene_render_rays: the other half, TraceUnit::render_ray (trace_unit.rs:81-132) for rays[i] as path first_path_index + i of
+ * stream `stream` under `seed`: bounce b draws from block 2 + b, which is what a camera path of that index draws after its camera
+ * ray.  The path starts with intensity 1 and continue chance 1 and follows the reference's loop (Scene::intersect, the material's
+ * new ray, the 1e-5 offset, continue chance * 0.96, Russian roulette) until it ends; results[i] says how (RlPathResult).
+ *   Identity.  For any scene, image size, seed, stream and path range: feed rl_scene_camera_rays(...)[i].ray to
+ *   rl_scene_render_rays with the same seed, stream and first_path_index; then results[i].value equals, bit for bit, the
+ *   `probability` of photon i of rl_trace_unit_render for those paths, samples[i].x, .y and .ray.wavelength equal that photon's
+ *   x, y and wavelength, and the sum of results[].segments equals the segments rl_trace_unit_stats reports for those paths.
+ *   Determinism.  A result depends only on (scene, seed, stream, path index, ray, max_segments): not on how a batch is split, on
+ *   primitive_fetch or the kernel variant, or on other callers.
+ *   Rays as given.  A segment whose direction is not within 2^-20 of unit length (|d|^2 further than 2^-20 from 1), or whose
+ *   origin or direction has a non-finite component, is intersected by an exact linear scan (the scan's culls assume a unit
+ *   direction, see rl_scene_intersect).  This is decided per segment: glass refraction and mirror reflection keep a non-unit
+ *   direction's length, so such a ray stays non-unit after those bounces.
+ *   Invalid wavelength (a deviation from the reference).  A ray with a NaN or infinite wavelength returns {0, 0 segments,
+ *   RL_OBJECT_NONE, RL_PATH_END_INVALID} without any scan: its intensity would be NaN, which never ends the roulette, and inside a
+ *   closed scene the path would never end.  Finite wavelengths outside [380, 780] nm are traced as given.
+ *   Segment limit (a deviation from the reference).  max_segments = 0 means RL_PATH_MAX_SEGMENTS (4096); otherwise it must be
+ *   1 .. RL_PATH_MAX_SEGMENTS_CAP (65536), a larger value is RL_E_INVALID.  A path that has used max_segments segments and not
+ *   ended returns value 0 and RL_PATH_END_LIMIT: the kernel's guarantee that it terminates.  At the default it changes no result
+ *   of a path with a finite wavelength in practice: from bounce ~2,500 on its f32 continue chance sits at its floor (1.7e-44), and
+ *   the path goes on only where a bounce's roulette draw is exactly 0 (probability 2^-24 each).
+ * Both calls, and their _device forms, work as rl_scene_intersect* do: n = 0 does nothing; a NULL scene, an unknown fetch mode,
+ * NULL buffers with n > 0 or path indices that reach 2^64 - 1 are RL_E_INVALID before any device work; the host forms stage the
+ * arrays through device buffers in chunks of 2^20 records, the _device forms take device pointers on the scene's device and
+ * refuse pageable host memory; all of them return when the results are written, are safe from several host threads at once on
+ * one scene, and order against renders as a query does: a call made while an open launch runs on the device (a blocking render in
+ * flight, or one begun with rl_trace_unit_render_begin / _fused_begin and not yet ended) waits until that launch drains, which it
+ * does by itself (rl_scene_intersect), so a call between _begin and _end completes and does not disturb the render. */
+int rl_scene_camera_rays(const RlScene* scene, uint32_t width, uint32_t height, uint64_t seed, uint32_t stream,
+                         uint64_t first_path_index, uint32_t n, RlCameraSample* samples);
+int rl_scene_camera_rays_device(const RlScene* scene, uint32_t width, uint32_t height, uint64_t seed, uint32_t stream,
+                                uint64_t first_path_index, uint32_t n, RlCameraSample* device_samples);
+int rl_scene_render_rays(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, uint64_t first_path_index,
+                         uint32_t max_segments, const RlSpectralRay* rays, uint32_t n_rays, RlPathResult* results);
+int rl_scene_render_rays_device(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream,
+                                uint64_t first_path_index, uint32_t max_segments, const RlSpectralRay* device_rays,
+                                uint32_t n_rays, RlPathResult* device_results);
+
 /* Largest image the units and rl_app_run accept: width * height <= RL_MAX_PIXELS = 2^31 - 1.  The kernels index
  * pixels in 32 bits: the splat's `py * width + px` is an int, the tonemap's pixel count and grid-stride index are
  * uint32_t.  rl_trace_unit_create, rl_plot_unit_create, rl_gather_unit_create, rl_tonemap_unit_create and rl_app_run

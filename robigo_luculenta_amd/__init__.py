@@ -8,8 +8,10 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (RlAppConfig, RlAppStats, RlCameraDesc, RlError, RlIntersection, RlMappedPhoton, RlObjectDesc, RlRay, RlRayHit, RlSceneDesc,
-                   RlTask, RlVector3, check, lib, RL_OBJECT_NONE, RL_TASK_MAX_UNITS)
+from ._lib import (RlAppConfig, RlAppStats, RlCameraDesc, RlCameraSample, RlError, RlIntersection, RlMappedPhoton, RlObjectDesc, RlPathResult,
+                   RlRay, RlRayHit, RlSceneDesc, RlSpectralRay, RlTask, RlVector3, check, lib, RL_OBJECT_NONE, RL_PATH_END_EMITTER,
+                   RL_PATH_END_INVALID, RL_PATH_END_LIMIT, RL_PATH_END_ROULETTE, RL_PATH_END_VOID, RL_PATH_MAX_SEGMENTS,
+                   RL_PATH_MAX_SEGMENTS_CAP, RL_TASK_MAX_UNITS)
 
 PHOTON_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("probability", "<f4"), ("wavelength", "<f4")])
 OBJECT_DTYPE = np.dtype([("surface_kind", "<u4"), ("material_kind", "<u4"), ("v0", "<f4", 3), ("v1", "<f4", 3),
@@ -18,6 +20,10 @@ OBJECT_DTYPE = np.dtype([("surface_kind", "<u4"), ("material_kind", "<u4"), ("v0
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("t_max", "<f4"), ("direction", "<f4", 3), ("reserved", "<u4")])
 HIT_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("tangent", "<f4", 3), ("distance", "<f4"), ("object", "<u4"),
                       ("reserved", "<u4")])
+# Scene.camera_rays / render_rays records: RlSpectralRay (32 bytes), RlCameraSample (48 bytes) and RlPathResult (16 bytes)
+SPECTRAL_RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("wavelength", "<f4"), ("direction", "<f4", 3), ("reserved", "<u4")])
+CAMERA_SAMPLE_DTYPE = np.dtype([("ray", SPECTRAL_RAY_DTYPE), ("x", "<f4"), ("y", "<f4"), ("reserved0", "<u4"), ("reserved1", "<u4")])
+PATH_RESULT_DTYPE = np.dtype([("value", "<f4"), ("segments", "<u4"), ("object", "<u4"), ("end", "<u4")])
 NUMBER_OF_PHOTONS = 1024 * 512  # trace_unit.rs:67
 
 SCENE_DEMO, SCENE_GLASS_STRESS = 0, 1
@@ -137,6 +143,53 @@ class Scene(_Handle):
         if n_bytes(rays) != n * RAY_DTYPE.itemsize or n_bytes(hits) < n * HIT_DTYPE.itemsize:
             raise ValueError("rays must hold whole 32-byte records and hits room for as many 48-byte ones")
         check(lib.rl_scene_intersect_device(self._h, fetch, C.c_void_p(rays.data_ptr()), n, C.c_void_p(hits.data_ptr())))
+
+    def camera_rays(self, width, height, seed, stream, first, n):
+        """rl_scene_camera_rays: the camera half of paths first .. first + n - 1 of (seed, stream) for a width x height image --
+        the ray, its wavelength and the screen position x, y that rl_trace_unit_render gives those paths.  Returns an (n,)
+        CAMERA_SAMPLE_DTYPE array."""
+        samples = np.empty(n, dtype=CAMERA_SAMPLE_DTYPE)
+        check(lib.rl_scene_camera_rays(self._h, width, height, seed, stream, first, n, samples.ctypes.data_as(C.c_void_p)))
+        return samples
+
+    def camera_rays_device(self, width, height, seed, stream, first, samples):
+        """rl_scene_camera_rays_device: fills a device buffer with data_ptr() (e.g. a torch tensor) with as many
+        CAMERA_SAMPLE_DTYPE records as it holds whole."""
+        n = samples.numel() * samples.element_size() // CAMERA_SAMPLE_DTYPE.itemsize
+        check(lib.rl_scene_camera_rays_device(self._h, width, height, seed, stream, first, n, C.c_void_p(samples.data_ptr())))
+
+    def render_rays(self, origins, directions, wavelengths, seed, stream, first=0, fetch=FETCH_LDS, max_segments=0):
+        """TraceUnit::render_ray (trace_unit.rs:81-132) for n caller-supplied rays as paths first .. first + n - 1 of (seed,
+        stream) (rl_scene_render_rays).  origins, directions: (n, 3) float32, directions used as given; wavelengths: a scalar or n
+        values in nm.  Returns an (n,) PATH_RESULT_DTYPE array: value, segments, object (the emitter, or RL_OBJECT_NONE), end
+        (RL_PATH_END_*).  max_segments 0 means RL_PATH_MAX_SEGMENTS."""
+        origins = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        directions = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        if len(origins) != len(directions):
+            raise ValueError("origins and directions differ in length")
+        rays = np.zeros(len(origins), dtype=SPECTRAL_RAY_DTYPE)
+        rays["origin"] = origins
+        rays["direction"] = directions
+        rays["wavelength"] = np.broadcast_to(np.asarray(wavelengths, dtype=np.float32), (len(rays),))
+        return self.render_spectral_rays(rays, seed, stream, first, fetch, max_segments)
+
+    def render_spectral_rays(self, rays, seed, stream, first=0, fetch=FETCH_LDS, max_segments=0):
+        """render_rays for an (n,) SPECTRAL_RAY_DTYPE array (e.g. camera_rays(...)["ray"])."""
+        rays = np.ascontiguousarray(rays, dtype=SPECTRAL_RAY_DTYPE)
+        results = np.empty(len(rays), dtype=PATH_RESULT_DTYPE)
+        check(lib.rl_scene_render_rays(self._h, fetch, seed, stream, first, max_segments, rays.ctypes.data_as(C.c_void_p), len(rays),
+                                       results.ctypes.data_as(C.c_void_p)))
+        return results
+
+    def render_rays_device(self, rays, results, seed, stream, first=0, fetch=FETCH_LDS, max_segments=0):
+        """rl_scene_render_rays_device: `rays` and `results` are device buffers on the scene's device with data_ptr() (e.g. torch
+        tensors) holding n SPECTRAL_RAY_DTYPE records and room for n PATH_RESULT_DTYPE records; n is taken from the sizes in bytes."""
+        n_bytes = lambda t: t.numel() * t.element_size()
+        n = n_bytes(rays) // SPECTRAL_RAY_DTYPE.itemsize
+        if n_bytes(rays) != n * SPECTRAL_RAY_DTYPE.itemsize or n_bytes(results) < n * PATH_RESULT_DTYPE.itemsize:
+            raise ValueError("rays must hold whole 32-byte records and results room for as many 16-byte ones")
+        check(lib.rl_scene_render_rays_device(self._h, fetch, seed, stream, first, max_segments, C.c_void_p(rays.data_ptr()), n,
+                                              C.c_void_p(results.data_ptr())))
 
 
 class TraceUnit(_Handle):
@@ -442,6 +495,14 @@ def query_launches():
     index = 2 * stage + 1 * prisms with a second bound, stage 0: nothing staged in LDS, 1: the scene's tables, 2: the whole scene."""
     out = (C.c_uint64 * 6)()
     check(lib.rl_debug_query_launches(out))
+    return list(out)
+
+
+def path_launches():
+    """rl_debug_path_launches: launches per instantiation of the path kernel (Scene.render_rays*) since the library was loaded,
+    indexed as query_launches()."""
+    out = (C.c_uint64 * 6)()
+    check(lib.rl_debug_path_launches(out))
     return list(out)
 
 

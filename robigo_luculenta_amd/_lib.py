@@ -57,6 +57,23 @@ class RlRayHit(C.Structure):
 RL_OBJECT_NONE = 0xffffffff
 
 
+class RlSpectralRay(C.Structure):
+    _fields_ = [("origin", RlVector3), ("wavelength", C.c_float), ("direction", RlVector3), ("reserved", C.c_uint32)]
+
+
+class RlCameraSample(C.Structure):
+    _fields_ = [("ray", RlSpectralRay), ("x", C.c_float), ("y", C.c_float), ("reserved0", C.c_uint32), ("reserved1", C.c_uint32)]
+
+
+class RlPathResult(C.Structure):
+    _fields_ = [("value", C.c_float), ("segments", C.c_uint32), ("object", C.c_uint32), ("end", C.c_uint32)]
+
+
+RL_PATH_END_VOID, RL_PATH_END_EMITTER, RL_PATH_END_ROULETTE, RL_PATH_END_LIMIT, RL_PATH_END_INVALID = range(5)
+RL_PATH_MAX_SEGMENTS = 4096
+RL_PATH_MAX_SEGMENTS_CAP = 65536
+
+
 class RlTask(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("unit", C.c_uint32), ("n_units", C.c_uint32),
                 ("units", C.c_uint32 * RL_TASK_MAX_UNITS)]
@@ -94,6 +111,10 @@ SIGNATURES = {
     "rl_scene_destroy": (_i, [_vp]),
     "rl_scene_intersect": (_i, [_vp, _i, _vp, _u32, _vp]),
     "rl_scene_intersect_device": (_i, [_vp, _i, _vp, _u32, _vp]),
+    "rl_scene_camera_rays": (_i, [_vp, _u32, _u32, _u64, _u32, _u64, _u32, _vp]),
+    "rl_scene_camera_rays_device": (_i, [_vp, _u32, _u32, _u64, _u32, _u64, _u32, _vp]),
+    "rl_scene_render_rays": (_i, [_vp, _i, _u64, _u32, _u64, _u32, _vp, _u32, _vp]),
+    "rl_scene_render_rays_device": (_i, [_vp, _i, _u64, _u32, _u64, _u32, _vp, _u32, _vp]),
     "rl_trace_unit_create": (_i, [_i, _u32, _u32, _u32, _u32, _pp]),
     "rl_trace_unit_destroy": (_i, [_vp]),
     "rl_trace_unit_set_fetch": (_i, [_vp, _i]),
@@ -153,6 +174,7 @@ DEBUG_SIGNATURES = {
     "rl_debug_batch_histogram": (_i, [_i, _vp]),
     "rl_debug_variant_launches": (_i, [_vp]),
     "rl_debug_query_launches": (_i, [_vp]),
+    "rl_debug_path_launches": (_i, [_vp]),
     "rl_debug_prism_probe": (_i, [_vp, _u32, _vp, _u32, _vp]),
     "rl_debug_prism_count": (_i, [_vp, C.POINTER(_u32)]),
 }

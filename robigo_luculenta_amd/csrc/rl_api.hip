@@ -41,6 +41,7 @@
 #include "../../include/robigo_luculenta_debug.h"
 #include "rl_kernels.hip.h"
 #include "rl_query.hip.h"
+#include "rl_paths.hip.h"
 #include "rl_scene.h"
 
 namespace {
@@ -326,16 +327,23 @@ QueryKernel query_kernel_variant(int stage, bool cyl) {
 // Each device keeps the contexts of finished calls for the next ones, so concurrent callers never share a stream or a buffer
 // and a steady caller allocates nothing.
 #define RL_QUERY_CHUNK (1u << 20)
+// The path calls (rl_scene_camera_rays*, rl_scene_render_rays*) run on the same contexts: their 32-byte rays go in `rays`, their
+// 16-byte results and 48-byte camera samples in `hits`, and the path kernel's queue is `queue`.
 struct QueryCtx {
     hipStream_t stream = nullptr;
     RlRay* rays = nullptr;    // host path only (allocated on first use)
     RlRayHit* hits = nullptr;
+    unsigned long long* queue = nullptr; // path calls only (allocated on first use)
 };
+static_assert(sizeof(RlSpectralRay) == sizeof(RlRay) && sizeof(RlCameraSample) == sizeof(RlRayHit) && sizeof(RlPathResult) <= sizeof(RlRayHit),
+              "the path calls stage their records through a query context's buffers");
 struct DeviceQueries {
     std::mutex lock;
     std::vector<QueryCtx*> idle;
-    int per_cu[6] = {}; // resident workgroups per CU of each variant, for the dynamic LDS size last seen (0: not set up)
-    size_t dyn[6] = {};
+    // resident workgroups per CU of each variant, for the dynamic LDS size last seen (0: not set up); slots 0-5 the query kernel's,
+    // 6-11 the path kernel's
+    int per_cu[12] = {};
+    size_t dyn[12] = {};
 };
 DeviceQueries* queries_of(int device) {
     static DeviceQueries all[64];
@@ -367,6 +375,21 @@ void query_ctx_release(int device, QueryCtx* q) {
     d->idle.push_back(q);
 }
 
+// Resident workgroups per CU of the persistent kernel in `slot` (DeviceQueries) with `dyn` bytes of dynamic LDS.
+int resident_per_cu(int device, int slot, const void* kernel, size_t dyn, int* out) {
+    DeviceQueries* d = queries_of(device);
+    std::lock_guard<std::mutex> guard(d->lock);
+    if (d->per_cu[slot] == 0 || d->dyn[slot] != dyn) {
+        RL_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        int k = 1;
+        RL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, kernel, RL_TRACE_BLOCK, dyn));
+        d->per_cu[slot] = k < 1 ? 1 : k;
+        d->dyn[slot] = dyn;
+    }
+    *out = d->per_cu[slot];
+    return RL_OK;
+}
+
 // One launch of the query kernel on q's stream for rays [0, n) of device arrays (n > 0).
 int launch_query(const RlScene* scene, int fetch, int cu_count, QueryCtx* q, const RlRay* rays, RlRayHit* hits, uint32_t n) {
     const size_t scratch_bytes = (RL_TRACE_BLOCK / 64) * sizeof(RlWaveScratch) + ring_t_bytes(scene);
@@ -376,19 +399,9 @@ int launch_query(const RlScene* scene, int fetch, int cu_count, QueryCtx* q, con
     const int index = 2 * stage + (cyl ? 1 : 0);
     auto kernel = query_kernel_variant(stage, cyl);
     const size_t dyn = scratch_bytes + blob_bytes;
-    DeviceQueries* d = queries_of(scene->device);
     int per_cu = 0;
-    {
-        std::lock_guard<std::mutex> guard(d->lock);
-        if (d->per_cu[index] == 0 || d->dyn[index] != dyn) {
-            RL_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            int k = 1;
-            RL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, kernel, RL_TRACE_BLOCK, dyn));
-            d->per_cu[index] = k < 1 ? 1 : k;
-            d->dyn[index] = dyn;
-        }
-        per_cu = d->per_cu[index];
-    }
+    const int rc = resident_per_cu(scene->device, index, (const void*)kernel, dyn, &per_cu);
+    if (rc != RL_OK) return rc;
     uint64_t blocks = (uint64_t)cu_count * (uint64_t)per_cu;
     const uint64_t needed = ((uint64_t)n + RL_TRACE_BLOCK - 1) / RL_TRACE_BLOCK;
     if (blocks > needed) blocks = needed;
@@ -401,6 +414,105 @@ int query_check(const RlScene* scene, int fetch, const void* rays, uint32_t n_ra
     if (fetch != RL_FETCH_LDS && fetch != RL_FETCH_GLOBAL) return fail(RL_E_INVALID, "unknown fetch mode");
     if (n_rays > 0 && (!rays || !hits)) return fail(RL_E_INVALID, "null ray or hit buffer");
     if (!scene) return fail(RL_E_INVALID, "null scene");
+    return RL_OK;
+}
+
+// Both arrays of a _device call must be memory the scene's device can address: a pageable host pointer there would fault the
+// device.  Accepted: device memory of the scene's device, managed memory, and pinned host memory mapped at the same address.  (The
+// runtime reports pageable host memory as hipMemoryTypeUnregistered, or fails.)
+int device_buffers_check(const RlScene* scene, const void* a, const void* b, const char* what, const char* host_form) {
+    for (const void* p : {a, b}) {
+        if (!p) continue;
+        hipPointerAttribute_t attr;
+        std::memset(&attr, 0, sizeof attr);
+        if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+            (void)hipGetLastError();
+            attr.type = hipMemoryTypeUnregistered;
+        }
+        const bool ok = (attr.type == hipMemoryTypeDevice && attr.device == scene->device) || attr.type == hipMemoryTypeManaged ||
+                        (attr.type == hipMemoryTypeHost && attr.devicePointer == p);
+        if (!ok)
+            return fail(RL_E_INVALID, std::string(what) + ": a buffer is not device memory of the scene's device (host arrays: " + host_form + ")");
+    }
+    return RL_OK;
+}
+
+// ---- caller-supplied paths (rl_scene_camera_rays*, rl_scene_render_rays*, rl_paths.hip.h) -----------------------------------
+typedef void (*PathKernel)(const RlF4*, RlSceneLayout, const RlSpectralRay*, RlPathResult*, uint32_t, uint64_t, uint32_t, uint64_t, uint32_t,
+                           unsigned long long*);
+std::atomic<uint64_t> g_path_launches[6]; // rl_debug_path_launches: launches per instantiation since the library was loaded
+// Index = 2 * stage + cylinders, as the query kernel's.
+PathKernel path_kernel_variant(int stage, bool cyl) {
+    const int index = 2 * stage + (cyl ? 1 : 0);
+    g_path_launches[index].fetch_add(1, std::memory_order_relaxed);
+    static const PathKernel table[6] = {
+        rl_ray_paths_kernel<RL_STAGE_NONE, false>,   rl_ray_paths_kernel<RL_STAGE_NONE, true>, rl_ray_paths_kernel<RL_STAGE_TABLES, false>,
+        rl_ray_paths_kernel<RL_STAGE_TABLES, true>, rl_ray_paths_kernel<RL_STAGE_ALL, false>, rl_ray_paths_kernel<RL_STAGE_ALL, true>,
+    };
+    return table[index];
+}
+
+struct PathJob {
+    uint64_t seed;
+    uint32_t stream;
+    uint32_t max_segments; // resolved: 1 .. RL_PATH_MAX_SEGMENTS_CAP
+};
+
+// rays [0, n) of device arrays as paths first_path .. first_path + n - 1 (n > 0): one launch of the path kernel on q's stream,
+// behind the zeroing of its queue.
+int launch_paths(const RlScene* scene, int fetch, int cu_count, QueryCtx* q, const PathJob& job, uint64_t first_path,
+                 const RlSpectralRay* rays, RlPathResult* results, uint32_t n) {
+    if (!q->queue) RL_HIP(hipMalloc((void**)&q->queue, sizeof(unsigned long long)));
+    const size_t scratch_bytes = (RL_TRACE_BLOCK / 64) * sizeof(RlWaveScratch) + ring_t_bytes(scene);
+    size_t blob_bytes = 0;
+    const int stage = stage_of(scene, fetch, scratch_bytes, &blob_bytes);
+    const bool cyl = scene->lay.prism_cylinders != 0u;
+    const int index = 2 * stage + (cyl ? 1 : 0);
+    auto kernel = path_kernel_variant(stage, cyl);
+    const size_t dyn = scratch_bytes + blob_bytes;
+    int per_cu = 0;
+    const int rc = resident_per_cu(scene->device, 6 + index, (const void*)kernel, dyn, &per_cu);
+    if (rc != RL_OK) return rc;
+    uint64_t blocks = (uint64_t)cu_count * (uint64_t)per_cu;
+    const uint64_t needed = ((uint64_t)n + RL_TRACE_BLOCK - 1) / RL_TRACE_BLOCK;
+    if (blocks > needed) blocks = needed;
+    RL_HIP(hipMemsetAsync(q->queue, 0, sizeof(unsigned long long), q->stream));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(RL_TRACE_BLOCK), dyn, q->stream, scene->blob, scene->lay, rays, results, n, job.seed,
+                       job.stream, first_path, job.max_segments, q->queue);
+    RL_HIP(hipGetLastError());
+    return RL_OK;
+}
+
+unsigned grid_for(uint64_t work_items, int cu_count);
+
+// The camera kernel for paths first_path .. first_path + n - 1 into device array `samples` (n > 0), on q's stream.
+int launch_camera(const RlScene* scene, int cu_count, QueryCtx* q, uint32_t width, uint32_t height, uint64_t seed, uint32_t stream,
+                  uint64_t first_path, RlCameraSample* samples, uint32_t n) {
+    const float aspect_ratio = (float)width / (float)height; // trace_unit.rs:73, as launch_trace has it
+    hipLaunchKernelGGL(rl_camera_rays_kernel, dim3(grid_for(n, cu_count)), dim3(RL_BLOCK), 0, q->stream, scene->blob, scene->lay, aspect_ratio,
+                       seed, stream, first_path, samples, n);
+    RL_HIP(hipGetLastError());
+    return RL_OK;
+}
+
+int paths_check(const RlScene* scene, int fetch, const void* rays, uint32_t n_rays, const void* results, uint64_t first_path,
+                uint32_t max_segments, PathJob* job) {
+    if (fetch != RL_FETCH_LDS && fetch != RL_FETCH_GLOBAL) return fail(RL_E_INVALID, "unknown fetch mode");
+    if (n_rays > 0 && (!rays || !results)) return fail(RL_E_INVALID, "null ray or result buffer");
+    int rc = query_check(scene, fetch, rays, n_rays, results);
+    if (rc != RL_OK) return rc;
+    if (max_segments > RL_PATH_MAX_SEGMENTS_CAP) return fail(RL_E_INVALID, "max_segments exceeds RL_PATH_MAX_SEGMENTS_CAP = 65536");
+    if (first_path + n_rays < first_path || first_path + n_rays == ~0ull) return fail(RL_E_INVALID, "path indices must stay below 2^64 - 1");
+    job->max_segments = max_segments == 0u ? RL_PATH_MAX_SEGMENTS : max_segments;
+    return RL_OK;
+}
+
+int camera_check(const RlScene* scene, uint32_t width, uint32_t height, uint64_t first_path, uint32_t n, const void* samples) {
+    if (!scene) return fail(RL_E_INVALID, "null scene");
+    if (n > 0 && !samples) return fail(RL_E_INVALID, "null sample buffer");
+    if (width == 0 || height == 0) return fail(RL_E_INVALID, "camera rays: zero image size");
+    if (check_image_size("camera rays", width, height) != RL_OK) return RL_E_INVALID;
+    if (first_path + n < first_path || first_path + n == ~0ull) return fail(RL_E_INVALID, "path indices must stay below 2^64 - 1");
     return RL_OK;
 }
 
@@ -430,6 +542,23 @@ int cu_count_of(int device, int* out) {
         std::lock_guard<std::mutex> guard(lock);
         cached[device] = *out;
     }
+    return RL_OK;
+}
+
+// Runs body(q, cu_count) on a query context of the scene's device and hands the context back once nothing of the call runs.
+template <class Body>
+int with_query_ctx(const RlScene* scene, Body body) {
+    int rc = use_device(scene->device);
+    if (rc != RL_OK) return rc;
+    int cus = 256;
+    if ((rc = cu_count_of(scene->device, &cus)) != RL_OK) return rc;
+    QueryCtx* q = nullptr;
+    if ((rc = query_ctx_acquire(scene->device, &q)) != RL_OK) return rc;
+    rc = body(q, cus);
+    const hipError_t e = hipStreamSynchronize(q->stream); // (nothing of this call may still run when its buffers are handed on)
+    query_ctx_release(scene->device, q);
+    if (rc != RL_OK) return rc;
+    RL_HIP(e);
     return RL_OK;
 }
 
@@ -651,20 +780,7 @@ int rl_scene_intersect_device(const RlScene* scene, int primitive_fetch, const R
     int rc = query_check(scene, primitive_fetch, device_rays, n_rays, device_hits);
     if (rc != RL_OK || n_rays == 0) return rc;
     if ((rc = use_device(scene->device)) != RL_OK) return rc;
-    // Both arrays must be memory the scene's device can address: a pageable host pointer here would fault the device.  Accepted:
-    // device memory of the scene's device, managed memory, and pinned host memory mapped at the same address.  (The runtime reports
-    // pageable host memory as hipMemoryTypeUnregistered, or fails.)
-    for (const void* p : {(const void*)device_rays, (const void*)device_hits}) {
-        hipPointerAttribute_t attr;
-        std::memset(&attr, 0, sizeof attr);
-        if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-            (void)hipGetLastError();
-            attr.type = hipMemoryTypeUnregistered;
-        }
-        const bool ok = (attr.type == hipMemoryTypeDevice && attr.device == scene->device) || attr.type == hipMemoryTypeManaged ||
-                        (attr.type == hipMemoryTypeHost && attr.devicePointer == p);
-        if (!ok) return fail(RL_E_INVALID, "rl_scene_intersect_device: a buffer is not device memory of the scene's device (host arrays: rl_scene_intersect)");
-    }
+    if ((rc = device_buffers_check(scene, device_rays, device_hits, "rl_scene_intersect_device", "rl_scene_intersect")) != RL_OK) return rc;
     int cus = 256;
     if ((rc = cu_count_of(scene->device, &cus)) != RL_OK) return rc;
     QueryCtx* q = nullptr;
@@ -675,6 +791,71 @@ int rl_scene_intersect_device(const RlScene* scene, int primitive_fetch, const R
     if (rc != RL_OK) return rc;
     RL_HIP(e);
     return RL_OK;
+}
+
+int rl_scene_camera_rays(const RlScene* scene, uint32_t width, uint32_t height, uint64_t seed, uint32_t stream, uint64_t first_path_index,
+                         uint32_t n, RlCameraSample* samples) {
+    const int rc = camera_check(scene, width, height, first_path_index, n, samples);
+    if (rc != RL_OK || n == 0) return rc;
+    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
+        if (!q->hits) RL_HIP(hipMalloc((void**)&q->hits, (size_t)RL_QUERY_CHUNK * sizeof(RlRayHit)));
+        RlCameraSample* staged = (RlCameraSample*)q->hits;
+        for (uint32_t first = 0; first < n;) {
+            const uint32_t k = n - first < RL_QUERY_CHUNK ? n - first : RL_QUERY_CHUNK;
+            const int r = launch_camera(scene, cus, q, width, height, seed, stream, first_path_index + first, staged, k);
+            if (r != RL_OK) return r;
+            RL_HIP(hipMemcpyAsync(samples + first, staged, (size_t)k * sizeof(RlCameraSample), hipMemcpyDeviceToHost, q->stream));
+            RL_HIP(hipStreamSynchronize(q->stream));
+            first += k;
+        }
+        return RL_OK;
+    });
+}
+
+int rl_scene_camera_rays_device(const RlScene* scene, uint32_t width, uint32_t height, uint64_t seed, uint32_t stream,
+                                uint64_t first_path_index, uint32_t n, RlCameraSample* device_samples) {
+    int rc = camera_check(scene, width, height, first_path_index, n, device_samples);
+    if (rc != RL_OK || n == 0) return rc;
+    if ((rc = use_device(scene->device)) != RL_OK) return rc;
+    if ((rc = device_buffers_check(scene, device_samples, nullptr, "rl_scene_camera_rays_device", "rl_scene_camera_rays")) != RL_OK) return rc;
+    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
+        return launch_camera(scene, cus, q, width, height, seed, stream, first_path_index, device_samples, n);
+    });
+}
+
+int rl_scene_render_rays(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, uint64_t first_path_index,
+                         uint32_t max_segments, const RlSpectralRay* rays, uint32_t n_rays, RlPathResult* results) {
+    PathJob job{seed, stream, 0u};
+    const int rc = paths_check(scene, primitive_fetch, rays, n_rays, results, first_path_index, max_segments, &job);
+    if (rc != RL_OK || n_rays == 0) return rc;
+    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
+        if (!q->rays) RL_HIP(hipMalloc((void**)&q->rays, (size_t)RL_QUERY_CHUNK * sizeof(RlRay)));
+        if (!q->hits) RL_HIP(hipMalloc((void**)&q->hits, (size_t)RL_QUERY_CHUNK * sizeof(RlRayHit)));
+        RlSpectralRay* staged_rays = (RlSpectralRay*)q->rays;
+        RlPathResult* staged_results = (RlPathResult*)q->hits;
+        for (uint32_t first = 0; first < n_rays;) {
+            const uint32_t k = n_rays - first < RL_QUERY_CHUNK ? n_rays - first : RL_QUERY_CHUNK;
+            RL_HIP(hipMemcpyAsync(staged_rays, rays + first, (size_t)k * sizeof(RlSpectralRay), hipMemcpyHostToDevice, q->stream));
+            const int r = launch_paths(scene, primitive_fetch, cus, q, job, first_path_index + first, staged_rays, staged_results, k);
+            if (r != RL_OK) return r;
+            RL_HIP(hipMemcpyAsync(results + first, staged_results, (size_t)k * sizeof(RlPathResult), hipMemcpyDeviceToHost, q->stream));
+            RL_HIP(hipStreamSynchronize(q->stream));
+            first += k;
+        }
+        return RL_OK;
+    });
+}
+
+int rl_scene_render_rays_device(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, uint64_t first_path_index,
+                                uint32_t max_segments, const RlSpectralRay* device_rays, uint32_t n_rays, RlPathResult* device_results) {
+    PathJob job{seed, stream, 0u};
+    int rc = paths_check(scene, primitive_fetch, device_rays, n_rays, device_results, first_path_index, max_segments, &job);
+    if (rc != RL_OK || n_rays == 0) return rc;
+    if ((rc = use_device(scene->device)) != RL_OK) return rc;
+    if ((rc = device_buffers_check(scene, device_rays, device_results, "rl_scene_render_rays_device", "rl_scene_render_rays")) != RL_OK) return rc;
+    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
+        return launch_paths(scene, primitive_fetch, cus, q, job, first_path_index, device_rays, device_results, n_rays);
+    });
 }
 
 // ---- TraceUnit ----------------------------------------------------------------------------------
@@ -1891,6 +2072,12 @@ int rl_debug_variant_launches(uint64_t* out) {
 int rl_debug_query_launches(uint64_t* out) {
     if (!out) return fail(RL_E_INVALID, "null output");
     for (int k = 0; k < 6; ++k) out[k] = g_query_launches[k].load(std::memory_order_relaxed);
+    return RL_OK;
+}
+
+int rl_debug_path_launches(uint64_t* out) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    for (int k = 0; k < 6; ++k) out[k] = g_path_launches[k].load(std::memory_order_relaxed);
     return RL_OK;
 }
 

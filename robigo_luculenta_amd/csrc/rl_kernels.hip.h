@@ -186,7 +186,9 @@ enum { RL_ST_ITER, RL_ST_SCAN_LANES, RL_ST_A_ROUNDS, RL_ST_A_LANES, RL_ST_B_ROUN
        RL_ST_ANY_DIFFUSE, RL_ST_S_ROUNDS, RL_ST_S_LANES, RL_ST_S_ITEMS, RL_ST_P_SLOW,
        // shader cycles (s_memtime) a wave spent in each region of the main loop, summed over waves
        RL_ST_T_TOTAL, RL_ST_T_REFILL, RL_ST_T_SMALL, RL_ST_T_DIRECT, RL_ST_T_CLUSTER, RL_ST_T_TAIL, RL_ST_T_PRISM, RL_ST_T_SHADE,
-       RL_ST_T_EMIT, RL_ST_T_A_ROUNDS, RL_ST_T_B_ROUNDS, RL_ST_T_P_ROUNDS, RL_ST_T_CAMERA, RL_ST_T_S_ROUNDS, RL_ST_COUNT };
+       RL_ST_T_EMIT, RL_ST_T_A_ROUNDS, RL_ST_T_B_ROUNDS, RL_ST_T_P_ROUNDS, RL_ST_T_CAMERA, RL_ST_T_S_ROUNDS,
+       RL_ST_X_LANES, RL_ST_X_ITERS, RL_ST_T_EXHAUSTIVE, // the path kernel's linear scans (rl_paths.hip.h)
+       RL_ST_COUNT };
 __device__ unsigned long long rl_stat_counters[48];
 // asm volatile + "memory": ordered against every LDS access, barrier and other timer read (the builtin may be
 // hoisted or sunk by the optimiser); pure ALU work may still drift across a read by a few instructions.

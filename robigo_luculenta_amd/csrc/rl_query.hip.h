@@ -81,6 +81,8 @@ __device__ __forceinline__ RlHit rl_query_exhaustive(const RlSceneView& sv, RlF3
 // the end get the idle bit (rl_scan_wave wants exec all ones).  The scan options are the plain launches' (128 registers, the
 // template arguments of the non-open rl_trace_kernel of the same stage): the body around the scan is far lighter than a path's.
 // Dynamic LDS: [scene blob (RL_STAGE_ALL) or its tables (RL_STAGE_TABLES)][ring T (a third level only)][RlWaveScratch x 16].
+// (rl_paths.hip.h: rl_stage_scene repeats this kernel's prologue statement for statement for the path kernel: change both together;
+// tests/test_path_query_abi.py compares the two.)
 template <int STAGE, bool CYL>
 __global__ __launch_bounds__(RL_TRACE_BLOCK, RL_TRACE_WPS) __attribute__((amdgpu_num_vgpr(RL_TRACE_VGPRS / 2))) void rl_query_kernel(
     const RlF4* __restrict__ scene, RlSceneLayout lay, const RlRay* __restrict__ rays, RlRayHit* __restrict__ hits, uint32_t n_rays) {
