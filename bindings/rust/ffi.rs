@@ -107,6 +107,15 @@ extern "C" {
     pub fn rl_plot_unit_device_buffer(u: *mut RlPlotUnit, device_xyz: *mut *mut f32) -> c_int;
     pub fn rl_plot_unit_download(u: *mut RlPlotUnit, out: *mut RlVector3) -> c_int;
     pub fn rl_plot_unit_upload(u: *mut RlPlotUnit, input: *const RlVector3) -> c_int;
+    // PlotUnit::plot for photons the caller holds, and render_ray for the caller's camera samples with the splat (a film).
+    pub fn rl_plot_unit_plot_photons(u: *mut RlPlotUnit, photons: *const RlMappedPhoton, n: u64) -> c_int;
+    pub fn rl_plot_unit_plot_photons_device(u: *mut RlPlotUnit, device_photons: *const RlMappedPhoton, n: u64) -> c_int;
+    pub fn rl_plot_unit_render_samples(u: *mut RlPlotUnit, scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32,
+                                       first_path_index: u64, max_segments: u32, samples: *const RlCameraSample, n: u32,
+                                       results: *mut RlPathResult) -> c_int;
+    pub fn rl_plot_unit_render_samples_device(u: *mut RlPlotUnit, scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32,
+                                              first_path_index: u64, max_segments: u32, device_samples: *const RlCameraSample, n: u32,
+                                              device_results: *mut RlPathResult) -> c_int;
 
     pub fn rl_gather_unit_create(device: c_int, w: u32, h: u32, out: *mut *mut RlGatherUnit) -> c_int;
     pub fn rl_gather_unit_destroy(u: *mut RlGatherUnit) -> c_int;

@@ -361,6 +361,41 @@ int rl_plot_unit_download(RlPlotUnit* unit, RlVector3* out);
 /* Overwrites tristimulus_buffer from host memory (after everything queued into the unit): the host-staged form
  * of the exchange, for ranks that share a GPU, and the tests. */
 int rl_plot_unit_upload(RlPlotUnit* unit, const RlVector3* in);
+/* PlotUnit::plot(&mut self, &[MappedPhoton]) (plot_unit.rs:87-95) for photons the caller holds: for every photon with
+ * probability != 0, get_tristimulus(wavelength) * probability (cie1931.rs:20-48) is added to the four pixels of
+ * plot_pixel(x, y) (plot_unit.rs:56-84) with f32 atomics, onto what the buffer holds.  Photons are used as given: x, y outside
+ * the screen clamp to the border pixels as in the reference, a wavelength outside [375, 785) nm contributes zero, a negative
+ * probability subtracts, a non-finite probability or wavelength is plotted as the arithmetic gives (NaN or inf into at most four
+ * pixels of the image).
+ *   Non-finite position (a deviation from the reference).  A photon whose x or y is NaN or infinite is skipped: the reference's
+ *   `floor() as isize` of such a value is not something to match, and no input ever indexes outside the buffer.
+ * The host form takes any n and stages the photons through a device buffer in chunks of 2^20 records; the _device form takes a
+ * device pointer on the plot unit's device and refuses pageable host memory (as rl_scene_render_rays_device does).  n = 0 does
+ * nothing; a NULL unit, or NULL photons with n > 0, is RL_E_INVALID before any device work.
+ *
+ * rl_plot_unit_render_samples: rl_scene_render_rays with a film.  samples[i].ray is traced as path first_path_index + i under every
+ * rule of rl_scene_render_rays (RNG blocks, the exact scan for non-unit or non-finite segments, RL_PATH_END_INVALID for a non-finite
+ * wavelength, max_segments), and a path that ends with value != 0 is splatted at samples[i].x, .y with samples[i].ray.wavelength
+ * into `unit` by the arithmetic above, in the same kernel: no photon record is written.  The image size and aspect ratio are the
+ * plot unit's.  A sample whose x or y is not finite is traced, not splatted; reserved fields are ignored.  If `results` is non-NULL
+ * it receives exactly what rl_scene_render_rays writes for the same rays, bit for bit; if NULL nothing but the film is written.
+ * Argument checks, in this order, each RL_E_INVALID before any device work: NULL unit, NULL scene, unknown fetch mode, max_segments
+ * > RL_PATH_MAX_SEGMENTS_CAP, path indices that reach 2^64 - 1, NULL samples with n > 0.  `unit` and `scene` on different devices
+ * is RL_E_STATE.  n = 0 does nothing.  Host and _device forms as above (the _device form's results, if given, are device memory).
+ *
+ * Ordering, all four calls.  They first end a render begun into `unit` with rl_trace_unit_render_fused_begin, run after everything
+ * queued into the unit (plots, fused renders, clears, exchanges) and return when their splats are in the buffer, so a following
+ * rl_gather_unit_accumulate, rl_plot_unit_download, _reduce or _add sees them.  The render_samples forms order against open
+ * launches as rl_scene_render_rays does.  One user per plot unit at a time; several threads may render samples into different
+ * plot units on one scene at once. */
+int rl_plot_unit_plot_photons(RlPlotUnit* unit, const RlMappedPhoton* photons, uint64_t n);
+int rl_plot_unit_plot_photons_device(RlPlotUnit* unit, const RlMappedPhoton* device_photons, uint64_t n);
+int rl_plot_unit_render_samples(RlPlotUnit* unit, const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream,
+                                uint64_t first_path_index, uint32_t max_segments, const RlCameraSample* samples, uint32_t n,
+                                RlPathResult* results);
+int rl_plot_unit_render_samples_device(RlPlotUnit* unit, const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream,
+                                       uint64_t first_path_index, uint32_t max_segments, const RlCameraSample* device_samples,
+                                       uint32_t n, RlPathResult* device_results);
 
 /* ---- GatherUnit (gather_unit.rs:24-92) ----------------------------------------------------- */
 

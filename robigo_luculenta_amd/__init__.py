@@ -292,6 +292,42 @@ class PlotUnit(_Handle):
         xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(self.height * self.width, 3)
         check(lib.rl_plot_unit_upload(self._h, xyz.ctypes.data_as(C.c_void_p)))
 
+    def plot_photons(self, photons):
+        """PlotUnit::plot(&[MappedPhoton]) (plot_unit.rs:87-95) for an (n,) PHOTON_DTYPE array of the caller's
+        (rl_plot_unit_plot_photons): added onto the buffer, complete on return.  A photon whose x or y is not finite is skipped."""
+        photons = np.ascontiguousarray(photons, dtype=PHOTON_DTYPE)
+        check(lib.rl_plot_unit_plot_photons(self._h, photons.ctypes.data_as(C.c_void_p), len(photons)))
+
+    def plot_photons_device(self, photons):
+        """rl_plot_unit_plot_photons_device: `photons` is a device buffer on the unit's device with data_ptr() (e.g. a torch tensor);
+        as many PHOTON_DTYPE records as it holds whole are plotted."""
+        n = photons.numel() * photons.element_size() // PHOTON_DTYPE.itemsize
+        check(lib.rl_plot_unit_plot_photons_device(self._h, C.c_void_p(photons.data_ptr()), n))
+
+    def render_samples(self, scene, samples, seed, stream, first=0, fetch=FETCH_LDS, max_segments=0, results=True):
+        """Scene.render_rays with a film (rl_plot_unit_render_samples): samples[i]["ray"] of an (n,) CAMERA_SAMPLE_DTYPE array is
+        traced as path first + i of (seed, stream) and a path that ends with a value is splatted at samples[i]["x"], ["y"] into
+        this unit, complete on return.  Returns the (n,) PATH_RESULT_DTYPE array Scene.render_spectral_rays gives for the same
+        rays, or None with results=False (then only the film is written)."""
+        samples = np.ascontiguousarray(samples, dtype=CAMERA_SAMPLE_DTYPE)
+        out = np.empty(len(samples), dtype=PATH_RESULT_DTYPE) if results else None
+        check(lib.rl_plot_unit_render_samples(self._h, scene.handle, fetch, seed, stream, first, max_segments,
+                                              samples.ctypes.data_as(C.c_void_p), len(samples),
+                                              out.ctypes.data_as(C.c_void_p) if results else None))
+        return out
+
+    def render_samples_device(self, scene, samples, seed, stream, first=0, fetch=FETCH_LDS, max_segments=0, results=None):
+        """rl_plot_unit_render_samples_device: `samples` (and `results`, if given) are device buffers on the unit's device with
+        data_ptr() (e.g. torch tensors) holding n CAMERA_SAMPLE_DTYPE records and room for n PATH_RESULT_DTYPE records; n is taken
+        from the sizes in bytes."""
+        n_bytes = lambda t: t.numel() * t.element_size()
+        n = n_bytes(samples) // CAMERA_SAMPLE_DTYPE.itemsize
+        if n_bytes(samples) != n * CAMERA_SAMPLE_DTYPE.itemsize or (results is not None and n_bytes(results) < n * PATH_RESULT_DTYPE.itemsize):
+            raise ValueError("samples must hold whole 48-byte records and results room for as many 16-byte ones")
+        check(lib.rl_plot_unit_render_samples_device(self._h, scene.handle, fetch, seed, stream, first, max_segments,
+                                                     C.c_void_p(samples.data_ptr()), n,
+                                                     C.c_void_p(results.data_ptr()) if results is not None else None))
+
 
 class GatherUnit(_Handle):
     """gather_unit.rs:24-92 (resume is explicit: load())."""
@@ -503,6 +539,14 @@ def path_launches():
     indexed as query_launches()."""
     out = (C.c_uint64 * 6)()
     check(lib.rl_debug_path_launches(out))
+    return list(out)
+
+
+def film_launches():
+    """rl_debug_film_launches: launches per instantiation of the film path kernel (PlotUnit.render_samples*) since the library was
+    loaded, indexed as query_launches()."""
+    out = (C.c_uint64 * 6)()
+    check(lib.rl_debug_film_launches(out))
     return list(out)
 
 

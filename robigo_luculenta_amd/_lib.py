@@ -148,6 +148,10 @@ SIGNATURES = {
     "rl_plot_unit_device_buffer": (_i, [_vp, _pp]),
     "rl_plot_unit_download": (_i, [_vp, _vp]),
     "rl_plot_unit_upload": (_i, [_vp, _vp]),
+    "rl_plot_unit_plot_photons": (_i, [_vp, _vp, _u64]),
+    "rl_plot_unit_plot_photons_device": (_i, [_vp, _vp, _u64]),
+    "rl_plot_unit_render_samples": (_i, [_vp, _vp, _i, _u64, _u32, _u64, _u32, _vp, _u32, _vp]),
+    "rl_plot_unit_render_samples_device": (_i, [_vp, _vp, _i, _u64, _u32, _u64, _u32, _vp, _u32, _vp]),
     "rl_gather_unit_sync": (_i, [_vp]),
     "rl_gather_unit_create": (_i, [_i, _u32, _u32, _pp]),
     "rl_gather_unit_destroy": (_i, [_vp]),
@@ -175,6 +179,7 @@ DEBUG_SIGNATURES = {
     "rl_debug_variant_launches": (_i, [_vp]),
     "rl_debug_query_launches": (_i, [_vp]),
     "rl_debug_path_launches": (_i, [_vp]),
+    "rl_debug_film_launches": (_i, [_vp]),
     "rl_debug_prism_probe": (_i, [_vp, _u32, _vp, _u32, _vp]),
     "rl_debug_prism_count": (_i, [_vp, C.POINTER(_u32)]),
 }

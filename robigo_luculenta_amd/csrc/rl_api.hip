@@ -42,6 +42,7 @@
 #include "rl_kernels.hip.h"
 #include "rl_query.hip.h"
 #include "rl_paths.hip.h"
+#include "rl_film.hip.h"
 #include "rl_scene.h"
 
 namespace {
@@ -333,7 +334,7 @@ struct QueryCtx {
     hipStream_t stream = nullptr;
     RlRay* rays = nullptr;    // host path only (allocated on first use)
     RlRayHit* hits = nullptr;
-    unsigned long long* queue = nullptr; // path calls only (allocated on first use)
+    unsigned long long* queue = nullptr; // path and film calls only (allocated on first use): the counter of an RlFilmQueue
 };
 static_assert(sizeof(RlSpectralRay) == sizeof(RlRay) && sizeof(RlCameraSample) == sizeof(RlRayHit) && sizeof(RlPathResult) <= sizeof(RlRayHit),
               "the path calls stage their records through a query context's buffers");
@@ -341,9 +342,9 @@ struct DeviceQueries {
     std::mutex lock;
     std::vector<QueryCtx*> idle;
     // resident workgroups per CU of each variant, for the dynamic LDS size last seen (0: not set up); slots 0-5 the query kernel's,
-    // 6-11 the path kernel's
-    int per_cu[12] = {};
-    size_t dyn[12] = {};
+    // 6-11 the path kernel's, 12-17 the film path kernel's
+    int per_cu[18] = {};
+    size_t dyn[18] = {};
 };
 DeviceQueries* queries_of(int device) {
     static DeviceQueries all[64];
@@ -420,7 +421,7 @@ int query_check(const RlScene* scene, int fetch, const void* rays, uint32_t n_ra
 // Both arrays of a _device call must be memory the scene's device can address: a pageable host pointer there would fault the
 // device.  Accepted: device memory of the scene's device, managed memory, and pinned host memory mapped at the same address.  (The
 // runtime reports pageable host memory as hipMemoryTypeUnregistered, or fails.)
-int device_buffers_check(const RlScene* scene, const void* a, const void* b, const char* what, const char* host_form) {
+int device_buffers_check(int device, const char* owner, const void* a, const void* b, const char* what, const char* host_form) {
     for (const void* p : {a, b}) {
         if (!p) continue;
         hipPointerAttribute_t attr;
@@ -429,12 +430,15 @@ int device_buffers_check(const RlScene* scene, const void* a, const void* b, con
             (void)hipGetLastError();
             attr.type = hipMemoryTypeUnregistered;
         }
-        const bool ok = (attr.type == hipMemoryTypeDevice && attr.device == scene->device) || attr.type == hipMemoryTypeManaged ||
+        const bool ok = (attr.type == hipMemoryTypeDevice && attr.device == device) || attr.type == hipMemoryTypeManaged ||
                         (attr.type == hipMemoryTypeHost && attr.devicePointer == p);
         if (!ok)
-            return fail(RL_E_INVALID, std::string(what) + ": a buffer is not device memory of the scene's device (host arrays: " + host_form + ")");
+            return fail(RL_E_INVALID, std::string(what) + ": a buffer is not device memory of the " + owner + "'s device (host arrays: " + host_form + ")");
     }
     return RL_OK;
+}
+int device_buffers_check(const RlScene* scene, const void* a, const void* b, const char* what, const char* host_form) {
+    return device_buffers_check(scene->device, "scene", a, b, what, host_form);
 }
 
 // ---- caller-supplied paths (rl_scene_camera_rays*, rl_scene_render_rays*, rl_paths.hip.h) -----------------------------------
@@ -462,7 +466,7 @@ struct PathJob {
 // behind the zeroing of its queue.
 int launch_paths(const RlScene* scene, int fetch, int cu_count, QueryCtx* q, const PathJob& job, uint64_t first_path,
                  const RlSpectralRay* rays, RlPathResult* results, uint32_t n) {
-    if (!q->queue) RL_HIP(hipMalloc((void**)&q->queue, sizeof(unsigned long long)));
+    if (!q->queue) RL_HIP(hipMalloc((void**)&q->queue, sizeof(RlFilmQueue)));
     const size_t scratch_bytes = (RL_TRACE_BLOCK / 64) * sizeof(RlWaveScratch) + ring_t_bytes(scene);
     size_t blob_bytes = 0;
     const int stage = stage_of(scene, fetch, scratch_bytes, &blob_bytes);
@@ -1556,6 +1560,174 @@ int rl_plot_unit_download(RlPlotUnit* u, RlVector3* out) {
     return RL_OK;
 }
 
+// ---- film for caller-supplied photons and samples (rl_plot_unit_plot_photons*, rl_plot_unit_render_samples*, rl_film.hip.h) ----
+// Everything here is queued on the plot unit's own stream, whose tail is every write into the buffer so far, and the calls
+// return when that stream has drained.  The host forms borrow a query context for its staging buffers (and the film path kernel
+// its queue counter); the context's own stream stays idle.
+
+namespace {
+typedef void (*FilmKernel)(const RlF4*, RlSceneLayout, const RlCameraSample*, RlPathResult*, uint32_t, uint64_t, uint32_t, uint64_t, uint32_t,
+                           unsigned long long*);
+std::atomic<uint64_t> g_film_launches[6]; // rl_debug_film_launches: launches per instantiation since the library was loaded
+// Index = 2 * stage + cylinders, as the path kernel's.
+FilmKernel film_kernel_variant(int stage, bool cyl) {
+    const int index = 2 * stage + (cyl ? 1 : 0);
+    g_film_launches[index].fetch_add(1, std::memory_order_relaxed);
+    static const FilmKernel table[6] = {
+        rl_film_paths_kernel<RL_STAGE_NONE, false>,   rl_film_paths_kernel<RL_STAGE_NONE, true>, rl_film_paths_kernel<RL_STAGE_TABLES, false>,
+        rl_film_paths_kernel<RL_STAGE_TABLES, true>, rl_film_paths_kernel<RL_STAGE_ALL, false>, rl_film_paths_kernel<RL_STAGE_ALL, true>,
+    };
+    return table[index];
+}
+
+// samples [0, n) of device arrays as paths first_path .. first_path + n - 1 (n > 0), splatted into u: one launch of the film path
+// kernel on u's stream, behind the copy that zeroes the context's queue counter and writes the film's constants after it.
+// `results` may be null.
+int launch_film(RlPlotUnit* u, const RlScene* scene, int fetch, int cu_count, QueryCtx* q, const PathJob& job, uint64_t first_path,
+                const RlCameraSample* samples, RlPathResult* results, uint32_t n) {
+    if (!q->queue) RL_HIP(hipMalloc((void**)&q->queue, sizeof(RlFilmQueue)));
+    const size_t scratch_bytes = (RL_TRACE_BLOCK / 64) * sizeof(RlWaveScratch) + ring_t_bytes(scene);
+    size_t blob_bytes = 0;
+    const int stage = stage_of(scene, fetch, scratch_bytes, &blob_bytes);
+    const bool cyl = scene->lay.prism_cylinders != 0u;
+    const int index = 2 * stage + (cyl ? 1 : 0);
+    auto kernel = film_kernel_variant(stage, cyl);
+    const size_t dyn = scratch_bytes + blob_bytes;
+    int per_cu = 0;
+    const int rc = resident_per_cu(scene->device, 12 + index, (const void*)kernel, dyn, &per_cu);
+    if (rc != RL_OK) return rc;
+    uint64_t blocks = (uint64_t)cu_count * (uint64_t)per_cu;
+    const uint64_t needed = ((uint64_t)n + RL_TRACE_BLOCK - 1) / RL_TRACE_BLOCK;
+    if (blocks > needed) blocks = needed;
+    RlFilmQueue fq;
+    fq.next = 0;
+    fq.film.plot = u->xyz;
+    fq.film.width = u->width;
+    fq.film.height = u->height;
+    fq.film.wm1 = (float)(int)u->width - 1.0f;
+    fq.film.hm1 = (float)(int)u->height - 1.0f;
+    fq.film.aspect_ratio = (float)u->width / (float)u->height; // plot_unit.rs:48
+    fq.film.off_cie = scene->lay.off_cie;
+    // (from pageable memory: the copy has left `fq` when the call returns)
+    RL_HIP(hipMemcpyAsync(q->queue, &fq, sizeof fq, hipMemcpyHostToDevice, u->stream));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(RL_TRACE_BLOCK), dyn, u->stream, scene->blob, scene->lay, samples, results, n, job.seed,
+                       job.stream, first_path, job.max_segments, q->queue);
+    RL_HIP(hipGetLastError());
+    return RL_OK;
+}
+
+// The photon splat kernel for device array photons [0, n) (n > 0) on u's stream.
+int launch_film_photons(RlPlotUnit* u, int cu_count, const RlMappedPhoton* photons, uint64_t n) {
+    const float aspect = (float)u->width / (float)u->height; // plot_unit.rs:48
+    hipLaunchKernelGGL(rl_film_photons_kernel, dim3(grid_for(n, cu_count)), dim3(RL_BLOCK), 0, u->stream, photons, n, u->cie, u->width,
+                       u->height, aspect, u->xyz);
+    RL_HIP(hipGetLastError());
+    return RL_OK;
+}
+
+// Runs body(q, cu_count) on the plot unit's device with a query context borrowed, behind a render begun into the unit, and
+// returns when the unit's stream has drained (also after a failure: nothing of the call may still run when the context's
+// buffers are handed on).
+extern "C++" template <class Body>
+int with_film_ctx(RlPlotUnit* u, Body body) {
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    if ((rc = plot_settle(u)) != RL_OK) return rc; // a fused render begun into this buffer ends first
+    int cus = 256;
+    if ((rc = cu_count_of(u->device, &cus)) != RL_OK) return rc;
+    QueryCtx* q = nullptr;
+    if ((rc = query_ctx_acquire(u->device, &q)) != RL_OK) return rc;
+    rc = body(q, cus);
+    const hipError_t e = hipStreamSynchronize(u->stream);
+    query_ctx_release(u->device, q);
+    if (rc != RL_OK) return rc;
+    RL_HIP(e);
+    return RL_OK;
+}
+
+int samples_check(const RlPlotUnit* u, const RlScene* scene, int fetch, uint32_t max_segments, uint64_t first_path, const void* samples,
+                  uint32_t n, PathJob* job) {
+    if (!u) return fail(RL_E_INVALID, "null plot unit");
+    if (!scene) return fail(RL_E_INVALID, "null scene");
+    if (fetch != RL_FETCH_LDS && fetch != RL_FETCH_GLOBAL) return fail(RL_E_INVALID, "unknown fetch mode");
+    if (max_segments > RL_PATH_MAX_SEGMENTS_CAP) return fail(RL_E_INVALID, "max_segments exceeds RL_PATH_MAX_SEGMENTS_CAP = 65536");
+    if (first_path + n < first_path || first_path + n == ~0ull) return fail(RL_E_INVALID, "path indices must stay below 2^64 - 1");
+    if (n > 0 && !samples) return fail(RL_E_INVALID, "null sample buffer");
+    job->max_segments = max_segments == 0u ? RL_PATH_MAX_SEGMENTS : max_segments;
+    return RL_OK;
+}
+} // namespace
+
+int rl_plot_unit_plot_photons(RlPlotUnit* u, const RlMappedPhoton* photons, uint64_t n) {
+    if (!u) return fail(RL_E_INVALID, "null plot unit");
+    if (n > 0 && !photons) return fail(RL_E_INVALID, "null photon buffer");
+    if (n == 0) return RL_OK;
+    return with_film_ctx(u, [&](QueryCtx* q, int cus) -> int {
+        if (!q->rays) RL_HIP(hipMalloc((void**)&q->rays, (size_t)RL_QUERY_CHUNK * sizeof(RlRay)));
+        RlMappedPhoton* staged = (RlMappedPhoton*)q->rays;
+        for (uint64_t first = 0; first < n;) {
+            const uint64_t k = n - first < RL_QUERY_CHUNK ? n - first : RL_QUERY_CHUNK;
+            RL_HIP(hipMemcpyAsync(staged, photons + first, (size_t)k * sizeof(RlMappedPhoton), hipMemcpyHostToDevice, u->stream));
+            const int r = launch_film_photons(u, cus, staged, k);
+            if (r != RL_OK) return r;
+            RL_HIP(hipStreamSynchronize(u->stream)); // (the next chunk overwrites the staging buffer)
+            first += k;
+        }
+        return RL_OK;
+    });
+}
+
+int rl_plot_unit_plot_photons_device(RlPlotUnit* u, const RlMappedPhoton* device_photons, uint64_t n) {
+    if (!u) return fail(RL_E_INVALID, "null plot unit");
+    if (n > 0 && !device_photons) return fail(RL_E_INVALID, "null photon buffer");
+    if (n == 0) return RL_OK;
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    if ((rc = device_buffers_check(u->device, "plot unit", device_photons, nullptr, "rl_plot_unit_plot_photons_device", "rl_plot_unit_plot_photons")) != RL_OK)
+        return rc;
+    return with_film_ctx(u, [&](QueryCtx*, int cus) -> int { return launch_film_photons(u, cus, device_photons, n); });
+}
+
+int rl_plot_unit_render_samples(RlPlotUnit* u, const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream,
+                                uint64_t first_path_index, uint32_t max_segments, const RlCameraSample* samples, uint32_t n,
+                                RlPathResult* results) {
+    PathJob job{seed, stream, 0u};
+    const int rc = samples_check(u, scene, primitive_fetch, max_segments, first_path_index, samples, n, &job);
+    if (rc != RL_OK || n == 0) return rc;
+    if (scene->device != u->device) return fail(RL_E_STATE, "scene and plot unit live on different devices");
+    return with_film_ctx(u, [&](QueryCtx* q, int cus) -> int {
+        if (!q->hits) RL_HIP(hipMalloc((void**)&q->hits, (size_t)RL_QUERY_CHUNK * sizeof(RlRayHit)));
+        if (results && !q->rays) RL_HIP(hipMalloc((void**)&q->rays, (size_t)RL_QUERY_CHUNK * sizeof(RlRay)));
+        RlCameraSample* staged_samples = (RlCameraSample*)q->hits;
+        RlPathResult* staged_results = results ? (RlPathResult*)q->rays : nullptr;
+        for (uint32_t first = 0; first < n;) {
+            const uint32_t k = n - first < RL_QUERY_CHUNK ? n - first : RL_QUERY_CHUNK;
+            RL_HIP(hipMemcpyAsync(staged_samples, samples + first, (size_t)k * sizeof(RlCameraSample), hipMemcpyHostToDevice, u->stream));
+            const int r = launch_film(u, scene, primitive_fetch, cus, q, job, first_path_index + first, staged_samples, staged_results, k);
+            if (r != RL_OK) return r;
+            if (results) RL_HIP(hipMemcpyAsync(results + first, staged_results, (size_t)k * sizeof(RlPathResult), hipMemcpyDeviceToHost, u->stream));
+            RL_HIP(hipStreamSynchronize(u->stream));
+            first += k;
+        }
+        return RL_OK;
+    });
+}
+
+int rl_plot_unit_render_samples_device(RlPlotUnit* u, const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream,
+                                       uint64_t first_path_index, uint32_t max_segments, const RlCameraSample* device_samples,
+                                       uint32_t n, RlPathResult* device_results) {
+    PathJob job{seed, stream, 0u};
+    int rc = samples_check(u, scene, primitive_fetch, max_segments, first_path_index, device_samples, n, &job);
+    if (rc != RL_OK || n == 0) return rc;
+    if (scene->device != u->device) return fail(RL_E_STATE, "scene and plot unit live on different devices");
+    if ((rc = use_device(u->device)) != RL_OK) return rc;
+    if ((rc = device_buffers_check(u->device, "plot unit", device_samples, device_results, "rl_plot_unit_render_samples_device", "rl_plot_unit_render_samples")) != RL_OK)
+        return rc;
+    return with_film_ctx(u, [&](QueryCtx* q, int cus) -> int {
+        return launch_film(u, scene, primitive_fetch, cus, q, job, first_path_index, device_samples, device_results, n);
+    });
+}
+
 // ---- GatherUnit ---------------------------------------------------------------------------------
 
 int rl_gather_unit_create(int device, uint32_t width, uint32_t height, RlGatherUnit** out) {
@@ -2078,6 +2250,12 @@ int rl_debug_query_launches(uint64_t* out) {
 int rl_debug_path_launches(uint64_t* out) {
     if (!out) return fail(RL_E_INVALID, "null output");
     for (int k = 0; k < 6; ++k) out[k] = g_path_launches[k].load(std::memory_order_relaxed);
+    return RL_OK;
+}
+
+int rl_debug_film_launches(uint64_t* out) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    for (int k = 0; k < 6; ++k) out[k] = g_film_launches[k].load(std::memory_order_relaxed);
     return RL_OK;
 }
 
