@@ -34,6 +34,13 @@ pub const RL_PATH_END_LIMIT: u32 = 3;
 pub const RL_PATH_END_INVALID: u32 = 4;
 pub const RL_PATH_MAX_SEGMENTS: u32 = 4096;
 pub const RL_PATH_MAX_SEGMENTS_CAP: u32 = 65536;
+// one turn of render_ray's loop at a time on states the caller holds (rl_scene_begin_paths*, rl_scene_step_paths*)
+#[repr(C)] #[derive(Copy, Clone)] pub struct RlPathState {
+    pub origin: RlVector3, pub wavelength: f32, pub direction: RlVector3, pub intensity: f32, pub continue_chance: f32,
+    pub segments: u32, pub end: u32, pub value: f32, pub path_index: u64, pub object: u32, pub reserved: u32,
+} // 64 bytes
+pub const RL_PATH_LIVE: u32 = 0xffff_ffff;
+pub const RL_STEP_NO_ROULETTE: u32 = 1;
 
 pub const RL_MAX_PIXELS: usize = 2147483647;
 pub const RL_TASK_MAX_UNITS: usize = 256;
@@ -81,6 +88,14 @@ extern "C" {
     pub fn rl_scene_render_rays_device(scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32, first_path_index: u64,
                                        max_segments: u32, device_rays: *const RlSpectralRay, n_rays: u32,
                                        device_results: *mut RlPathResult) -> c_int;
+    pub fn rl_scene_begin_paths(scene: *const RlScene, first_path_index: u64, rays: *const RlSpectralRay, n: u32,
+                                states: *mut RlPathState) -> c_int;
+    pub fn rl_scene_begin_paths_device(scene: *const RlScene, first_path_index: u64, device_rays: *const RlSpectralRay, n: u32,
+                                       device_states: *mut RlPathState) -> c_int;
+    pub fn rl_scene_step_paths(scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32, flags: u32,
+                               states: *mut RlPathState, n: u32, hits: *mut RlRayHit) -> c_int;
+    pub fn rl_scene_step_paths_device(scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32, flags: u32,
+                                      device_states: *mut RlPathState, n: u32, device_hits: *mut RlRayHit) -> c_int;
 
     pub fn rl_trace_unit_create(device: c_int, id: u32, w: u32, h: u32, n_photons: u32, out: *mut *mut RlTraceUnit) -> c_int;
     pub fn rl_trace_unit_destroy(u: *mut RlTraceUnit) -> c_int;

@@ -266,6 +266,71 @@ int rl_scene_render_rays_device(const RlScene* scene, int primitive_fetch, uint6
                                 uint64_t first_path_index, uint32_t max_segments, const RlSpectralRay* device_rays,
                                 uint32_t n_rays, RlPathResult* device_results);
 
+/* ---- one turn of render_ray's loop at a time: path states the caller holds ------------------- */
+
+#define RL_PATH_LIVE 0xffffffffu /* RlPathState::end of a path that has not ended */
+#define RL_STEP_NO_ROULETTE 1u   /* rl_scene_step_paths flags: the roulette's outcome is ignored */
+
+/* Everything TraceUnit::render_ray carries from one turn of its loop to the next (trace_unit.rs:81-132), plus how the path
+ * ended.  Frozen: 16 words. */
+typedef struct RlPathState {
+    RlVector3 origin;       /* the next segment's ray, as RlSpectralRay */
+    float wavelength;       /* nm */
+    RlVector3 direction;    /* used as given, not normalised */
+    float intensity;        /* trace_unit.rs:88 */
+    float continue_chance;  /* trace_unit.rs:84 */
+    uint32_t segments;      /* Scene::intersect calls made so far; the next bounce draws RNG block 2 + segments */
+    uint32_t end;           /* RL_PATH_LIVE, or an enum RlPathEnd value */
+    float value;            /* RlPathResult::value once the path has ended, 0 while it is live */
+    uint64_t path_index;    /* the RNG path of this state: it travels with the record */
+    uint32_t object;        /* the emitter the path ended on, else RL_OBJECT_NONE */
+    uint32_t reserved;      /* written 0 */
+} RlPathState;              /* 64 bytes */
+
+/* A wavefront form of rl_scene_render_rays: the path state lives in the caller's buffer, and every call makes one segment, so
+ * that the caller can act between segments (end paths by a rule of their own, record vertices, cast shadow rays from a vertex
+ * with rl_scene_intersect, re-weight or re-aim paths).
+ *
+ * rl_scene_begin_paths: states[i] is rays[i] as path first_path_index + i before its first segment: intensity 1, continue
+ * chance 1, segments 0, value 0, object RL_OBJECT_NONE, end RL_PATH_LIVE.  A ray with a NaN or infinite wavelength gets end
+ * RL_PATH_END_INVALID (rl_scene_render_rays' rule) and is never stepped.
+ *
+ * rl_scene_step_paths: every state with end == RL_PATH_LIVE makes exactly one segment, in place: Scene::intersect for the
+ * state's ray (by the exact linear scan where rl_scene_render_rays takes it, decided per segment), segments += 1, then the
+ * rest of the loop body as path path_index of stream `stream` under `seed`.
+ *   The Void: end = RL_PATH_END_VOID.  An emitter: end = RL_PATH_END_EMITTER, value = intensity * get_intensity(wavelength),
+ *   object = the emitter.  In both cases the ray, intensity and continue chance stay as they were.
+ *   Any other hit: origin (with the 1e-5 offset), direction, intensity and continue chance (* 0.96) become what render_ray makes
+ *   of them; if the roulette ends the path, end = RL_PATH_END_ROULETTE.
+ *   A state that is not live is not written: every byte of the record stays as it is.
+ *   hits may be NULL.  Otherwise hits[i] of every stepped state is, bit for bit, what rl_scene_intersect returns for that
+ *   segment's ray with t_max = INFINITY; hits[i] of a state that was not stepped is left as it is.
+ *   flags: 0 or RL_STEP_NO_ROULETTE.  With the flag the roulette's outcome is ignored and the state stays live; it is otherwise
+ *   identical, including continue_chance * 0.96, so a caller who applies the reference's comparison themselves
+ *   (`unit(word 2 of block 2 + segments - 1) * 0.85 > continue_chance * (1 - exp(intensity * -20))`) gets the reference's path.
+ *   There is no segment limit: the caller's loop is the limit.
+ * Identity.  For any scene, seed, stream, rays and first index: rl_scene_begin_paths, then rl_scene_step_paths with flags 0
+ *   repeated until no state is live -- with or without the caller compacting or reordering the states between steps -- leaves
+ *   {value, segments, object, end} of each state equal, bit for bit, to rl_scene_render_rays' RlPathResult for that ray, for
+ *   every path that rl_scene_render_rays ends before its max_segments.
+ * Determinism.  A stepped state depends only on the scene, seed, stream, flags and the state itself: not on its position in
+ *   the batch, on how a batch is split, on primitive_fetch or the kernel variant, or on other callers.
+ * The four calls work as rl_scene_render_rays* do: n == 0 does nothing; the arguments are checked in this order, each
+ * failure RL_E_INVALID with a message before any device work: an unknown fetch mode, an unknown flag bit, NULL rays or states
+ * with n > 0, a NULL scene, path indices that reach 2^64 - 1 (rl_scene_begin_paths).  The host forms stage the records through
+ * device buffers in chunks of 2^20; the _device forms take device pointers on the scene's device (states 16-byte aligned) and
+ * refuse pageable host memory.  All of them return when the states and hits are written, are safe from several host threads
+ * at once on one scene (on different states), and order against renders as rl_scene_intersect does: a call waits for an open
+ * launch to drain, so a call between rl_trace_unit_render_begin and _end completes and does not disturb the render. */
+int rl_scene_begin_paths(const RlScene* scene, uint64_t first_path_index, const RlSpectralRay* rays, uint32_t n,
+                         RlPathState* states);
+int rl_scene_begin_paths_device(const RlScene* scene, uint64_t first_path_index, const RlSpectralRay* device_rays, uint32_t n,
+                                RlPathState* device_states);
+int rl_scene_step_paths(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, uint32_t flags,
+                        RlPathState* states, uint32_t n, RlRayHit* hits);
+int rl_scene_step_paths_device(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, uint32_t flags,
+                               RlPathState* device_states, uint32_t n, RlRayHit* device_hits);
+
 /* Largest image the units and rl_app_run accept: width * height <= RL_MAX_PIXELS = 2^31 - 1.  The kernels index
  * pixels in 32 bits: the splat's `py * width + px` is an int, the tonemap's pixel count and grid-stride index are
  * uint32_t.  rl_trace_unit_create, rl_plot_unit_create, rl_gather_unit_create, rl_tonemap_unit_create and rl_app_run

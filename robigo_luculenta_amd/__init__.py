@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (RlAppConfig, RlAppStats, RlCameraDesc, RlCameraSample, RlError, RlIntersection, RlMappedPhoton, RlObjectDesc, RlPathResult,
-                   RlRay, RlRayHit, RlSceneDesc, RlSpectralRay, RlTask, RlVector3, check, lib, RL_OBJECT_NONE, RL_PATH_END_EMITTER,
+                   RlPathState, RL_PATH_LIVE, RL_STEP_NO_ROULETTE, RlRay, RlRayHit, RlSceneDesc, RlSpectralRay, RlTask, RlVector3, check, lib, RL_OBJECT_NONE, RL_PATH_END_EMITTER,
                    RL_PATH_END_INVALID, RL_PATH_END_LIMIT, RL_PATH_END_ROULETTE, RL_PATH_END_VOID, RL_PATH_MAX_SEGMENTS,
                    RL_PATH_MAX_SEGMENTS_CAP, RL_TASK_MAX_UNITS)
 
@@ -24,6 +24,10 @@ HIT_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("tangent", 
 SPECTRAL_RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("wavelength", "<f4"), ("direction", "<f4", 3), ("reserved", "<u4")])
 CAMERA_SAMPLE_DTYPE = np.dtype([("ray", SPECTRAL_RAY_DTYPE), ("x", "<f4"), ("y", "<f4"), ("reserved0", "<u4"), ("reserved1", "<u4")])
 PATH_RESULT_DTYPE = np.dtype([("value", "<f4"), ("segments", "<u4"), ("object", "<u4"), ("end", "<u4")])
+# Scene.begin_paths / step_paths records: RlPathState (64 bytes)
+PATH_STATE_DTYPE = np.dtype([("origin", "<f4", 3), ("wavelength", "<f4"), ("direction", "<f4", 3), ("intensity", "<f4"),
+                             ("continue_chance", "<f4"), ("segments", "<u4"), ("end", "<u4"), ("value", "<f4"), ("path_index", "<u8"),
+                             ("object", "<u4"), ("reserved", "<u4")])
 NUMBER_OF_PHOTONS = 1024 * 512  # trace_unit.rs:67
 
 SCENE_DEMO, SCENE_GLASS_STRESS = 0, 1
@@ -190,6 +194,47 @@ class Scene(_Handle):
             raise ValueError("rays must hold whole 32-byte records and results room for as many 16-byte ones")
         check(lib.rl_scene_render_rays_device(self._h, fetch, seed, stream, first, max_segments, C.c_void_p(rays.data_ptr()), n,
                                               C.c_void_p(results.data_ptr())))
+
+    def begin_paths(self, rays, first=0):
+        """rl_scene_begin_paths: an (n,) SPECTRAL_RAY_DTYPE array as the (n,) PATH_STATE_DTYPE states of paths first .. first + n - 1
+        before their first segment (end RL_PATH_LIVE; RL_PATH_END_INVALID for a wavelength that is not finite)."""
+        rays = np.ascontiguousarray(rays, dtype=SPECTRAL_RAY_DTYPE)
+        states = np.empty(len(rays), dtype=PATH_STATE_DTYPE)
+        check(lib.rl_scene_begin_paths(self._h, first, rays.ctypes.data_as(C.c_void_p), len(rays), states.ctypes.data_as(C.c_void_p)))
+        return states
+
+    def begin_paths_device(self, rays, states, first=0):
+        """rl_scene_begin_paths_device: `rays` and `states` are device buffers on the scene's device with data_ptr() (e.g. torch
+        tensors) holding n SPECTRAL_RAY_DTYPE records and room for n PATH_STATE_DTYPE records; n is taken from the sizes in bytes."""
+        n_bytes = lambda t: t.numel() * t.element_size()
+        n = n_bytes(rays) // SPECTRAL_RAY_DTYPE.itemsize
+        if n_bytes(rays) != n * SPECTRAL_RAY_DTYPE.itemsize or n_bytes(states) < n * PATH_STATE_DTYPE.itemsize:
+            raise ValueError("rays must hold whole 32-byte records and states room for as many 64-byte ones")
+        check(lib.rl_scene_begin_paths_device(self._h, first, C.c_void_p(rays.data_ptr()), n, C.c_void_p(states.data_ptr())))
+
+    def step_paths(self, states, seed, stream, fetch=FETCH_LDS, flags=0, hits=None):
+        """rl_scene_step_paths: one segment for every live state of an (n,) PATH_STATE_DTYPE array, in place (the array must be
+        contiguous).  hits: None, or an (n,) HIT_DTYPE array that receives the segment's hit of every stepped state.  flags: 0 or
+        RL_STEP_NO_ROULETTE.  Returns `states`."""
+        if states.dtype != PATH_STATE_DTYPE or not states.flags.c_contiguous or not states.flags.writeable:
+            raise ValueError("states must be a contiguous, writeable PATH_STATE_DTYPE array")
+        hp = None
+        if hits is not None:
+            if hits.dtype != HIT_DTYPE or not hits.flags.c_contiguous or len(hits) < len(states):
+                raise ValueError("hits must be a contiguous HIT_DTYPE array with room for every state")
+            hp = hits.ctypes.data_as(C.c_void_p)
+        check(lib.rl_scene_step_paths(self._h, fetch, seed, stream, flags, states.ctypes.data_as(C.c_void_p), len(states), hp))
+        return states
+
+    def step_paths_device(self, states, seed, stream, fetch=FETCH_LDS, flags=0, hits=None):
+        """rl_scene_step_paths_device: `states` is a device buffer on the scene's device with data_ptr() (e.g. a torch tensor)
+        holding n PATH_STATE_DTYPE records, stepped in place; `hits` None or a device buffer with room for n HIT_DTYPE records."""
+        n_bytes = lambda t: t.numel() * t.element_size()
+        n = n_bytes(states) // PATH_STATE_DTYPE.itemsize
+        if n_bytes(states) != n * PATH_STATE_DTYPE.itemsize or (hits is not None and n_bytes(hits) < n * HIT_DTYPE.itemsize):
+            raise ValueError("states must hold whole 64-byte records and hits room for as many 48-byte ones")
+        check(lib.rl_scene_step_paths_device(self._h, fetch, seed, stream, flags, C.c_void_p(states.data_ptr()), n,
+                                             C.c_void_p(hits.data_ptr()) if hits is not None else None))
 
 
 class TraceUnit(_Handle):
@@ -547,6 +592,14 @@ def film_launches():
     loaded, indexed as query_launches()."""
     out = (C.c_uint64 * 6)()
     check(lib.rl_debug_film_launches(out))
+    return list(out)
+
+
+def step_launches():
+    """rl_debug_step_launches: launches per instantiation of the step kernel (Scene.step_paths*) since the library was loaded,
+    indexed as query_launches()."""
+    out = (C.c_uint64 * 6)()
+    check(lib.rl_debug_step_launches(out))
     return list(out)
 
 

@@ -72,6 +72,14 @@ class RlPathResult(C.Structure):
 RL_PATH_END_VOID, RL_PATH_END_EMITTER, RL_PATH_END_ROULETTE, RL_PATH_END_LIMIT, RL_PATH_END_INVALID = range(5)
 RL_PATH_MAX_SEGMENTS = 4096
 RL_PATH_MAX_SEGMENTS_CAP = 65536
+RL_PATH_LIVE = 0xffffffff
+RL_STEP_NO_ROULETTE = 1
+
+
+class RlPathState(C.Structure):
+    _fields_ = [("origin", RlVector3), ("wavelength", C.c_float), ("direction", RlVector3), ("intensity", C.c_float),
+                ("continue_chance", C.c_float), ("segments", C.c_uint32), ("end", C.c_uint32), ("value", C.c_float),
+                ("path_index", C.c_uint64), ("object", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class RlTask(C.Structure):
@@ -115,6 +123,10 @@ SIGNATURES = {
     "rl_scene_camera_rays_device": (_i, [_vp, _u32, _u32, _u64, _u32, _u64, _u32, _vp]),
     "rl_scene_render_rays": (_i, [_vp, _i, _u64, _u32, _u64, _u32, _vp, _u32, _vp]),
     "rl_scene_render_rays_device": (_i, [_vp, _i, _u64, _u32, _u64, _u32, _vp, _u32, _vp]),
+    "rl_scene_begin_paths": (_i, [_vp, _u64, _vp, _u32, _vp]),
+    "rl_scene_begin_paths_device": (_i, [_vp, _u64, _vp, _u32, _vp]),
+    "rl_scene_step_paths": (_i, [_vp, _i, _u64, _u32, _u32, _vp, _u32, _vp]),
+    "rl_scene_step_paths_device": (_i, [_vp, _i, _u64, _u32, _u32, _vp, _u32, _vp]),
     "rl_trace_unit_create": (_i, [_i, _u32, _u32, _u32, _u32, _pp]),
     "rl_trace_unit_destroy": (_i, [_vp]),
     "rl_trace_unit_set_fetch": (_i, [_vp, _i]),
@@ -180,6 +192,7 @@ DEBUG_SIGNATURES = {
     "rl_debug_query_launches": (_i, [_vp]),
     "rl_debug_path_launches": (_i, [_vp]),
     "rl_debug_film_launches": (_i, [_vp]),
+    "rl_debug_step_launches": (_i, [_vp]),
     "rl_debug_prism_probe": (_i, [_vp, _u32, _vp, _u32, _vp]),
     "rl_debug_prism_count": (_i, [_vp, C.POINTER(_u32)]),
 }

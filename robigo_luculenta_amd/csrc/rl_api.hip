@@ -43,6 +43,7 @@
 #include "rl_query.hip.h"
 #include "rl_paths.hip.h"
 #include "rl_film.hip.h"
+#include "rl_step.hip.h"
 #include "rl_scene.h"
 
 namespace {
@@ -334,7 +335,8 @@ struct QueryCtx {
     hipStream_t stream = nullptr;
     RlRay* rays = nullptr;    // host path only (allocated on first use)
     RlRayHit* hits = nullptr;
-    unsigned long long* queue = nullptr; // path and film calls only (allocated on first use): the counter of an RlFilmQueue
+    unsigned long long* queue = nullptr; // path, film and step calls only (allocated on first use): the counter of an RlFilmQueue
+    RlPathState* states = nullptr;       // host path of the step calls only (allocated on first use)
 };
 static_assert(sizeof(RlSpectralRay) == sizeof(RlRay) && sizeof(RlCameraSample) == sizeof(RlRayHit) && sizeof(RlPathResult) <= sizeof(RlRayHit),
               "the path calls stage their records through a query context's buffers");
@@ -342,9 +344,9 @@ struct DeviceQueries {
     std::mutex lock;
     std::vector<QueryCtx*> idle;
     // resident workgroups per CU of each variant, for the dynamic LDS size last seen (0: not set up); slots 0-5 the query kernel's,
-    // 6-11 the path kernel's, 12-17 the film path kernel's
-    int per_cu[18] = {};
-    size_t dyn[18] = {};
+    // 6-11 the path kernel's, 12-17 the film path kernel's, 18-23 the step kernel's
+    int per_cu[24] = {};
+    size_t dyn[24] = {};
 };
 DeviceQueries* queries_of(int device) {
     static DeviceQueries all[64];
@@ -563,6 +565,72 @@ int with_query_ctx(const RlScene* scene, Body body) {
     query_ctx_release(scene->device, q);
     if (rc != RL_OK) return rc;
     RL_HIP(e);
+    return RL_OK;
+}
+
+// ---- caller-held path states (rl_scene_begin_paths*, rl_scene_step_paths*, rl_step.hip.h) -----------------------------------
+typedef void (*StepKernel)(const RlF4*, RlSceneLayout, RlPathState*, RlRayHit*, uint32_t, uint64_t, uint32_t, uint32_t, unsigned long long*);
+std::atomic<uint64_t> g_step_launches[6]; // rl_debug_step_launches: launches per instantiation since the library was loaded
+// Index = 2 * stage + cylinders, as the query kernel's.
+StepKernel step_kernel_variant(int stage, bool cyl) {
+    const int index = 2 * stage + (cyl ? 1 : 0);
+    g_step_launches[index].fetch_add(1, std::memory_order_relaxed);
+    static const StepKernel table[6] = {
+        rl_step_kernel<RL_STAGE_NONE, false>,   rl_step_kernel<RL_STAGE_NONE, true>, rl_step_kernel<RL_STAGE_TABLES, false>,
+        rl_step_kernel<RL_STAGE_TABLES, true>, rl_step_kernel<RL_STAGE_ALL, false>, rl_step_kernel<RL_STAGE_ALL, true>,
+    };
+    return table[index];
+}
+
+// One segment for the live states of device array states [0, n) (n > 0): one launch of the step kernel on q's stream, behind the
+// zeroing of its chunk counter.  `hits` may be null.
+int launch_step(const RlScene* scene, int fetch, int cu_count, QueryCtx* q, uint64_t seed, uint32_t stream, uint32_t flags,
+                RlPathState* states, RlRayHit* hits, uint32_t n) {
+    if (!q->queue) RL_HIP(hipMalloc((void**)&q->queue, sizeof(RlFilmQueue)));
+    const size_t scratch_bytes = (RL_TRACE_BLOCK / 64) * sizeof(RlWaveScratch) + ring_t_bytes(scene);
+    size_t blob_bytes = 0;
+    const int stage = stage_of(scene, fetch, scratch_bytes, &blob_bytes);
+    const bool cyl = scene->lay.prism_cylinders != 0u;
+    const int index = 2 * stage + (cyl ? 1 : 0);
+    auto kernel = step_kernel_variant(stage, cyl);
+    const size_t dyn = scratch_bytes + blob_bytes;
+    int per_cu = 0;
+    const int rc = resident_per_cu(scene->device, 18 + index, (const void*)kernel, dyn, &per_cu);
+    if (rc != RL_OK) return rc;
+    uint64_t blocks = (uint64_t)cu_count * (uint64_t)per_cu;
+    const uint64_t needed = ((uint64_t)n + RL_TRACE_BLOCK - 1) / RL_TRACE_BLOCK;
+    if (blocks > needed) blocks = needed;
+    RL_HIP(hipMemsetAsync(q->queue, 0, sizeof(unsigned long long), q->stream));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(RL_TRACE_BLOCK), dyn, q->stream, scene->blob, scene->lay, states, hits, n, seed, stream,
+                       flags, q->queue);
+    RL_HIP(hipGetLastError());
+    return RL_OK;
+}
+
+// The begin kernel for device arrays rays, states [0, n) (n > 0) as paths first_path .. first_path + n - 1, on q's stream.
+int launch_begin(int cu_count, QueryCtx* q, uint64_t first_path, const RlSpectralRay* rays, RlPathState* states, uint32_t n) {
+    hipLaunchKernelGGL(rl_begin_paths_kernel, dim3(grid_for(n, cu_count)), dim3(RL_BLOCK), 0, q->stream, rays, first_path, states, n);
+    RL_HIP(hipGetLastError());
+    return RL_OK;
+}
+
+int step_check(const RlScene* scene, int fetch, uint32_t flags, const void* states, uint32_t n) {
+    if (fetch != RL_FETCH_LDS && fetch != RL_FETCH_GLOBAL) return fail(RL_E_INVALID, "unknown fetch mode");
+    if (flags & ~(uint32_t)RL_STEP_NO_ROULETTE) return fail(RL_E_INVALID, "unknown step flag");
+    if (n > 0 && !states) return fail(RL_E_INVALID, "null state buffer");
+    if (!scene) return fail(RL_E_INVALID, "null scene");
+    return RL_OK;
+}
+
+int begin_check(const RlScene* scene, uint64_t first_path, const void* rays, uint32_t n, const void* states) {
+    if (n > 0 && (!rays || !states)) return fail(RL_E_INVALID, "null ray or state buffer");
+    if (!scene) return fail(RL_E_INVALID, "null scene");
+    if (first_path + n < first_path || first_path + n == ~0ull) return fail(RL_E_INVALID, "path indices must stay below 2^64 - 1");
+    return RL_OK;
+}
+
+int states_aligned(const void* states, const char* what) {
+    if (((uintptr_t)states & 15u) != 0) return fail(RL_E_INVALID, std::string(what) + ": the state buffer is not 16-byte aligned");
     return RL_OK;
 }
 
@@ -859,6 +927,73 @@ int rl_scene_render_rays_device(const RlScene* scene, int primitive_fetch, uint6
     if ((rc = device_buffers_check(scene, device_rays, device_results, "rl_scene_render_rays_device", "rl_scene_render_rays")) != RL_OK) return rc;
     return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
         return launch_paths(scene, primitive_fetch, cus, q, job, first_path_index, device_rays, device_results, n_rays);
+    });
+}
+
+int rl_scene_begin_paths(const RlScene* scene, uint64_t first_path_index, const RlSpectralRay* rays, uint32_t n, RlPathState* states) {
+    const int rc = begin_check(scene, first_path_index, rays, n, states);
+    if (rc != RL_OK || n == 0) return rc;
+    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
+        if (!q->rays) RL_HIP(hipMalloc((void**)&q->rays, (size_t)RL_QUERY_CHUNK * sizeof(RlRay)));
+        if (!q->states) RL_HIP(hipMalloc((void**)&q->states, (size_t)RL_QUERY_CHUNK * sizeof(RlPathState)));
+        RlSpectralRay* staged_rays = (RlSpectralRay*)q->rays;
+        for (uint32_t first = 0; first < n;) {
+            const uint32_t k = n - first < RL_QUERY_CHUNK ? n - first : RL_QUERY_CHUNK;
+            RL_HIP(hipMemcpyAsync(staged_rays, rays + first, (size_t)k * sizeof(RlSpectralRay), hipMemcpyHostToDevice, q->stream));
+            const int r = launch_begin(cus, q, first_path_index + first, staged_rays, q->states, k);
+            if (r != RL_OK) return r;
+            RL_HIP(hipMemcpyAsync(states + first, q->states, (size_t)k * sizeof(RlPathState), hipMemcpyDeviceToHost, q->stream));
+            RL_HIP(hipStreamSynchronize(q->stream));
+            first += k;
+        }
+        return RL_OK;
+    });
+}
+
+int rl_scene_begin_paths_device(const RlScene* scene, uint64_t first_path_index, const RlSpectralRay* device_rays, uint32_t n,
+                                RlPathState* device_states) {
+    int rc = begin_check(scene, first_path_index, device_rays, n, device_states);
+    if (rc != RL_OK || n == 0) return rc;
+    if ((rc = states_aligned(device_states, "rl_scene_begin_paths_device")) != RL_OK) return rc;
+    if ((rc = use_device(scene->device)) != RL_OK) return rc;
+    if ((rc = device_buffers_check(scene, device_rays, device_states, "rl_scene_begin_paths_device", "rl_scene_begin_paths")) != RL_OK) return rc;
+    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
+        return launch_begin(cus, q, first_path_index, device_rays, device_states, n);
+    });
+}
+
+int rl_scene_step_paths(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, uint32_t flags, RlPathState* states,
+                        uint32_t n, RlRayHit* hits) {
+    const int rc = step_check(scene, primitive_fetch, flags, states, n);
+    if (rc != RL_OK || n == 0) return rc;
+    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
+        if (!q->states) RL_HIP(hipMalloc((void**)&q->states, (size_t)RL_QUERY_CHUNK * sizeof(RlPathState)));
+        if (hits && !q->hits) RL_HIP(hipMalloc((void**)&q->hits, (size_t)RL_QUERY_CHUNK * sizeof(RlRayHit)));
+        for (uint32_t first = 0; first < n;) {
+            const uint32_t k = n - first < RL_QUERY_CHUNK ? n - first : RL_QUERY_CHUNK;
+            RL_HIP(hipMemcpyAsync(q->states, states + first, (size_t)k * sizeof(RlPathState), hipMemcpyHostToDevice, q->stream));
+            // (the caller's hits go in too: the slots of the states that are not stepped come back as they were)
+            if (hits) RL_HIP(hipMemcpyAsync(q->hits, hits + first, (size_t)k * sizeof(RlRayHit), hipMemcpyHostToDevice, q->stream));
+            const int r = launch_step(scene, primitive_fetch, cus, q, seed, stream, flags, q->states, hits ? q->hits : nullptr, k);
+            if (r != RL_OK) return r;
+            RL_HIP(hipMemcpyAsync(states + first, q->states, (size_t)k * sizeof(RlPathState), hipMemcpyDeviceToHost, q->stream));
+            if (hits) RL_HIP(hipMemcpyAsync(hits + first, q->hits, (size_t)k * sizeof(RlRayHit), hipMemcpyDeviceToHost, q->stream));
+            RL_HIP(hipStreamSynchronize(q->stream));
+            first += k;
+        }
+        return RL_OK;
+    });
+}
+
+int rl_scene_step_paths_device(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, uint32_t flags,
+                               RlPathState* device_states, uint32_t n, RlRayHit* device_hits) {
+    int rc = step_check(scene, primitive_fetch, flags, device_states, n);
+    if (rc != RL_OK || n == 0) return rc;
+    if ((rc = states_aligned(device_states, "rl_scene_step_paths_device")) != RL_OK) return rc;
+    if ((rc = use_device(scene->device)) != RL_OK) return rc;
+    if ((rc = device_buffers_check(scene, device_states, device_hits, "rl_scene_step_paths_device", "rl_scene_step_paths")) != RL_OK) return rc;
+    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
+        return launch_step(scene, primitive_fetch, cus, q, seed, stream, flags, device_states, device_hits, n);
     });
 }
 
@@ -2256,6 +2391,12 @@ int rl_debug_path_launches(uint64_t* out) {
 int rl_debug_film_launches(uint64_t* out) {
     if (!out) return fail(RL_E_INVALID, "null output");
     for (int k = 0; k < 6; ++k) out[k] = g_film_launches[k].load(std::memory_order_relaxed);
+    return RL_OK;
+}
+
+int rl_debug_step_launches(uint64_t* out) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    for (int k = 0; k < 6; ++k) out[k] = g_step_launches[k].load(std::memory_order_relaxed);
     return RL_OK;
 }
 

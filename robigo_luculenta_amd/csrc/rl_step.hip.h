@@ -1,0 +1,201 @@
+// rl_step.hip.h -- the kernels behind rl_scene_begin_paths* and rl_scene_step_paths*: one turn of TraceUnit::render_ray's loop
+// body (trace_unit.rs:92-126) for path states a caller holds between segments (RlPathState).  Included by rl_api.hip after
+// rl_paths.hip.h (rl_stage_scene) and rl_query.hip.h (rl_query_exhaustive).
+#pragma once
+
+// RlPathState as the kernels move it: four 16-byte words.
+//   q0 = origin.xyz, wavelength      q1 = direction.xyz, intensity
+//   q2 = continue_chance, segments, end, value      q3 = path_index (low, high), object, reserved
+static_assert(sizeof(RlPathState) == 64 && offsetof(RlPathState, wavelength) == 12 && offsetof(RlPathState, direction) == 16 &&
+                  offsetof(RlPathState, intensity) == 28 && offsetof(RlPathState, continue_chance) == 32 &&
+                  offsetof(RlPathState, segments) == 36 && offsetof(RlPathState, end) == 40 && offsetof(RlPathState, value) == 44 &&
+                  offsetof(RlPathState, path_index) == 48 && offsetof(RlPathState, object) == 56 && offsetof(RlPathState, reserved) == 60,
+              "RlPathState is frozen: 16 words");
+
+// rl_scene_begin_paths: rays[i] as the state of path first_path + i before its first segment (grid-stride, one ray per lane).  A
+// ray whose wavelength is NaN or infinite becomes a state that has ended (RL_PATH_END_INVALID), as rl_ray_paths_kernel ends it.
+__global__ __launch_bounds__(RL_BLOCK) void rl_begin_paths_kernel(const RlSpectralRay* __restrict__ rays, uint64_t first_path,
+                                                                  RlPathState* __restrict__ states, uint32_t n) {
+    // (64-bit: a 32-bit index plus the grid's stride wraps past 2^32 for n near 2^32, rl_camera_rays_kernel)
+    for (uint64_t i = (uint64_t)blockIdx.x * RL_BLOCK + threadIdx.x; i < n; i += (uint64_t)gridDim.x * RL_BLOCK) {
+        const RlF4* in = (const RlF4*)(rays + i);
+        const RlF4 r0 = in[0], r1 = in[1];
+        const uint64_t path = first_path + i;
+        RlF4 q1 = r1, q2, q3;
+        q1.w = 1.0f;           // intensity, trace_unit.rs:88
+        q2.x = 1.0f;           // continue chance, trace_unit.rs:84
+        q2.y = rl_u2f(0u);     // segments
+        q2.z = rl_u2f(fabsf(r0.w) < INFINITY ? RL_PATH_LIVE : (uint32_t)RL_PATH_END_INVALID);
+        q2.w = 0.0f;           // value
+        q3.x = rl_u2f((uint32_t)path);
+        q3.y = rl_u2f((uint32_t)(path >> 32));
+        q3.z = rl_u2f(RL_OBJECT_NONE);
+        q3.w = rl_u2f(0u);
+        RlF4* out = (RlF4*)(states + i);
+        out[0] = r0;
+        out[1] = q1;
+        out[2] = q2;
+        out[3] = q3;
+    }
+}
+
+// The kernel's `hits` argument where it is tested for null and used: opaque, so that the test is made there, on the pointer's two
+// scalar registers, instead of being kept as a loop invariant in two more across the persistent loop (rl_film_results).
+__device__ __forceinline__ RlRayHit* rl_step_hits(RlRayHit* hits) {
+    asm volatile("" : "+s"(hits));
+    return hits;
+}
+
+// One segment for every live state of states[0, n).  The work per call is one scan per record, so the kernel has the query kernel's
+// shape, not the path kernel's: persistent workgroups of RL_TRACE_BLOCK threads that stage the scene once (rl_stage_scene), every
+// wave taking chunks of 64 states from one counter (`queue`, zeroed on the call's stream; a slice of four chunks per atomic in large
+// calls) and scanning them together, no refill.
+// Lanes past the end or on a state that has ended idle through the scan as null rays, as the path kernel's free lanes do, and
+// write nothing.  Per chunk: the state's four 16-byte loads, the wave's scan with the path kernel's options and a full exec mask,
+// the exact linear scan for the segments the culls do not cover (decided per segment, as the path kernel decides it), rl_bounce
+// with RNG block 2 + segments, the emitter term inline under the lanes on a light, the hit record as the query kernel writes it
+// (when `hits` is not null), and the state's four stores.  p.ior is a function of the wavelength alone: it is evaluated under the
+// lanes whose hit is glass, which gives the bits the path kernel's per-path evaluation gives.
+// flags: RL_STEP_NO_ROULETTE leaves a state live whose bounce the roulette would have ended.
+template <int STAGE, bool CYL>
+__global__ __launch_bounds__(RL_TRACE_BLOCK, RL_TRACE_WPS) __attribute__((amdgpu_num_vgpr(RL_TRACE_VGPRS / 2))) void rl_step_kernel(
+    const RlF4* __restrict__ scene, RlSceneLayout lay, RlPathState* __restrict__ states, RlRayHit* __restrict__ hits, uint32_t n_states,
+    uint64_t seed, uint32_t stream, uint32_t flags, unsigned long long* __restrict__ queue) {
+    const RlStagedScene staged = rl_stage_scene<STAGE>(scene, lay);
+    const RlSceneView& sv = staged.sv;
+    const RlF4* base = staged.base;
+    const uint32_t tab0 = staged.tab0;
+    const uint32_t lane = threadIdx.x & 63u;
+    RlWaveScratch* ws = &staged.scratch[threadIdx.x >> 6];
+#ifdef RL_STATS
+    unsigned long long st[RL_ST_COUNT] = {}; // (the diagnostic build: reported to rl_stat_counters at the end, as the path kernel does)
+#endif
+    const uint32_t n_chunks = (uint32_t)(((uint64_t)n_states + 63u) / 64u); // (c * 64 + lane below stays under 2^32)
+    // The counter is in chunks.  Large calls (16 states or more per lane of the grid) take RL_CHUNK / 64 chunks per atomic, as the
+    // path kernel takes its ray indices: one atomic per chunk, all on one address, cost more than the chunk's scan.
+    const uint32_t slice = (uint64_t)n_states >= (uint64_t)gridDim.x * (RL_TRACE_BLOCK * 16ull) ? (uint32_t)(RL_CHUNK / 64ull) : 1u;
+    uint32_t chunk_next = 0, chunk_left = 0; // wave-uniform: this wave's slice of the counter
+    RL_T0(t_total);
+    for (;;) {
+        RL_T0(t_refill);
+        if (chunk_left == 0) {
+            unsigned long long taken = 0;
+            if (lane == 0) taken = atomicAdd(queue, (unsigned long long)slice);
+            chunk_next = __builtin_amdgcn_readfirstlane((uint32_t)taken); // (the counter stays below n_chunks + slice x waves of the grid)
+            chunk_left = slice;
+        }
+        const uint32_t c = chunk_next;
+        if (c >= n_chunks) break;
+        chunk_next += 1;
+        chunk_left -= 1;
+        const uint32_t i = c * 64u + lane;
+        RlF4* rec = (RlF4*)(states + i);
+        RlF4 q0 = {0.0f, 0.0f, 0.0f, 0.0f}, q1 = q0, q2 = q0, q3 = q0;
+        bool live = false;
+        if (i < n_states) {
+            q0 = rec[0];
+            q1 = rec[1];
+            q2 = rec[2];
+            q3 = rec[3];
+            live = rl_f2u(q2.z) == RL_PATH_LIVE;
+        }
+        RL_T1(RL_ST_T_REFILL, t_refill);
+        RL_STAT(RL_ST_ITER, 1);
+        RL_STAT(RL_ST_SCAN_LANES, __popcll(__builtin_amdgcn_ballot_w64(live)));
+        RlPath p;
+        p.origin = rl_f3(q0.x, q0.y, q0.z);
+        p.direction = rl_f3(q1.x, q1.y, q1.z);
+        p.wavelength = q0.w;
+        p.intensity = q1.w;
+        p.continue_chance = q2.x;
+        p.sx = p.sy = 0.0f;
+        p.ior = 1.0f;
+        p.bounce = rl_f2u(q2.y); // the bounce draws block 2 + segments
+
+        // ---- Scene::intersect for every lane's segment (rl_ray_paths_kernel) ----
+        const RlF3 o = p.origin, d = p.direction;
+        const float d2 = d.x * d.x + d.y * d.y + d.z * d.z;
+        const bool exhaustive = live && !(fabsf(d2 - 1.0f) <= 0x1p-20f && fabsf(o.x) < INFINITY && fabsf(o.y) < INFINITY && fabsf(o.z) < INFINITY);
+        const bool scanned = live && !exhaustive;
+        RlHit hit = rl_scan_wave<CYL, RL_LEAN_SPLIT, STAGE != RL_STAGE_NONE, STAGE != RL_STAGE_NONE && RL_W_S && RL_LEAN_HOIST, STAGE == RL_STAGE_ALL,
+                                 STAGE != RL_STAGE_NONE, STAGE != RL_STAGE_ALL>(sv, base + (lay.off_cull - tab0), CYL ? base + (lay.off_prism_cyl - tab0) : nullptr,
+                                                                                lay.group_gc, lay.small_ordered, lay.cull_cmax2, lay.n_cluster_groups,
+                                                                                lay.n_prism_groups, lay.n_cluster_supers, lay.super_g, staged.ring_t,
+                                                                                scanned ? o : rl_f3(0.0f, 0.0f, 0.0f), scanned ? d : rl_f3(0.0f, 0.0f, 0.0f),
+                                                                                scanned ? 0u : 0x80000000u, ws, lane RL_TACC_ARG);
+        RL_T0(t_exhaustive);
+        RL_STAT(RL_ST_X_LANES, __popcll(__builtin_amdgcn_ballot_w64(exhaustive)));
+        RL_STAT(RL_ST_X_ITERS, __builtin_amdgcn_ballot_w64(exhaustive) != 0);
+        if (exhaustive) hit = rl_query_exhaustive(sv, o, d);
+        RL_T1(RL_ST_T_EXHAUSTIVE, t_exhaustive);
+
+        // ---- the hit record, as rl_query_kernel writes it for t_max = INFINITY ----
+        RL_T0(t_camera);
+        if (live) {
+            if (RlRayHit* out_hits = rl_step_hits(hits)) {
+                RlRayHit out;
+                out.isect.position = out.isect.normal = out.isect.tangent = RlVector3{0.0f, 0.0f, 0.0f};
+                out.isect.distance = 0.0f;
+                out.object = RL_OBJECT_NONE;
+                out.reserved = 0u;
+                if (hit.obj != RL_HIT_NONE) {
+                    const uint32_t kinds = rl_f2u(sv.objects[hit.obj].w);
+                    const uint32_t surface_kind = rl_object_surface(kinds);
+                    const RlIsect is = rl_finish_hit(sv, o, d, hit, surface_kind, rl_object_group(kinds));
+                    const RlF3 axis = surface_kind == RL_SURFACE_SPHERE ? rl_cross(rl_f3(0.0f, 1.0f, 0.0f), is.normal) : rl_f3(0.0f, 0.0f, 0.0f);
+                    const RlF3 tangent = rl_normalise(axis);
+                    out.isect.position = RlVector3{is.position.x, is.position.y, is.position.z};
+                    out.isect.normal = RlVector3{is.normal.x, is.normal.y, is.normal.z};
+                    out.isect.tangent = RlVector3{tangent.x, tangent.y, tangent.z};
+                    out.isect.distance = hit.t;
+                    out.object = hit.obj;
+                }
+                out_hits[i] = out;
+            }
+        }
+        RL_T1(RL_ST_T_CAMERA, t_camera);
+
+        // ---- the rest of the loop body (trace_unit.rs:92-126) ----
+        RL_T0(t_shade);
+        int status = RL_PATH_CONTINUES;
+        uint32_t emitter = RL_OBJECT_NONE;
+        float value = 0.0f;
+        if (live) {
+            if (hit.obj != RL_HIT_NONE && rl_object_material(rl_f2u(sv.objects[hit.obj].w)) == RL_MATERIAL_SF10_GLASS)
+                p.ior = rl_sf10_ior(p.wavelength);
+            const uint64_t path = ((uint64_t)rl_f2u(q3.y) << 32) | rl_f2u(q3.x);
+            status = rl_bounce(sv, seed, stream, path, &p, hit, &value, &emitter);
+        }
+        RL_T1(RL_ST_T_SHADE, t_shade);
+        RL_T0(t_emit);
+        const bool on_light = status == RL_PATH_ENDED_ON_EMITTER;
+        RL_STAT(RL_ST_END_EMITTER, __popcll(__builtin_amdgcn_ballot_w64(on_light)));
+        if (on_light) value = rl_emission(sv, p.intensity, p.wavelength, emitter);
+        if (live) {
+            uint32_t end = RL_PATH_LIVE;
+            if (on_light) end = RL_PATH_END_EMITTER;
+            else if (hit.obj == RL_HIT_NONE) end = RL_PATH_END_VOID;
+            else if (status == RL_PATH_ENDED && !(flags & RL_STEP_NO_ROULETTE)) end = RL_PATH_END_ROULETTE;
+            q0.x = p.origin.x, q0.y = p.origin.y, q0.z = p.origin.z;
+            q1.x = p.direction.x, q1.y = p.direction.y, q1.z = p.direction.z;
+            q1.w = p.intensity;
+            q2.x = p.continue_chance;
+            q2.y = rl_u2f(rl_f2u(q2.y) + 1u);
+            q2.z = rl_u2f(end);
+            q2.w = on_light ? value : 0.0f;
+            q3.z = rl_u2f(on_light ? emitter : RL_OBJECT_NONE);
+            q3.w = rl_u2f(0u);
+            rec[0] = q0;
+            rec[1] = q1;
+            rec[2] = q2;
+            rec[3] = q3;
+        }
+        RL_T1(RL_ST_T_EMIT, t_emit);
+        rl_wave_sync(); // (the next chunk's scan rewrites the wave's scratch)
+    }
+    RL_T1(RL_ST_T_TOTAL, t_total);
+#ifdef RL_STATS
+    if (lane == 0)
+        for (int k = 0; k < RL_ST_COUNT; ++k) atomicAdd(&rl_stat_counters[k], st[k]);
+#endif
+}
