@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -41,8 +42,8 @@
 #include "../../include/robigo_luculenta_debug.h"
 #include "rl_kernels.hip.h"
 #include "rl_query.hip.h"
-#include "rl_paths.hip.h"
 #include "rl_film.hip.h"
+#include "rl_paths.hip.h"
 #include "rl_step.hip.h"
 #include "rl_scene.h"
 
@@ -239,13 +240,27 @@ int stage_of(const RlScene* scene, int fetch, size_t scratch_bytes, size_t* byte
     return RL_STAGE_NONE;
 }
 
+// The argument checks the calls share (one message each).
+int fetch_check(int fetch) {
+    if (fetch != RL_FETCH_LDS && fetch != RL_FETCH_GLOBAL) return fail(RL_E_INVALID, "unknown fetch mode");
+    return RL_OK;
+}
+int path_range_check(uint64_t first_path, uint64_t n) {
+    if (first_path + n < first_path || first_path + n == ~0ull) return fail(RL_E_INVALID, "path indices must stay below 2^64 - 1");
+    return RL_OK;
+}
+int max_segments_resolve(uint32_t max_segments, uint32_t* resolved) {
+    if (max_segments > RL_PATH_MAX_SEGMENTS_CAP) return fail(RL_E_INVALID, "max_segments exceeds RL_PATH_MAX_SEGMENTS_CAP = 65536");
+    *resolved = max_segments == 0u ? RL_PATH_MAX_SEGMENTS : max_segments;
+    return RL_OK;
+}
+
 // One launch of the trace kernel on u's stream: n_paths paths from first_path on, into `photons` (un-fused) or splatted
 // into plot_unit's buffer (fused).
 int launch_trace(RlTraceUnit* u, const RlScene* scene, RlMappedPhoton* photons, RlPlotUnit* plot_unit, uint64_t seed,
                  uint32_t stream_id, uint64_t first_path, uint64_t n_paths) {
     if (n_paths == 0) return RL_OK;
-    if (first_path + n_paths < first_path || first_path + n_paths == ~0ull)
-        return fail(RL_E_INVALID, "path indices must stay below 2^64 - 1");
+    if (path_range_check(first_path, n_paths) != RL_OK) return RL_E_INVALID;
     float* plot = plot_unit ? plot_unit->xyz : nullptr;
     if (scene->device != u->device) return fail(RL_E_STATE, "scene and trace unit live on different devices");
     RlTraceJob job;
@@ -311,42 +326,48 @@ int launch_trace(RlTraceUnit* u, const RlScene* scene, RlMappedPhoton* photons, 
     return RL_OK;
 }
 
-// ---- scene queries (rl_scene_intersect*, rl_query.hip.h) ----------------------------------------------------------
-typedef void (*QueryKernel)(const RlF4*, RlSceneLayout, const RlRay*, RlRayHit*, uint32_t);
-std::atomic<uint64_t> g_query_launches[6]; // rl_debug_query_launches: launches per instantiation since the library was loaded
-// Index = 2 * stage + cylinders.
-QueryKernel query_kernel_variant(int stage, bool cyl) {
-    const int index = 2 * stage + (cyl ? 1 : 0);
-    g_query_launches[index].fetch_add(1, std::memory_order_relaxed);
-    static const QueryKernel table[6] = {
-        rl_query_kernel<RL_STAGE_NONE, false>,   rl_query_kernel<RL_STAGE_NONE, true>, rl_query_kernel<RL_STAGE_TABLES, false>,
-        rl_query_kernel<RL_STAGE_TABLES, true>, rl_query_kernel<RL_STAGE_ALL, false>, rl_query_kernel<RL_STAGE_ALL, true>,
-    };
-    return table[index];
+// ---- the persistent ray kernels beside the trace kernel (rl_query.hip.h, rl_paths.hip.h, rl_step.hip.h) -------------------
+// A family is one kernel template's six instantiations, index = 2 * stage + cylinders, and the launches of each since the library
+// was loaded (rl_debug_{query,path,film,step}_launches).  P: the kernel's parameters behind the scene blob and its layout.
+template <class... P>
+struct KernelFamily {
+    void (*variants[6])(const RlF4*, RlSceneLayout, P...);
+    std::atomic<uint64_t> launches[6];
+};
+#define RL_VARIANTS(K) {{K<RL_STAGE_NONE, false>, K<RL_STAGE_NONE, true>, K<RL_STAGE_TABLES, false>, K<RL_STAGE_TABLES, true>, K<RL_STAGE_ALL, false>, K<RL_STAGE_ALL, true>}, {}}
+KernelFamily<const RlRay*, RlRayHit*, uint32_t> g_query_kernels = RL_VARIANTS(rl_query_kernel);
+KernelFamily<const RlSpectralRay*, RlPathResult*, uint32_t, uint64_t, uint32_t, uint64_t, uint32_t, unsigned long long*> g_path_kernels = RL_VARIANTS(rl_ray_paths_kernel);
+KernelFamily<const RlCameraSample*, RlPathResult*, uint32_t, uint64_t, uint32_t, uint64_t, uint32_t, unsigned long long*> g_film_kernels = RL_VARIANTS(rl_film_paths_kernel);
+KernelFamily<RlPathState*, RlRayHit*, uint32_t, uint64_t, uint32_t, uint32_t, unsigned long long*> g_step_kernels = RL_VARIANTS(rl_step_kernel);
+#undef RL_VARIANTS
+template <class... P>
+int family_launches(const KernelFamily<P...>& family, uint64_t* out) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    for (int k = 0; k < 6; ++k) out[k] = family.launches[k].load(std::memory_order_relaxed);
+    return RL_OK;
 }
 
-// What a query call runs on: a stream of its own and, for the host path, device buffers of RL_QUERY_CHUNK rays and hits.
+// What a query call runs on: a stream of its own and, for the host path, device buffers of RL_QUERY_CHUNK records.
 // Each device keeps the contexts of finished calls for the next ones, so concurrent callers never share a stream or a buffer
 // and a steady caller allocates nothing.
 #define RL_QUERY_CHUNK (1u << 20)
-// The path calls (rl_scene_camera_rays*, rl_scene_render_rays*) run on the same contexts: their 32-byte rays go in `rays`, their
-// 16-byte results and 48-byte camera samples in `hits`, and the path kernel's queue is `queue`.
+// The path, film and step calls run on the same contexts: 32-byte records (rays, spectral rays, photons; the film's results) go
+// through STAGING_RAYS, 48-byte ones (hits, camera samples; the path results) through STAGING_HITS, path states through STAGING_STATES.
+enum { STAGING_RAYS, STAGING_HITS, STAGING_STATES, STAGING_COUNT };
+const size_t staging_record_bytes[STAGING_COUNT] = {sizeof(RlRay), sizeof(RlRayHit), sizeof(RlPathState)};
 struct QueryCtx {
     hipStream_t stream = nullptr;
-    RlRay* rays = nullptr;    // host path only (allocated on first use)
-    RlRayHit* hits = nullptr;
+    void* staging[STAGING_COUNT] = {};   // host path only (allocated on first use, RL_QUERY_CHUNK records each)
     unsigned long long* queue = nullptr; // path, film and step calls only (allocated on first use): the counter of an RlFilmQueue
-    RlPathState* states = nullptr;       // host path of the step calls only (allocated on first use)
 };
-static_assert(sizeof(RlSpectralRay) == sizeof(RlRay) && sizeof(RlCameraSample) == sizeof(RlRayHit) && sizeof(RlPathResult) <= sizeof(RlRayHit),
-              "the path calls stage their records through a query context's buffers");
+static_assert(sizeof(RlSpectralRay) == sizeof(RlRay) && sizeof(RlMappedPhoton) <= sizeof(RlRay) && sizeof(RlCameraSample) == sizeof(RlRayHit) &&
+                  sizeof(RlPathResult) <= sizeof(RlRay),
+              "the path and film calls stage their records through a query context's buffers");
 struct DeviceQueries {
     std::mutex lock;
     std::vector<QueryCtx*> idle;
-    // resident workgroups per CU of each variant, for the dynamic LDS size last seen (0: not set up); slots 0-5 the query kernel's,
-    // 6-11 the path kernel's, 12-17 the film path kernel's, 18-23 the step kernel's
-    int per_cu[24] = {};
-    size_t dyn[24] = {};
+    // resident workgroups per CU of each persistent kernel launched so far, for the dynamic LDS size last seen: by the kernel's address
+    std::map<const void*, std::pair<size_t, int>> resident;
 };
 DeviceQueries* queries_of(int device) {
     static DeviceQueries all[64];
@@ -377,44 +398,84 @@ void query_ctx_release(int device, QueryCtx* q) {
     std::lock_guard<std::mutex> guard(d->lock);
     d->idle.push_back(q);
 }
-
-// Resident workgroups per CU of the persistent kernel in `slot` (DeviceQueries) with `dyn` bytes of dynamic LDS.
-int resident_per_cu(int device, int slot, const void* kernel, size_t dyn, int* out) {
-    DeviceQueries* d = queries_of(device);
-    std::lock_guard<std::mutex> guard(d->lock);
-    if (d->per_cu[slot] == 0 || d->dyn[slot] != dyn) {
-        RL_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        int k = 1;
-        RL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, kernel, RL_TRACE_BLOCK, dyn));
-        d->per_cu[slot] = k < 1 ? 1 : k;
-        d->dyn[slot] = dyn;
-    }
-    *out = d->per_cu[slot];
+// The context's queue counter (an RlFilmQueue: the film's constants sit behind it), allocated on first use.
+int query_ctx_queue(QueryCtx* q) {
+    if (!q->queue) RL_HIP(hipMalloc((void**)&q->queue, sizeof(RlFilmQueue)));
     return RL_OK;
 }
 
-// One launch of the query kernel on q's stream for rays [0, n) of device arrays (n > 0).
-int launch_query(const RlScene* scene, int fetch, int cu_count, QueryCtx* q, const RlRay* rays, RlRayHit* hits, uint32_t n) {
+// Resident workgroups per CU of a persistent kernel with `dyn` bytes of dynamic LDS.
+int resident_per_cu(int device, const void* kernel, size_t dyn, int* out) {
+    DeviceQueries* d = queries_of(device);
+    std::lock_guard<std::mutex> guard(d->lock);
+    std::pair<size_t, int>& slot = d->resident[kernel];
+    if (slot.second == 0 || slot.first != dyn) {
+        RL_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        int k = 1;
+        RL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, kernel, RL_TRACE_BLOCK, dyn));
+        slot = {dyn, k < 1 ? 1 : k};
+    }
+    *out = slot.second;
+    return RL_OK;
+}
+
+// One launch of a family's kernel on `stream` for n (> 0) records of device arrays: the instantiation for what the scene stages
+// and how its prisms are bound, as many workgroups as stay resident (or as the records need), args... behind the blob and the layout.
+// What a family's queue needs before the launch is the caller's.
+template <class... P, class... A>
+int launch_persistent(KernelFamily<P...>& family, const RlScene* scene, int fetch, int cu_count, hipStream_t stream, uint32_t n, A... args) {
     const size_t scratch_bytes = (RL_TRACE_BLOCK / 64) * sizeof(RlWaveScratch) + ring_t_bytes(scene);
     size_t blob_bytes = 0;
     const int stage = stage_of(scene, fetch, scratch_bytes, &blob_bytes);
-    const bool cyl = scene->lay.prism_cylinders != 0u;
-    const int index = 2 * stage + (cyl ? 1 : 0);
-    auto kernel = query_kernel_variant(stage, cyl);
+    const int index = 2 * stage + (scene->lay.prism_cylinders != 0u ? 1 : 0);
+    family.launches[index].fetch_add(1, std::memory_order_relaxed);
+    auto kernel = family.variants[index];
     const size_t dyn = scratch_bytes + blob_bytes;
     int per_cu = 0;
-    const int rc = resident_per_cu(scene->device, index, (const void*)kernel, dyn, &per_cu);
+    const int rc = resident_per_cu(scene->device, (const void*)kernel, dyn, &per_cu);
     if (rc != RL_OK) return rc;
     uint64_t blocks = (uint64_t)cu_count * (uint64_t)per_cu;
     const uint64_t needed = ((uint64_t)n + RL_TRACE_BLOCK - 1) / RL_TRACE_BLOCK;
     if (blocks > needed) blocks = needed;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(RL_TRACE_BLOCK), dyn, q->stream, scene->blob, scene->lay, rays, hits, n);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(RL_TRACE_BLOCK), dyn, stream, scene->blob, scene->lay, args...);
     RL_HIP(hipGetLastError());
     return RL_OK;
 }
 
+// One array of a host-staged call: the caller's records, which of the context's buffers they go through, and which way.
+struct Staged {
+    int slot;
+    void* host; // (null: the call does without this array)
+    size_t record_bytes;
+    bool in, out;
+};
+Staged staged_in(int slot, const void* host, size_t record_bytes) { return Staged{slot, const_cast<void*>(host), record_bytes, true, false}; }
+Staged staged_out(int slot, void* host, size_t record_bytes) { return Staged{slot, host, record_bytes, false, true}; }
+Staged staged_inout(int slot, void* host, size_t record_bytes) { return Staged{slot, host, record_bytes, true, true}; }
+// The host forms: records [0, n) in chunks of RL_QUERY_CHUNK through q's staging buffers (allocated here on first use) -- copy in,
+// launch(first, k) for records [first, first + k), copy out, synchronise (the next chunk overwrites the buffers).
+template <class N, class Launch>
+int staged_chunks(QueryCtx* q, hipStream_t stream, N n, std::initializer_list<Staged> arrays, Launch launch) {
+    for (const Staged& a : arrays)
+        if (a.host && !q->staging[a.slot]) RL_HIP(hipMalloc(&q->staging[a.slot], (size_t)RL_QUERY_CHUNK * staging_record_bytes[a.slot]));
+    for (N first = 0; first < n;) {
+        const N k = n - first < RL_QUERY_CHUNK ? n - first : (N)RL_QUERY_CHUNK;
+        for (const Staged& a : arrays)
+            if (a.host && a.in)
+                RL_HIP(hipMemcpyAsync(q->staging[a.slot], (const char*)a.host + (size_t)first * a.record_bytes, (size_t)k * a.record_bytes, hipMemcpyHostToDevice, stream));
+        const int r = launch(first, k);
+        if (r != RL_OK) return r;
+        for (const Staged& a : arrays)
+            if (a.host && a.out)
+                RL_HIP(hipMemcpyAsync((char*)a.host + (size_t)first * a.record_bytes, q->staging[a.slot], (size_t)k * a.record_bytes, hipMemcpyDeviceToHost, stream));
+        RL_HIP(hipStreamSynchronize(stream));
+        first += k;
+    }
+    return RL_OK;
+}
+
 int query_check(const RlScene* scene, int fetch, const void* rays, uint32_t n_rays, const void* hits) {
-    if (fetch != RL_FETCH_LDS && fetch != RL_FETCH_GLOBAL) return fail(RL_E_INVALID, "unknown fetch mode");
+    if (fetch_check(fetch) != RL_OK) return RL_E_INVALID;
     if (n_rays > 0 && (!rays || !hits)) return fail(RL_E_INVALID, "null ray or hit buffer");
     if (!scene) return fail(RL_E_INVALID, "null scene");
     return RL_OK;
@@ -444,20 +505,6 @@ int device_buffers_check(const RlScene* scene, const void* a, const void* b, con
 }
 
 // ---- caller-supplied paths (rl_scene_camera_rays*, rl_scene_render_rays*, rl_paths.hip.h) -----------------------------------
-typedef void (*PathKernel)(const RlF4*, RlSceneLayout, const RlSpectralRay*, RlPathResult*, uint32_t, uint64_t, uint32_t, uint64_t, uint32_t,
-                           unsigned long long*);
-std::atomic<uint64_t> g_path_launches[6]; // rl_debug_path_launches: launches per instantiation since the library was loaded
-// Index = 2 * stage + cylinders, as the query kernel's.
-PathKernel path_kernel_variant(int stage, bool cyl) {
-    const int index = 2 * stage + (cyl ? 1 : 0);
-    g_path_launches[index].fetch_add(1, std::memory_order_relaxed);
-    static const PathKernel table[6] = {
-        rl_ray_paths_kernel<RL_STAGE_NONE, false>,   rl_ray_paths_kernel<RL_STAGE_NONE, true>, rl_ray_paths_kernel<RL_STAGE_TABLES, false>,
-        rl_ray_paths_kernel<RL_STAGE_TABLES, true>, rl_ray_paths_kernel<RL_STAGE_ALL, false>, rl_ray_paths_kernel<RL_STAGE_ALL, true>,
-    };
-    return table[index];
-}
-
 struct PathJob {
     uint64_t seed;
     uint32_t stream;
@@ -468,25 +515,11 @@ struct PathJob {
 // behind the zeroing of its queue.
 int launch_paths(const RlScene* scene, int fetch, int cu_count, QueryCtx* q, const PathJob& job, uint64_t first_path,
                  const RlSpectralRay* rays, RlPathResult* results, uint32_t n) {
-    if (!q->queue) RL_HIP(hipMalloc((void**)&q->queue, sizeof(RlFilmQueue)));
-    const size_t scratch_bytes = (RL_TRACE_BLOCK / 64) * sizeof(RlWaveScratch) + ring_t_bytes(scene);
-    size_t blob_bytes = 0;
-    const int stage = stage_of(scene, fetch, scratch_bytes, &blob_bytes);
-    const bool cyl = scene->lay.prism_cylinders != 0u;
-    const int index = 2 * stage + (cyl ? 1 : 0);
-    auto kernel = path_kernel_variant(stage, cyl);
-    const size_t dyn = scratch_bytes + blob_bytes;
-    int per_cu = 0;
-    const int rc = resident_per_cu(scene->device, 6 + index, (const void*)kernel, dyn, &per_cu);
+    const int rc = query_ctx_queue(q);
     if (rc != RL_OK) return rc;
-    uint64_t blocks = (uint64_t)cu_count * (uint64_t)per_cu;
-    const uint64_t needed = ((uint64_t)n + RL_TRACE_BLOCK - 1) / RL_TRACE_BLOCK;
-    if (blocks > needed) blocks = needed;
     RL_HIP(hipMemsetAsync(q->queue, 0, sizeof(unsigned long long), q->stream));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(RL_TRACE_BLOCK), dyn, q->stream, scene->blob, scene->lay, rays, results, n, job.seed,
-                       job.stream, first_path, job.max_segments, q->queue);
-    RL_HIP(hipGetLastError());
-    return RL_OK;
+    return launch_persistent(g_path_kernels, scene, fetch, cu_count, q->stream, n, rays, results, n, job.seed, job.stream, first_path, job.max_segments,
+                             q->queue);
 }
 
 unsigned grid_for(uint64_t work_items, int cu_count);
@@ -503,14 +536,12 @@ int launch_camera(const RlScene* scene, int cu_count, QueryCtx* q, uint32_t widt
 
 int paths_check(const RlScene* scene, int fetch, const void* rays, uint32_t n_rays, const void* results, uint64_t first_path,
                 uint32_t max_segments, PathJob* job) {
-    if (fetch != RL_FETCH_LDS && fetch != RL_FETCH_GLOBAL) return fail(RL_E_INVALID, "unknown fetch mode");
+    if (fetch_check(fetch) != RL_OK) return RL_E_INVALID;
     if (n_rays > 0 && (!rays || !results)) return fail(RL_E_INVALID, "null ray or result buffer");
     int rc = query_check(scene, fetch, rays, n_rays, results);
     if (rc != RL_OK) return rc;
-    if (max_segments > RL_PATH_MAX_SEGMENTS_CAP) return fail(RL_E_INVALID, "max_segments exceeds RL_PATH_MAX_SEGMENTS_CAP = 65536");
-    if (first_path + n_rays < first_path || first_path + n_rays == ~0ull) return fail(RL_E_INVALID, "path indices must stay below 2^64 - 1");
-    job->max_segments = max_segments == 0u ? RL_PATH_MAX_SEGMENTS : max_segments;
-    return RL_OK;
+    if ((rc = max_segments_resolve(max_segments, &job->max_segments)) != RL_OK) return rc;
+    return path_range_check(first_path, n_rays);
 }
 
 int camera_check(const RlScene* scene, uint32_t width, uint32_t height, uint64_t first_path, uint32_t n, const void* samples) {
@@ -518,8 +549,7 @@ int camera_check(const RlScene* scene, uint32_t width, uint32_t height, uint64_t
     if (n > 0 && !samples) return fail(RL_E_INVALID, "null sample buffer");
     if (width == 0 || height == 0) return fail(RL_E_INVALID, "camera rays: zero image size");
     if (check_image_size("camera rays", width, height) != RL_OK) return RL_E_INVALID;
-    if (first_path + n < first_path || first_path + n == ~0ull) return fail(RL_E_INVALID, "path indices must stay below 2^64 - 1");
-    return RL_OK;
+    return path_range_check(first_path, n);
 }
 
 unsigned grid_for(uint64_t work_items, int cu_count) {
@@ -569,42 +599,14 @@ int with_query_ctx(const RlScene* scene, Body body) {
 }
 
 // ---- caller-held path states (rl_scene_begin_paths*, rl_scene_step_paths*, rl_step.hip.h) -----------------------------------
-typedef void (*StepKernel)(const RlF4*, RlSceneLayout, RlPathState*, RlRayHit*, uint32_t, uint64_t, uint32_t, uint32_t, unsigned long long*);
-std::atomic<uint64_t> g_step_launches[6]; // rl_debug_step_launches: launches per instantiation since the library was loaded
-// Index = 2 * stage + cylinders, as the query kernel's.
-StepKernel step_kernel_variant(int stage, bool cyl) {
-    const int index = 2 * stage + (cyl ? 1 : 0);
-    g_step_launches[index].fetch_add(1, std::memory_order_relaxed);
-    static const StepKernel table[6] = {
-        rl_step_kernel<RL_STAGE_NONE, false>,   rl_step_kernel<RL_STAGE_NONE, true>, rl_step_kernel<RL_STAGE_TABLES, false>,
-        rl_step_kernel<RL_STAGE_TABLES, true>, rl_step_kernel<RL_STAGE_ALL, false>, rl_step_kernel<RL_STAGE_ALL, true>,
-    };
-    return table[index];
-}
-
 // One segment for the live states of device array states [0, n) (n > 0): one launch of the step kernel on q's stream, behind the
 // zeroing of its chunk counter.  `hits` may be null.
 int launch_step(const RlScene* scene, int fetch, int cu_count, QueryCtx* q, uint64_t seed, uint32_t stream, uint32_t flags,
                 RlPathState* states, RlRayHit* hits, uint32_t n) {
-    if (!q->queue) RL_HIP(hipMalloc((void**)&q->queue, sizeof(RlFilmQueue)));
-    const size_t scratch_bytes = (RL_TRACE_BLOCK / 64) * sizeof(RlWaveScratch) + ring_t_bytes(scene);
-    size_t blob_bytes = 0;
-    const int stage = stage_of(scene, fetch, scratch_bytes, &blob_bytes);
-    const bool cyl = scene->lay.prism_cylinders != 0u;
-    const int index = 2 * stage + (cyl ? 1 : 0);
-    auto kernel = step_kernel_variant(stage, cyl);
-    const size_t dyn = scratch_bytes + blob_bytes;
-    int per_cu = 0;
-    const int rc = resident_per_cu(scene->device, 18 + index, (const void*)kernel, dyn, &per_cu);
+    const int rc = query_ctx_queue(q);
     if (rc != RL_OK) return rc;
-    uint64_t blocks = (uint64_t)cu_count * (uint64_t)per_cu;
-    const uint64_t needed = ((uint64_t)n + RL_TRACE_BLOCK - 1) / RL_TRACE_BLOCK;
-    if (blocks > needed) blocks = needed;
     RL_HIP(hipMemsetAsync(q->queue, 0, sizeof(unsigned long long), q->stream));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(RL_TRACE_BLOCK), dyn, q->stream, scene->blob, scene->lay, states, hits, n, seed, stream,
-                       flags, q->queue);
-    RL_HIP(hipGetLastError());
-    return RL_OK;
+    return launch_persistent(g_step_kernels, scene, fetch, cu_count, q->stream, n, states, hits, n, seed, stream, flags, q->queue);
 }
 
 // The begin kernel for device arrays rays, states [0, n) (n > 0) as paths first_path .. first_path + n - 1, on q's stream.
@@ -615,7 +617,7 @@ int launch_begin(int cu_count, QueryCtx* q, uint64_t first_path, const RlSpectra
 }
 
 int step_check(const RlScene* scene, int fetch, uint32_t flags, const void* states, uint32_t n) {
-    if (fetch != RL_FETCH_LDS && fetch != RL_FETCH_GLOBAL) return fail(RL_E_INVALID, "unknown fetch mode");
+    if (fetch_check(fetch) != RL_OK) return RL_E_INVALID;
     if (flags & ~(uint32_t)RL_STEP_NO_ROULETTE) return fail(RL_E_INVALID, "unknown step flag");
     if (n > 0 && !states) return fail(RL_E_INVALID, "null state buffer");
     if (!scene) return fail(RL_E_INVALID, "null scene");
@@ -625,8 +627,7 @@ int step_check(const RlScene* scene, int fetch, uint32_t flags, const void* stat
 int begin_check(const RlScene* scene, uint64_t first_path, const void* rays, uint32_t n, const void* states) {
     if (n > 0 && (!rays || !states)) return fail(RL_E_INVALID, "null ray or state buffer");
     if (!scene) return fail(RL_E_INVALID, "null scene");
-    if (first_path + n < first_path || first_path + n == ~0ull) return fail(RL_E_INVALID, "path indices must stay below 2^64 - 1");
-    return RL_OK;
+    return path_range_check(first_path, n);
 }
 
 int states_aligned(const void* states, const char* what) {
@@ -821,31 +822,15 @@ int rl_scene_destroy(RlScene* scene) {
 }
 
 int rl_scene_intersect(const RlScene* scene, int primitive_fetch, const RlRay* rays, uint32_t n_rays, RlRayHit* hits) {
-    int rc = query_check(scene, primitive_fetch, rays, n_rays, hits);
+    const int rc = query_check(scene, primitive_fetch, rays, n_rays, hits);
     if (rc != RL_OK || n_rays == 0) return rc;
-    if ((rc = use_device(scene->device)) != RL_OK) return rc;
-    int cus = 256;
-    if ((rc = cu_count_of(scene->device, &cus)) != RL_OK) return rc;
-    QueryCtx* q = nullptr;
-    if ((rc = query_ctx_acquire(scene->device, &q)) != RL_OK) return rc;
-    auto run = [&]() -> int {
-        if (!q->rays) RL_HIP(hipMalloc((void**)&q->rays, (size_t)RL_QUERY_CHUNK * sizeof(RlRay)));
-        if (!q->hits) RL_HIP(hipMalloc((void**)&q->hits, (size_t)RL_QUERY_CHUNK * sizeof(RlRayHit)));
-        for (uint32_t first = 0; first < n_rays;) {
-            const uint32_t n = n_rays - first < RL_QUERY_CHUNK ? n_rays - first : RL_QUERY_CHUNK;
-            RL_HIP(hipMemcpyAsync(q->rays, rays + first, (size_t)n * sizeof(RlRay), hipMemcpyHostToDevice, q->stream));
-            const int r = launch_query(scene, primitive_fetch, cus, q, q->rays, q->hits, n);
-            if (r != RL_OK) return r;
-            RL_HIP(hipMemcpyAsync(hits + first, q->hits, (size_t)n * sizeof(RlRayHit), hipMemcpyDeviceToHost, q->stream));
-            RL_HIP(hipStreamSynchronize(q->stream));
-            first += n;
-        }
-        return RL_OK;
-    };
-    rc = run();
-    if (rc != RL_OK) (void)hipStreamSynchronize(q->stream); // (nothing of this call may still run when its buffers are handed on)
-    query_ctx_release(scene->device, q);
-    return rc;
+    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
+        return staged_chunks(q, q->stream, n_rays, {staged_in(STAGING_RAYS, rays, sizeof(RlRay)), staged_out(STAGING_HITS, hits, sizeof(RlRayHit))},
+                             [&](uint32_t, uint32_t k) -> int {
+                                 return launch_persistent(g_query_kernels, scene, primitive_fetch, cus, q->stream, k, (const RlRay*)q->staging[STAGING_RAYS],
+                                                          (RlRayHit*)q->staging[STAGING_HITS], k);
+                             });
+    });
 }
 
 int rl_scene_intersect_device(const RlScene* scene, int primitive_fetch, const RlRay* device_rays, uint32_t n_rays, RlRayHit* device_hits) {
@@ -853,16 +838,9 @@ int rl_scene_intersect_device(const RlScene* scene, int primitive_fetch, const R
     if (rc != RL_OK || n_rays == 0) return rc;
     if ((rc = use_device(scene->device)) != RL_OK) return rc;
     if ((rc = device_buffers_check(scene, device_rays, device_hits, "rl_scene_intersect_device", "rl_scene_intersect")) != RL_OK) return rc;
-    int cus = 256;
-    if ((rc = cu_count_of(scene->device, &cus)) != RL_OK) return rc;
-    QueryCtx* q = nullptr;
-    if ((rc = query_ctx_acquire(scene->device, &q)) != RL_OK) return rc;
-    rc = launch_query(scene, primitive_fetch, cus, q, device_rays, device_hits, n_rays);
-    const hipError_t e = hipStreamSynchronize(q->stream);
-    query_ctx_release(scene->device, q);
-    if (rc != RL_OK) return rc;
-    RL_HIP(e);
-    return RL_OK;
+    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
+        return launch_persistent(g_query_kernels, scene, primitive_fetch, cus, q->stream, n_rays, device_rays, device_hits, n_rays);
+    });
 }
 
 int rl_scene_camera_rays(const RlScene* scene, uint32_t width, uint32_t height, uint64_t seed, uint32_t stream, uint64_t first_path_index,
@@ -870,17 +848,9 @@ int rl_scene_camera_rays(const RlScene* scene, uint32_t width, uint32_t height, 
     const int rc = camera_check(scene, width, height, first_path_index, n, samples);
     if (rc != RL_OK || n == 0) return rc;
     return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
-        if (!q->hits) RL_HIP(hipMalloc((void**)&q->hits, (size_t)RL_QUERY_CHUNK * sizeof(RlRayHit)));
-        RlCameraSample* staged = (RlCameraSample*)q->hits;
-        for (uint32_t first = 0; first < n;) {
-            const uint32_t k = n - first < RL_QUERY_CHUNK ? n - first : RL_QUERY_CHUNK;
-            const int r = launch_camera(scene, cus, q, width, height, seed, stream, first_path_index + first, staged, k);
-            if (r != RL_OK) return r;
-            RL_HIP(hipMemcpyAsync(samples + first, staged, (size_t)k * sizeof(RlCameraSample), hipMemcpyDeviceToHost, q->stream));
-            RL_HIP(hipStreamSynchronize(q->stream));
-            first += k;
-        }
-        return RL_OK;
+        return staged_chunks(q, q->stream, n, {staged_out(STAGING_HITS, samples, sizeof(RlCameraSample))}, [&](uint32_t first, uint32_t k) -> int {
+            return launch_camera(scene, cus, q, width, height, seed, stream, first_path_index + first, (RlCameraSample*)q->staging[STAGING_HITS], k);
+        });
     });
 }
 
@@ -901,20 +871,12 @@ int rl_scene_render_rays(const RlScene* scene, int primitive_fetch, uint64_t see
     const int rc = paths_check(scene, primitive_fetch, rays, n_rays, results, first_path_index, max_segments, &job);
     if (rc != RL_OK || n_rays == 0) return rc;
     return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
-        if (!q->rays) RL_HIP(hipMalloc((void**)&q->rays, (size_t)RL_QUERY_CHUNK * sizeof(RlRay)));
-        if (!q->hits) RL_HIP(hipMalloc((void**)&q->hits, (size_t)RL_QUERY_CHUNK * sizeof(RlRayHit)));
-        RlSpectralRay* staged_rays = (RlSpectralRay*)q->rays;
-        RlPathResult* staged_results = (RlPathResult*)q->hits;
-        for (uint32_t first = 0; first < n_rays;) {
-            const uint32_t k = n_rays - first < RL_QUERY_CHUNK ? n_rays - first : RL_QUERY_CHUNK;
-            RL_HIP(hipMemcpyAsync(staged_rays, rays + first, (size_t)k * sizeof(RlSpectralRay), hipMemcpyHostToDevice, q->stream));
-            const int r = launch_paths(scene, primitive_fetch, cus, q, job, first_path_index + first, staged_rays, staged_results, k);
-            if (r != RL_OK) return r;
-            RL_HIP(hipMemcpyAsync(results + first, staged_results, (size_t)k * sizeof(RlPathResult), hipMemcpyDeviceToHost, q->stream));
-            RL_HIP(hipStreamSynchronize(q->stream));
-            first += k;
-        }
-        return RL_OK;
+        return staged_chunks(q, q->stream, n_rays,
+                             {staged_in(STAGING_RAYS, rays, sizeof(RlSpectralRay)), staged_out(STAGING_HITS, results, sizeof(RlPathResult))},
+                             [&](uint32_t first, uint32_t k) -> int {
+                                 return launch_paths(scene, primitive_fetch, cus, q, job, first_path_index + first,
+                                                     (const RlSpectralRay*)q->staging[STAGING_RAYS], (RlPathResult*)q->staging[STAGING_HITS], k);
+                             });
     });
 }
 
@@ -934,19 +896,11 @@ int rl_scene_begin_paths(const RlScene* scene, uint64_t first_path_index, const 
     const int rc = begin_check(scene, first_path_index, rays, n, states);
     if (rc != RL_OK || n == 0) return rc;
     return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
-        if (!q->rays) RL_HIP(hipMalloc((void**)&q->rays, (size_t)RL_QUERY_CHUNK * sizeof(RlRay)));
-        if (!q->states) RL_HIP(hipMalloc((void**)&q->states, (size_t)RL_QUERY_CHUNK * sizeof(RlPathState)));
-        RlSpectralRay* staged_rays = (RlSpectralRay*)q->rays;
-        for (uint32_t first = 0; first < n;) {
-            const uint32_t k = n - first < RL_QUERY_CHUNK ? n - first : RL_QUERY_CHUNK;
-            RL_HIP(hipMemcpyAsync(staged_rays, rays + first, (size_t)k * sizeof(RlSpectralRay), hipMemcpyHostToDevice, q->stream));
-            const int r = launch_begin(cus, q, first_path_index + first, staged_rays, q->states, k);
-            if (r != RL_OK) return r;
-            RL_HIP(hipMemcpyAsync(states + first, q->states, (size_t)k * sizeof(RlPathState), hipMemcpyDeviceToHost, q->stream));
-            RL_HIP(hipStreamSynchronize(q->stream));
-            first += k;
-        }
-        return RL_OK;
+        return staged_chunks(q, q->stream, n, {staged_in(STAGING_RAYS, rays, sizeof(RlSpectralRay)), staged_out(STAGING_STATES, states, sizeof(RlPathState))},
+                             [&](uint32_t first, uint32_t k) -> int {
+                                 return launch_begin(cus, q, first_path_index + first, (const RlSpectralRay*)q->staging[STAGING_RAYS],
+                                                     (RlPathState*)q->staging[STAGING_STATES], k);
+                             });
     });
 }
 
@@ -967,21 +921,12 @@ int rl_scene_step_paths(const RlScene* scene, int primitive_fetch, uint64_t seed
     const int rc = step_check(scene, primitive_fetch, flags, states, n);
     if (rc != RL_OK || n == 0) return rc;
     return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
-        if (!q->states) RL_HIP(hipMalloc((void**)&q->states, (size_t)RL_QUERY_CHUNK * sizeof(RlPathState)));
-        if (hits && !q->hits) RL_HIP(hipMalloc((void**)&q->hits, (size_t)RL_QUERY_CHUNK * sizeof(RlRayHit)));
-        for (uint32_t first = 0; first < n;) {
-            const uint32_t k = n - first < RL_QUERY_CHUNK ? n - first : RL_QUERY_CHUNK;
-            RL_HIP(hipMemcpyAsync(q->states, states + first, (size_t)k * sizeof(RlPathState), hipMemcpyHostToDevice, q->stream));
-            // (the caller's hits go in too: the slots of the states that are not stepped come back as they were)
-            if (hits) RL_HIP(hipMemcpyAsync(q->hits, hits + first, (size_t)k * sizeof(RlRayHit), hipMemcpyHostToDevice, q->stream));
-            const int r = launch_step(scene, primitive_fetch, cus, q, seed, stream, flags, q->states, hits ? q->hits : nullptr, k);
-            if (r != RL_OK) return r;
-            RL_HIP(hipMemcpyAsync(states + first, q->states, (size_t)k * sizeof(RlPathState), hipMemcpyDeviceToHost, q->stream));
-            if (hits) RL_HIP(hipMemcpyAsync(hits + first, q->hits, (size_t)k * sizeof(RlRayHit), hipMemcpyDeviceToHost, q->stream));
-            RL_HIP(hipStreamSynchronize(q->stream));
-            first += k;
-        }
-        return RL_OK;
+        // (the caller's hits go in too: the slots of the states that are not stepped come back as they were)
+        return staged_chunks(q, q->stream, n, {staged_inout(STAGING_STATES, states, sizeof(RlPathState)), staged_inout(STAGING_HITS, hits, sizeof(RlRayHit))},
+                             [&](uint32_t, uint32_t k) -> int {
+                                 return launch_step(scene, primitive_fetch, cus, q, seed, stream, flags, (RlPathState*)q->staging[STAGING_STATES],
+                                                    hits ? (RlRayHit*)q->staging[STAGING_HITS] : nullptr, k);
+                             });
     });
 }
 
@@ -1701,39 +1646,13 @@ int rl_plot_unit_download(RlPlotUnit* u, RlVector3* out) {
 // its queue counter); the context's own stream stays idle.
 
 namespace {
-typedef void (*FilmKernel)(const RlF4*, RlSceneLayout, const RlCameraSample*, RlPathResult*, uint32_t, uint64_t, uint32_t, uint64_t, uint32_t,
-                           unsigned long long*);
-std::atomic<uint64_t> g_film_launches[6]; // rl_debug_film_launches: launches per instantiation since the library was loaded
-// Index = 2 * stage + cylinders, as the path kernel's.
-FilmKernel film_kernel_variant(int stage, bool cyl) {
-    const int index = 2 * stage + (cyl ? 1 : 0);
-    g_film_launches[index].fetch_add(1, std::memory_order_relaxed);
-    static const FilmKernel table[6] = {
-        rl_film_paths_kernel<RL_STAGE_NONE, false>,   rl_film_paths_kernel<RL_STAGE_NONE, true>, rl_film_paths_kernel<RL_STAGE_TABLES, false>,
-        rl_film_paths_kernel<RL_STAGE_TABLES, true>, rl_film_paths_kernel<RL_STAGE_ALL, false>, rl_film_paths_kernel<RL_STAGE_ALL, true>,
-    };
-    return table[index];
-}
-
 // samples [0, n) of device arrays as paths first_path .. first_path + n - 1 (n > 0), splatted into u: one launch of the film path
 // kernel on u's stream, behind the copy that zeroes the context's queue counter and writes the film's constants after it.
 // `results` may be null.
 int launch_film(RlPlotUnit* u, const RlScene* scene, int fetch, int cu_count, QueryCtx* q, const PathJob& job, uint64_t first_path,
                 const RlCameraSample* samples, RlPathResult* results, uint32_t n) {
-    if (!q->queue) RL_HIP(hipMalloc((void**)&q->queue, sizeof(RlFilmQueue)));
-    const size_t scratch_bytes = (RL_TRACE_BLOCK / 64) * sizeof(RlWaveScratch) + ring_t_bytes(scene);
-    size_t blob_bytes = 0;
-    const int stage = stage_of(scene, fetch, scratch_bytes, &blob_bytes);
-    const bool cyl = scene->lay.prism_cylinders != 0u;
-    const int index = 2 * stage + (cyl ? 1 : 0);
-    auto kernel = film_kernel_variant(stage, cyl);
-    const size_t dyn = scratch_bytes + blob_bytes;
-    int per_cu = 0;
-    const int rc = resident_per_cu(scene->device, 12 + index, (const void*)kernel, dyn, &per_cu);
+    const int rc = query_ctx_queue(q);
     if (rc != RL_OK) return rc;
-    uint64_t blocks = (uint64_t)cu_count * (uint64_t)per_cu;
-    const uint64_t needed = ((uint64_t)n + RL_TRACE_BLOCK - 1) / RL_TRACE_BLOCK;
-    if (blocks > needed) blocks = needed;
     RlFilmQueue fq;
     fq.next = 0;
     fq.film.plot = u->xyz;
@@ -1745,10 +1664,8 @@ int launch_film(RlPlotUnit* u, const RlScene* scene, int fetch, int cu_count, Qu
     fq.film.off_cie = scene->lay.off_cie;
     // (from pageable memory: the copy has left `fq` when the call returns)
     RL_HIP(hipMemcpyAsync(q->queue, &fq, sizeof fq, hipMemcpyHostToDevice, u->stream));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(RL_TRACE_BLOCK), dyn, u->stream, scene->blob, scene->lay, samples, results, n, job.seed,
-                       job.stream, first_path, job.max_segments, q->queue);
-    RL_HIP(hipGetLastError());
-    return RL_OK;
+    return launch_persistent(g_film_kernels, scene, fetch, cu_count, u->stream, n, samples, results, n, job.seed, job.stream, first_path, job.max_segments,
+                             q->queue);
 }
 
 // The photon splat kernel for device array photons [0, n) (n > 0) on u's stream.
@@ -1784,11 +1701,9 @@ int samples_check(const RlPlotUnit* u, const RlScene* scene, int fetch, uint32_t
                   uint32_t n, PathJob* job) {
     if (!u) return fail(RL_E_INVALID, "null plot unit");
     if (!scene) return fail(RL_E_INVALID, "null scene");
-    if (fetch != RL_FETCH_LDS && fetch != RL_FETCH_GLOBAL) return fail(RL_E_INVALID, "unknown fetch mode");
-    if (max_segments > RL_PATH_MAX_SEGMENTS_CAP) return fail(RL_E_INVALID, "max_segments exceeds RL_PATH_MAX_SEGMENTS_CAP = 65536");
-    if (first_path + n < first_path || first_path + n == ~0ull) return fail(RL_E_INVALID, "path indices must stay below 2^64 - 1");
+    if (fetch_check(fetch) != RL_OK || max_segments_resolve(max_segments, &job->max_segments) != RL_OK) return RL_E_INVALID;
+    if (path_range_check(first_path, n) != RL_OK) return RL_E_INVALID;
     if (n > 0 && !samples) return fail(RL_E_INVALID, "null sample buffer");
-    job->max_segments = max_segments == 0u ? RL_PATH_MAX_SEGMENTS : max_segments;
     return RL_OK;
 }
 } // namespace
@@ -1798,17 +1713,9 @@ int rl_plot_unit_plot_photons(RlPlotUnit* u, const RlMappedPhoton* photons, uint
     if (n > 0 && !photons) return fail(RL_E_INVALID, "null photon buffer");
     if (n == 0) return RL_OK;
     return with_film_ctx(u, [&](QueryCtx* q, int cus) -> int {
-        if (!q->rays) RL_HIP(hipMalloc((void**)&q->rays, (size_t)RL_QUERY_CHUNK * sizeof(RlRay)));
-        RlMappedPhoton* staged = (RlMappedPhoton*)q->rays;
-        for (uint64_t first = 0; first < n;) {
-            const uint64_t k = n - first < RL_QUERY_CHUNK ? n - first : RL_QUERY_CHUNK;
-            RL_HIP(hipMemcpyAsync(staged, photons + first, (size_t)k * sizeof(RlMappedPhoton), hipMemcpyHostToDevice, u->stream));
-            const int r = launch_film_photons(u, cus, staged, k);
-            if (r != RL_OK) return r;
-            RL_HIP(hipStreamSynchronize(u->stream)); // (the next chunk overwrites the staging buffer)
-            first += k;
-        }
-        return RL_OK;
+        return staged_chunks(q, u->stream, n, {staged_in(STAGING_RAYS, photons, sizeof(RlMappedPhoton))}, [&](uint64_t, uint64_t k) -> int {
+            return launch_film_photons(u, cus, (const RlMappedPhoton*)q->staging[STAGING_RAYS], k);
+        });
     });
 }
 
@@ -1831,20 +1738,11 @@ int rl_plot_unit_render_samples(RlPlotUnit* u, const RlScene* scene, int primiti
     if (rc != RL_OK || n == 0) return rc;
     if (scene->device != u->device) return fail(RL_E_STATE, "scene and plot unit live on different devices");
     return with_film_ctx(u, [&](QueryCtx* q, int cus) -> int {
-        if (!q->hits) RL_HIP(hipMalloc((void**)&q->hits, (size_t)RL_QUERY_CHUNK * sizeof(RlRayHit)));
-        if (results && !q->rays) RL_HIP(hipMalloc((void**)&q->rays, (size_t)RL_QUERY_CHUNK * sizeof(RlRay)));
-        RlCameraSample* staged_samples = (RlCameraSample*)q->hits;
-        RlPathResult* staged_results = results ? (RlPathResult*)q->rays : nullptr;
-        for (uint32_t first = 0; first < n;) {
-            const uint32_t k = n - first < RL_QUERY_CHUNK ? n - first : RL_QUERY_CHUNK;
-            RL_HIP(hipMemcpyAsync(staged_samples, samples + first, (size_t)k * sizeof(RlCameraSample), hipMemcpyHostToDevice, u->stream));
-            const int r = launch_film(u, scene, primitive_fetch, cus, q, job, first_path_index + first, staged_samples, staged_results, k);
-            if (r != RL_OK) return r;
-            if (results) RL_HIP(hipMemcpyAsync(results + first, staged_results, (size_t)k * sizeof(RlPathResult), hipMemcpyDeviceToHost, u->stream));
-            RL_HIP(hipStreamSynchronize(u->stream));
-            first += k;
-        }
-        return RL_OK;
+        return staged_chunks(q, u->stream, n, {staged_in(STAGING_HITS, samples, sizeof(RlCameraSample)), staged_out(STAGING_RAYS, results, sizeof(RlPathResult))},
+                             [&](uint32_t first, uint32_t k) -> int {
+                                 return launch_film(u, scene, primitive_fetch, cus, q, job, first_path_index + first,
+                                                    (const RlCameraSample*)q->staging[STAGING_HITS], results ? (RlPathResult*)q->staging[STAGING_RAYS] : nullptr, k);
+                             });
     });
 }
 
@@ -2376,29 +2274,10 @@ int rl_debug_variant_launches(uint64_t* out) {
     return RL_OK;
 }
 
-int rl_debug_query_launches(uint64_t* out) {
-    if (!out) return fail(RL_E_INVALID, "null output");
-    for (int k = 0; k < 6; ++k) out[k] = g_query_launches[k].load(std::memory_order_relaxed);
-    return RL_OK;
-}
-
-int rl_debug_path_launches(uint64_t* out) {
-    if (!out) return fail(RL_E_INVALID, "null output");
-    for (int k = 0; k < 6; ++k) out[k] = g_path_launches[k].load(std::memory_order_relaxed);
-    return RL_OK;
-}
-
-int rl_debug_film_launches(uint64_t* out) {
-    if (!out) return fail(RL_E_INVALID, "null output");
-    for (int k = 0; k < 6; ++k) out[k] = g_film_launches[k].load(std::memory_order_relaxed);
-    return RL_OK;
-}
-
-int rl_debug_step_launches(uint64_t* out) {
-    if (!out) return fail(RL_E_INVALID, "null output");
-    for (int k = 0; k < 6; ++k) out[k] = g_step_launches[k].load(std::memory_order_relaxed);
-    return RL_OK;
-}
+int rl_debug_query_launches(uint64_t* out) { return family_launches(g_query_kernels, out); }
+int rl_debug_path_launches(uint64_t* out) { return family_launches(g_path_kernels, out); }
+int rl_debug_film_launches(uint64_t* out) { return family_launches(g_film_kernels, out); }
+int rl_debug_step_launches(uint64_t* out) { return family_launches(g_step_kernels, out); }
 
 // ---- device-side math probe (tests) -------------------------------------------------------------
 

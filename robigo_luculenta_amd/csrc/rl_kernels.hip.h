@@ -1206,6 +1206,73 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
     return best;
 }
 
+// The prologue of the query, path, film and step kernels (and, as its own text, of rl_trace_body): the workgroup stages the
+// whole scene, its tables or nothing in LDS, ring T goes in front of the per-wave scratch where the cull table has a third level, and
+// the scene view points into whichever copy holds each array.
+// Dynamic LDS: [scene blob (RL_STAGE_ALL) or its tables (RL_STAGE_TABLES)][ring T (a third level only)][RlWaveScratch x 16].
+struct RlStagedScene {
+    RlSceneView sv;
+    const RlF4* base;       // the tables
+    uint32_t tab0;          // blob offset of `base`'s first record
+    RlWaveScratch* scratch; // RL_TRACE_BLOCK / 64 blocks, 512-byte aligned
+    RlLdsU32* ring_t;       // this wave's ring T, or null
+};
+template <int STAGE>
+__device__ __forceinline__ RlStagedScene rl_stage_scene(const RlF4* __restrict__ scene, const RlSceneLayout& lay) {
+    extern __shared__ __attribute__((aligned(512))) RlF4 smem[]; // (512: the ring pushes OR slot offsets into a wave's scratch address, RL_RING_SLOT)
+    const RlF4* base = scene; // the tables
+    const RlF4* big = scene;  // the per-sphere and per-object arrays
+    RlWaveScratch* scratch = (RlWaveScratch*)smem;
+    if (STAGE == RL_STAGE_ALL) {
+        for (uint32_t i = threadIdx.x; i < lay.total_f4; i += RL_TRACE_BLOCK) smem[i] = scene[i];
+        __syncthreads();
+        base = big = smem;
+        scratch = (RlWaveScratch*)(smem + ((lay.total_f4 + 31u) & ~31u)); // 512-byte aligned (rl_scan_wave's ring addressing; stage_of() rounds up likewise)
+    } else if (STAGE == RL_STAGE_TABLES) {
+        const uint32_t n_staged = lay.off_objects - lay.off_planes;
+        for (uint32_t i = threadIdx.x; i < n_staged; i += RL_TRACE_BLOCK) smem[i] = scene[lay.off_planes + i];
+        __syncthreads();
+        base = smem;
+        scratch = (RlWaveScratch*)(smem + ((n_staged + 31u) & ~31u));
+    }
+    // A scene whose cull table has a third level (never one that is staged whole) gets 512 bytes per wave in front of the scratch
+    // blocks: ring T (rl_scan_wave, SUPER).  The host sizes the launch's LDS accordingly (rl_api.hip: ring_t_bytes).
+    RlLdsU32* ring_t = nullptr;
+    if (STAGE != RL_STAGE_ALL && lay.n_cluster_supers != 0u) {
+        ring_t = (RlLdsU32*)scratch + 128u * (threadIdx.x >> 6);
+        scratch = (RlWaveScratch*)((RlF4*)scratch + 32u * (RL_TRACE_BLOCK / 64));
+    }
+    const uint32_t tab0 = STAGE == RL_STAGE_TABLES ? lay.off_planes : 0u; // blob offset of `base`'s first record
+
+    RlSceneView sv;
+    sv.spheres = big;
+    sv.planes = base + (lay.off_planes - tab0);
+    sv.parabs = base + (lay.off_parabs - tab0);
+    sv.prisms = base + (lay.off_prisms - tab0);
+    sv.objects = big + lay.off_objects;
+    sv.cie = big + lay.off_cie;
+    sv.sphere_obj = (const uint32_t*)(big + lay.off_sphere_obj);
+    sv.sphere_r2 = (const float*)(big + lay.off_sphere_r2);
+    sv.n_direct = lay.n_direct;
+    sv.n_direct_padded = lay.n_direct_padded;
+    sv.cluster_base = lay.cluster_base;
+    sv.n_clusters = lay.n_clusters;
+    sv.cluster_k = lay.cluster_k;
+    sv.n_planes = lay.n_planes;
+    sv.n_parabs = lay.n_parabs;
+    sv.n_prisms = lay.n_prisms;
+    sv.n_objects = lay.n_objects;
+    sv.camera_rec = base + (lay.off_camera - tab0);
+    sv.records = big; // (a tables-only stage completes its hits from the blob in global memory, like its spheres)
+    RlStagedScene st;
+    st.sv = sv;
+    st.base = base;
+    st.tab0 = tab0;
+    st.scratch = scratch;
+    st.ring_t = ring_t;
+    return st;
+}
+
 // queue[0] = next unassigned path offset of this launch (zeroed before each launch),
 // queue[1] = cumulative segments, queue[2] = cumulative paths.
 // Dynamic LDS: [scene blob (RL_STAGE_ALL) or its tables (RL_STAGE_TABLES)][RlWaveScratch x 16].
@@ -1220,6 +1287,8 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
 template <int STAGE, bool FUSED, bool OPEN, bool CYL>
 __device__ __forceinline__ void rl_trace_body(const RlF4* __restrict__ scene, const RlSceneLayout& lay, const RlTraceJob& job, RlMappedPhoton* __restrict__ photons,
                                               float* __restrict__ plot, unsigned long long* __restrict__ queue, const RlJobEntry* jobs, RlOpenDev* od, RlOpenCtl* ctl) {
+    // (rl_stage_scene's statements, kept as text: called from here it changed the instructions of 16 of the 24 trace bodies and
+    // gave one of them 8 bytes of scratch -- measured on the commit after 69f31a2, profiles/refactor_isa_diff.txt)
     extern __shared__ __attribute__((aligned(512))) RlF4 smem[]; // (512: the ring pushes OR slot offsets into a wave's scratch address, RL_RING_SLOT)
     const RlF4* base = scene; // the tables
     const RlF4* big = scene;  // the per-sphere and per-object arrays

@@ -1,6 +1,7 @@
 // rl_query.hip.h -- the query kernel behind rl_scene_intersect / rl_scene_intersect_device: Scene::intersect (scene.rs:39-60)
 // for a batch of independent rays, through the trace kernel's own scan (rl_scan_wave) and hit completion (rl_finish_hit).
-// Included by rl_api.hip after rl_kernels.hip.h and the public header (RlRay, RlRayHit).
+// Also what the path, film and step kernels share with it: one segment's intersection (rl_intersect_segment) and the hit record
+// (rl_ray_hit_of).  Included by rl_api.hip after rl_kernels.hip.h (rl_stage_scene) and the public header (RlRay, RlRayHit).
 #pragma once
 
 // Scene::intersect for one ray by the linear scan of rl_scan (rl_core.h) WITHOUT the cull of the sphere clusters, for the rays the
@@ -75,62 +76,66 @@ __device__ __forceinline__ RlHit rl_query_exhaustive(const RlSceneView& sv, RlF3
     return best;
 }
 
+// Scene::intersect for every lane's segment, as the query, path, film and step kernels make it: the wave's scan with a full exec
+// mask and the plain launches' options (128 registers, the template arguments of the non-open rl_trace_kernel of the same stage),
+// then the exact linear scan under the lanes the scan's culls are not sized for (rl_query_exhaustive): |direction|^2 further than
+// 2^-20 from 1, or a NaN / infinite component -- decided per segment, refraction and reflection keep a non-unit direction's
+// length.  Those lanes, and the lanes that are not `active`, scan a null ray, muted by the idle bit (rl_scan_wave wants exec all ones).
+template <int STAGE, bool CYL>
+__device__ __forceinline__ RlHit rl_intersect_segment(const RlStagedScene& staged, const RlSceneLayout& lay, bool active, RlF3 o, RlF3 d, RlWaveScratch* ws,
+                                                      uint32_t lane RL_TACC_PARAM) {
+    const RlF4* base = staged.base;
+    const uint32_t tab0 = staged.tab0;
+    const float d2 = d.x * d.x + d.y * d.y + d.z * d.z;
+    const bool exhaustive = active && !(fabsf(d2 - 1.0f) <= 0x1p-20f && fabsf(o.x) < INFINITY && fabsf(o.y) < INFINITY && fabsf(o.z) < INFINITY);
+    const bool scanned = active && !exhaustive;
+    RlHit hit = rl_scan_wave<CYL, RL_LEAN_SPLIT, STAGE != RL_STAGE_NONE, STAGE != RL_STAGE_NONE && RL_W_S && RL_LEAN_HOIST, STAGE == RL_STAGE_ALL,
+                             STAGE != RL_STAGE_NONE, STAGE != RL_STAGE_ALL>(staged.sv, base + (lay.off_cull - tab0), CYL ? base + (lay.off_prism_cyl - tab0) : nullptr,
+                                                                            lay.group_gc, lay.small_ordered, lay.cull_cmax2, lay.n_cluster_groups,
+                                                                            lay.n_prism_groups, lay.n_cluster_supers, lay.super_g, staged.ring_t,
+                                                                            scanned ? o : rl_f3(0.0f, 0.0f, 0.0f), scanned ? d : rl_f3(0.0f, 0.0f, 0.0f),
+                                                                            scanned ? 0u : 0x80000000u, ws, lane RL_TACC_ARG);
+    RL_T0(t_exhaustive);
+    RL_STAT(RL_ST_X_LANES, __popcll(__builtin_amdgcn_ballot_w64(exhaustive)));
+    RL_STAT(RL_ST_X_ITERS, __builtin_amdgcn_ballot_w64(exhaustive) != 0);
+    if (exhaustive) hit = rl_query_exhaustive(staged.sv, o, d);
+    RL_T1(RL_ST_T_EXHAUSTIVE, t_exhaustive);
+    return hit;
+}
+
+// The RlRayHit of a segment's nearest hit (`found`: there is one that counts; all zero and RL_OBJECT_NONE otherwise).
+__device__ __forceinline__ RlRayHit rl_ray_hit_of(const RlSceneView& sv, RlF3 o, RlF3 d, const RlHit& hit, bool found) {
+    RlRayHit out;
+    out.isect.position = out.isect.normal = out.isect.tangent = RlVector3{0.0f, 0.0f, 0.0f};
+    out.isect.distance = 0.0f;
+    out.object = RL_OBJECT_NONE;
+    out.reserved = 0u;
+    if (found) {
+        const uint32_t kinds = rl_f2u(sv.objects[hit.obj].w);
+        const uint32_t surface_kind = rl_object_surface(kinds);
+        const RlIsect is = rl_finish_hit(sv, o, d, hit, surface_kind, rl_object_group(kinds));
+        // Intersection.tangent: normalise(cross((0, 1, 0), normal)) on spheres (geometry.rs:250-251), the zero vector on every
+        // other surface -- which normalise returns unchanged (the soap bubble's form, rl_core.h: rl_bounce)
+        const RlF3 axis = surface_kind == RL_SURFACE_SPHERE ? rl_cross(rl_f3(0.0f, 1.0f, 0.0f), is.normal) : rl_f3(0.0f, 0.0f, 0.0f);
+        const RlF3 tangent = rl_normalise(axis);
+        out.isect.position = RlVector3{is.position.x, is.position.y, is.position.z};
+        out.isect.normal = RlVector3{is.normal.x, is.normal.y, is.normal.z};
+        out.isect.tangent = RlVector3{tangent.x, tangent.y, tangent.z};
+        out.isect.distance = hit.t;
+        out.object = hit.obj; // the flattened object table is in description order
+    }
+    return out;
+}
+
 // Persistent workgroups of RL_TRACE_BLOCK threads, laid out like the trace kernel's plain launches: each stages the scene once
-// (the whole blob, its tables, or nothing), ring T in front of the per-wave scratch where the cull table has a third level, then
-// every wave takes chunks of 64 rays -- chunk c goes to wave c mod (waves of the grid) -- and scans them together; lanes past
-// the end get the idle bit (rl_scan_wave wants exec all ones).  The scan options are the plain launches' (128 registers, the
-// template arguments of the non-open rl_trace_kernel of the same stage): the body around the scan is far lighter than a path's.
-// Dynamic LDS: [scene blob (RL_STAGE_ALL) or its tables (RL_STAGE_TABLES)][ring T (a third level only)][RlWaveScratch x 16].
-// (rl_paths.hip.h: rl_stage_scene repeats this kernel's prologue statement for statement for the path kernel: change both together;
-// tests/test_path_query_abi.py compares the two.)
+// (rl_stage_scene), then every wave takes chunks of 64 rays -- chunk c goes to wave c mod (waves of the grid) -- and scans them
+// together (rl_intersect_segment); lanes past the end idle.  The body around the scan is far lighter than a path's.
 template <int STAGE, bool CYL>
 __global__ __launch_bounds__(RL_TRACE_BLOCK, RL_TRACE_WPS) __attribute__((amdgpu_num_vgpr(RL_TRACE_VGPRS / 2))) void rl_query_kernel(
     const RlF4* __restrict__ scene, RlSceneLayout lay, const RlRay* __restrict__ rays, RlRayHit* __restrict__ hits, uint32_t n_rays) {
-    extern __shared__ __attribute__((aligned(512))) RlF4 smem[]; // (512: the ring pushes OR slot offsets into a wave's scratch address)
-    const RlF4* base = scene; // the tables
-    const RlF4* big = scene;  // the per-sphere and per-object arrays
-    RlWaveScratch* scratch = (RlWaveScratch*)smem;
-    if (STAGE == RL_STAGE_ALL) {
-        for (uint32_t i = threadIdx.x; i < lay.total_f4; i += RL_TRACE_BLOCK) smem[i] = scene[i];
-        __syncthreads();
-        base = big = smem;
-        scratch = (RlWaveScratch*)(smem + ((lay.total_f4 + 31u) & ~31u));
-    } else if (STAGE == RL_STAGE_TABLES) {
-        const uint32_t n_staged = lay.off_objects - lay.off_planes;
-        for (uint32_t i = threadIdx.x; i < n_staged; i += RL_TRACE_BLOCK) smem[i] = scene[lay.off_planes + i];
-        __syncthreads();
-        base = smem;
-        scratch = (RlWaveScratch*)(smem + ((n_staged + 31u) & ~31u));
-    }
-    RlLdsU32* ring_t = nullptr;
-    if (STAGE != RL_STAGE_ALL && lay.n_cluster_supers != 0u) {
-        ring_t = (RlLdsU32*)scratch + 128u * (threadIdx.x >> 6);
-        scratch = (RlWaveScratch*)((RlF4*)scratch + 32u * (RL_TRACE_BLOCK / 64));
-    }
-    const uint32_t tab0 = STAGE == RL_STAGE_TABLES ? lay.off_planes : 0u; // blob offset of `base`'s first record
-
-    RlSceneView sv;
-    sv.spheres = big;
-    sv.planes = base + (lay.off_planes - tab0);
-    sv.parabs = base + (lay.off_parabs - tab0);
-    sv.prisms = base + (lay.off_prisms - tab0);
-    sv.objects = big + lay.off_objects;
-    sv.cie = big + lay.off_cie;
-    sv.sphere_obj = (const uint32_t*)(big + lay.off_sphere_obj);
-    sv.sphere_r2 = (const float*)(big + lay.off_sphere_r2);
-    sv.n_direct = lay.n_direct;
-    sv.n_direct_padded = lay.n_direct_padded;
-    sv.cluster_base = lay.cluster_base;
-    sv.n_clusters = lay.n_clusters;
-    sv.cluster_k = lay.cluster_k;
-    sv.n_planes = lay.n_planes;
-    sv.n_parabs = lay.n_parabs;
-    sv.n_prisms = lay.n_prisms;
-    sv.n_objects = lay.n_objects;
-    sv.camera_rec = base + (lay.off_camera - tab0);
-    sv.records = big;
+    const RlStagedScene staged = rl_stage_scene<STAGE>(scene, lay);
     const uint32_t lane = threadIdx.x & 63u;
-    RlWaveScratch* ws = &scratch[threadIdx.x >> 6];
+    RlWaveScratch* ws = &staged.scratch[threadIdx.x >> 6];
 #ifdef RL_STATS
     unsigned long long st[RL_ST_COUNT] = {}; // (the scan's event counters: kept per wave and dropped, the query reports none)
 #endif
@@ -148,40 +153,10 @@ __global__ __launch_bounds__(RL_TRACE_BLOCK, RL_TRACE_WPS) __attribute__((amdgpu
             d = rl_f3(r.direction.x, r.direction.y, r.direction.z);
             t_max = r.t_max;
         }
-        // Rays the scan's culls are not sized for (rl_query_exhaustive): |direction|^2 further than 2^-20 from 1, or a NaN / infinite
-        // component.  They scan a null ray as idle lanes and take the linear scan after the wave's scan.
-        const float d2 = d.x * d.x + d.y * d.y + d.z * d.z;
-        const bool exhaustive = active && !(fabsf(d2 - 1.0f) <= 0x1p-20f && fabsf(o.x) < INFINITY && fabsf(o.y) < INFINITY && fabsf(o.z) < INFINITY);
-        const bool scanned = active && !exhaustive;
-        RlHit hit = rl_scan_wave<CYL, RL_LEAN_SPLIT, STAGE != RL_STAGE_NONE, STAGE != RL_STAGE_NONE && RL_W_S && RL_LEAN_HOIST, STAGE == RL_STAGE_ALL,
-                                       STAGE != RL_STAGE_NONE, STAGE != RL_STAGE_ALL>(sv, base + (lay.off_cull - tab0), CYL ? base + (lay.off_prism_cyl - tab0) : nullptr,
-                                                                                      lay.group_gc, lay.small_ordered, lay.cull_cmax2, lay.n_cluster_groups,
-                                                                                      lay.n_prism_groups, lay.n_cluster_supers, lay.super_g, ring_t,
-                                                                                      scanned ? o : rl_f3(0.0f, 0.0f, 0.0f), scanned ? d : rl_f3(0.0f, 0.0f, 0.0f),
-                                                                                      scanned ? 0u : 0x80000000u, ws, lane RL_TACC_ARG);
-        if (exhaustive) hit = rl_query_exhaustive(sv, o, d);
+        const RlHit hit = rl_intersect_segment<STAGE, CYL>(staged, lay, active, o, d, ws, lane RL_TACC_ARG);
         // Filtering after the scan is exact: when the nearest hit is at or beyond t_max no other hit can count.  (`<`: a hit at
         // exactly t_max misses, and so does every hit for a t_max that is NaN, zero or negative.)
-        const bool found = hit.obj != RL_HIT_NONE && hit.t < t_max;
-        RlRayHit out;
-        out.isect.position = out.isect.normal = out.isect.tangent = RlVector3{0.0f, 0.0f, 0.0f};
-        out.isect.distance = 0.0f;
-        out.object = RL_OBJECT_NONE;
-        out.reserved = 0u;
-        if (found) {
-            const uint32_t kinds = rl_f2u(sv.objects[hit.obj].w);
-            const uint32_t surface_kind = rl_object_surface(kinds);
-            const RlIsect is = rl_finish_hit(sv, o, d, hit, surface_kind, rl_object_group(kinds));
-            // Intersection.tangent: normalise(cross((0, 1, 0), normal)) on spheres (geometry.rs:250-251), the zero vector on every
-            // other surface -- which normalise returns unchanged (the soap bubble's form, rl_core.h: rl_bounce)
-            const RlF3 axis = surface_kind == RL_SURFACE_SPHERE ? rl_cross(rl_f3(0.0f, 1.0f, 0.0f), is.normal) : rl_f3(0.0f, 0.0f, 0.0f);
-            const RlF3 tangent = rl_normalise(axis);
-            out.isect.position = RlVector3{is.position.x, is.position.y, is.position.z};
-            out.isect.normal = RlVector3{is.normal.x, is.normal.y, is.normal.z};
-            out.isect.tangent = RlVector3{tangent.x, tangent.y, tangent.z};
-            out.isect.distance = hit.t;
-            out.object = hit.obj; // the flattened object table is in description order
-        }
+        const RlRayHit out = rl_ray_hit_of(staged.sv, o, d, hit, hit.obj != RL_HIT_NONE && hit.t < t_max);
         if (active) hits[i] = out;
         rl_wave_sync(); // (the next chunk's scan rewrites the wave's scratch)
     }

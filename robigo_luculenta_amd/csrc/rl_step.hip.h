@@ -1,6 +1,6 @@
 // rl_step.hip.h -- the kernels behind rl_scene_begin_paths* and rl_scene_step_paths*: one turn of TraceUnit::render_ray's loop
 // body (trace_unit.rs:92-126) for path states a caller holds between segments (RlPathState).  Included by rl_api.hip after
-// rl_paths.hip.h (rl_stage_scene) and rl_query.hip.h (rl_query_exhaustive).
+// rl_query.hip.h (rl_intersect_segment, rl_ray_hit_of) and rl_paths.hip.h (rl_opaque).
 #pragma once
 
 // RlPathState as the kernels move it: four 16-byte words.
@@ -39,22 +39,14 @@ __global__ __launch_bounds__(RL_BLOCK) void rl_begin_paths_kernel(const RlSpectr
     }
 }
 
-// The kernel's `hits` argument where it is tested for null and used: opaque, so that the test is made there, on the pointer's two
-// scalar registers, instead of being kept as a loop invariant in two more across the persistent loop (rl_film_results).
-__device__ __forceinline__ RlRayHit* rl_step_hits(RlRayHit* hits) {
-    asm volatile("" : "+s"(hits));
-    return hits;
-}
-
 // One segment for every live state of states[0, n).  The work per call is one scan per record, so the kernel has the query kernel's
 // shape, not the path kernel's: persistent workgroups of RL_TRACE_BLOCK threads that stage the scene once (rl_stage_scene), every
 // wave taking chunks of 64 states from one counter (`queue`, zeroed on the call's stream; a slice of four chunks per atomic in large
 // calls) and scanning them together, no refill.
 // Lanes past the end or on a state that has ended idle through the scan as null rays, as the path kernel's free lanes do, and
-// write nothing.  Per chunk: the state's four 16-byte loads, the wave's scan with the path kernel's options and a full exec mask,
-// the exact linear scan for the segments the culls do not cover (decided per segment, as the path kernel decides it), rl_bounce
+// write nothing.  Per chunk: the state's four 16-byte loads, every lane's segment (rl_intersect_segment), rl_bounce
 // with RNG block 2 + segments, the emitter term inline under the lanes on a light, the hit record as the query kernel writes it
-// (when `hits` is not null), and the state's four stores.  p.ior is a function of the wavelength alone: it is evaluated under the
+// (when `hits` is not null: tested through rl_opaque), and the state's four stores.  p.ior is a function of the wavelength alone: it is evaluated under the
 // lanes whose hit is glass, which gives the bits the path kernel's per-path evaluation gives.
 // flags: RL_STEP_NO_ROULETTE leaves a state live whose bounce the roulette would have ended.
 template <int STAGE, bool CYL>
@@ -63,8 +55,6 @@ __global__ __launch_bounds__(RL_TRACE_BLOCK, RL_TRACE_WPS) __attribute__((amdgpu
     uint64_t seed, uint32_t stream, uint32_t flags, unsigned long long* __restrict__ queue) {
     const RlStagedScene staged = rl_stage_scene<STAGE>(scene, lay);
     const RlSceneView& sv = staged.sv;
-    const RlF4* base = staged.base;
-    const uint32_t tab0 = staged.tab0;
     const uint32_t lane = threadIdx.x & 63u;
     RlWaveScratch* ws = &staged.scratch[threadIdx.x >> 6];
 #ifdef RL_STATS
@@ -112,46 +102,13 @@ __global__ __launch_bounds__(RL_TRACE_BLOCK, RL_TRACE_WPS) __attribute__((amdgpu
         p.ior = 1.0f;
         p.bounce = rl_f2u(q2.y); // the bounce draws block 2 + segments
 
-        // ---- Scene::intersect for every lane's segment (rl_ray_paths_kernel) ----
-        const RlF3 o = p.origin, d = p.direction;
-        const float d2 = d.x * d.x + d.y * d.y + d.z * d.z;
-        const bool exhaustive = live && !(fabsf(d2 - 1.0f) <= 0x1p-20f && fabsf(o.x) < INFINITY && fabsf(o.y) < INFINITY && fabsf(o.z) < INFINITY);
-        const bool scanned = live && !exhaustive;
-        RlHit hit = rl_scan_wave<CYL, RL_LEAN_SPLIT, STAGE != RL_STAGE_NONE, STAGE != RL_STAGE_NONE && RL_W_S && RL_LEAN_HOIST, STAGE == RL_STAGE_ALL,
-                                 STAGE != RL_STAGE_NONE, STAGE != RL_STAGE_ALL>(sv, base + (lay.off_cull - tab0), CYL ? base + (lay.off_prism_cyl - tab0) : nullptr,
-                                                                                lay.group_gc, lay.small_ordered, lay.cull_cmax2, lay.n_cluster_groups,
-                                                                                lay.n_prism_groups, lay.n_cluster_supers, lay.super_g, staged.ring_t,
-                                                                                scanned ? o : rl_f3(0.0f, 0.0f, 0.0f), scanned ? d : rl_f3(0.0f, 0.0f, 0.0f),
-                                                                                scanned ? 0u : 0x80000000u, ws, lane RL_TACC_ARG);
-        RL_T0(t_exhaustive);
-        RL_STAT(RL_ST_X_LANES, __popcll(__builtin_amdgcn_ballot_w64(exhaustive)));
-        RL_STAT(RL_ST_X_ITERS, __builtin_amdgcn_ballot_w64(exhaustive) != 0);
-        if (exhaustive) hit = rl_query_exhaustive(sv, o, d);
-        RL_T1(RL_ST_T_EXHAUSTIVE, t_exhaustive);
+        // ---- Scene::intersect for every lane's segment ----
+        const RlHit hit = rl_intersect_segment<STAGE, CYL>(staged, lay, live, p.origin, p.direction, ws, lane RL_TACC_ARG);
 
         // ---- the hit record, as rl_query_kernel writes it for t_max = INFINITY ----
         RL_T0(t_camera);
         if (live) {
-            if (RlRayHit* out_hits = rl_step_hits(hits)) {
-                RlRayHit out;
-                out.isect.position = out.isect.normal = out.isect.tangent = RlVector3{0.0f, 0.0f, 0.0f};
-                out.isect.distance = 0.0f;
-                out.object = RL_OBJECT_NONE;
-                out.reserved = 0u;
-                if (hit.obj != RL_HIT_NONE) {
-                    const uint32_t kinds = rl_f2u(sv.objects[hit.obj].w);
-                    const uint32_t surface_kind = rl_object_surface(kinds);
-                    const RlIsect is = rl_finish_hit(sv, o, d, hit, surface_kind, rl_object_group(kinds));
-                    const RlF3 axis = surface_kind == RL_SURFACE_SPHERE ? rl_cross(rl_f3(0.0f, 1.0f, 0.0f), is.normal) : rl_f3(0.0f, 0.0f, 0.0f);
-                    const RlF3 tangent = rl_normalise(axis);
-                    out.isect.position = RlVector3{is.position.x, is.position.y, is.position.z};
-                    out.isect.normal = RlVector3{is.normal.x, is.normal.y, is.normal.z};
-                    out.isect.tangent = RlVector3{tangent.x, tangent.y, tangent.z};
-                    out.isect.distance = hit.t;
-                    out.object = hit.obj;
-                }
-                out_hits[i] = out;
-            }
+            if (RlRayHit* out_hits = rl_opaque(hits)) out_hits[i] = rl_ray_hit_of(sv, p.origin, p.direction, hit, hit.obj != RL_HIT_NONE);
         }
         RL_T1(RL_ST_T_CAMERA, t_camera);
 

@@ -4,18 +4,16 @@ declarations, and the compiled film kernels' resources (hipcc cross-compiles her
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import robigo_luculenta_amd as R
 from robigo_luculenta_amd import _lib
+from _device_build import device_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "robigo_luculenta_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 RL_E_INVALID = -1
 FILM_VARIANTS = 6   # (nothing / the tables / the whole scene staged in LDS) x prisms with / without a second bound
 ENTRY_POINTS = ("rl_plot_unit_plot_photons", "rl_plot_unit_plot_photons_device", "rl_plot_unit_render_samples",
@@ -100,25 +98,10 @@ def test_render_samples_bad_arguments_are_invalid_in_the_documented_order(name):
 
 
 @pytest.fixture(scope="module")
-def film_kernels(tmp_path_factory):
+def film_kernels():
     """Metadata of every kernel of the module from the device-only -S compile with the library's own flags."""
-    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
-        pytest.skip("no hipcc")
-    make = open(os.path.join(CSRC, "Makefile")).read()
-    flags = re.search(r"^FLAGS = (.*?)\n(?!\s)", make, re.S | re.M).group(1).replace("\\\n", " ")
-    flags = flags.replace("$(ARCH)", "gfx950").replace("$(EXTRA)", "").split()
-    asm = str(tmp_path_factory.mktemp("film") / "k.s")
-    run = subprocess.run([HIPCC] + flags + ["-DRL_BUILD_ID=\"x\"", "--cuda-device-only", "-S", "-o", asm, "rl_api.hip"], cwd=CSRC,
-                         capture_output=True, timeout=900)
-    assert run.returncode == 0, run.stderr.decode()[-2000:]
-    text = open(asm).read()
-    meta = text[text.index(".amdgpu_metadata"):]
-    kernels = {}
-    for entry in re.split(r"\n  - ", meta):
-        m = re.search(r"^\s+\.name:\s+(\S+)$", entry, re.M)
-        if m:
-            kernels[m.group(1)] = {k: int(v) for k, v in re.findall(r"^\s+\.(\w+):\s+(\d+)$", entry, re.M)}
-    return kernels
+    return device_build()[1]
+
 
 
 def test_film_kernels_are_free_of_scratch_and_spills(film_kernels):

@@ -3,46 +3,20 @@ every variant of rl_trace_kernel fits 120 VGPRs -- at four waves per SIMD that l
 which is what lets PlotUnit::plot, GatherUnit::accumulate and the clears run BESIDE a resident (open) trace kernel
 instead of behind it (DESIGN.md 5; the behavioural check is tests/test_gpu_multi.py::test_small_kernels_run_beside...),
 no variant uses scratch memory, and the small kernels fit the registers that are left."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "robigo_luculenta_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from _device_build import device_build
 
 
 @pytest.fixture(scope="module")
-def usage(tmp_path_factory):
-    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
-        pytest.skip("no hipcc")
-    make = open(os.path.join(CSRC, "Makefile")).read()
-    flags = re.search(r"^FLAGS = (.*?)\n(?!\s)", make, re.S | re.M).group(1).replace("\\\n", " ")
-    flags = flags.replace("$(ARCH)", "gfx950").replace("$(EXTRA)", "").split()
-    out = str(tmp_path_factory.mktemp("res") / "k.o")
-    run = subprocess.run([HIPCC] + flags + ["-DRL_BUILD_ID=\"x\"", "--cuda-device-only", "-c", "-o", out, "rl_api.hip",
-                                            "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, capture_output=True, timeout=900)
-    assert run.returncode == 0, run.stderr.decode()[-2000:]
-    kernels, name = {}, None
-    for line in run.stderr.decode().splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+) \[", line)
-        if m and name:
-            kernels[name][m.group(1).strip()] = int(m.group(2))
-    assert kernels, run.stderr.decode()[-2000:]
-    asm = out[:-2] + ".s"   # the same compilation as text, for the checks that read instructions
-    run = subprocess.run([HIPCC] + flags + ["-DRL_BUILD_ID=\"x\"", "--cuda-device-only", "-S", "-o", asm, "rl_api.hip"], cwd=CSRC,
-                         capture_output=True, timeout=900)
-    assert run.returncode == 0, run.stderr.decode()[-2000:]
-    kernels["__asm__"] = open(asm).read()
+def usage():
+    text, _, remarks = device_build()
+    kernels = dict(remarks)
+    kernels["__asm__"] = text   # the same compilation as text, for the checks that read instructions
     return kernels
+
 
 
 TRACE_NAME = r"_Z(?:15rl_trace_kernel|20rl_trace_kernel_open)ILi([012])ELb([01])ELb([01])E"   # <stage, fused, cylinders>

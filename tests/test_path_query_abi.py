@@ -5,18 +5,16 @@ oracle's own render on camera rays of the host build of the kernel's per-path he
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import robigo_luculenta_amd as R
 from robigo_luculenta_amd import _lib
+from _device_build import device_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "robigo_luculenta_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 RL_E_INVALID = -1
 PATH_VARIANTS = 6   # (nothing / the tables / the whole scene staged in LDS) x prisms with / without a second bound
 ENTRY_POINTS = ("rl_scene_camera_rays", "rl_scene_camera_rays_device", "rl_scene_render_rays", "rl_scene_render_rays_device")
@@ -118,25 +116,11 @@ def test_bad_arguments_after_the_scene_check():
 
 
 @pytest.fixture(scope="module")
-def path_kernels(tmp_path_factory):
+def path_kernels():
     """Metadata of the path and camera kernels from the device-only -S compile with the library's own flags."""
-    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
-        pytest.skip("no hipcc")
-    make = open(os.path.join(CSRC, "Makefile")).read()
-    flags = re.search(r"^FLAGS = (.*?)\n(?!\s)", make, re.S | re.M).group(1).replace("\\\n", " ")
-    flags = flags.replace("$(ARCH)", "gfx950").replace("$(EXTRA)", "").split()
-    asm = str(tmp_path_factory.mktemp("paths") / "k.s")
-    run = subprocess.run([HIPCC] + flags + ["-DRL_BUILD_ID=\"x\"", "--cuda-device-only", "-S", "-o", asm, "rl_api.hip"], cwd=CSRC,
-                         capture_output=True, timeout=900)
-    assert run.returncode == 0, run.stderr.decode()[-2000:]
-    text = open(asm).read()
-    meta = text[text.index(".amdgpu_metadata"):]
-    kernels = {}
-    for entry in re.split(r"\n  - ", meta):
-        m = re.search(r"^\s+\.name:\s+(\S+)$", entry, re.M)
-        if m and ("rl_ray_paths_kernel" in m.group(1) or "rl_camera_rays_kernel" in m.group(1)):
-            kernels[m.group(1)] = {k: int(v) for k, v in re.findall(r"^\s+\.(\w+):\s+(\d+)$", entry, re.M)}
-    return kernels
+    metadata = device_build()[1]
+    return {n: k for n, k in metadata.items() if "rl_ray_paths_kernel" in n or "rl_camera_rays_kernel" in n}
+
 
 
 def test_path_and_camera_kernels_are_free_of_scratch_and_spills(path_kernels):
@@ -191,10 +175,25 @@ def _prologue(text, start):
     return re.sub(r"\s+", " ", body).strip()
 
 
-def test_path_kernel_stages_the_scene_as_the_query_kernel_does():
-    """rl_stage_scene (rl_paths.hip.h) is the query kernel's prologue, statement for statement: the two must not drift apart."""
-    query = open(os.path.join(CSRC, "rl_query.hip.h")).read()
-    paths = open(os.path.join(CSRC, "rl_paths.hip.h")).read()
-    a = _prologue(query, query.index("void rl_query_kernel("))
-    b = _prologue(paths, paths.index("RlStagedScene rl_stage_scene("))
+def test_the_scene_is_staged_in_one_place():
+    """The staging prologue is rl_stage_scene (rl_kernels.hip.h) and every persistent kernel beside the trace kernel calls it.  The
+    trace body keeps the statements as its own text (calling the function changed its instructions): the one other place they
+    appear, and it must not drift from the function."""
+    headers = {n: open(os.path.join(CSRC, n)).read() for n in sorted(os.listdir(CSRC)) if n.endswith((".h", ".hip"))}
+    code = {n: re.sub(r"//[^\n]*", "", t) for n, t in headers.items()}
+    for needle in ("extern __shared__ __attribute__((aligned(512)))", "sv.records = big"):
+        assert {n: t.count(needle) for n, t in code.items() if needle in t} == {"rl_kernels.hip.h": 2}, needle
+    kernels = headers["rl_kernels.hip.h"]
+    first, second = kernels.index("RlStagedScene rl_stage_scene("), kernels.index("void rl_trace_body(")
+    assert first < second
+    a, b = _prologue(kernels, first), _prologue(kernels, second)
     assert a == b and len(a) > 1000
+    assert kernels.index("extern __shared__", first) < second   # (the first copy is the function's, the second the trace body's)
+    for name, kernel in (("rl_query.hip.h", "void rl_query_kernel("), ("rl_paths.hip.h", "void rl_paths_body("), ("rl_step.hip.h", "void rl_step_kernel(")):
+        text = headers[name]
+        start = text.index(kernel)
+        assert "rl_stage_scene<STAGE>(scene, lay)" in text[start:start + 1500], name
+    paths = headers["rl_paths.hip.h"]
+    for wrapper in ("void rl_ray_paths_kernel(", "void rl_film_paths_kernel("):
+        start = paths.index(wrapper)
+        assert "rl_paths_body<STAGE, CYL," in paths[start:start + 800], wrapper

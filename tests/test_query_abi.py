@@ -4,18 +4,16 @@ here): every instantiation free of scratch memory and spills."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import robigo_luculenta_amd as R
 from robigo_luculenta_amd import _lib
+from _device_build import device_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "robigo_luculenta_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 RL_E_INVALID = -1
 QUERY_VARIANTS = 6   # (nothing / the tables / the whole scene staged in LDS) x prisms with / without a second bound
 
@@ -60,25 +58,11 @@ def test_bad_arguments_are_invalid_with_a_message(name):
 
 
 @pytest.fixture(scope="module")
-def query_kernels(tmp_path_factory):
+def query_kernels():
     """Metadata of every rl_query_kernel instantiation from the device-only -S compile with the library's own flags."""
-    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
-        pytest.skip("no hipcc")
-    make = open(os.path.join(CSRC, "Makefile")).read()
-    flags = re.search(r"^FLAGS = (.*?)\n(?!\s)", make, re.S | re.M).group(1).replace("\\\n", " ")
-    flags = flags.replace("$(ARCH)", "gfx950").replace("$(EXTRA)", "").split()
-    asm = str(tmp_path_factory.mktemp("query") / "k.s")
-    run = subprocess.run([HIPCC] + flags + ["-DRL_BUILD_ID=\"x\"", "--cuda-device-only", "-S", "-o", asm, "rl_api.hip"], cwd=CSRC,
-                         capture_output=True, timeout=900)
-    assert run.returncode == 0, run.stderr.decode()[-2000:]
-    text = open(asm).read()
-    meta = text[text.index(".amdgpu_metadata"):]
-    kernels = {}
-    for entry in re.split(r"\n  - ", meta):
-        m = re.search(r"^\s+\.name:\s+(\S+)$", entry, re.M)
-        if m and "rl_query_kernel" in m.group(1):
-            kernels[m.group(1)] = {k: int(v) for k, v in re.findall(r"^\s+\.(\w+):\s+(\d+)$", entry, re.M)}
-    return kernels, text
+    text, metadata, _ = device_build()
+    return {n: k for n, k in metadata.items() if "rl_query_kernel" in n}, text
+
 
 
 def test_every_query_kernel_variant_is_free_of_scratch_and_spills(query_kernels):

@@ -5,18 +5,16 @@ restatement of the whole loop (tests/_path_oracle.py), which test_path_query_abi
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import robigo_luculenta_amd as R
 from robigo_luculenta_amd import _lib
+from _device_build import device_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "robigo_luculenta_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 RL_E_INVALID = -1
 STEP_VARIANTS = 6   # (nothing / the tables / the whole scene staged in LDS) x prisms with / without a second bound
 ENTRY_POINTS = ("rl_scene_begin_paths", "rl_scene_begin_paths_device", "rl_scene_step_paths", "rl_scene_step_paths_device")
@@ -107,26 +105,11 @@ def test_begin_paths_bad_arguments_are_invalid_with_a_message(name):
 
 
 @pytest.fixture(scope="module")
-def step_kernels(tmp_path_factory):
+def step_kernels():
     """Metadata of the step and begin kernels from the device-only -S compile with the library's own flags."""
-    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
-        pytest.skip("no hipcc")
-    make = open(os.path.join(CSRC, "Makefile")).read()
-    flags = re.search(r"^FLAGS = (.*?)\n(?!\s)", make, re.S | re.M).group(1).replace("\\\n", " ")
-    flags = flags.replace("$(ARCH)", "gfx950").replace("$(EXTRA)", "").split()
-    asm = str(tmp_path_factory.mktemp("step") / "k.s")
-    run = subprocess.run([HIPCC] + flags + ["-DRL_BUILD_ID=\"x\"", "--cuda-device-only", "-S", "-o", asm, "rl_api.hip"], cwd=CSRC,
-                         capture_output=True, timeout=900)
-    assert run.returncode == 0, run.stderr.decode()[-2000:]
-    text = open(asm).read()
-    meta = text[text.index(".amdgpu_metadata"):]
-    kernels = {}
-    for entry in re.split(r"\n  - ", meta):
-        m = re.search(r"^\s+\.name:\s+(\S+)$", entry, re.M)
-        if m and any(k in m.group(1) for k in ("rl_step_kernel", "rl_begin_paths_kernel", "rl_ray_paths_kernel")):
-            kernels[m.group(1)] = {k: int(v) for k, v in re.findall(r"^\s+\.(\w+):\s+(\d+)$", entry, re.M)}
-            kernels[m.group(1)]["dynamic_stack"] = int(bool(re.search(r"^\s+\.uses_dynamic_stack:\s+true", entry, re.M)))
-    return kernels
+    metadata = device_build()[1]
+    return {n: k for n, k in metadata.items() if any(sub in n for sub in ("rl_step_kernel", "rl_begin_paths_kernel", "rl_ray_paths_kernel"))}
+
 
 
 def test_step_and_begin_kernels_are_free_of_scratch_and_spills(step_kernels):
