@@ -79,6 +79,10 @@ extern "C" {
     pub fn rl_scene_intersect(scene: *const RlScene, primitive_fetch: c_int, rays: *const RlRay, n_rays: u32, hits: *mut RlRayHit) -> c_int;
     pub fn rl_scene_intersect_device(scene: *const RlScene, primitive_fetch: c_int, device_rays: *const RlRay, n_rays: u32,
                                      device_hits: *mut RlRayHit) -> c_int;
+    // the any-hit form: one byte per ray, 1 where rl_scene_intersect would report an object
+    pub fn rl_scene_occluded(scene: *const RlScene, primitive_fetch: c_int, rays: *const RlRay, n_rays: u32, occluded: *mut u8) -> c_int;
+    pub fn rl_scene_occluded_device(scene: *const RlScene, primitive_fetch: c_int, device_rays: *const RlRay, n_rays: u32,
+                                    device_occluded: *mut u8) -> c_int;
     pub fn rl_scene_camera_rays(scene: *const RlScene, width: u32, height: u32, seed: u64, stream: u32, first_path_index: u64, n: u32,
                                 samples: *mut RlCameraSample) -> c_int;
     pub fn rl_scene_camera_rays_device(scene: *const RlScene, width: u32, height: u32, seed: u64, stream: u32, first_path_index: u64,

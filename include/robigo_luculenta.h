@@ -188,6 +188,24 @@ int rl_scene_intersect(const RlScene* scene, int primitive_fetch, const RlRay* r
 int rl_scene_intersect_device(const RlScene* scene, int primitive_fetch, const RlRay* device_rays, uint32_t n_rays,
                               RlRayHit* device_hits);
 
+/* The any-hit form of the query above, for shadow rays, ambient occlusion and visibility between two points: occluded[i] is 1 if
+ * rl_scene_intersect would return object != RL_OBJECT_NONE for rays[i], and 0 otherwise -- some object has a reference hit
+ * distance d with d < t_max and d < 1e12.  A hit at exactly t_max does not block; a t_max that is NaN, zero or negative never
+ * blocks; t_max = INFINITY asks whether the ray hits anything at all.  One byte per ray and nothing else is written: bytes past
+ * n_rays are not touched.  The answer depends on the scene and the ray alone -- not on how a batch is split, the fetch mode, the
+ * kernel variant, the order of evaluation or other callers: "some hit below t_max" and "the nearest hit is below t_max" are the
+ * same predicate, so the kernel may stop at the first hit it finds below the ray's bound, and it scans no further than t_max (a
+ * short ray in a large scene costs far less than rl_scene_intersect with the same t_max).  Rays are used as given: a ray with
+ * |direction|^2 further than 2^-20 from 1, or with a non-finite component, is decided by the exact linear scan, as in
+ * rl_scene_intersect.  Everything else is that call's: the argument checks in the same order (an unknown fetch mode, NULL rays
+ * or NULL output with n_rays > 0, a NULL scene: RL_E_INVALID), n_rays == 0 does nothing, the host form stages in chunks of 2^20
+ * rays, the _device form takes device pointers on the scene's device and refuses pageable host memory, both return when the
+ * bytes are written, calls are safe from several host threads at once on one scene, and a call orders against open launches
+ * as rl_scene_intersect does. */
+int rl_scene_occluded(const RlScene* scene, int primitive_fetch, const RlRay* rays, uint32_t n_rays, uint8_t* occluded);
+int rl_scene_occluded_device(const RlScene* scene, int primitive_fetch, const RlRay* device_rays, uint32_t n_rays,
+                             uint8_t* device_occluded);
+
 /* ---- TraceUnit::render_ray as a batched call: caller-supplied spectral rays ----------------- */
 
 /* Ray (ray.rs:19-33) with its wavelength; the probability is folded into the path's intensity, which starts at 1. */
@@ -289,7 +307,7 @@ typedef struct RlPathState {
 
 /* A wavefront form of rl_scene_render_rays: the path state lives in the caller's buffer, and every call makes one segment, so
  * that the caller can act between segments (end paths by a rule of their own, record vertices, cast shadow rays from a vertex
- * with rl_scene_intersect, re-weight or re-aim paths).
+ * with rl_scene_occluded, re-weight or re-aim paths).
  *
  * rl_scene_begin_paths: states[i] is rays[i] as path first_path_index + i before its first segment: intensity 1, continue
  * chance 1, segments 0, value 0, object RL_OBJECT_NONE, end RL_PATH_LIVE.  A ray with a NaN or infinite wavelength gets end

@@ -38,6 +38,9 @@ int rl_debug_variant_launches(uint64_t* out);
 /* out[v], v = 0..5: launches of instantiation v of the query kernel (rl_scene_intersect*) since the library was loaded;
  * v = 2 * stage + (prisms carry a second bound), stage 0: nothing staged in LDS, 1: the scene's tables, 2: the whole scene. */
 int rl_debug_query_launches(uint64_t* out);
+/* out[v], v = 0..5: launches of instantiation v of the occlusion kernel (rl_scene_occluded*) since the library was loaded, indexed
+ * as rl_debug_query_launches is. */
+int rl_debug_occlusion_launches(uint64_t* out);
 /* out[v], v = 0..5: launches of instantiation v of the path kernel (rl_scene_render_rays*) since the library was loaded, indexed
  * as rl_debug_query_launches is. */
 int rl_debug_path_launches(uint64_t* out);

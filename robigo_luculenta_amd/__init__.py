@@ -148,6 +148,30 @@ class Scene(_Handle):
             raise ValueError("rays must hold whole 32-byte records and hits room for as many 48-byte ones")
         check(lib.rl_scene_intersect_device(self._h, fetch, C.c_void_p(rays.data_ptr()), n, C.c_void_p(hits.data_ptr())))
 
+    def occluded(self, origins, directions, t_max=np.inf, fetch=FETCH_LDS):
+        """rl_scene_occluded: is there a hit with distance < t_max on each of n rays -- would intersect() report an object?
+        origins, directions: (n, 3) float32; t_max: a scalar or n values.  Returns an (n,) uint8 array of 1 (blocked) and 0."""
+        origins = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        directions = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        if len(origins) != len(directions):
+            raise ValueError("origins and directions differ in length")
+        rays = np.zeros(len(origins), dtype=RAY_DTYPE)
+        rays["origin"] = origins
+        rays["direction"] = directions
+        rays["t_max"] = np.broadcast_to(np.asarray(t_max, dtype=np.float32), (len(rays),))
+        out = np.empty(len(rays), dtype=np.uint8)
+        check(lib.rl_scene_occluded(self._h, fetch, rays.ctypes.data_as(C.c_void_p), len(rays), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def occluded_device(self, rays, occluded, fetch=FETCH_LDS):
+        """rl_scene_occluded_device: `rays` and `occluded` are device buffers on the scene's device with data_ptr() (e.g. torch
+        tensors) holding n RAY_DTYPE records and room for n bytes; n is taken from the rays' size in bytes."""
+        n_bytes = lambda t: t.numel() * t.element_size()
+        n = n_bytes(rays) // RAY_DTYPE.itemsize
+        if n_bytes(rays) != n * RAY_DTYPE.itemsize or n_bytes(occluded) < n:
+            raise ValueError("rays must hold whole 32-byte records and occluded room for as many bytes")
+        check(lib.rl_scene_occluded_device(self._h, fetch, C.c_void_p(rays.data_ptr()), n, C.c_void_p(occluded.data_ptr())))
+
     def camera_rays(self, width, height, seed, stream, first, n):
         """rl_scene_camera_rays: the camera half of paths first .. first + n - 1 of (seed, stream) for a width x height image --
         the ray, its wavelength and the screen position x, y that rl_trace_unit_render gives those paths.  Returns an (n,)
@@ -576,6 +600,14 @@ def query_launches():
     index = 2 * stage + 1 * prisms with a second bound, stage 0: nothing staged in LDS, 1: the scene's tables, 2: the whole scene."""
     out = (C.c_uint64 * 6)()
     check(lib.rl_debug_query_launches(out))
+    return list(out)
+
+
+def occlusion_launches():
+    """rl_debug_occlusion_launches: launches per instantiation of the occlusion kernel (Scene.occluded*) since the library was
+    loaded, indexed as query_launches()."""
+    out = (C.c_uint64 * 6)()
+    check(lib.rl_debug_occlusion_launches(out))
     return list(out)
 
 

@@ -119,6 +119,8 @@ SIGNATURES = {
     "rl_scene_destroy": (_i, [_vp]),
     "rl_scene_intersect": (_i, [_vp, _i, _vp, _u32, _vp]),
     "rl_scene_intersect_device": (_i, [_vp, _i, _vp, _u32, _vp]),
+    "rl_scene_occluded": (_i, [_vp, _i, _vp, _u32, _vp]),
+    "rl_scene_occluded_device": (_i, [_vp, _i, _vp, _u32, _vp]),
     "rl_scene_camera_rays": (_i, [_vp, _u32, _u32, _u64, _u32, _u64, _u32, _vp]),
     "rl_scene_camera_rays_device": (_i, [_vp, _u32, _u32, _u64, _u32, _u64, _u32, _vp]),
     "rl_scene_render_rays": (_i, [_vp, _i, _u64, _u32, _u64, _u32, _vp, _u32, _vp]),
@@ -190,6 +192,7 @@ DEBUG_SIGNATURES = {
     "rl_debug_batch_histogram": (_i, [_i, _vp]),
     "rl_debug_variant_launches": (_i, [_vp]),
     "rl_debug_query_launches": (_i, [_vp]),
+    "rl_debug_occlusion_launches": (_i, [_vp]),
     "rl_debug_path_launches": (_i, [_vp]),
     "rl_debug_film_launches": (_i, [_vp]),
     "rl_debug_step_launches": (_i, [_vp]),

@@ -42,6 +42,7 @@
 #include "../../include/robigo_luculenta_debug.h"
 #include "rl_kernels.hip.h"
 #include "rl_query.hip.h"
+#include "rl_occlusion.hip.h"
 #include "rl_film.hip.h"
 #include "rl_paths.hip.h"
 #include "rl_step.hip.h"
@@ -326,9 +327,9 @@ int launch_trace(RlTraceUnit* u, const RlScene* scene, RlMappedPhoton* photons, 
     return RL_OK;
 }
 
-// ---- the persistent ray kernels beside the trace kernel (rl_query.hip.h, rl_paths.hip.h, rl_step.hip.h) -------------------
+// ---- the persistent ray kernels beside the trace kernel (rl_query.hip.h, rl_occlusion.hip.h, rl_paths.hip.h, rl_step.hip.h) ----
 // A family is one kernel template's six instantiations, index = 2 * stage + cylinders, and the launches of each since the library
-// was loaded (rl_debug_{query,path,film,step}_launches).  P: the kernel's parameters behind the scene blob and its layout.
+// was loaded (rl_debug_{query,occlusion,path,film,step}_launches).  P: the kernel's parameters behind the scene blob and its layout.
 template <class... P>
 struct KernelFamily {
     void (*variants[6])(const RlF4*, RlSceneLayout, P...);
@@ -336,6 +337,7 @@ struct KernelFamily {
 };
 #define RL_VARIANTS(K) {{K<RL_STAGE_NONE, false>, K<RL_STAGE_NONE, true>, K<RL_STAGE_TABLES, false>, K<RL_STAGE_TABLES, true>, K<RL_STAGE_ALL, false>, K<RL_STAGE_ALL, true>}, {}}
 KernelFamily<const RlRay*, RlRayHit*, uint32_t> g_query_kernels = RL_VARIANTS(rl_query_kernel);
+KernelFamily<const RlRay*, uint8_t*, uint32_t> g_occlusion_kernels = RL_VARIANTS(rl_occlusion_kernel);
 KernelFamily<const RlSpectralRay*, RlPathResult*, uint32_t, uint64_t, uint32_t, uint64_t, uint32_t, unsigned long long*> g_path_kernels = RL_VARIANTS(rl_ray_paths_kernel);
 KernelFamily<const RlCameraSample*, RlPathResult*, uint32_t, uint64_t, uint32_t, uint64_t, uint32_t, unsigned long long*> g_film_kernels = RL_VARIANTS(rl_film_paths_kernel);
 KernelFamily<RlPathState*, RlRayHit*, uint32_t, uint64_t, uint32_t, uint32_t, unsigned long long*> g_step_kernels = RL_VARIANTS(rl_step_kernel);
@@ -840,6 +842,29 @@ int rl_scene_intersect_device(const RlScene* scene, int primitive_fetch, const R
     if ((rc = device_buffers_check(scene, device_rays, device_hits, "rl_scene_intersect_device", "rl_scene_intersect")) != RL_OK) return rc;
     return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
         return launch_persistent(g_query_kernels, scene, primitive_fetch, cus, q->stream, n_rays, device_rays, device_hits, n_rays);
+    });
+}
+
+// One byte per ray: the host form stages them through the hit records' buffer.
+int rl_scene_occluded(const RlScene* scene, int primitive_fetch, const RlRay* rays, uint32_t n_rays, uint8_t* occluded) {
+    const int rc = query_check(scene, primitive_fetch, rays, n_rays, occluded);
+    if (rc != RL_OK || n_rays == 0) return rc;
+    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
+        return staged_chunks(q, q->stream, n_rays, {staged_in(STAGING_RAYS, rays, sizeof(RlRay)), staged_out(STAGING_HITS, occluded, sizeof(uint8_t))},
+                             [&](uint32_t, uint32_t k) -> int {
+                                 return launch_persistent(g_occlusion_kernels, scene, primitive_fetch, cus, q->stream, k, (const RlRay*)q->staging[STAGING_RAYS],
+                                                          (uint8_t*)q->staging[STAGING_HITS], k);
+                             });
+    });
+}
+
+int rl_scene_occluded_device(const RlScene* scene, int primitive_fetch, const RlRay* device_rays, uint32_t n_rays, uint8_t* device_occluded) {
+    int rc = query_check(scene, primitive_fetch, device_rays, n_rays, device_occluded);
+    if (rc != RL_OK || n_rays == 0) return rc;
+    if ((rc = use_device(scene->device)) != RL_OK) return rc;
+    if ((rc = device_buffers_check(scene, device_rays, device_occluded, "rl_scene_occluded_device", "rl_scene_occluded")) != RL_OK) return rc;
+    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
+        return launch_persistent(g_occlusion_kernels, scene, primitive_fetch, cus, q->stream, n_rays, device_rays, device_occluded, n_rays);
     });
 }
 
@@ -2275,6 +2300,7 @@ int rl_debug_variant_launches(uint64_t* out) {
 }
 
 int rl_debug_query_launches(uint64_t* out) { return family_launches(g_query_kernels, out); }
+int rl_debug_occlusion_launches(uint64_t* out) { return family_launches(g_occlusion_kernels, out); }
 int rl_debug_path_launches(uint64_t* out) { return family_launches(g_path_kernels, out); }
 int rl_debug_film_launches(uint64_t* out) { return family_launches(g_film_kernels, out); }
 int rl_debug_step_launches(uint64_t* out) { return family_launches(g_step_kernels, out); }

@@ -442,10 +442,21 @@ struct RlOpenWg {
 //     when one of its pairs is undecided, then min-merges.
 // Results are min-merged per owning ray as 64-bit (distance bits, object index) keys in LDS: exactly
 // scene.rs:51's strict `<` over objects in scan order, in any evaluation order.
-template <bool CYL, bool SPLIT, bool UNROLL_S, bool HOIST_S, bool SPHERES_IN_LDS, bool TABLES_IN_LDS, bool SUPER>
+//
+// BOUNDED (the occlusion kernel, rl_occlusion.hip.h; every other caller leaves it off and gets the scan above, instruction for
+// instruction): the any-hit form.  The scan starts from the caller's bound `t_bound` = min(t_max, 1e12) instead of 1e12 -- the small
+// primitives reject candidates at or beyond it, the far bound of every cull test is derived from it from the first round on (the
+// cull is conservative in `far`: this only removes work), and the merge keys are seeded with it -- and a lane stops once it
+// holds a hit below its bound: behind the small primitives it turns idle, behind a nested round of the progressive-far variants it
+// fails every further wave-uniform cull, in front of the prisms it turns idle again; a wave whose lanes are all idle skips the
+// stages that are left.  "Some hit below the bound" and "the nearest hit is below the bound" are the same predicate, so the
+// caller's `hit.t < t_max` on what comes back is exact -- and it stays the caller's: a key seeded (bits(t_bound), 0xffffffff) loses
+// to a real hit at exactly t_bound, the seed is an accelerator and not the predicate.  hit.obj / hit.t are those of SOME hit below
+// the bound then, not of the nearest.
+template <bool CYL, bool SPLIT, bool UNROLL_S, bool HOIST_S, bool SPHERES_IN_LDS, bool TABLES_IN_LDS, bool SUPER, bool BOUNDED = false>
 __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4* cull, const RlF4* prism_cyl, uint32_t group_gc, uint32_t small_ordered, float sv_cull_cmax2,
                                               uint32_t n_cluster_groups, uint32_t n_prism_groups, uint32_t n_cluster_supers, uint32_t super_g, RlLdsU32* ring_t, RlF3 o, RlF3 dir,
-                                              uint32_t idle_bit, RlWaveScratch* ws, uint32_t lane RL_TACC_PARAM) {
+                                              uint32_t idle_bit, RlWaveScratch* ws, uint32_t lane RL_TACC_PARAM, float t_bound = 1.0e12f) {
     // Explicit LDS address space: generic pointers here would become flat_* accesses.
     constexpr bool PF = SUPER && RL_PROGRESSIVE_FAR;
     RlLdsU64* keys = (RlLdsU64*)ws->key;
@@ -561,6 +572,7 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
     }
     RlHit best;
     best.t = 1.0e12f; // scene.rs:43
+    if constexpr (BOUNDED) best.t = t_bound;
     best.obj = RL_HIT_NONE;
     best.sub = 0;
     RL_T0(t_small);
@@ -658,6 +670,11 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
     keys[lane] = ((unsigned long long)rl_f2u(best.t) << 32) |
                  (unsigned long long)(best.obj == RL_HIT_NONE ? 0xffffffffu : (best.obj << 3));
     RL_T1(RL_ST_T_SMALL, t_small);
+    if constexpr (BOUNDED) {
+        // (`<`: the general form of the small primitives' compare takes a candidate at exactly the bound, which decides nothing)
+        if (best.obj != RL_HIT_NONE && best.t < t_bound) idle_bit = 0x80000000u;
+        if (__builtin_amdgcn_ballot_w64(idle_bit == 0u) == 0) return best;
+    }
 
     // The ray's cull terms (RlCullRay) and its far bound -- the nearest hit so far: here the planes, circles and paraboloids (in
     // the built-in scene the floor, the walls and the ceiling: every ray has one), before the prisms also the spheres -- go to this
@@ -667,8 +684,14 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
     float far = best.t * cr.len;
     rl_store_cull_ray<PF>(ws, lane, cr, far);
     // (RL_PROGRESSIVE_FAR) this lane's own far bound for the wave-uniform loops, refreshed behind a nested round: its key may have come nearer
-#define RL_REFRESH_FAR() \
-    if (PF) far = rl_u2f(((const RlLdsU32*)keys)[2u * lane + 1u]) * cr.len;
+#define RL_REFRESH_FAR()                                                                                \
+    if (PF) {                                                                                           \
+        far = rl_u2f(((const RlLdsU32*)keys)[2u * lane + 1u]) * cr.len;                                 \
+        /* (BOUNDED: a lane that has a hit below its bound by now fails every wave-uniform cull from here on) */ \
+        if constexpr (BOUNDED) {                                                                        \
+            if (rl_u2f(((const RlLdsU32*)keys)[2u * lane + 1u]) < t_bound) cr.q = -__builtin_inff();    \
+        }                                                                                               \
+    }
 
     // ---- ring B round: exact sphere tail for (record position, owner) pairs ----
     auto process_spheres = [&](uint32_t count) {
@@ -1085,6 +1108,16 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
     RL_T0(t_prism);
     far = rl_u2f((uint32_t)(keys[lane] >> 32)) * cr.len; // every sphere has been merged by now (process_spheres ends in a wave sync)
     if (!PF) ((RlLdsF*)&ws->far[0])[lane] = far;
+    if constexpr (BOUNDED) {
+        const unsigned long long k_now = keys[lane];
+        if (rl_u2f((uint32_t)(k_now >> 32)) < t_bound) idle_bit = 0x80000000u;
+        if (__builtin_amdgcn_ballot_w64(idle_bit == 0u) == 0) { // nobody is left to ask the prisms: the answer as the end of the scan reads it
+            best.t = rl_u2f((uint32_t)(k_now >> 32));
+            best.obj = (uint32_t)k_now == 0xffffffffu ? RL_HIT_NONE : (uint32_t)k_now >> 3;
+            best.sub = (uint32_t)k_now == 0xffffffffu ? 0u : (uint32_t)k_now & 7u;
+            return best;
+        }
+    }
 
     // ---- hexagonal prisms: cull -> compact -> evaluate -> merge ----
     auto process_prisms = [&](uint32_t count) {
