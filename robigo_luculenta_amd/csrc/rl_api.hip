@@ -87,6 +87,12 @@ int use_device(int device) {
     return RL_OK;
 }
 
+// A unit's own stream: non-blocking, so that it never waits for the null stream (RL_BLOCKING_STREAMS in the environment:
+// measurement runs ask for a blocking one).
+hipError_t create_unit_stream(hipStream_t* stream) {
+    return hipStreamCreateWithFlags(stream, getenv("RL_BLOCKING_STREAMS") ? hipStreamDefault : hipStreamNonBlocking);
+}
+
 struct EventPair {
     hipEvent_t start, stop;
 };
@@ -1000,7 +1006,7 @@ int rl_trace_unit_create(int device, uint32_t id, uint32_t width, uint32_t heigh
     if (e == hipSuccess) e = hipMemset(u->photons, 0, (size_t)n_photons * sizeof(RlMappedPhoton)); // MappedPhoton::new
     if (e == hipSuccess) e = hipMalloc((void**)&u->queue, 3 * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemset(u->queue, 0, 3 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&u->stream, getenv("RL_BLOCKING_STREAMS") ? hipStreamDefault : hipStreamNonBlocking);
+    if (e == hipSuccess) e = create_unit_stream(&u->stream);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&u->rendered, hipEventDisableTiming);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr); // the memsets above ran on the null stream
     if (e != hipSuccess) {
@@ -1557,7 +1563,7 @@ int rl_plot_unit_create(int device, uint32_t id, uint32_t width, uint32_t height
     }
     if (e == hipSuccess) e = hipMalloc((void**)&u->cie, sizeof RL_CIE1931_XYZ0);
     if (e == hipSuccess) e = hipMemcpy(u->cie, RL_CIE1931_XYZ0, sizeof RL_CIE1931_XYZ0, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&u->stream, getenv("RL_BLOCKING_STREAMS") ? hipStreamDefault : hipStreamNonBlocking);
+    if (e == hipSuccess) e = create_unit_stream(&u->stream);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&u->plotted, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&u->ready, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&u->cleared, hipEventDisableTiming);
@@ -1808,7 +1814,7 @@ int rl_gather_unit_create(int device, uint32_t width, uint32_t height, RlGatherU
     if (e == hipSuccess) e = hipMemset(u->acc, 0, bytes);
     if (e == hipSuccess) e = hipMalloc((void**)&u->comp, bytes);
     if (e == hipSuccess) e = hipMemset(u->comp, 0, bytes);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&u->stream, getenv("RL_BLOCKING_STREAMS") ? hipStreamDefault : hipStreamNonBlocking);
+    if (e == hipSuccess) e = create_unit_stream(&u->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr); // (the null stream only: a resident open trace kernel of another unit is not waited for)
     if (e != hipSuccess) {
         rl_gather_unit_destroy(u);

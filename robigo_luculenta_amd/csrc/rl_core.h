@@ -336,14 +336,9 @@ RL_HD float rl_paraboloid_t(RlF3 offset, RlF3 normal, RlF3 focal_point, RlF3 o, 
     // two floats is a multiple of the smaller one's ulp, so a non-zero -b +- sq is either dominated by the larger operand (>= 2^-91)
     // or a cancellation between two operands that are both >= 2^-91, i.e. a multiple of 2^-114.  (A NaN among them fails the fast
     // path's `pick < 0` as it fails every compare of the literal form: no hit both ways.)
-#ifndef RL_PARAB_CHECK_OLD
     float largest; // max(|b|, sq) -- spelled out: fmaxf comes with a canonicalising v_max_f32 x, x in front (see rl_hex_prism_fast)
     asm("v_max_f32 %0, |%1|, %2" : "=v"(largest) : "v"(b), "v"(sq));
     const bool plain = (a < 0.0f) & ((disc < 0.0f) | (largest >= 8.0779356694631609e-28f)); // 2^-90
-#else
-    const uint32_t up = (rl_f2u(np) & 0x7fffffffu) - 1u, uq = (rl_f2u(nq) & 0x7fffffffu) - 1u;
-    const bool plain = (a < 0.0f) & ((disc < 0.0f) | ((up >= 0x02000000u - 1u) & (uq >= 0x02000000u - 1u)));
-#endif
     if (RL_LIKELY(__builtin_amdgcn_ballot_w64(!plain) == 0)) {
         const float t = 0.5f * pick / a; // (for every lane: the quotient of a miss is discarded -- no branch around the division)
         if (hit_out) {
@@ -543,13 +538,10 @@ RL_HD int rl_hex_prism_fast(const RlF4* pr, RlF3 o, RlF3 d, RlCand* out, RlF4 pr
     float t_in = -INF, t_out = INF;  // carry the plane number in their low 3 bits
     float min_dn = INF, min_ta = INF;
     uint32_t min_pos = 0xffffffffu;  // the smallest positive ta: positive floats order like their bits, negative ones are larger
-#ifndef RL_W_P
-#define RL_W_P 1 // rl_hex_prism_fast on the device: the next plane's records in flight behind this plane's arithmetic (A/B builds set 0)
-#endif
 #if defined(__HIP_DEVICE_COMPILE__)
     float pair_in = 0.0f, pair_out = 0.0f, pair_dn = 0.0f, pair_ta = 0.0f; // the even plane of the current pair (below)
     RlF4 rec_n, rec_off;
-    if (PIPELINED && RL_W_P) {
+    if (PIPELINED) {
         if (PRELOADED) rec_n = pre_n, rec_off = pre_off;
         else rec_n = pr[0], rec_off = pr[1];
     }
@@ -562,7 +554,7 @@ RL_HD int rl_hex_prism_fast(const RlF4* pr, RlF3 o, RlF3 d, RlCand* out, RlF4 pr
         // The next plane's two records are requested before this plane's arithmetic and waited for behind it: one plane
         // in flight, not sixteen loads at once (the round would spill) and not eight LDS round trips in a row either.
         RlF4 cur_n, cur_off;
-        if (PIPELINED && RL_W_P) {
+        if (PIPELINED) {
             cur_n = rec_n, cur_off = rec_off;
             if (k < 7) {
                 rec_n = pr[2 * k + 2];

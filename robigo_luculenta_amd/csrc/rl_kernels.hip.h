@@ -18,8 +18,8 @@
 //     12 hardware f32 atomics per contributing path into the XYZ buffer (fused TraceUnit+PlotUnit);
 //     in fused mode the paths that ended on a light wait in a per-wave LDS queue until 64 of them can
 //     be evaluated (f64 Planck term) and splatted with a full exec mask;
-//   * no MFMA: there is no dense contraction in this workload.  What bounds it (round 5; probes in this file under
-//     RL_EXP_EXTRA): not the vector ALU's lanes but what ONE WAVE can issue -- at four waves per SIMD a wave spends half of its
+//   * no MFMA: there is no dense contraction in this workload.  What bounds it (round 5; the probes' results in
+//     profiles/r05_issue_cost_probes.txt): not the vector ALU's lanes but what ONE WAVE can issue -- at four waves per SIMD a wave spends half of its
 //     time issuing instructions, vector, scalar and LDS alike (a scalar instruction costs what a vector one does, a packed FMA
 //     two, a taken branch two), a third waiting for LDS round trips (an exposed one costs ten instructions, a ds_bpermute_b32
 //     five) and a fifth issue-stalled.  Hence: record loads issued ahead of the data they are used with, the rays' cull terms
@@ -45,7 +45,9 @@
 #define RL_TRACE_BLOCK 1024 // trace kernel: one workgroup of 16 waves per CU shares one LDS copy of the scene
 #endif
 #ifndef RL_TRACE_WPS
-#define RL_TRACE_WPS 4      // waves per SIMD the trace kernel is compiled for (launch bounds; the register caps below follow from it)
+#define RL_TRACE_WPS 4      // waves per SIMD the trace kernel is compiled for (launch bounds; the register caps below follow from it).
+                            // The scan is written for four: a fifth wave was measured and decided against (profiles/r06_fifth_wave.txt),
+                            // and the forms that traded latency for its 96 registers are gone.
 #endif
 #ifndef RL_TRACE_VGPRS
 #define RL_TRACE_VGPRS (RL_TRACE_WPS == 4 ? 128 : 96)      // plain launches: all a wave can have at that occupancy (512 / waves, in eights)
@@ -53,49 +55,7 @@
 #ifndef RL_TRACE_VGPRS_OPEN
 #define RL_TRACE_VGPRS_OPEN (RL_TRACE_WPS == 4 ? 120 : 96) // open launches leave the small kernels of the other units their registers
 #endif
-#ifndef RL_W_S
-#define RL_W_S 1 // ring-S rounds of the plain launches: the children's bounds requested ahead of the cross-lane fetch (A/B builds set 0)
-#endif
-#ifndef RL_W_B
-#define RL_W_B 1 // ring-B rounds: the sphere record, its radius^2 and its object likewise
-#endif
-#ifndef RL_W_M
-#define RL_W_M 1 // cluster-member rounds: the first member likewise
-#endif
-#ifndef RL_W_PR
-#define RL_W_PR 1 // prism rounds: the first plane's two records likewise
-#endif
-#ifndef RL_EMIT_MAX_AGE
-#define RL_EMIT_MAX_AGE 8u
-#endif
-#ifndef RL_OPEN_FULL
-#define RL_OPEN_FULL 1
-#endif
-#ifndef RL_SMALL_UNROLL
-#define RL_SMALL_UNROLL 1
-#endif
-#ifndef RL_DIRECT_ONE
-#define RL_DIRECT_ONE 1
-#endif
-#ifndef RL_S_AHEAD2
-#define RL_S_AHEAD2 1 // ring-S rounds of a scene whose cull table is in global memory: two children's bounds requested ahead
-#endif
-#ifndef RL_MEMBER_AHEAD2
-#define RL_MEMBER_AHEAD2 0 // cluster-member rounds of a scene whose spheres are in global memory: two records requested ahead instead of one (measured: 4,539 objects -4.5 %, 5,019 random spheres +-0 -- the gathers are bound by the lines the L1 serves per cycle, not by latency)
-#endif
-#ifndef RL_MEMBER_FENCE
-#define RL_MEMBER_FENCE (RL_TRACE_WPS > 4)
-#endif
-// Five waves per SIMD leave a wave 96 registers: the options that buy latency with registers are off there unless a build asks
-#ifndef RL_LEAN_SPLIT
-#define RL_LEAN_SPLIT (RL_TRACE_WPS <= 4)
-#endif
-#ifndef RL_LEAN_HOIST
-#define RL_LEAN_HOIST (RL_TRACE_WPS <= 4)
-#endif
-#ifndef RL_PROGRESSIVE_FAR
-#define RL_PROGRESSIVE_FAR 1 // in the variants for scenes that are not staged whole (rl_scan_wave: SUPER): the rounds' far bound follows the merge keys -- the nearest hit found SO FAR in this scan -- not just the small primitives' hit
-#endif
+#define RL_EMIT_MAX_AGE 8u  // fused mode: iterations a partly filled emitter queue waits before it is evaluated with what it has
 #define RL_CHUNK 256ull     // paths a wave takes from the global queue at a time (4 stash refills) in large launches
 
 struct RlSceneLayout {
@@ -357,13 +317,13 @@ struct RlWaveScratch {
     // The cull terms of the wave's 64 rays, two 16-byte slots per lane: {d.xyz, p}, {m.xyz, q} (RlCullRay), and the far bounds.
     // Written by every lane once per scan; a round's lane reads the slot of its pair's OWNER with two 16-byte loads and one
     // 4-byte load.  Rounds 1-4 fetched the nine values across lanes with nine ds_bpermute_b32 -- ~430 cycles of a wave's
-    // time per round measured in the kernel (tools/ab3.sh, the RL_EXP_EXTRA probes), against ~90 for the gathers; five such
+    // time per round measured in the kernel (profiles/r05_issue_cost_probes.txt), against ~90 for the gathers; five such
     // rounds per iteration.  The room came from the emitter queue (128 -> 64 slots), the stash's path indices (derived
     // now) and the object table (one record per object).
     float terms_d[64][4]; // {d.xyz, p}: two arrays of 16-byte slots rather than one of 32-byte ones -- a 16-byte gather is served
     float terms_m[64][4]; // {m.xyz, q}  in groups of 16 lanes, and 16-byte strides spread 16 owners over all 16 bank quads
     // The far bound of the lane's ray: the distance of its nearest plane / circle / paraboloid hit (before the prisms: of its nearest
-    // hit) in the cull's units -- or, in the variants for scenes that are not staged whole (RL_PROGRESSIVE_FAR), RlCullRay::len alone:
+    // hit) in the cull's units -- or, in the variants for scenes that are not staged whole (rl_scan_wave: PF), RlCullRay::len alone:
     // a round's far bound is then the distance of the nearest hit its owner has SO FAR -- the high word of the owner's merge key,
     // which every sphere-tail round lowers -- times this, so that bounds behind a sphere an earlier round of the SAME scan found are
     // culled like those behind the walls.  (Dense scenes: 5,000 random spheres 1.7 -> 3.6 Grays/s, 20,000: 0.41 -> 5.3; one LDS
@@ -458,7 +418,7 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
                                               uint32_t n_cluster_groups, uint32_t n_prism_groups, uint32_t n_cluster_supers, uint32_t super_g, RlLdsU32* ring_t, RlF3 o, RlF3 dir,
                                               uint32_t idle_bit, RlWaveScratch* ws, uint32_t lane RL_TACC_PARAM, float t_bound = 1.0e12f) {
     // Explicit LDS address space: generic pointers here would become flat_* accesses.
-    constexpr bool PF = SUPER && RL_PROGRESSIVE_FAR;
+    constexpr bool PF = SUPER;
     RlLdsU64* keys = (RlLdsU64*)ws->key;
     RlLdsU32* ring_a = (RlLdsU32*)ws->ring_a;
     RlLdsU32* ring_b = (RlLdsU32*)ws->ring_b;
@@ -476,10 +436,6 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
     // `if (pass) *slot = entry` is s_and_saveexec / s_cbranch_execz / ... / s_or exec around the store and re-materialises the
     // slot mask in a scalar register at every push -- four instructions of a wave's issue for each of the ~35
     // pushes of an iteration: here the mask becomes exec for the one store, without a branch.
-#ifndef RL_PUSH_ASM
-#define RL_PUSH_ASM 1
-#endif
-#if RL_PUSH_ASM
 #define RL_RING_PUSH(RING, COND, M, TAIL, ENTRY)                                                                        \
     {                                                                                                                   \
         uint32_t slot_;                                                                                                 \
@@ -492,16 +448,9 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
                        "v"(ENTRY), "n"(offsetof(RlWaveScratch, RING))                                                   \
                      : "memory");                                                                                       \
     }
-#else
-#define RL_RING_PUSH(RING, COND, M, TAIL, ENTRY) if (COND) *RL_RING_SLOT(RING, M, TAIL) = (ENTRY);
-#endif
     // RL_LE_PUSH: test (LHS <= RHS, the cull's compare) AND push in one: v_cmpx writes the compare's mask to vcc and to exec at
     // once, the store runs under it, and the ring's tail advances by the mask's population -- one instruction less than a
     // compare into a scalar pair followed by RL_RING_PUSH and the count.
-#ifndef RL_PUSH_CMPX
-#define RL_PUSH_CMPX 1
-#endif
-#if RL_PUSH_ASM && RL_PUSH_CMPX
 #define RL_LE_PUSH(RING, LHS, RHS, TAIL, ENTRY)                                                                        \
     {                                                                                                                   \
         uint32_t slot_, n_;                                                                                             \
@@ -516,20 +465,10 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
                      : "vcc", "scc", "memory");                                                                         \
         TAIL += n_;                                                                                                     \
     }
-#else
-#define RL_LE_PUSH(RING, LHS, RHS, TAIL, ENTRY)                                                                        \
-    {                                                                                                                   \
-        const bool pass_ = (LHS) <= (RHS);                                                                              \
-        const uint64_t m_ = __builtin_amdgcn_ballot_w64(pass_);                                                         \
-        RL_RING_PUSH(RING, pass_, m_, TAIL, ENTRY)                                                                      \
-        TAIL += (uint32_t)__popcll(m_);                                                                                 \
-    }
-#endif
     // ... and the same push into ring T (SUPER: the third level's (super, ray) pairs), which lives outside the wave's scratch -- 512 bytes
     // per wave between the staged tables and the scratch blocks, 512-byte aligned like the rings inside
     const uint32_t wt_addr = (uint32_t)(size_t)ring_t;
     uint32_t rt_lim = 64u, rt_tail = 0;
-#if RL_PUSH_ASM && RL_PUSH_CMPX
 #define RL_LE_PUSH_T(LHS, RHS, TAIL, ENTRY)                                                                             \
     {                                                                                                                   \
         uint32_t slot_, n_;                                                                                             \
@@ -542,15 +481,6 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
                      : "vcc", "scc", "memory");                                                                         \
         TAIL += n_;                                                                                                     \
     }
-#else
-#define RL_LE_PUSH_T(LHS, RHS, TAIL, ENTRY)                                                                             \
-    {                                                                                                                   \
-        const bool pass_ = (LHS) <= (RHS);                                                                              \
-        const uint64_t m_ = __builtin_amdgcn_ballot_w64(pass_);                                                         \
-        if (pass_) ring_t[(rl_mbcnt(m_) + (TAIL)) & 127u] = (ENTRY);                                                    \
-        TAIL += (uint32_t)__popcll(m_);                                                                                 \
-    }
-#endif
     uint32_t ring_mask = 0x1fcu;
     asm volatile("" : "+s"(ring_mask)); // (opaque: one scalar register for the scan instead of an s_movk at every push)
     const RlF4* sph = sv.spheres;
@@ -566,7 +496,7 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
     // (round 6: a scene with ONE direct sphere -- the built-in scenes' sun -- has its record requested here, ahead of the small
     // primitives' arithmetic, and tested straight-line below instead of in the direct list's loop with its four-record prefetch)
     RlF4 first_direct = RlF4();
-    if (SPHERES_IN_LDS && RL_DIRECT_ONE) {
+    if (SPHERES_IN_LDS) {
         first_direct = sph[0]; // (the list is padded: record 0 always exists)
         asm volatile("" ::: "memory");
     }
@@ -610,7 +540,7 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
     // (three paraboloids and three planes / circles -- the room of every built-in scene, app.rs:166-236 -- get straight-line code: the
     // records' addresses are immediates, their loads can be requested ahead of the arithmetic that is in the way, and the two loops'
     // counters and branches go; any other count takes the loops)
-    if (RL_SMALL_UNROLL && TABLES_IN_LDS && (small_ordered & 1u) != 0u && n_parabs == 3u && n_planes == 3u) { // (from global memory the records are scalar loads: two objects in flight cost 24 scalar registers the global-fetch variants do not have)
+    if (TABLES_IN_LDS && (small_ordered & 1u) != 0u && n_parabs == 3u && n_planes == 3u) { // (from global memory the records are scalar loads: two objects in flight cost 24 scalar registers the global-fetch variants do not have)
         // (bit 1 of the flag word: every normal of the six is along z -- the built-in room's are -- and the dot products with it are
         // one product each, rl_paraboloid_t<AXIS_Z>: ~50 instructions of the ~390 this block costs a wave per iteration)
         auto six = [&](auto axz) {
@@ -683,7 +613,7 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
     RlCullRay cr = rl_cull_ray(o, dir, sv_cull_cmax2, idle_bit != 0u);
     float far = best.t * cr.len;
     rl_store_cull_ray<PF>(ws, lane, cr, far);
-    // (RL_PROGRESSIVE_FAR) this lane's own far bound for the wave-uniform loops, refreshed behind a nested round: its key may have come nearer
+    // (PF) this lane's own far bound for the wave-uniform loops, refreshed behind a nested round: its key may have come nearer
 #define RL_REFRESH_FAR()                                                                                \
     if (PF) {                                                                                           \
         far = rl_u2f(((const RlLdsU32*)keys)[2u * lane + 1u]) * cr.len;                                 \
@@ -707,16 +637,14 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
         // kernel started: an LDS read beyond the allocation returns zero, a global one faults, so where the spheres are in
         // global memory such lanes read record 0)
         const uint32_t pos = (SPHERES_IN_LDS || lane < count) ? e >> 6 : 0u;
-        RlF4 s;
-        float s_r2;     // (a clustered sphere's s.w is its cull term)
-        uint32_t s_obj;
-        if (RL_W_B) s = sph[pos], s_r2 = sv.sphere_r2[pos], s_obj = sv.sphere_obj[pos];
+        const RlF4 s = sph[pos];
+        const float s_r2 = sv.sphere_r2[pos]; // (a clustered sphere's s.w is its cull term)
+        const uint32_t s_obj = sv.sphere_obj[pos];
         RlF3 fo, fd;
         rl_fetch_ray(ws, owner, dir, fo, fd);
-        if (RL_W_B) asm volatile("" : : "v"(s.w)); // (a 16-byte LDS load: a 12-byte one takes twice the LDS time)
+        asm volatile("" : : "v"(s.w)); // (a 16-byte LDS load: a 12-byte one takes twice the LDS time)
         const float ox = fo.x, oy = fo.y, oz = fo.z, dx = fd.x, dy = fd.y, dz = fd.z;
         if (lane < count) {
-            if (!RL_W_B) s = sph[pos], s_r2 = sv.sphere_r2[pos];
             const float cox = s.x - ox, coy = s.y - oy, coz = s.z - oz;
             const float dd = dx * cox + dy * coy + dz * coz;
             const float c = (cox * cox + coy * coy + coz * coz) - s_r2;
@@ -725,8 +653,7 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
             const float t1 = dd - sq;
             const float t2 = dd + sq;
             if ((q >= 0.0f) & (t1 > 0.0f) & (t1 < t2)) {
-                const uint32_t obj = RL_W_B ? s_obj : sv.sphere_obj[pos];
-                __hip_atomic_fetch_min(keys + owner, ((unsigned long long)rl_f2u(t1) << 32) | (unsigned long long)(obj << 3),
+                __hip_atomic_fetch_min(keys + owner, ((unsigned long long)rl_f2u(t1) << 32) | (unsigned long long)(s_obj << 3),
                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             }
         }
@@ -758,7 +685,7 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
     // ---- direct spheres: every ray against every record; groups of 4 with one group of prefetch, then
     // the remainder one by one (the padding of rl_scene.h keeps every prefetch in bounds) ----
     RL_T0(t_direct);
-    if (SPHERES_IN_LDS && RL_DIRECT_ONE && n_direct == 1u) {
+    if (SPHERES_IN_LDS && n_direct == 1u) {
         RL_SPHERE_REJECT(first_direct, 0u, lane, idle_bit, o.x, o.y, o.z, dir.x, dir.y, dir.z)
     } else if (n_direct != 0) {
         const uint32_t full = n_direct & ~3u;
@@ -807,12 +734,10 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
         // lanes beyond the round hold stale ring entries: point them at cluster 0 so their (ignored) loads stay in bounds
         uint32_t first = sv.cluster_base + __umul24(cluster_k + 1u, slot < count ? (e >> 6) : 0u) + 1u; // (24-bit multiply: full rate)
         if (split) first += (lane >> 5) * (n_members >> 1);
-        RlF4 mb;
-        if (RL_W_M) mb = sph[first]; // (ahead of the cross-lane fetch: one wait for both)
+        RlF4 mb = sph[first]; // (ahead of the cross-lane fetch: one wait for both)
         RlCullRay r;
         float r_far;
         rl_fetch_cull_ray<PF>(ws, owner, r, r_far);
-        if (!RL_W_M) mb = sph[first];
         // The members that pass are collected as one bit per member in a lane-private mask (one v_alignbit per member: shift
         // left, take in the sign of the test's margin) and pushed afterwards, lowest set bit of every lane per step -- ~0.5 members pass
         // per pair, so two or three steps replace ten ballot / count / write sequences.
@@ -823,15 +748,10 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
 #define RL_MEMBERS(N)                                                                                                    \
         {                                                                                                                \
             uint32_t failed = 0; /* one bit per member: the sign of the test's margin, shifted in with one v_alignbit */  \
-            /* (spheres in global memory: TWO records of prefetch -- a member is a per-lane 16-byte gather from L2 / HBM, the loop is    \
-               bound by that latency, and 57 % of the time of a 5,000-sphere scene went into these rounds with one) */          \
-            RlF4 mb_ahead = RlF4();                                                                                      \
-            if (!SPHERES_IN_LDS && RL_MEMBER_AHEAD2) mb_ahead = sph[first + 1];                                           \
+            /* (ONE record of prefetch, spheres in global memory included: two requested ahead were measured and not kept -- 4,539 objects \
+               -4.5 %, 5,019 random spheres +-0: the per-lane gathers are bound by the lines the L1 serves per cycle, not by latency) */ \
             for (uint32_t j = 0; j < (N); ++j) {                                                                         \
-                RlF4 mb_next; /* one record of prefetch (behind the last member: the next cluster's bound, or the blob's next array) */ \
-                if (!SPHERES_IN_LDS && RL_MEMBER_AHEAD2) mb_next = mb_ahead, mb_ahead = sph[first + j + 2];               \
-                else mb_next = sph[first + j + 1];                                                                       \
-                if (RL_MEMBER_FENCE) asm volatile("" ::: "memory"); /* ONE record in flight: without it a tight register budget makes the scheduler request all N up front and spill them */ \
+                const RlF4 mb_next = sph[first + j + 1]; /* (behind the last member: the next cluster's bound, or the blob's next array) */ \
                 failed = __builtin_amdgcn_alignbit(failed, rl_f2u(rl_cull_margin(r, mb, r_far)), 31u); /* member j ends up at bit N - 1 - j */ \
                 mb = mb_next;                                                                                            \
             }                                                                                                            \
@@ -924,7 +844,7 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
         }                                                                                               \
         /* (the table in global memory: the rolled loop below keeps two bounds requested ahead -- a child's bound is a per-lane    \
            gather from L2 / HBM -- the first two ahead of the cross-lane fetch) */                       \
-        constexpr bool S_AHEAD = !UNROLL_S && !TABLES_IN_LDS && SPLIT && RL_S_AHEAD2; /* (plain launches: the open ones have no registers for it) */ \
+        constexpr bool S_AHEAD = !UNROLL_S && !TABLES_IN_LDS && SPLIT; /* (plain launches: the open ones have no registers for it) */ \
         constexpr bool S_AHEAD_TWO = S_AHEAD;                                                           \
         RlF4 pa_ = RlF4(), pb_ = RlF4();                                                                \
         if (S_AHEAD) pa_ = cull[first];                                                                 \
@@ -1131,7 +1051,7 @@ __device__ __forceinline__ RlHit rl_scan_wave(const RlSceneView& sv, const RlF4*
         const RlF4* pr = sv.prisms + __umul24((uint32_t)RL_PRISM_STRIDE, lane < count ? prism : 0u);
         // (the plain launches of a scene whose prisms are staged in LDS: the first plane's records depend on the ring entry alone
         // and are requested ahead of the cross-lane fetch, whose wait covers them)
-        constexpr bool PRE = HOIST_S && SPLIT && RL_W_PR;
+        constexpr bool PRE = HOIST_S && SPLIT;
         RlF4 pre_n = RlF4(), pre_off = RlF4();
         if (PRE) pre_n = pr[0], pre_off = pr[1];
         RlF3 ro, rd;
@@ -1369,9 +1289,9 @@ __device__ __forceinline__ void rl_trace_body(const RlF4* __restrict__ scene, co
     sv.records = big; // (a tables-only stage completes its hits from the blob in global memory, like its spheres)
     const uint32_t lane = threadIdx.x & 63u;
     RlWaveScratch* ws = &scratch[threadIdx.x >> 6];
-#if defined(RL_STATS) || defined(RL_DEBUG_ALIGN)
+#ifdef RL_STATS
     // (the ring addressing is only right on a 512-byte aligned scratch, i.e. with the dynamic LDS at offset 0 of the
-    // workgroup's allocation and nothing static in front of it; the diagnostic builds stop here if that ever changes)
+    // workgroup's allocation and nothing static in front of it; the diagnostic build stops here if that ever changes)
     if (((uint32_t)(size_t)(RlLdsU32*)ws & 511u) != 0u) __builtin_trap();
 #endif
     typedef __attribute__((address_space(3))) float RlLdsF32;
@@ -1557,90 +1477,6 @@ __device__ __forceinline__ void rl_trace_body(const RlF4* __restrict__ scene, co
             settle();
             flush(3000u);
         }
-#if defined(RL_EXP_EXTRA)
-        // sensitivity probe (timing only, tools/ab3.sh): what does one more instruction of a kind cost the kernel?
-        {
-            uint32_t xs = lane, xv = lane;
-#if RL_EXP_EXTRA == 1 // 256 scalar instructions
-            uint32_t ss = 1;
-#pragma unroll
-            for (int k = 0; k < 256; ++k) asm volatile("s_add_u32 %0, %0, 3" : "+s"(ss));
-            xs = ss;
-#elif RL_EXP_EXTRA == 2 // 256 vector instructions (four chains)
-            uint32_t a = lane, b = lane + 1, c = lane + 2, d = lane + 3;
-#pragma unroll
-            for (int k = 0; k < 64; ++k) asm volatile("v_add_u32 %0, 3, %0\n\tv_add_u32 %1, 5, %1\n\tv_add_u32 %2, 7, %2\n\tv_add_u32 %3, 9, %3" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
-            xv = a ^ b ^ c ^ d;
-#elif RL_EXP_EXTRA == 3 // 16 exposed LDS round trips
-#pragma unroll
-            for (int k = 0; k < 16; ++k) asm volatile("ds_read_b32 %0, %0\n\ts_waitcnt lgkmcnt(0)\n\tv_and_b32 %0, 0xfc, %0" : "+v"(xv) : : "memory");
-#elif RL_EXP_EXTRA == 4 // 256 s_nop 0
-#pragma unroll
-            for (int k = 0; k < 256; ++k) asm volatile("s_nop 0");
-#elif RL_EXP_EXTRA == 5 // 256 vector instructions in ONE dependent chain
-#pragma unroll
-            for (int k = 0; k < 256; ++k) asm volatile("v_add_u32 %0, 3, %0" : "+v"(xv));
-#elif RL_EXP_EXTRA == 8 // 64 taken branches
-#pragma unroll
-            for (int k = 0; k < 64; ++k) asm volatile("s_branch 0");
-#elif RL_EXP_EXTRA == 9 // 64 conditional branches that are not taken
-            asm volatile("s_cmp_eq_u32 0, 1");
-#pragma unroll
-            for (int k = 0; k < 64; ++k) asm volatile("s_cbranch_scc1 0");
-#elif RL_EXP_EXTRA == 6 // 128 packed FMAs (four chains)
-            {
-                typedef float F2 __attribute__((ext_vector_type(2)));
-                F2 pa = {(float)lane, 1.0f}, pb = {2.0f, (float)lane}, pc = {3.0f, 1.5f}, pd = {0.5f, 0.25f};
-#pragma unroll
-                for (int k = 0; k < 32; ++k) asm volatile("v_pk_fma_f32 %0, %0, %1, %2\n\tv_pk_fma_f32 %1, %1, %2, %3\n\tv_pk_fma_f32 %2, %2, %3, %0\n\tv_pk_fma_f32 %3, %3, %0, %1" : "+v"(pa), "+v"(pb), "+v"(pc), "+v"(pd));
-                xv = rl_f2u(pa.x + pb.y + pc.x + pd.y);
-            }
-#elif RL_EXP_EXTRA == 7 // 256 scalar-operand-free FMAs (four chains)
-            {
-                float fa = (float)lane, fb = 2.0f, fc = 3.0f, fd = 0.5f;
-#pragma unroll
-                for (int k = 0; k < 64; ++k) asm volatile("v_fma_f32 %0, %0, %1, %2\n\tv_fma_f32 %1, %1, %2, %3\n\tv_fma_f32 %2, %2, %3, %0\n\tv_fma_f32 %3, %3, %0, %1" : "+v"(fa), "+v"(fb), "+v"(fc), "+v"(fd));
-                xv = rl_f2u(fa + fb + fc + fd);
-            }
-#elif RL_EXP_EXTRA == 10 // 4 batches of nine ds_bpermute_b32 with one wait each (how rounds 1-4 fetched a pair's ray)
-            {
-                float t0 = (float)lane;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const uint32_t addr = ((lane * 7u + 3u) & 63u) << 2;
-                    float r0, r1, r2, r3, r4, r5, r6, r7, r8;
-                    asm volatile("ds_bpermute_b32 %0, %9, %10\n\tds_bpermute_b32 %1, %9, %10\n\tds_bpermute_b32 %2, %9, %10\n\t"
-                                 "ds_bpermute_b32 %3, %9, %10\n\tds_bpermute_b32 %4, %9, %10\n\tds_bpermute_b32 %5, %9, %10\n\t"
-                                 "ds_bpermute_b32 %6, %9, %10\n\tds_bpermute_b32 %7, %9, %10\n\tds_bpermute_b32 %8, %9, %10\n\t"
-                                 "s_waitcnt lgkmcnt(0)"
-                                 : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(r4), "=&v"(r5), "=&v"(r6), "=&v"(r7), "=&v"(r8)
-                                 : "v"(addr), "v"(t0) : "memory");
-                    t0 = r0 + r1 + r2 + r3 + r4 + r5 + r6 + r7 + r8;
-                }
-                xv = rl_f2u(t0);
-            }
-#elif RL_EXP_EXTRA == 12 // 4 batches of two 16-byte gathers + one 4-byte gather from the wave's scratch, one wait each (round 5's fetch)
-            {
-                float t0 = (float)lane;
-                uint32_t who = (lane * 7u + 3u) & 63u;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    RlCullRay r;
-                    float f;
-                    rl_fetch_cull_ray(ws, who, r, f);
-                    t0 += r.d.x + r.d.y + r.d.z + r.p + r.m.x + r.m.y + r.m.z + r.q + f;
-                    who = (who * 5u + (rl_f2u(t0) & 1u)) & 63u;
-                    asm volatile("" ::: "memory");
-                }
-                xv = rl_f2u(t0);
-            }
-#elif RL_EXP_EXTRA == 11 // 64 s_and_saveexec / s_or exec pairs
-#pragma unroll
-            for (int k = 0; k < 64; ++k) asm volatile("s_and_saveexec_b64 s[2:3], exec\n\ts_or_b64 exec, exec, s[2:3]" ::: "s2", "s3");
-#endif
-            if (xs == 0xdeadbeefu || xv == 0xdeadbeefu) segments += 1; // keep the probe alive
-        }
-#endif
         // ---- hand new paths to the lanes whose path ended (trace_unit.rs:152-167) ----
         RL_T0(t_refill);
         // Two steps, written straight-line (at most: refill, hand out, and -- when more lanes asked than the stash held -- once
@@ -1879,8 +1715,8 @@ __device__ __forceinline__ void rl_trace_body(const RlF4* __restrict__ scene, co
         // open launches of a tables-only scene, 64-bit global addresses again)
         // (round 6: the Compound tree's lean form freed ~15 registers, and the open launches of a scene that is staged whole now take
         // every one of these options inside their 120 registers; the tables-only and global-fetch open variants still do not)
-        constexpr bool FULL = !OPEN || (RL_OPEN_FULL && STAGE == RL_STAGE_ALL && (FUSED || !CYL)); // (the un-fused open variant of a scene with prism cylinders spills one scalar register with them)
-        const RlHit hit = rl_scan_wave<CYL, FULL && RL_LEAN_SPLIT, STAGE != RL_STAGE_NONE && (!(FUSED && OPEN) || FULL), STAGE != RL_STAGE_NONE && (!(OPEN && (FUSED || STAGE == RL_STAGE_TABLES)) || FULL) && RL_W_S && RL_LEAN_HOIST, STAGE == RL_STAGE_ALL, STAGE != RL_STAGE_NONE, STAGE != RL_STAGE_ALL>(sv, base + (lay.off_cull - tab0), CYL ? base + (lay.off_prism_cyl - tab0) : nullptr, lay.group_gc, lay.small_ordered, lay.cull_cmax2, lay.n_cluster_groups, lay.n_prism_groups,
+        constexpr bool FULL = !OPEN || (STAGE == RL_STAGE_ALL && (FUSED || !CYL)); // (the un-fused open variant of a scene with prism cylinders spills one scalar register with them)
+        const RlHit hit = rl_scan_wave<CYL, FULL, STAGE != RL_STAGE_NONE && (!(FUSED && OPEN) || FULL), STAGE != RL_STAGE_NONE && (!(OPEN && (FUSED || STAGE == RL_STAGE_TABLES)) || FULL), STAGE == RL_STAGE_ALL, STAGE != RL_STAGE_NONE, STAGE != RL_STAGE_ALL>(sv, base + (lay.off_cull - tab0), CYL ? base + (lay.off_prism_cyl - tab0) : nullptr, lay.group_gc, lay.small_ordered, lay.cull_cmax2, lay.n_cluster_groups, lay.n_prism_groups,
                                        lay.n_cluster_supers, lay.super_g, ring_t, p.origin, p.direction, active ? 0u : 0x80000000u, ws, lane RL_TACC_ARG);
 #ifdef RL_STATS
         {

@@ -89,7 +89,7 @@ __device__ __forceinline__ RlHit rl_intersect_segment(const RlStagedScene& stage
     const float d2 = d.x * d.x + d.y * d.y + d.z * d.z;
     const bool exhaustive = active && !(fabsf(d2 - 1.0f) <= 0x1p-20f && fabsf(o.x) < INFINITY && fabsf(o.y) < INFINITY && fabsf(o.z) < INFINITY);
     const bool scanned = active && !exhaustive;
-    RlHit hit = rl_scan_wave<CYL, RL_LEAN_SPLIT, STAGE != RL_STAGE_NONE, STAGE != RL_STAGE_NONE && RL_W_S && RL_LEAN_HOIST, STAGE == RL_STAGE_ALL,
+    RlHit hit = rl_scan_wave<CYL, true, STAGE != RL_STAGE_NONE, STAGE != RL_STAGE_NONE, STAGE == RL_STAGE_ALL,
                              STAGE != RL_STAGE_NONE, STAGE != RL_STAGE_ALL>(staged.sv, base + (lay.off_cull - tab0), CYL ? base + (lay.off_prism_cyl - tab0) : nullptr,
                                                                             lay.group_gc, lay.small_ordered, lay.cull_cmax2, lay.n_cluster_groups,
                                                                             lay.n_prism_groups, lay.n_cluster_supers, lay.super_g, staged.ring_t,

@@ -653,13 +653,9 @@ std::vector<uint32_t> order_by_groups(const std::vector<RlF4>& bounds, std::vect
 // groups and more, tighter ones.  So rl_flatten_scene builds the table for every size in RL_CLUSTER_K_CHOICES x {3, 4}
 // clusters per group and keeps the one that costs the kernel least, estimated from the rays of a few hundred sample paths
 // with the kernel's measured cost per step (plan_cost).  Which table is chosen never changes a result.
-#ifndef RL_SUPER_MIN_GROUPS
-#define RL_SUPER_MIN_GROUPS 112 // cluster groups from which the cull table gets its third level (tools/spill_ab.py with RL_SUPER_MIN / RL_SUPER_G:
-                                // 88 groups lose 3 % with it, 128-136 gain 0-10 %, 504 gain 76 %; 8 per super is at or near the best of 4 / 8 / 12 / 16 everywhere)
-#endif
-#ifndef RL_SUPER_G_DEFAULT
-#define RL_SUPER_G_DEFAULT 8   // cluster groups per super
-#endif
+constexpr uint32_t RL_SUPER_MIN_GROUPS = 112; // cluster groups from which the cull table gets its third level (tools/spill_ab.py with RL_SUPER_MIN / RL_SUPER_G:
+                                              // 88 groups lose 3 % with it, 128-136 gain 0-10 %, 504 gain 76 %; 8 per super is at or near the best of 4 / 8 / 12 / 16 everywhere)
+constexpr uint32_t RL_SUPER_G_DEFAULT = 8;    // cluster groups per super
 // From how many cluster groups on a table gets its third level, and how many groups a super bound covers (environment: measurement runs).
 void super_params(uint32_t* min_groups, uint32_t* sg) {
     *min_groups = RL_SUPER_MIN_GROUPS;
@@ -808,10 +804,6 @@ double plan_cost(const ClusterPlan& plan, const std::vector<RlF4>& rays) {
                                             : 0.59 * (double)super_bounds.size() + super_pairs / n_rays * (2.3 + 0.9 * (double)sg);
     const double cost = top + group_pairs / n_rays * (2.13 + 0.83 * ((double)plan.group_gc - 3.0)) +
                         cluster_pairs / n_rays * (0.25 + 0.40 * plan.k);
-#ifdef RL_PLAN_DEBUG
-    std::fprintf(stderr, "plan: %u per cluster, %u per group: %zu groups, %.2f group pairs and %.2f cluster pairs per sample ray, cost %.2f\n", plan.k,
-                 plan.group_gc, plan.group_bounds.size(), group_pairs / n_rays, cluster_pairs / n_rays, cost);
-#endif
     return cost;
 }
 
@@ -982,12 +974,7 @@ int rl_flatten_scene(const RlSceneDesc* desc, RlFlatScene* out, const char** err
                 for (const SphereIn& si : sph_in) balls.push_back(Ball{{si.rec.x, si.rec.y, si.rec.z}, si.radius});
                 improve_partition(balls, clusters, k);
             }
-#ifdef RL_GROUP_GC
-            static_assert(RL_GROUP_GC == 3 || RL_GROUP_GC == 4, "the kernel's unrolled ring-S rounds test three bounds of a group unconditionally and a fourth if there is one");
-            for (uint32_t g : {(uint32_t)RL_GROUP_GC}) {
-#else
-            for (uint32_t g : {3u, 4u}) {
-#endif
+            for (uint32_t g : {3u, 4u}) { // (the kernel's unrolled ring-S rounds test three bounds of a group unconditionally and a fourth if there is one)
                 ClusterPlan candidate = plan_clusters(sph_in, clusters, k, g);
                 candidate.cost = plan_cost(candidate, rays);
                 // (RL_PLAN="k,g": measurement runs force one plan -- tools/plan_ab.sh -- to check the cost model against the kernel as it is now)

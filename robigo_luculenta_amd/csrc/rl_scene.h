@@ -49,10 +49,8 @@ struct alignas(16) RlF4 {
 #define RL_CLUSTER_K_MAX 31
 #define RL_CLUSTER_K_CHOICES {10, 14} // (the kernel's member loop is unrolled for exactly these)
 // Bounds per second-level group of the cull table.  Clusters: 3 or 4, chosen per scene together with the cluster size
-// (RlFlatScene::group_gc; -DRL_GROUP_GC=n forces one).  Prisms: threes (the glass-stress scene loses 2.5 % with fours).
-#ifndef RL_GROUP_GP
+// (RlFlatScene::group_gc).  Prisms: threes (the glass-stress scene loses 2.5 % with fours).
 #define RL_GROUP_GP 3
-#endif
 
 // Everything the per-path code needs to read; pointers are device or host memory depending on
 // who built the view.

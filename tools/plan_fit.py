@@ -2,7 +2,8 @@
 """Least-squares fit behind rl_scene.cpp's plan_cost(): what a group bound, a (group, ray) pair and a (cluster, ray) pair cost
 the trace kernel, from the measured throughput of builds that force one cluster size and one group size each.
 
-The table below was measured on MI355X in round 3 (tools/ab.sh over libraries built with -DRL_CLUSTER_K=k -DRL_GROUP_GC=g,
+The table below was measured on MI355X in round 3 (tools/ab.sh over libraries built with -DRL_CLUSTER_K=k and a second build-time
+switch, since removed, that forced g clusters per group -- RL_PLAN="k,g" in the environment forces a plan at run time now, tools/plan_ab.sh --
 two bench.py runs each, member loop rolled for every size); groups / pairs per ray are counted by the host mirror on the
 segments of 20,000 paths of the same scene (tests/host_mirror: mirror_cull_counts).  Model, picoseconds per ray of a whole
 MI355X:  T = T0(scene) + a_g * groups + pairs_g * (a_s + a_s4 * (G - 3)) + pairs_c * (a_c + a_m * K).
