@@ -10,6 +10,7 @@ import pytest
 
 import _image_cases as IC
 import _oracle as O
+from _lds_poison import _poison_lds
 
 pytestmark = pytest.mark.gpu
 
@@ -481,18 +482,6 @@ def test_scene_too_large_for_lds_spills_to_global_fetch():
     assert t.mapped_photons.tobytes() == want.tobytes() and t.stats()[1] == segs
     ran = [a - b for a, b in zip(R.variant_launches(), before)]
     assert sum(ran[16:]) >= 1 and sum(ran[:16]) == 0, ran       # an instantiation that stages the tables only, although the unit asked for LDS
-
-
-def _poison_lds(pattern):
-    """tests/lds_poison: every CU's LDS filled with `pattern` (test infrastructure, built by __graft_entry__.build())."""
-    so = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lds_poison", "_build", "liblds_poison.so")
-    if not os.path.exists(so):
-        import subprocess
-        subprocess.run(["make", "-s", "-C", os.path.dirname(os.path.dirname(so))], check=True)
-    lib = C.CDLL(so)
-    lib.lds_poison.argtypes = [C.c_int, C.c_uint32, C.c_uint32]
-    rc = lib.lds_poison(0, pattern, 2048)
-    assert rc == 0, rc
 
 
 @pytest.mark.parametrize("pattern", [0xFFFFFFFF, 0x7FC00000, 0x00ABCDEF])
