@@ -100,6 +100,12 @@ extern "C" {
                                states: *mut RlPathState, n: u32, hits: *mut RlRayHit) -> c_int;
     pub fn rl_scene_step_paths_device(scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32, flags: u32,
                                       device_states: *mut RlPathState, n: u32, device_hits: *mut RlRayHit) -> c_int;
+    pub fn rl_scene_step_path_list(scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32, flags: u32,
+                                   states: *mut RlPathState, n_states: u32, list: *const u32, n_list: u32, hits: *mut RlRayHit,
+                                   live_list: *mut u32, n_live: *mut u32) -> c_int;
+    pub fn rl_scene_step_path_list_device(scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32, flags: u32,
+                                          device_states: *mut RlPathState, n_states: u32, device_list: *const u32, n_list: u32,
+                                          device_hits: *mut RlRayHit, device_live_list: *mut u32, n_live: *mut u32) -> c_int;
 
     pub fn rl_trace_unit_create(device: c_int, id: u32, w: u32, h: u32, n_photons: u32, out: *mut *mut RlTraceUnit) -> c_int;
     pub fn rl_trace_unit_destroy(u: *mut RlTraceUnit) -> c_int;

@@ -349,6 +349,43 @@ int rl_scene_step_paths(const RlScene* scene, int primitive_fetch, uint64_t seed
 int rl_scene_step_paths_device(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, uint32_t flags,
                                RlPathState* device_states, uint32_t n, RlRayHit* device_hits);
 
+/* rl_scene_step_paths for the states an index list names, and the list of those that are still live: what a wavefront loop
+ * needs between segments, so that it moves 4 bytes per live path instead of the 64-byte records.  The states stay where they are.
+ *
+ * The list.  list[k], k < n_list, names states[list[k]] of states[0, n_states).  list == NULL is the identity list
+ *   0 .. n_list - 1; then n_list > n_states is RL_E_INVALID.  An entry >= n_states is skipped: nothing is read or written for it
+ *   and it is not reported live; no content of the list makes the call touch memory outside the buffers.  Entries must be
+ *   distinct: for a state named twice the call is memory-safe and that state's result is unspecified.  list is never written.
+ * Stepping.  Every listed state with end == RL_PATH_LIVE makes exactly one segment, in place: bit for bit what
+ *   rl_scene_step_paths makes of that record under the same seed, stream and flags.  hits may be NULL; otherwise hits[i] --
+ *   indexed by STATE, not by list position, so it has room for n_states records -- is written for every stepped state i as that
+ *   call writes it.  A listed state that is not live is not written.  A state that is not listed is neither read nor written, nor
+ *   is its hits slot.
+ * Survivors.  live_list may be NULL; otherwise it has room for n_list entries and receives the indices of the listed states that
+ *   are live after the step: each exactly once, in the order they had in list (a stable compaction; ascending when list was),
+ *   and nothing is written behind them.  *n_live (n_live may be NULL) receives their number on return, whether or not live_list
+ *   is given.  The _device form accepts live_list == list.  The order is fixed so that the call is deterministic like every other
+ *   call here, and so that neighbouring paths stay neighbours in the next step's waves.
+ * Determinism.  States, hits, live_list and n_live depend only on the scene, seed, stream, flags, the states and the list: not
+ *   on primitive_fetch or the kernel variant, on how the work is handed out, or on other callers.
+ * Arguments, checked in this order, each failure RL_E_INVALID with a message before any device work: an unknown fetch mode, an
+ *   unknown flag bit, NULL states with n_list > 0, a NULL scene, list == NULL with n_list > n_states.  n_list == 0 does nothing
+ *   but *n_live = 0.
+ * The _device form takes device pointers on the scene's device for states (16-byte aligned), list, hits and live_list (4-byte
+ *   aligned) and refuses pageable host memory; n_live is a HOST pointer.  It returns when everything is written, is safe from
+ *   several host threads at once on one scene (on different states), and orders against renders as rl_scene_intersect does.
+ * The host form is a convenience and is NOT chunked: it copies the whole arrays (states, hits, list) into device buffers of the
+ *   call's own, runs the device path, copies states, hits and the n_live entries of live_list back, and frees the buffers.
+ * Scratch memory.  For the compaction (live_list or n_live given) the library keeps device scratch of at most 4 bytes per listed
+ *   state plus 4 bytes per 64 listed states (rounded up), for the largest n_list seen: it lives with the query context the call
+ *   runs on (one per concurrent caller and device), grows on demand and is reused. */
+int rl_scene_step_path_list(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, uint32_t flags,
+                            RlPathState* states, uint32_t n_states, const uint32_t* list, uint32_t n_list, RlRayHit* hits,
+                            uint32_t* live_list, uint32_t* n_live);
+int rl_scene_step_path_list_device(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, uint32_t flags,
+                                   RlPathState* device_states, uint32_t n_states, const uint32_t* device_list, uint32_t n_list,
+                                   RlRayHit* device_hits, uint32_t* device_live_list, uint32_t* n_live);
+
 /* Largest image the units and rl_app_run accept: width * height <= RL_MAX_PIXELS = 2^31 - 1.  The kernels index
  * pixels in 32 bits: the splat's `py * width + px` is an int, the tonemap's pixel count and grid-stride index are
  * uint32_t.  rl_trace_unit_create, rl_plot_unit_create, rl_gather_unit_create, rl_tonemap_unit_create and rl_app_run

@@ -50,6 +50,9 @@ int rl_debug_film_launches(uint64_t* out);
 /* out[v], v = 0..5: launches of instantiation v of the step kernel (rl_scene_step_paths*) since the library was loaded, indexed
  * as rl_debug_query_launches is. */
 int rl_debug_step_launches(uint64_t* out);
+/* out[v], v = 0..5: launches of instantiation v of the list-step kernel (rl_scene_step_path_list*) since the library was loaded,
+ * indexed as rl_debug_query_launches is. */
+int rl_debug_path_list_launches(uint64_t* out);
 /* The prism shortcut (csrc/rl_core.h: rl_hex_prism_fast) against the Compound tree it stands in for
  * (geometry.rs:380-407), both evaluated ON THE GPU -- with the hardware's v_rcp_f32 -- for n rays against prism
  * `prism` (0-based, in the scene's flattened order) of `scene`.  rays: n x {origin.xyz, direction.xyz}.

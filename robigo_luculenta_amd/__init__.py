@@ -260,6 +260,50 @@ class Scene(_Handle):
         check(lib.rl_scene_step_paths_device(self._h, fetch, seed, stream, flags, C.c_void_p(states.data_ptr()), n,
                                              C.c_void_p(hits.data_ptr()) if hits is not None else None))
 
+    def step_path_list(self, states, seed, stream, list=None, n_list=None, fetch=FETCH_LDS, flags=0, hits=None):
+        """rl_scene_step_path_list: one segment, in place, for the live states of an (n,) PATH_STATE_DTYPE array that `list` names
+        (an array of indices, converted to uint32; entries >= n are skipped), or for states 0 .. n_list - 1 when list is None
+        (n_list defaults to n).  hits: None, or an (n,) HIT_DTYPE array indexed by state.  Returns the indices of the listed states
+        that are live after the step, in the list's order, as a uint32 array."""
+        if states.dtype != PATH_STATE_DTYPE or not states.flags.c_contiguous or not states.flags.writeable:
+            raise ValueError("states must be a contiguous, writeable PATH_STATE_DTYPE array")
+        hp = lp = None
+        if hits is not None:
+            if hits.dtype != HIT_DTYPE or not hits.flags.c_contiguous or len(hits) < len(states):
+                raise ValueError("hits must be a contiguous HIT_DTYPE array with room for every state")
+            hp = hits.ctypes.data_as(C.c_void_p)
+        if list is not None:
+            list = np.ascontiguousarray(list, dtype=np.uint32)
+            if n_list is None:
+                n_list = len(list)
+            if list.ndim != 1 or n_list > len(list):
+                raise ValueError("list must be a one-dimensional array of at least n_list indices")
+            lp = list.ctypes.data_as(C.c_void_p)
+        elif n_list is None:
+            n_list = len(states)
+        live = np.empty(n_list, dtype=np.uint32)
+        n_live = C.c_uint32(0)
+        check(lib.rl_scene_step_path_list(self._h, fetch, seed, stream, flags, states.ctypes.data_as(C.c_void_p), len(states), lp, n_list, hp,
+                                          live.ctypes.data_as(C.c_void_p), C.byref(n_live)))
+        return live[:n_live.value].copy()
+
+    def step_path_list_device(self, states, seed, stream, list, n_list, live_list, fetch=FETCH_LDS, flags=0, hits=None):
+        """rl_scene_step_path_list_device: `states` is a device buffer on the scene's device with data_ptr() (e.g. a torch tensor)
+        holding n PATH_STATE_DTYPE records; `list` None (states 0 .. n_list - 1) or a device buffer of at least n_list uint32
+        indices; `live_list` None or a device buffer with room for n_list of them (it may be `list`); `hits` None or a device buffer
+        with room for n HIT_DTYPE records.  Returns n_live."""
+        n_bytes = lambda t: t.numel() * t.element_size()
+        n = n_bytes(states) // PATH_STATE_DTYPE.itemsize
+        if n_bytes(states) != n * PATH_STATE_DTYPE.itemsize or (hits is not None and n_bytes(hits) < n * HIT_DTYPE.itemsize):
+            raise ValueError("states must hold whole 64-byte records and hits room for as many 48-byte ones")
+        if any(t is not None and n_bytes(t) < 4 * n_list for t in (list, live_list)):
+            raise ValueError("list and live_list must have room for n_list 4-byte indices")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        n_live = C.c_uint32(0)
+        check(lib.rl_scene_step_path_list_device(self._h, fetch, seed, stream, flags, ptr(states), n, ptr(list), n_list, ptr(hits), ptr(live_list),
+                                                 C.byref(n_live)))
+        return n_live.value
+
 
 class TraceUnit(_Handle):
     """trace_unit.rs:51-168."""
@@ -632,6 +676,14 @@ def step_launches():
     indexed as query_launches()."""
     out = (C.c_uint64 * 6)()
     check(lib.rl_debug_step_launches(out))
+    return list(out)
+
+
+def path_list_launches():
+    """rl_debug_path_list_launches: launches per instantiation of the list-step kernel (Scene.step_path_list*) since the library
+    was loaded, indexed as query_launches()."""
+    out = (C.c_uint64 * 6)()
+    check(lib.rl_debug_path_list_launches(out))
     return list(out)
 
 

@@ -129,6 +129,8 @@ SIGNATURES = {
     "rl_scene_begin_paths_device": (_i, [_vp, _u64, _vp, _u32, _vp]),
     "rl_scene_step_paths": (_i, [_vp, _i, _u64, _u32, _u32, _vp, _u32, _vp]),
     "rl_scene_step_paths_device": (_i, [_vp, _i, _u64, _u32, _u32, _vp, _u32, _vp]),
+    "rl_scene_step_path_list": (_i, [_vp, _i, _u64, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
+    "rl_scene_step_path_list_device": (_i, [_vp, _i, _u64, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
     "rl_trace_unit_create": (_i, [_i, _u32, _u32, _u32, _u32, _pp]),
     "rl_trace_unit_destroy": (_i, [_vp]),
     "rl_trace_unit_set_fetch": (_i, [_vp, _i]),
@@ -196,6 +198,7 @@ DEBUG_SIGNATURES = {
     "rl_debug_path_launches": (_i, [_vp]),
     "rl_debug_film_launches": (_i, [_vp]),
     "rl_debug_step_launches": (_i, [_vp]),
+    "rl_debug_path_list_launches": (_i, [_vp]),
     "rl_debug_prism_probe": (_i, [_vp, _u32, _vp, _u32, _vp]),
     "rl_debug_prism_count": (_i, [_vp, C.POINTER(_u32)]),
 }

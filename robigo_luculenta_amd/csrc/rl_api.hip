@@ -46,6 +46,7 @@
 #include "rl_film.hip.h"
 #include "rl_paths.hip.h"
 #include "rl_step.hip.h"
+#include "rl_path_list.hip.h"
 #include "rl_scene.h"
 
 namespace {
@@ -333,9 +334,9 @@ int launch_trace(RlTraceUnit* u, const RlScene* scene, RlMappedPhoton* photons, 
     return RL_OK;
 }
 
-// ---- the persistent ray kernels beside the trace kernel (rl_query.hip.h, rl_occlusion.hip.h, rl_paths.hip.h, rl_step.hip.h) ----
+// ---- the persistent ray kernels beside the trace kernel (rl_query.hip.h, rl_occlusion.hip.h, rl_paths.hip.h, rl_step.hip.h, rl_path_list.hip.h) ----
 // A family is one kernel template's six instantiations, index = 2 * stage + cylinders, and the launches of each since the library
-// was loaded (rl_debug_{query,occlusion,path,film,step}_launches).  P: the kernel's parameters behind the scene blob and its layout.
+// was loaded (rl_debug_{query,occlusion,path,film,step,path_list}_launches).  P: the kernel's parameters behind the scene blob and its layout.
 template <class... P>
 struct KernelFamily {
     void (*variants[6])(const RlF4*, RlSceneLayout, P...);
@@ -347,6 +348,7 @@ KernelFamily<const RlRay*, uint8_t*, uint32_t> g_occlusion_kernels = RL_VARIANTS
 KernelFamily<const RlSpectralRay*, RlPathResult*, uint32_t, uint64_t, uint32_t, uint64_t, uint32_t, unsigned long long*> g_path_kernels = RL_VARIANTS(rl_ray_paths_kernel);
 KernelFamily<const RlCameraSample*, RlPathResult*, uint32_t, uint64_t, uint32_t, uint64_t, uint32_t, unsigned long long*> g_film_kernels = RL_VARIANTS(rl_film_paths_kernel);
 KernelFamily<RlPathState*, RlRayHit*, uint32_t, uint64_t, uint32_t, uint32_t, unsigned long long*> g_step_kernels = RL_VARIANTS(rl_step_kernel);
+KernelFamily<RlPathState*, RlRayHit*, unsigned long long*> g_list_step_kernels = RL_VARIANTS(rl_list_step_kernel);
 #undef RL_VARIANTS
 template <class... P>
 int family_launches(const KernelFamily<P...>& family, uint64_t* out) {
@@ -367,6 +369,8 @@ struct QueryCtx {
     hipStream_t stream = nullptr;
     void* staging[STAGING_COUNT] = {};   // host path only (allocated on first use, RL_QUERY_CHUNK records each)
     unsigned long long* queue = nullptr; // path, film and step calls only (allocated on first use): the counter of an RlFilmQueue
+    uint32_t* pack = nullptr;            // rl_scene_step_path_list* only: the compaction's counts and survivors (query_ctx_pack)
+    size_t pack_bytes = 0;
 };
 static_assert(sizeof(RlSpectralRay) == sizeof(RlRay) && sizeof(RlMappedPhoton) <= sizeof(RlRay) && sizeof(RlCameraSample) == sizeof(RlRayHit) &&
                   sizeof(RlPathResult) <= sizeof(RlRay),
@@ -406,9 +410,20 @@ void query_ctx_release(int device, QueryCtx* q) {
     std::lock_guard<std::mutex> guard(d->lock);
     d->idle.push_back(q);
 }
-// The context's queue counter (an RlFilmQueue: the film's constants sit behind it), allocated on first use.
+// The context's queue counter (an RlFilmQueue or an RlPathListQueue: a launch's constants sit behind it), allocated on first use.
 int query_ctx_queue(QueryCtx* q) {
-    if (!q->queue) RL_HIP(hipMalloc((void**)&q->queue, sizeof(RlFilmQueue)));
+    if (!q->queue) RL_HIP(hipMalloc((void**)&q->queue, sizeof(RlFilmQueue) > sizeof(RlPathListQueue) ? sizeof(RlFilmQueue) : sizeof(RlPathListQueue)));
+    return RL_OK;
+}
+
+// The context's compaction scratch (launch_list_step) with room for `bytes`: grown on demand, never shrunk.  (q's stream is idle.)
+int query_ctx_pack(QueryCtx* q, size_t bytes) {
+    if (q->pack_bytes >= bytes) return RL_OK;
+    if (q->pack) RL_HIP(hipFree(q->pack));
+    q->pack = nullptr;
+    q->pack_bytes = 0;
+    RL_HIP(hipMalloc((void**)&q->pack, bytes));
+    q->pack_bytes = bytes;
     return RL_OK;
 }
 
@@ -617,6 +632,48 @@ int launch_step(const RlScene* scene, int fetch, int cu_count, QueryCtx* q, uint
     return launch_persistent(g_step_kernels, scene, fetch, cu_count, q->stream, n, states, hits, n, seed, stream, flags, q->queue);
 }
 
+// One segment for the states of device array states [0, n_states) that device array list [0, n_list) names (n_list > 0; a null
+// list: states 0 .. n_list - 1), then the indices of the listed states that are still live to device array live_list, in the
+// list's order, and their number to host word *n_live when q's stream is next synchronised.  hits, live_list and n_live may be
+// null; live_list may be list.  On q's stream: the copy that zeroes the chunk counter and writes the list's block behind it
+// (RlPathListQueue), the list-step kernel and, when live_list or n_live is given, the scan of the chunks' counts, the pack into live_list and the 4-byte copy of the last running total.  The
+// scratch of the compaction is the context's: one count per chunk of 64 list positions, then one survivor slot per list position.
+int launch_list_step(const RlScene* scene, int fetch, int cu_count, QueryCtx* q, uint64_t seed, uint32_t stream, uint32_t flags,
+                     RlPathState* states, uint32_t n_states, const uint32_t* list, uint32_t n_list, RlRayHit* hits, uint32_t* live_list,
+                     uint32_t* n_live) {
+    int rc = query_ctx_queue(q);
+    if (rc != RL_OK) return rc;
+    const uint32_t n_chunks = (uint32_t)(((uint64_t)n_list + 63u) / 64u);
+    uint32_t *counts = nullptr, *survivors = nullptr;
+    if (live_list || n_live) {
+        if ((rc = query_ctx_pack(q, ((size_t)n_chunks + n_list) * sizeof(uint32_t))) != RL_OK) return rc;
+        counts = q->pack;
+        survivors = q->pack + n_chunks;
+    }
+    RlPathListQueue lq;
+    lq.next = 0;
+    lq.job.list = list;
+    lq.job.survivors = survivors;
+    lq.job.n_list = n_list;
+    lq.job.n_states = n_states;
+    lq.job.seed = seed;
+    lq.job.stream = stream;
+    lq.job.flags = flags;
+    // (from pageable memory: the copy has left `lq` when the call returns)
+    RL_HIP(hipMemcpyAsync(q->queue, &lq, sizeof lq, hipMemcpyHostToDevice, q->stream));
+    rc = launch_persistent(g_list_step_kernels, scene, fetch, cu_count, q->stream, n_list, states, hits, q->queue);
+    if (rc != RL_OK || !counts) return rc;
+    hipLaunchKernelGGL(rl_list_scan_kernel, dim3(1), dim3(RL_LIST_SCAN_BLOCK), 0, q->stream, counts, n_chunks);
+    RL_HIP(hipGetLastError());
+    if (live_list) {
+        hipLaunchKernelGGL(rl_list_pack_kernel, dim3(grid_for((uint64_t)n_chunks * 64u, cu_count)), dim3(RL_BLOCK), 0, q->stream, (const uint32_t*)counts,
+                           (const uint32_t*)survivors, n_chunks, live_list);
+        RL_HIP(hipGetLastError());
+    }
+    if (n_live) RL_HIP(hipMemcpyAsync(n_live, counts + (n_chunks - 1u), sizeof(uint32_t), hipMemcpyDeviceToHost, q->stream));
+    return RL_OK;
+}
+
 // The begin kernel for device arrays rays, states [0, n) (n > 0) as paths first_path .. first_path + n - 1, on q's stream.
 int launch_begin(int cu_count, QueryCtx* q, uint64_t first_path, const RlSpectralRay* rays, RlPathState* states, uint32_t n) {
     hipLaunchKernelGGL(rl_begin_paths_kernel, dim3(grid_for(n, cu_count)), dim3(RL_BLOCK), 0, q->stream, rays, first_path, states, n);
@@ -629,6 +686,13 @@ int step_check(const RlScene* scene, int fetch, uint32_t flags, const void* stat
     if (flags & ~(uint32_t)RL_STEP_NO_ROULETTE) return fail(RL_E_INVALID, "unknown step flag");
     if (n > 0 && !states) return fail(RL_E_INVALID, "null state buffer");
     if (!scene) return fail(RL_E_INVALID, "null scene");
+    return RL_OK;
+}
+
+int path_list_check(const RlScene* scene, int fetch, uint32_t flags, const void* states, uint32_t n_states, const void* list, uint32_t n_list) {
+    const int rc = step_check(scene, fetch, flags, states, n_list);
+    if (rc != RL_OK) return rc;
+    if (!list && n_list > n_states) return fail(RL_E_INVALID, "the identity list (list = NULL) is longer than the state buffer");
     return RL_OK;
 }
 
@@ -971,6 +1035,69 @@ int rl_scene_step_paths_device(const RlScene* scene, int primitive_fetch, uint64
     return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
         return launch_step(scene, primitive_fetch, cus, q, seed, stream, flags, device_states, device_hits, n);
     });
+}
+
+int rl_scene_step_path_list_device(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, uint32_t flags,
+                                   RlPathState* device_states, uint32_t n_states, const uint32_t* device_list, uint32_t n_list,
+                                   RlRayHit* device_hits, uint32_t* device_live_list, uint32_t* n_live) {
+    int rc = path_list_check(scene, primitive_fetch, flags, device_states, n_states, device_list, n_list);
+    if (rc != RL_OK) return rc;
+    if (n_live) *n_live = 0u;
+    if (n_list == 0) return RL_OK;
+    const char* what = "rl_scene_step_path_list_device";
+    if ((rc = states_aligned(device_states, what)) != RL_OK) return rc;
+    if (((uintptr_t)device_list | (uintptr_t)device_live_list) & 3u) return fail(RL_E_INVALID, std::string(what) + ": a list is not 4-byte aligned");
+    if ((rc = use_device(scene->device)) != RL_OK) return rc;
+    if ((rc = device_buffers_check(scene, device_states, device_hits, what, "rl_scene_step_path_list")) != RL_OK) return rc;
+    if ((rc = device_buffers_check(scene, device_list, device_live_list, what, "rl_scene_step_path_list")) != RL_OK) return rc;
+    uint32_t total = 0; // (written by the call's copy, read behind with_query_ctx's synchronise)
+    rc = with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
+        return launch_list_step(scene, primitive_fetch, cus, q, seed, stream, flags, device_states, n_states, device_list, n_list, device_hits,
+                                device_live_list, n_live ? &total : nullptr);
+    });
+    if (rc == RL_OK && n_live) *n_live = total;
+    return rc;
+}
+
+// Not chunked: device buffers of the call's own for the whole arrays (the context's staging buffers hold 2^20 records, and a
+// list names states anywhere in the array).
+int rl_scene_step_path_list(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, uint32_t flags, RlPathState* states,
+                            uint32_t n_states, const uint32_t* list, uint32_t n_list, RlRayHit* hits, uint32_t* live_list, uint32_t* n_live) {
+    int rc = path_list_check(scene, primitive_fetch, flags, states, n_states, list, n_list);
+    if (rc != RL_OK) return rc;
+    if (n_live) *n_live = 0u;
+    if (n_list == 0) return RL_OK;
+    if ((rc = use_device(scene->device)) != RL_OK) return rc;
+    struct Buffers { // freed on every way out
+        void* p[4] = {};
+        ~Buffers() {
+            for (void* b : p)
+                if (b) (void)hipFree(b);
+        }
+    } dev;
+    enum { STATES, HITS, LIST, LIVE };
+    const size_t bytes[4] = {(size_t)n_states * sizeof(RlPathState), hits ? (size_t)n_states * sizeof(RlRayHit) : 0u,
+                             list ? (size_t)n_list * sizeof(uint32_t) : 0u, live_list ? (size_t)n_list * sizeof(uint32_t) : 0u};
+    for (int k = 0; k < 4; ++k)
+        if (bytes[k]) RL_HIP(hipMalloc(&dev.p[k], bytes[k]));
+    uint32_t total = 0;
+    rc = with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
+        // (the caller's hits go in too: the slots of the states that are not stepped come back as they were)
+        const void* in[3] = {states, hits, list};
+        for (int k = 0; k < 3; ++k)
+            if (bytes[k]) RL_HIP(hipMemcpyAsync(dev.p[k], in[k], bytes[k], hipMemcpyHostToDevice, q->stream));
+        const int r = launch_list_step(scene, primitive_fetch, cus, q, seed, stream, flags, (RlPathState*)dev.p[STATES], n_states,
+                                       (const uint32_t*)dev.p[LIST], n_list, (RlRayHit*)dev.p[HITS], (uint32_t*)dev.p[LIVE],
+                                       live_list || n_live ? &total : nullptr);
+        if (r != RL_OK) return r;
+        if (bytes[STATES]) RL_HIP(hipMemcpyAsync(states, dev.p[STATES], bytes[STATES], hipMemcpyDeviceToHost, q->stream));
+        if (bytes[HITS]) RL_HIP(hipMemcpyAsync(hits, dev.p[HITS], bytes[HITS], hipMemcpyDeviceToHost, q->stream));
+        RL_HIP(hipStreamSynchronize(q->stream)); // (`total` is known from here)
+        if (live_list && total) RL_HIP(hipMemcpyAsync(live_list, dev.p[LIVE], (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, q->stream));
+        return RL_OK;
+    });
+    if (rc == RL_OK && n_live) *n_live = total;
+    return rc;
 }
 
 // ---- TraceUnit ----------------------------------------------------------------------------------
@@ -2310,6 +2437,7 @@ int rl_debug_occlusion_launches(uint64_t* out) { return family_launches(g_occlus
 int rl_debug_path_launches(uint64_t* out) { return family_launches(g_path_kernels, out); }
 int rl_debug_film_launches(uint64_t* out) { return family_launches(g_film_kernels, out); }
 int rl_debug_step_launches(uint64_t* out) { return family_launches(g_step_kernels, out); }
+int rl_debug_path_list_launches(uint64_t* out) { return family_launches(g_list_step_kernels, out); }
 
 // ---- device-side math probe (tests) -------------------------------------------------------------
 

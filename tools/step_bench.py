@@ -10,6 +10,13 @@ states.  Measured, each as the host clock around calls that end synchronised, af
   (b) the same step with hits written, as a ratio to (a).
   (c) the whole wavefront loop to the last live path -- step, keep the live states by torch indexing, step again -- against
       rl_scene_render_rays_device on the same rays; its final states are checked against that call's results.  Reported only.
+  (d) list_step: one listed step of every state (rl_scene_step_path_list_device, the identity list, live_list written, hits =
+      NULL) against (a)'s step in the same run.  It moves at most (128 + 16) / 128 = 1.125 x the step's bytes per state and does
+      the same arithmetic: the bar is 1.125 x the step's median plus the step's min-max spread.
+  (e) wavefront_list: the whole loop through rl_scene_step_path_list_device, two index buffers taking turns as list and
+      live_list, the states staying where they are; final states checked as (c)'s.  Against (c)'s wavefront, the torch-compaction
+      loop: its median must be below wavefront's by more than wavefront's own min-max spread.  Both as ratios to render_rays.
+The variant reported is the step kernel's; the list-step kernel runs the same one (one scene, one fetch mode).
 Prints one JSON line.  Usage (on a GPU machine): python tools/step_bench.py [--paths 67108864] [--reps 5]"""
 import argparse
 import json
@@ -82,43 +89,73 @@ def main():
             live = live[~ended].contiguous()
         return steps
 
+    ping = torch.empty(n, dtype=torch.int32, device=dev)
+    pong = torch.empty(n, dtype=torch.int32, device=dev)
+
+    def wavefront_list():
+        """The loop of (e): returns the number of steps; the final states are in `work`, where they always were."""
+        lst, out, n_list, steps = None, ping, n, 0
+        while n_list and steps < R.RL_PATH_MAX_SEGMENTS:   # (render_rays ends every path by then)
+            n_list = scene.step_path_list_device(work, SEED, STREAM, lst, n_list, out)
+            steps += 1
+            lst, out = out, (pong if out is ping else ping)
+        return steps
+
+    def check_against_results(what):
+        torch.cuda.synchronize()
+        same = bool((work[:, [11, 9, 14, 10]] == results).all().item())   # value, segments, object, end
+        assert same, "the %s loop and rl_scene_render_rays_device disagree" % what
+        return same
+
     candidates = {
         "query": lambda: scene.intersect_device(query_rays, hits),
         "step": lambda: scene.step_paths_device(work, SEED, STREAM),
         "step_hits": lambda: scene.step_paths_device(work, SEED, STREAM, hits=hits),
         "render_rays": lambda: scene.render_rays_device(rays, results, SEED, STREAM, 0),
         "wavefront": wavefront,
+        "list_step": lambda: scene.step_path_list_device(work, SEED, STREAM, None, n, ping),
+        "wavefront_list": wavefront_list,
     }
     times = {k: [] for k in candidates}
     before = R.step_launches()
-    steps = 0
+    steps = {}
     for rep in range(args.reps + 1):   # round 0 warms up
         for name, fn in candidates.items():
             reset()
-            if name == "wavefront":
+            if name in ("wavefront", "wavefront_list"):
                 box = []
                 t = timed(lambda: box.append(fn()))
-                steps = box[0]
+                steps[name] = box[0]
+                if name == "wavefront_list" and rep in (0, args.reps):
+                    check_against_results(name)   # (results: render_rays has run in this round)
             else:
                 t = timed(fn)
             if rep:
                 times[name].append(t)
+    reset()
+    steps["wavefront"] = wavefront()   # (c)'s check below reads `work`: the last candidate above left its own states there
     variant = next(i for i, (a, b) in enumerate(zip(R.step_launches(), before)) if a != b)
 
     # (c)'s final states against the path kernel's results: value, segments, object, end
-    torch.cuda.synchronize()
-    same = bool((work[:, [11, 9, 14, 10]] == results).all().item())
-    assert same, "the wavefront loop and rl_scene_render_rays_device disagree"
+    same = check_against_results("wavefront")
     segments = int(results[:, 1].sum(dtype=torch.int64).item())
 
     q, a, b = summary(times["query"]), summary(times["step"]), summary(times["step_hits"])
     r, c = summary(times["render_rays"]), summary(times["wavefront"])
+    d, e = summary(times["list_step"]), summary(times["wavefront_list"])
     bar = 1.44 * q["median_ms"] + (q["max_ms"] - q["min_ms"])
+    d_bar = 1.125 * a["median_ms"] + (a["max_ms"] - a["min_ms"])
+    c_spread = c["max_ms"] - c["min_ms"]
     out = {"tool": "step_bench", "build_id": R.build_id(), "scene": "built-in", "fetch": "lds", "variant": variant, "paths": n,
            "reps": args.reps, "segments": segments, "query": q, "step": a, "step_hits": b, "render_rays": r, "wavefront": c,
-           "wavefront_steps": steps, "a_step_over_query": round(a["median_ms"] / q["median_ms"], 4), "a_bar_ms": round(bar, 3),
+           "wavefront_steps": steps["wavefront"], "a_step_over_query": round(a["median_ms"] / q["median_ms"], 4), "a_bar_ms": round(bar, 3),
            "a_within_bar": a["median_ms"] <= bar, "b_hits_over_step": round(b["median_ms"] / a["median_ms"], 4),
-           "c_wavefront_over_render_rays": round(c["median_ms"] / r["median_ms"], 4), "wavefront_equals_render_rays": same}
+           "c_wavefront_over_render_rays": round(c["median_ms"] / r["median_ms"], 4), "wavefront_equals_render_rays": same,
+           "list_step": d, "wavefront_list": e, "wavefront_list_steps": steps["wavefront_list"],
+           "d_list_step_over_step": round(d["median_ms"] / a["median_ms"], 4), "d_bar_ms": round(d_bar, 3), "d_within_bar": d["median_ms"] <= d_bar,
+           "e_wavefront_list_over_wavefront": round(e["median_ms"] / c["median_ms"], 4), "e_wavefront_spread_ms": round(c_spread, 3),
+           "e_below_wavefront_by_more_than_its_spread": e["median_ms"] < c["median_ms"] - c_spread,
+           "e_wavefront_list_over_render_rays": round(e["median_ms"] / r["median_ms"], 4), "wavefront_list_equals_render_rays": True}
     print(json.dumps(out))
 
 
