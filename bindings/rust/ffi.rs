@@ -41,6 +41,10 @@ pub const RL_PATH_MAX_SEGMENTS_CAP: u32 = 65536;
 } // 64 bytes
 pub const RL_PATH_LIVE: u32 = 0xffff_ffff;
 pub const RL_STEP_NO_ROULETTE: u32 = 1;
+#[repr(C)] #[derive(Copy, Clone)] pub struct RlLightSample {      // rl_scene_light_paths: one direct-light sample per path vertex
+    pub direction: RlVector3, pub distance: f32, pub value: f32, pub weight: f32, pub emitter: u32,
+    pub status: u32,    // 0 skipped, 1 backfacing, 2 occluded, 3 visible
+} // 32 bytes
 
 pub const RL_MAX_PIXELS: usize = 2147483647;
 pub const RL_TASK_MAX_UNITS: usize = 256;
@@ -106,6 +110,12 @@ extern "C" {
     pub fn rl_scene_step_path_list_device(scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32, flags: u32,
                                           device_states: *mut RlPathState, n_states: u32, device_list: *const u32, n_list: u32,
                                           device_hits: *mut RlRayHit, device_live_list: *mut u32, n_live: *mut u32) -> c_int;
+    pub fn rl_scene_emitters(scene: *const RlScene, objects: *mut u32, cap: u32, n_emitters: *mut u32) -> c_int;
+    pub fn rl_scene_light_paths(scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32, states: *const RlPathState,
+                                n_states: u32, list: *const u32, n_list: u32, hits: *const RlRayHit, samples: *mut RlLightSample) -> c_int;
+    pub fn rl_scene_light_paths_device(scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32,
+                                       device_states: *const RlPathState, n_states: u32, device_list: *const u32, n_list: u32,
+                                       device_hits: *const RlRayHit, device_samples: *mut RlLightSample) -> c_int;
 
     pub fn rl_trace_unit_create(device: c_int, id: u32, w: u32, h: u32, n_photons: u32, out: *mut *mut RlTraceUnit) -> c_int;
     pub fn rl_trace_unit_destroy(u: *mut RlTraceUnit) -> c_int;

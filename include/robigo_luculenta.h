@@ -386,6 +386,94 @@ int rl_scene_step_path_list_device(const RlScene* scene, int primitive_fetch, ui
                                    RlPathState* device_states, uint32_t n_states, const uint32_t* device_list, uint32_t n_list,
                                    RlRayHit* device_hits, uint32_t* device_live_list, uint32_t* n_live);
 
+/* ---- direct light at a path vertex (not in the reference: "there is always an option of trying direct illumination, which
+ * could be implemented here, but is not", trace_unit.rs:128-131) ---------------------------------------------------------- */
+
+/* The sampleable emitters of a scene, fixed at rl_scene_create: the objects whose material is RL_MATERIAL_BLACK_BODY and whose
+ * surface is an RL_SURFACE_SPHERE with a finite radius > 0, or an RL_SURFACE_CIRCLE with a finite radius > 0 and a normal whose
+ * |n|^2 is within 2^-20 of 1.  Planes, paraboloids and prisms are unbounded or have no simple area measure: they are never
+ * sampled, and paths still end on them as before.  rl_scene_emitters writes their object indices in scan order; host-only, no
+ * device work; rl_scene_builtin_desc's capacity protocol: *n_emitters receives their number, and when cap is too small (or
+ * objects is NULL with emitters to report) the call returns RL_E_INVALID with *n_emitters set.  A NULL scene or a NULL
+ * n_emitters is RL_E_INVALID. */
+int rl_scene_emitters(const RlScene* scene, uint32_t* objects, uint32_t cap, uint32_t* n_emitters);
+
+enum RlLightStatus {
+    RL_LIGHT_SKIPPED = 0,    /* no sample was drawn for this state (rule below) */
+    RL_LIGHT_BACKFACING = 1, /* a point was drawn, but it is not in front of both surfaces: no ray cast */
+    RL_LIGHT_OCCLUDED = 2,   /* the shadow ray is blocked */
+    RL_LIGHT_VISIBLE = 3     /* it is not: value is the contribution */
+};
+
+typedef struct RlLightSample {
+    RlVector3 direction; /* unit vector from the vertex to the sampled point; zero when SKIPPED */
+    float distance;      /* from the vertex to the sampled point; 0 when SKIPPED */
+    float value;         /* state.intensity * weight when VISIBLE, else 0 */
+    float weight;        /* emitted intensity * geometry term * area * n_emitters / pi, whatever the ray found;
+                            0 when SKIPPED or BACKFACING */
+    uint32_t emitter;    /* object index of the sampled emitter; RL_OBJECT_NONE when SKIPPED */
+    uint32_t status;     /* enum RlLightStatus */
+} RlLightSample;         /* 32 bytes */
+
+/* Next-event estimation for path states a step has just moved: for every listed state the call picks one of the scene's
+ * sampleable emitters and a point on it, casts the shadow ray from the state's last vertex on rl_scene_occluded's bounded scan, and
+ * writes the connection's contribution.  hits[i] must be the record rl_scene_step_paths* / rl_scene_step_path_list* wrote for
+ * state i's last segment: the call trusts its position, normal and object, and no content of any buffer makes it touch memory
+ * outside the buffers.
+ *
+ * The list is rl_scene_step_path_list's: list == NULL is the identity list 0 .. n_list - 1 (then n_list > n_states is
+ *   RL_E_INVALID); an entry >= n_states is skipped with nothing read or written; entries must be distinct (a state named twice is
+ *   memory-safe and its sample unspecified).  hits and samples are indexed by STATE and have room for n_states records.  states,
+ *   hits and list are never written.  samples[i] is written, all 32 bytes, for every listed state i < n_states; samples[j] of a
+ *   state that is not listed is not touched.
+ * Which states get a sample.  State i is sampled if its end is RL_PATH_LIVE or RL_PATH_END_ROULETTE (the vertex exists either
+ *   way), segments >= 1, hits[i].object < the scene's object count, that object's material is RL_MATERIAL_DIFFUSE_GREY or
+ *   RL_MATERIAL_DIFFUSE_COLOURED (the two whose BRDF the library can state: glossy, glass and soap vertices are not sampled) and
+ *   the scene has at least one sampleable emitter.  Every other listed state gets RL_LIGHT_SKIPPED: every field zero but
+ *   emitter = RL_OBJECT_NONE.
+ * The sample, all in f32 without contraction, in this order (csrc/rl_core.h: rl_light_sample, the same function on the device
+ *   and in the host's rl_debug_light_sample):
+ *   Draws.  w = Philox block 0x80000000 + state.segments (32-bit sum) of (seed, stream, state.path_index): disjoint from the
+ *     path's own blocks (csrc/rl_rng.h).  k = ((uint64_t)w[2] * n_emitters) >> 32 picks emitter k of rl_scene_emitters' list;
+ *     u = closed01(w[0]) in [0, 1]; phi = the half-open longitude of w[1] in [0, 2 pi); slot 3 is unused.
+ *   A sphere (c, R): z = 1 - 2u, r = sqrt(max(0, 1 - z z)), nl = (r cos phi, r sin phi, z), q = c + nl R, area4 = 4 R R.
+ *   A circle (n, p, R): r = R sqrt(u), q = p + rotate_towards((r cos phi, r sin phi, 0), n) (vector3.rs:69-83), nl = n,
+ *     area4 = R R.
+ *   The vertex: x = hits[i].position; facing = hits[i].normal if dot(state.direction, hits[i].normal) >= 0, else its negation --
+ *     the side the path leaves on (the state holds the bounced ray, and a diffuse bounce leaves on the facing side);
+ *     v = q - x, d2 = dot(v, v), distance = sqrt(d2), direction = normalise(v) (vector3.rs:56-67);
+ *     cos_s = dot(facing, direction); cos_l = -dot(nl, direction) for a sphere and |dot(nl, direction)| for a circle, which emits
+ *     from both faces as in the reference.
+ *   RL_LIGHT_BACKFACING unless cos_s > 0, cos_l > 0 and d2 > 0 with all three finite: weight and value 0, no ray.  If d2 is not
+ *     a finite number > 0 (a vertex on the sampled point, a hit record that is not finite), direction and distance are written
+ *     zero as well.
+ *   weight = (L * ((cos_s * cos_l) / d2)) * (area4 * (float)n_emitters), L = (float)planck(wavelength, kelvins) * normalisation:
+ *     get_intensity of the emitter at the state's wavelength (material.rs:61-74,101-105).  The pi of the diffuse BRDF and the pi
+ *     of the area cancel, and state.intensity already carries the reflectance (the reference's diffuse bounce is cosine-weighted
+ *     with probability = reflectance).
+ *   The shadow ray: origin x + direction * 1e-5 (the reference's offset, trace_unit.rs:114), the direction above,
+ *     t_max = (distance - 1e-5) * 0.9990234375.  The factor 1 - 2^-10 keeps the emitter from blocking its own point: an occluder in
+ *     the last 2^-10 of the segment is NOT seen.  The ray is blocked exactly when rl_scene_occluded returns 1 for that RlRay,
+ *     including its rays-as-given rule for the exact linear scan.  Blocked: RL_LIGHT_OCCLUDED, value 0.  Otherwise
+ *     RL_LIGHT_VISIBLE, value = state.intensity * weight.
+ * Determinism.  A sample depends only on the scene, seed, stream, the state and its hit: not on primitive_fetch or the kernel
+ *   variant, on the list, on how a batch is split, or on other callers.
+ * Arguments, checked in this order, each failure RL_E_INVALID with a message before any device work: an unknown fetch mode; NULL
+ *   states, hits or samples with n_list > 0; a NULL scene; list == NULL with n_list > n_states.  n_list == 0 does nothing.
+ * The _device form takes device pointers on the scene's device -- states and samples 16-byte aligned, list 4-byte aligned, hits as
+ *   the step calls take them -- refuses pageable host memory and returns when the samples are written.  The host form is NOT
+ *   chunked: like rl_scene_step_path_list it copies the whole arrays (states, hits, list, samples) through device buffers of the
+ *   call's own.  Both are safe from several host threads at once on one scene and order against open launches as
+ *   rl_scene_intersect does.
+ * Counting light once.  A path that ENDS on an emitter listed by rl_scene_emitters directly after a diffuse-grey or
+ *   diffuse-coloured vertex carries light that this call's sample at that vertex has already estimated.  A caller who adds
+ *   samples drops, or weights, that RlPathState::value.  The library does not do it for them. */
+int rl_scene_light_paths(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, const RlPathState* states,
+                         uint32_t n_states, const uint32_t* list, uint32_t n_list, const RlRayHit* hits, RlLightSample* samples);
+int rl_scene_light_paths_device(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream,
+                                const RlPathState* device_states, uint32_t n_states, const uint32_t* device_list, uint32_t n_list,
+                                const RlRayHit* device_hits, RlLightSample* device_samples);
+
 /* Largest image the units and rl_app_run accept: width * height <= RL_MAX_PIXELS = 2^31 - 1.  The kernels index
  * pixels in 32 bits: the splat's `py * width + px` is an int, the tonemap's pixel count and grid-stride index are
  * uint32_t.  rl_trace_unit_create, rl_plot_unit_create, rl_gather_unit_create, rl_tonemap_unit_create and rl_app_run

@@ -53,6 +53,19 @@ int rl_debug_step_launches(uint64_t* out);
 /* out[v], v = 0..5: launches of instantiation v of the list-step kernel (rl_scene_step_path_list*) since the library was loaded,
  * indexed as rl_debug_query_launches is. */
 int rl_debug_path_list_launches(uint64_t* out);
+/* out[v], v = 0..5: launches of instantiation v of the light kernel (rl_scene_light_paths*) since the library was loaded, indexed
+ * as rl_debug_query_launches is. */
+int rl_debug_light_launches(uint64_t* out);
+/* rl_scene_emitters for a description instead of a scene: the sampleable emitters' object indices in scan order, by the function
+ * rl_scene_create builds a scene's table with.  Host arithmetic only: callable without a GPU.  The same capacity protocol. */
+int rl_debug_scene_emitters(const RlObjectDesc* objects, uint32_t n_objects, uint32_t* out, uint32_t cap, uint32_t* n_emitters);
+/* The HOST compile of the sampling function behind rl_scene_light_paths (csrc/rl_core.h: rl_light_sample, the function the
+ * kernel calls) for n (state, hit) pairs and the emitter table of a description, under (seed, stream); no device.  samples[i] is
+ * what the call writes for states[i], hits[i] when the shadow ray is not blocked: RL_LIGHT_VISIBLE with its value wherever a ray
+ * is cast.  rays (may be NULL) receives that ray -- the RlRay rl_scene_occluded decides -- and an all-zero record where none is
+ * cast. */
+int rl_debug_light_sample(const RlObjectDesc* objects, uint32_t n_objects, uint64_t seed, uint32_t stream, const RlPathState* states,
+                          const RlRayHit* hits, uint32_t n, RlLightSample* samples, RlRay* rays);
 /* The prism shortcut (csrc/rl_core.h: rl_hex_prism_fast) against the Compound tree it stands in for
  * (geometry.rs:380-407), both evaluated ON THE GPU -- with the hardware's v_rcp_f32 -- for n rays against prism
  * `prism` (0-based, in the scene's flattened order) of `scene`.  rays: n x {origin.xyz, direction.xyz}.

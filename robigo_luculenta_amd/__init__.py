@@ -11,7 +11,8 @@ import numpy as np
 from ._lib import (RlAppConfig, RlAppStats, RlCameraDesc, RlCameraSample, RlError, RlIntersection, RlMappedPhoton, RlObjectDesc, RlPathResult,
                    RlPathState, RL_PATH_LIVE, RL_STEP_NO_ROULETTE, RlRay, RlRayHit, RlSceneDesc, RlSpectralRay, RlTask, RlVector3, check, lib, RL_OBJECT_NONE, RL_PATH_END_EMITTER,
                    RL_PATH_END_INVALID, RL_PATH_END_LIMIT, RL_PATH_END_ROULETTE, RL_PATH_END_VOID, RL_PATH_MAX_SEGMENTS,
-                   RL_PATH_MAX_SEGMENTS_CAP, RL_TASK_MAX_UNITS)
+                   RL_PATH_MAX_SEGMENTS_CAP, RL_TASK_MAX_UNITS, RlLightSample, RL_LIGHT_SKIPPED, RL_LIGHT_BACKFACING, RL_LIGHT_OCCLUDED,
+                   RL_LIGHT_VISIBLE)
 
 PHOTON_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("probability", "<f4"), ("wavelength", "<f4")])
 OBJECT_DTYPE = np.dtype([("surface_kind", "<u4"), ("material_kind", "<u4"), ("v0", "<f4", 3), ("v1", "<f4", 3),
@@ -28,6 +29,9 @@ PATH_RESULT_DTYPE = np.dtype([("value", "<f4"), ("segments", "<u4"), ("object", 
 PATH_STATE_DTYPE = np.dtype([("origin", "<f4", 3), ("wavelength", "<f4"), ("direction", "<f4", 3), ("intensity", "<f4"),
                              ("continue_chance", "<f4"), ("segments", "<u4"), ("end", "<u4"), ("value", "<f4"), ("path_index", "<u8"),
                              ("object", "<u4"), ("reserved", "<u4")])
+# Scene.light_paths records: RlLightSample (32 bytes)
+LIGHT_SAMPLE_DTYPE = np.dtype([("direction", "<f4", 3), ("distance", "<f4"), ("value", "<f4"), ("weight", "<f4"), ("emitter", "<u4"),
+                               ("status", "<u4")])
 NUMBER_OF_PHOTONS = 1024 * 512  # trace_unit.rs:67
 
 SCENE_DEMO, SCENE_GLASS_STRESS = 0, 1
@@ -303,6 +307,59 @@ class Scene(_Handle):
         check(lib.rl_scene_step_path_list_device(self._h, fetch, seed, stream, flags, ptr(states), n, ptr(list), n_list, ptr(hits), ptr(live_list),
                                                  C.byref(n_live)))
         return n_live.value
+
+
+    def emitters(self):
+        """rl_scene_emitters: the object indices of the scene's sampleable emitters (black-body spheres and circles), in scan
+        order, as a uint32 array."""
+        n = C.c_uint32(0)
+        lib.rl_scene_emitters(self._h, None, 0, C.byref(n))
+        out = np.zeros(n.value, dtype=np.uint32)
+        check(lib.rl_scene_emitters(self._h, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        return out
+
+    def light_paths(self, states, hits, seed, stream, list=None, n_list=None, fetch=FETCH_LDS, samples=None):
+        """rl_scene_light_paths: one direct-light sample for the states of an (n,) PATH_STATE_DTYPE array that `list` names (an
+        array of indices, converted to uint32; entries >= n are skipped), or for states 0 .. n_list - 1 when list is None (n_list
+        defaults to n).  hits: the (n,) HIT_DTYPE array the step wrote, indexed by state.  samples: None (a zeroed array is made),
+        or an (n,) LIGHT_SAMPLE_DTYPE array whose records of the listed states are overwritten.  Returns `samples`."""
+        if states.dtype != PATH_STATE_DTYPE or not states.flags.c_contiguous:
+            raise ValueError("states must be a contiguous PATH_STATE_DTYPE array")
+        if hits.dtype != HIT_DTYPE or not hits.flags.c_contiguous or len(hits) < len(states):
+            raise ValueError("hits must be a contiguous HIT_DTYPE array with room for every state")
+        if samples is None:
+            samples = np.zeros(len(states), dtype=LIGHT_SAMPLE_DTYPE)
+        if samples.dtype != LIGHT_SAMPLE_DTYPE or not samples.flags.c_contiguous or not samples.flags.writeable or len(samples) < len(states):
+            raise ValueError("samples must be a contiguous, writeable LIGHT_SAMPLE_DTYPE array with room for every state")
+        lp = None
+        if list is not None:
+            list = np.ascontiguousarray(list, dtype=np.uint32)
+            if n_list is None:
+                n_list = len(list)
+            if list.ndim != 1 or n_list > len(list):
+                raise ValueError("list must be a one-dimensional array of at least n_list indices")
+            lp = list.ctypes.data_as(C.c_void_p)
+        elif n_list is None:
+            n_list = len(states)
+        check(lib.rl_scene_light_paths(self._h, fetch, seed, stream, states.ctypes.data_as(C.c_void_p), len(states), lp, n_list,
+                                       hits.ctypes.data_as(C.c_void_p), samples.ctypes.data_as(C.c_void_p)))
+        return samples
+
+    def light_paths_device(self, states, hits, samples, seed, stream, list=None, n_list=None, fetch=FETCH_LDS):
+        """rl_scene_light_paths_device: `states`, `hits` and `samples` are device buffers on the scene's device with data_ptr()
+        (e.g. torch tensors) holding n PATH_STATE_DTYPE records, n HIT_DTYPE records and room for n LIGHT_SAMPLE_DTYPE records;
+        `list` None (states 0 .. n_list - 1, n_list defaults to n) or a device buffer of at least n_list uint32 indices."""
+        n_bytes = lambda t: t.numel() * t.element_size()
+        n = n_bytes(states) // PATH_STATE_DTYPE.itemsize
+        if n_bytes(states) != n * PATH_STATE_DTYPE.itemsize or n_bytes(hits) < n * HIT_DTYPE.itemsize or n_bytes(samples) < n * LIGHT_SAMPLE_DTYPE.itemsize:
+            raise ValueError("states must hold whole 64-byte records, hits room for as many 48-byte ones and samples for as many 32-byte ones")
+        if n_list is None:
+            n_list = n if list is None else n_bytes(list) // 4
+        if list is not None and n_bytes(list) < 4 * n_list:
+            raise ValueError("list must have room for n_list 4-byte indices")
+        check(lib.rl_scene_light_paths_device(self._h, fetch, seed, stream, C.c_void_p(states.data_ptr()), n,
+                                              C.c_void_p(list.data_ptr()) if list is not None else None, n_list, C.c_void_p(hits.data_ptr()),
+                                              C.c_void_p(samples.data_ptr())))
 
 
 class TraceUnit(_Handle):
@@ -685,6 +742,40 @@ def path_list_launches():
     out = (C.c_uint64 * 6)()
     check(lib.rl_debug_path_list_launches(out))
     return list(out)
+
+
+def light_launches():
+    """Launches per light-kernel instantiation since the library was loaded (rl_debug_light_launches); index = 2 * stage +
+    (prisms carry a second bound), as query_launches()."""
+    out = (C.c_uint64 * 6)()
+    check(lib.rl_debug_light_launches(out))
+    return list(out)
+
+
+def description_emitters(objects):
+    """rl_debug_scene_emitters: the object indices of the sampleable emitters of an OBJECT_DTYPE description, without a device."""
+    objects = np.ascontiguousarray(objects, dtype=OBJECT_DTYPE)
+    n = C.c_uint32(0)
+    lib.rl_debug_scene_emitters(objects.ctypes.data_as(C.c_void_p), len(objects), None, 0, C.byref(n))
+    out = np.zeros(n.value, dtype=np.uint32)
+    check(lib.rl_debug_scene_emitters(objects.ctypes.data_as(C.c_void_p), len(objects), out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+    return out
+
+
+def light_sample_host(objects, states, hits, seed, stream):
+    """rl_debug_light_sample: the host compile of the light sampling function for (n,) PATH_STATE_DTYPE states and HIT_DTYPE hits
+    against the emitters of an OBJECT_DTYPE description; no device.  Returns (samples, rays): LIGHT_SAMPLE_DTYPE records as the
+    call writes them for an unblocked ray, and the RAY_DTYPE shadow rays (all zero where none is cast)."""
+    objects = np.ascontiguousarray(objects, dtype=OBJECT_DTYPE)
+    states = np.ascontiguousarray(states, dtype=PATH_STATE_DTYPE)
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    if len(hits) != len(states):
+        raise ValueError("states and hits differ in length")
+    samples = np.zeros(len(states), dtype=LIGHT_SAMPLE_DTYPE)
+    rays = np.zeros(len(states), dtype=RAY_DTYPE)
+    check(lib.rl_debug_light_sample(objects.ctypes.data_as(C.c_void_p), len(objects), seed, stream, states.ctypes.data_as(C.c_void_p),
+                                    hits.ctypes.data_as(C.c_void_p), len(states), samples.ctypes.data_as(C.c_void_p), rays.ctypes.data_as(C.c_void_p)))
+    return samples, rays
 
 
 def math_probe(fn, x, device=0):

@@ -82,6 +82,14 @@ class RlPathState(C.Structure):
                 ("path_index", C.c_uint64), ("object", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+RL_LIGHT_SKIPPED, RL_LIGHT_BACKFACING, RL_LIGHT_OCCLUDED, RL_LIGHT_VISIBLE = range(4)
+
+
+class RlLightSample(C.Structure):
+    _fields_ = [("direction", RlVector3), ("distance", C.c_float), ("value", C.c_float), ("weight", C.c_float),
+                ("emitter", C.c_uint32), ("status", C.c_uint32)]
+
+
 class RlTask(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("unit", C.c_uint32), ("n_units", C.c_uint32),
                 ("units", C.c_uint32 * RL_TASK_MAX_UNITS)]
@@ -131,6 +139,9 @@ SIGNATURES = {
     "rl_scene_step_paths_device": (_i, [_vp, _i, _u64, _u32, _u32, _vp, _u32, _vp]),
     "rl_scene_step_path_list": (_i, [_vp, _i, _u64, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
     "rl_scene_step_path_list_device": (_i, [_vp, _i, _u64, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
+    "rl_scene_emitters": (_i, [_vp, _vp, _u32, C.POINTER(_u32)]),
+    "rl_scene_light_paths": (_i, [_vp, _i, _u64, _u32, _vp, _u32, _vp, _u32, _vp, _vp]),
+    "rl_scene_light_paths_device": (_i, [_vp, _i, _u64, _u32, _vp, _u32, _vp, _u32, _vp, _vp]),
     "rl_trace_unit_create": (_i, [_i, _u32, _u32, _u32, _u32, _pp]),
     "rl_trace_unit_destroy": (_i, [_vp]),
     "rl_trace_unit_set_fetch": (_i, [_vp, _i]),
@@ -199,6 +210,9 @@ DEBUG_SIGNATURES = {
     "rl_debug_film_launches": (_i, [_vp]),
     "rl_debug_step_launches": (_i, [_vp]),
     "rl_debug_path_list_launches": (_i, [_vp]),
+    "rl_debug_light_launches": (_i, [_vp]),
+    "rl_debug_scene_emitters": (_i, [_vp, _u32, _vp, _u32, C.POINTER(_u32)]),
+    "rl_debug_light_sample": (_i, [_vp, _u32, _u64, _u32, _vp, _vp, _u32, _vp, _vp]),
     "rl_debug_prism_probe": (_i, [_vp, _u32, _vp, _u32, _vp]),
     "rl_debug_prism_count": (_i, [_vp, C.POINTER(_u32)]),
 }

@@ -47,6 +47,7 @@
 #include "rl_paths.hip.h"
 #include "rl_step.hip.h"
 #include "rl_path_list.hip.h"
+#include "rl_light.hip.h"
 #include "rl_scene.h"
 
 namespace {
@@ -106,6 +107,10 @@ struct RlScene {
     RlSceneLayout lay;
     size_t staged_bytes; // the whole blob
     size_t tables_bytes; // its tables: records [off_planes, off_objects)
+    // The sampleable emitters (rl_scene_emitters, rl_scene_light_paths*): a device buffer of its own beside the blob,
+    // RL_EMITTER_STRIDE records each, and their object indices in scan order.  Null and empty for a scene without one.
+    RlF4* emitters;
+    std::vector<uint32_t> emitter_objects;
 };
 
 namespace {
@@ -336,7 +341,7 @@ int launch_trace(RlTraceUnit* u, const RlScene* scene, RlMappedPhoton* photons, 
 
 // ---- the persistent ray kernels beside the trace kernel (rl_query.hip.h, rl_occlusion.hip.h, rl_paths.hip.h, rl_step.hip.h, rl_path_list.hip.h) ----
 // A family is one kernel template's six instantiations, index = 2 * stage + cylinders, and the launches of each since the library
-// was loaded (rl_debug_{query,occlusion,path,film,step,path_list}_launches).  P: the kernel's parameters behind the scene blob and its layout.
+// was loaded (rl_debug_{query,occlusion,path,film,step,path_list,light}_launches).  P: the kernel's parameters behind the scene blob and its layout.
 template <class... P>
 struct KernelFamily {
     void (*variants[6])(const RlF4*, RlSceneLayout, P...);
@@ -349,6 +354,7 @@ KernelFamily<const RlSpectralRay*, RlPathResult*, uint32_t, uint64_t, uint32_t, 
 KernelFamily<const RlCameraSample*, RlPathResult*, uint32_t, uint64_t, uint32_t, uint64_t, uint32_t, unsigned long long*> g_film_kernels = RL_VARIANTS(rl_film_paths_kernel);
 KernelFamily<RlPathState*, RlRayHit*, uint32_t, uint64_t, uint32_t, uint32_t, unsigned long long*> g_step_kernels = RL_VARIANTS(rl_step_kernel);
 KernelFamily<RlPathState*, RlRayHit*, unsigned long long*> g_list_step_kernels = RL_VARIANTS(rl_list_step_kernel);
+KernelFamily<unsigned long long*> g_light_kernels = RL_VARIANTS(rl_light_kernel);
 #undef RL_VARIANTS
 template <class... P>
 int family_launches(const KernelFamily<P...>& family, uint64_t* out) {
@@ -410,9 +416,11 @@ void query_ctx_release(int device, QueryCtx* q) {
     std::lock_guard<std::mutex> guard(d->lock);
     d->idle.push_back(q);
 }
-// The context's queue counter (an RlFilmQueue or an RlPathListQueue: a launch's constants sit behind it), allocated on first use.
+// The context's queue counter (an RlFilmQueue, an RlPathListQueue or an RlLightQueue: a launch's constants sit behind it), allocated on first use.
 int query_ctx_queue(QueryCtx* q) {
-    if (!q->queue) RL_HIP(hipMalloc((void**)&q->queue, sizeof(RlFilmQueue) > sizeof(RlPathListQueue) ? sizeof(RlFilmQueue) : sizeof(RlPathListQueue)));
+    size_t bytes = sizeof(RlFilmQueue) > sizeof(RlPathListQueue) ? sizeof(RlFilmQueue) : sizeof(RlPathListQueue);
+    if (sizeof(RlLightQueue) > bytes) bytes = sizeof(RlLightQueue);
+    if (!q->queue) RL_HIP(hipMalloc((void**)&q->queue, bytes));
     return RL_OK;
 }
 
@@ -674,6 +682,67 @@ int launch_list_step(const RlScene* scene, int fetch, int cu_count, QueryCtx* q,
     return RL_OK;
 }
 
+// One direct-light sample for the states of device array states [0, n_states) that device array list [0, n_list) names (n_list > 0;
+// a null list: states 0 .. n_list - 1), from device array hits into device array samples, both indexed by state.  On q's stream: the
+// copy that zeroes the chunk counter and writes the launch's block behind it (RlLightQueue), then the light kernel.
+int launch_light(const RlScene* scene, int fetch, int cu_count, QueryCtx* q, uint64_t seed, uint32_t stream, const RlPathState* states,
+                 uint32_t n_states, const uint32_t* list, uint32_t n_list, const RlRayHit* hits, RlLightSample* samples) {
+    const int rc = query_ctx_queue(q);
+    if (rc != RL_OK) return rc;
+    RlLightQueue lq;
+    std::memset(&lq, 0, sizeof lq);
+    lq.job.states = states;
+    lq.job.hits = hits;
+    lq.job.list = list;
+    lq.job.emitters = scene->emitters;
+    lq.job.samples = samples;
+    lq.job.n_list = n_list;
+    lq.job.n_states = n_states;
+    lq.job.n_emitters = (uint32_t)scene->emitter_objects.size();
+    lq.job.stream = stream;
+    lq.job.seed = seed;
+    // (from pageable memory: the copy has left `lq` when the call returns)
+    RL_HIP(hipMemcpyAsync(q->queue, &lq, sizeof lq, hipMemcpyHostToDevice, q->stream));
+    return launch_persistent(g_light_kernels, scene, fetch, cu_count, q->stream, n_list, q->queue);
+}
+
+int light_check(const RlScene* scene, int fetch, const void* states, uint32_t n_states, const void* list, uint32_t n_list, const void* hits,
+                const void* samples) {
+    if (fetch_check(fetch) != RL_OK) return RL_E_INVALID;
+    if (n_list > 0 && (!states || !hits || !samples)) return fail(RL_E_INVALID, "null state, hit or sample buffer");
+    if (!scene) return fail(RL_E_INVALID, "null scene");
+    if (!list && n_list > n_states) return fail(RL_E_INVALID, "the identity list (list = NULL) is longer than the state buffer");
+    return RL_OK;
+}
+
+// The sampleable emitters of a description, in scan order (include/robigo_luculenta.h: rl_scene_emitters): their table as
+// rl_light_sample reads it (rl_core.h, RL_EMITTER_STRIDE records each) and their object indices.
+void emitter_table(const RlObjectDesc* objects, uint32_t n_objects, std::vector<RlF4>* table, std::vector<uint32_t>* indices) {
+    table->clear();
+    indices->clear();
+    for (uint32_t i = 0; i < n_objects; ++i) {
+        const RlObjectDesc& o = objects[i];
+        if (o.material_kind != RL_MATERIAL_BLACK_BODY) continue;
+        const bool bounded = o.f0 > 0.0f && o.f0 < INFINITY; // (false for NaN)
+        const float n2 = o.v0.x * o.v0.x + o.v0.y * o.v0.y + o.v0.z * o.v0.z;
+        RlF4 a, b, c;
+        if (o.surface_kind == RL_SURFACE_SPHERE && bounded) {
+            a = RlF4{o.v0.x, o.v0.y, o.v0.z, o.f0};
+            b = RlF4{0.0f, 0.0f, 0.0f, rl_u2f((uint32_t)RL_SURFACE_SPHERE)};
+        } else if (o.surface_kind == RL_SURFACE_CIRCLE && bounded && fabsf(n2 - 1.0f) <= 0x1p-20f) {
+            a = RlF4{o.v1.x, o.v1.y, o.v1.z, o.f0};
+            b = RlF4{o.v0.x, o.v0.y, o.v0.z, rl_u2f((uint32_t)RL_SURFACE_CIRCLE)};
+        } else {
+            continue;
+        }
+        c = RlF4{o.m0, rl_black_body_normalisation(o.m0, o.m1), rl_u2f(i), 0.0f}; // (the factor rl_flatten_scene gives the object record)
+        table->push_back(a);
+        table->push_back(b);
+        table->push_back(c);
+        indices->push_back(i);
+    }
+}
+
 // The begin kernel for device arrays rays, states [0, n) (n > 0) as paths first_path .. first_path + n - 1, on q's stream.
 int launch_begin(int cu_count, QueryCtx* q, uint64_t first_path, const RlSpectralRay* rays, RlPathState* states, uint32_t n) {
     hipLaunchKernelGGL(rl_begin_paths_kernel, dim3(grid_for(n, cu_count)), dim3(RL_BLOCK), 0, q->stream, rays, first_path, states, n);
@@ -867,9 +936,15 @@ int rl_scene_create(const RlSceneDesc* desc, int device, RlScene** out) {
     s->staged_bytes = blob.size() * sizeof(RlF4);
     s->tables_bytes = (size_t)(lay.off_objects - lay.off_planes) * sizeof(RlF4);
     s->blob = nullptr;
+    s->emitters = nullptr;
+    std::vector<RlF4> emitters;
+    emitter_table(desc->objects, desc->n_objects, &emitters, &s->emitter_objects);
     hipError_t e = hipMalloc((void**)&s->blob, s->staged_bytes);
     if (e == hipSuccess) e = hipMemcpy(s->blob, blob.data(), s->staged_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !emitters.empty()) e = hipMalloc((void**)&s->emitters, emitters.size() * sizeof(RlF4));
+    if (e == hipSuccess && !emitters.empty()) e = hipMemcpy(s->emitters, emitters.data(), emitters.size() * sizeof(RlF4), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
+        if (s->emitters) (void)hipFree(s->emitters);
         if (s->blob) (void)hipFree(s->blob);
         delete s;
         return fail(RL_E_HIP, std::string("scene upload: ") + hipGetErrorString(e));
@@ -889,6 +964,7 @@ int rl_scene_destroy(RlScene* scene) {
     (void)hipSetDevice(scene->device);
     (void)sessions_quiesce(scene->device); // an open launch may still be reading the blob
     (void)hipFree(scene->blob);
+    if (scene->emitters) (void)hipFree(scene->emitters);
     delete scene;
     return RL_OK;
 }
@@ -1098,6 +1174,66 @@ int rl_scene_step_path_list(const RlScene* scene, int primitive_fetch, uint64_t 
     });
     if (rc == RL_OK && n_live) *n_live = total;
     return rc;
+}
+
+int rl_scene_emitters(const RlScene* scene, uint32_t* objects, uint32_t cap, uint32_t* n_emitters) {
+    if (!scene) return fail(RL_E_INVALID, "null scene");
+    if (!n_emitters) return fail(RL_E_INVALID, "null output");
+    const uint32_t n = (uint32_t)scene->emitter_objects.size();
+    *n_emitters = n;
+    if (n == 0) return RL_OK;
+    if (!objects || cap < n) return fail(RL_E_INVALID, "index array too small for the scene's emitters");
+    std::memcpy(objects, scene->emitter_objects.data(), n * sizeof(uint32_t));
+    return RL_OK;
+}
+
+int rl_scene_light_paths_device(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, const RlPathState* device_states,
+                                uint32_t n_states, const uint32_t* device_list, uint32_t n_list, const RlRayHit* device_hits,
+                                RlLightSample* device_samples) {
+    int rc = light_check(scene, primitive_fetch, device_states, n_states, device_list, n_list, device_hits, device_samples);
+    if (rc != RL_OK || n_list == 0) return rc;
+    const char* what = "rl_scene_light_paths_device";
+    if ((rc = states_aligned(device_states, what)) != RL_OK) return rc;
+    if (((uintptr_t)device_samples & 15u) != 0) return fail(RL_E_INVALID, std::string(what) + ": the sample buffer is not 16-byte aligned");
+    if ((uintptr_t)device_list & 3u) return fail(RL_E_INVALID, std::string(what) + ": the list is not 4-byte aligned");
+    if ((rc = use_device(scene->device)) != RL_OK) return rc;
+    if ((rc = device_buffers_check(scene, device_states, device_hits, what, "rl_scene_light_paths")) != RL_OK) return rc;
+    if ((rc = device_buffers_check(scene, device_list, device_samples, what, "rl_scene_light_paths")) != RL_OK) return rc;
+    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
+        return launch_light(scene, primitive_fetch, cus, q, seed, stream, device_states, n_states, device_list, n_list, device_hits, device_samples);
+    });
+}
+
+// Not chunked, as rl_scene_step_path_list: device buffers of the call's own for the whole arrays.  The caller's samples go in too:
+// the records of the states that are not listed come back as they were.
+int rl_scene_light_paths(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, const RlPathState* states, uint32_t n_states,
+                         const uint32_t* list, uint32_t n_list, const RlRayHit* hits, RlLightSample* samples) {
+    int rc = light_check(scene, primitive_fetch, states, n_states, list, n_list, hits, samples);
+    if (rc != RL_OK || n_list == 0) return rc;
+    if (n_states == 0) return RL_OK; // (a given list of a state buffer without states: every entry is skipped)
+    if ((rc = use_device(scene->device)) != RL_OK) return rc;
+    struct Buffers { // freed on every way out
+        void* p[4] = {};
+        ~Buffers() {
+            for (void* b : p)
+                if (b) (void)hipFree(b);
+        }
+    } dev;
+    enum { STATES, HITS, SAMPLES, LIST };
+    const size_t bytes[4] = {(size_t)n_states * sizeof(RlPathState), (size_t)n_states * sizeof(RlRayHit), (size_t)n_states * sizeof(RlLightSample),
+                             list ? (size_t)n_list * sizeof(uint32_t) : 0u};
+    for (int k = 0; k < 4; ++k)
+        if (bytes[k]) RL_HIP(hipMalloc(&dev.p[k], bytes[k]));
+    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
+        const void* in[4] = {states, hits, samples, list};
+        for (int k = 0; k < 4; ++k)
+            if (bytes[k]) RL_HIP(hipMemcpyAsync(dev.p[k], in[k], bytes[k], hipMemcpyHostToDevice, q->stream));
+        const int r = launch_light(scene, primitive_fetch, cus, q, seed, stream, (const RlPathState*)dev.p[STATES], n_states, (const uint32_t*)dev.p[LIST],
+                                   n_list, (const RlRayHit*)dev.p[HITS], (RlLightSample*)dev.p[SAMPLES]);
+        if (r != RL_OK) return r;
+        RL_HIP(hipMemcpyAsync(samples, dev.p[SAMPLES], bytes[SAMPLES], hipMemcpyDeviceToHost, q->stream));
+        return RL_OK;
+    });
 }
 
 // ---- TraceUnit ----------------------------------------------------------------------------------
@@ -2438,6 +2574,57 @@ int rl_debug_path_launches(uint64_t* out) { return family_launches(g_path_kernel
 int rl_debug_film_launches(uint64_t* out) { return family_launches(g_film_kernels, out); }
 int rl_debug_step_launches(uint64_t* out) { return family_launches(g_step_kernels, out); }
 int rl_debug_path_list_launches(uint64_t* out) { return family_launches(g_list_step_kernels, out); }
+int rl_debug_light_launches(uint64_t* out) { return family_launches(g_light_kernels, out); }
+
+int rl_debug_scene_emitters(const RlObjectDesc* objects, uint32_t n_objects, uint32_t* out, uint32_t cap, uint32_t* n_emitters) {
+    if ((!objects && n_objects) || !n_emitters) return fail(RL_E_INVALID, "null argument");
+    std::vector<RlF4> table;
+    std::vector<uint32_t> indices;
+    emitter_table(objects, n_objects, &table, &indices);
+    *n_emitters = (uint32_t)indices.size();
+    if (indices.empty()) return RL_OK;
+    if (!out || cap < indices.size()) return fail(RL_E_INVALID, "index array too small for the description's emitters");
+    std::memcpy(out, indices.data(), indices.size() * sizeof(uint32_t));
+    return RL_OK;
+}
+
+int rl_debug_light_sample(const RlObjectDesc* objects, uint32_t n_objects, uint64_t seed, uint32_t stream, const RlPathState* states,
+                          const RlRayHit* hits, uint32_t n, RlLightSample* samples, RlRay* rays) {
+    if ((!objects && n_objects) || (n && (!states || !hits || !samples))) return fail(RL_E_INVALID, "null argument");
+    std::vector<RlF4> table, records(n_objects);
+    std::vector<uint32_t> indices;
+    emitter_table(objects, n_objects, &table, &indices);
+    for (uint32_t i = 0; i < n_objects; ++i) // (the object records as far as rl_light_sample reads them: the material kind)
+        records[i] = RlF4{objects[i].m0, objects[i].m1, objects[i].m2, rl_u2f(rl_object_bits(objects[i].surface_kind, objects[i].material_kind, 0u))};
+    for (uint32_t i = 0; i < n; ++i) {
+        const RlPathState& st = states[i];
+        const RlRayHit& h = hits[i];
+        const RlLightDraw s = rl_light_sample(records.data(), n_objects, table.data(), (uint32_t)indices.size(), seed, stream, st.path_index, st.segments, st.end,
+                                              st.wavelength, rl_f3(st.direction.x, st.direction.y, st.direction.z),
+                                              rl_f3(h.isect.position.x, h.isect.position.y, h.isect.position.z),
+                                              rl_f3(h.isect.normal.x, h.isect.normal.y, h.isect.normal.z), h.object);
+        const bool cast = s.status == RL_LIGHT_VISIBLE;
+        RlLightSample out;
+        out.direction = RlVector3{s.direction.x, s.direction.y, s.direction.z};
+        out.distance = s.distance;
+        out.value = cast ? st.intensity * s.weight : 0.0f;
+        out.weight = s.weight;
+        out.emitter = s.emitter;
+        out.status = s.status;
+        samples[i] = out;
+        if (rays) {
+            RlRay r;
+            std::memset(&r, 0, sizeof r);
+            if (cast) {
+                r.origin = RlVector3{s.origin.x, s.origin.y, s.origin.z};
+                r.direction = out.direction;
+                r.t_max = s.t_max;
+            }
+            rays[i] = r;
+        }
+    }
+    return RL_OK;
+}
 
 // ---- device-side math probe (tests) -------------------------------------------------------------
 

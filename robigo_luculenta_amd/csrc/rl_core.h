@@ -990,6 +990,88 @@ RL_HD int rl_bounce(const RlSceneView& sv, uint64_t seed, uint32_t stream, uint6
     return rl_roulette_ends(rl_get_unit(rb.w[2]), p->continue_chance, p->intensity) ? RL_PATH_ENDED : RL_PATH_CONTINUES;
 }
 
+// ---- direct light at a path vertex (rl_scene_light_paths; not in the reference, trace_unit.rs:128-131) -----------------------
+
+// A sampleable emitter of the scene's emitter table: three records {centre.xyz, radius}, {normal.xyz, surface kind},
+// {kelvins, normalisation factor, object index, 0} (rl_api.hip: emitter_table).
+#define RL_EMITTER_STRIDE 3
+
+// What rl_light_sample leaves: the RlLightSample fields but `value`, and the shadow ray where one is to be cast
+// (status RL_LIGHT_VISIBLE: the caller makes it RL_LIGHT_OCCLUDED when the ray is blocked).
+struct RlLightDraw {
+    RlF3 direction;
+    float distance, weight;
+    uint32_t emitter, status;
+    RlF3 origin; // the shadow ray's; its direction is `direction`
+    float t_max;
+};
+
+// The sample of include/robigo_luculenta.h (rl_scene_light_paths, "The sample"), statement for statement, for one state and the
+// hit record of its last segment.  `objects`: the scene's object records (the hit object's material is read from it), `emitters`:
+// the emitter table.  The f64 Planck term runs only where a point faces the vertex and the vertex the point: on the device the
+// branch is skipped when no lane of the wave got there.
+RL_HD RlLightDraw rl_light_sample(const RlF4* objects, uint32_t n_objects, const RlF4* emitters, uint32_t n_emitters, uint64_t seed,
+                                  uint32_t stream, uint64_t path_index, uint32_t segments, uint32_t end, float wavelength,
+                                  RlF3 state_direction, RlF3 x, RlF3 hit_normal, uint32_t hit_object) {
+    RlLightDraw s;
+    s.direction = s.origin = rl_f3(0.0f, 0.0f, 0.0f);
+    s.distance = s.weight = s.t_max = 0.0f;
+    s.emitter = RL_OBJECT_NONE;
+    s.status = RL_LIGHT_SKIPPED;
+    if (!((end == RL_PATH_LIVE || end == (uint32_t)RL_PATH_END_ROULETTE) && segments >= 1u && hit_object < n_objects && n_emitters != 0u)) return s;
+    const uint32_t material = rl_object_material(rl_f2u(objects[hit_object].w));
+    if (material != RL_MATERIAL_DIFFUSE_GREY && material != RL_MATERIAL_DIFFUSE_COLOURED) return s;
+
+    const RlRngBlock rb = rl_rng_block(seed, stream, path_index, 0x80000000u + segments);
+    const uint32_t k = (uint32_t)(((uint64_t)rb.w[2] * n_emitters) >> 32);
+    const float u = rl_closed01(rb.w[0]);
+    const float phi = rl_get_longitude(rb.w[1]);
+    float sin_phi, cos_phi;
+    rl_sincosf(phi, &sin_phi, &cos_phi); // (rl_sinf and rl_cosf are the two halves of this evaluation)
+    const RlF4 e0 = emitters[RL_EMITTER_STRIDE * k], e1 = emitters[RL_EMITTER_STRIDE * k + 1u], e2 = emitters[RL_EMITTER_STRIDE * k + 2u];
+    const float radius = e0.w;
+    const bool circle = rl_f2u(e1.w) == (uint32_t)RL_SURFACE_CIRCLE;
+    RlF3 q, nl = rl_xyz(e1);
+    float area4;
+    // rotate_towards' first axis, normalised for the wave at once (rl_bounce does the same): the function returns before it
+    // reads the axis when |n.z| > 0.9999, and those lanes and the spheres' get a unit vector so that the normalisation keeps its
+    // short form.
+    RlF3 axis = rl_cross(rl_f3(0.0f, 0.0f, 1.0f), nl);
+    if (!circle || fabsf(nl.z) > 0.9999f) axis = rl_f3(1.0f, 0.0f, 0.0f);
+    const RlF3 unit_axis = rl_normalise(axis);
+    if (circle) {
+        const float r = radius * rl_sqrtf(u);
+        q = rl_add(rl_xyz(e0), rl_rotate_towards(rl_f3(r * cos_phi, r * sin_phi, 0.0f), nl, unit_axis));
+        area4 = radius * radius;
+    } else {
+        const float z = 1.0f - 2.0f * u;
+        const float r = rl_sqrtf(fmaxf(0.0f, 1.0f - z * z));
+        nl = rl_f3(r * cos_phi, r * sin_phi, z);
+        q = rl_add(rl_xyz(e0), rl_mul(nl, radius));
+        area4 = 4.0f * radius * radius;
+    }
+    s.emitter = rl_f2u(e2.z);
+    s.status = RL_LIGHT_BACKFACING;
+
+    const RlF3 facing = (rl_dot(state_direction, hit_normal) >= 0.0f) ? hit_normal : rl_neg(hit_normal);
+    const RlF3 v = rl_sub(q, x);
+    const float d2 = rl_dot(v, v);
+    if (!(d2 > 0.0f && d2 < INFINITY)) return s; // (NaN too)
+    s.distance = rl_sqrtf(d2);
+    s.direction = rl_normalise(v);
+    const float cos_s = rl_dot(facing, s.direction);
+    const float along = rl_dot(nl, s.direction);
+    const float cos_l = circle ? fabsf(along) : -along;
+    if (!(cos_s > 0.0f && cos_l > 0.0f && cos_s < INFINITY && cos_l < INFINITY)) return s;
+
+    const float emitted = (float)rl_boltzmann((double)wavelength, (double)e2.x) * e2.y; // rl_emission's factor
+    s.weight = (emitted * ((cos_s * cos_l) / d2)) * (area4 * (float)n_emitters);
+    s.status = RL_LIGHT_VISIBLE;
+    s.origin = rl_add(x, rl_mul(s.direction, 0.00001f));
+    s.t_max = (s.distance - 0.00001f) * 0.9990234375f;
+    return s;
+}
+
 // ---- cie1931.rs:20-48 and plot_unit.rs:56-84 ----------------------------------------------------
 
 RL_HD RlF3 rl_tristimulus(const RlF4* cie, float wavelength) {

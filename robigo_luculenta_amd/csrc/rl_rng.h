@@ -16,6 +16,10 @@
 //   block 2 + b    : bounce b: slot 0 hemisphere longitude (half-open) or the soap-bubble
 //                    reflect/pass draw, slot 1 hemisphere radius^2, slot 2 Russian roulette
 //                    (monte_carlo.rs:48-49, material.rs:273, trace_unit.rs:122)
+//   block 2^31 + s : the direct-light sample at the vertex a path reached with its segment s (rl_core.h: rl_light_sample; not in
+//                    the reference): slot 0 the point's first coordinate (closed unit), slot 1 its longitude (half-open),
+//                    slot 2 which emitter, slot 3 unused.  Disjoint from the bounces' blocks for every path of fewer than
+//                    2^31 - 2 segments.
 //
 // Every lane of a wave therefore makes exactly one Philox call per bounce regardless of which
 // material it hit -- no divergence and no cached words live across the intersection scan.

@@ -1,0 +1,351 @@
+"""rl_scene_light_paths* at the boundary, without a GPU: the record, the entry points and their argument checks in the documented
+order, the emitters of a description, the host compile of the sampling function (rl_debug_light_sample) against the numpy
+restatement (tests/_light_oracle.py) bit for bit, the estimator's mean against the path's own emitter hits on the CPU oracle, and
+the compiled kernels' resources (hipcc cross-compiles here)."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import robigo_luculenta_amd as R
+from robigo_luculenta_amd import _lib
+import _light_oracle as LO
+import _oracle as O
+import _random_scene as RS
+import _step_oracle as S
+from _device_build import device_build
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RL_E_INVALID = -1
+ENTRY_POINTS = ("rl_scene_light_paths", "rl_scene_light_paths_device")
+W, H = 320, 180
+
+
+def _err():
+    return _lib.lib.rl_last_error()
+
+
+def test_the_record_is_as_specified():
+    assert C.sizeof(_lib.RlLightSample) == R.LIGHT_SAMPLE_DTYPE.itemsize == LO.SAMPLE_DTYPE.itemsize == 32
+    offsets = {"direction": 0, "distance": 12, "value": 16, "weight": 20, "emitter": 24, "status": 28}
+    for name, off in offsets.items():
+        assert getattr(_lib.RlLightSample, name).offset == off == R.LIGHT_SAMPLE_DTYPE.fields[name][1], name
+    assert (R.RL_LIGHT_SKIPPED, R.RL_LIGHT_BACKFACING, R.RL_LIGHT_OCCLUDED, R.RL_LIGHT_VISIBLE) == (0, 1, 2, 3)
+    header = open(os.path.join(ROOT, "include", "robigo_luculenta.h")).read()
+    for k, name in enumerate(("RL_LIGHT_SKIPPED", "RL_LIGHT_BACKFACING", "RL_LIGHT_OCCLUDED", "RL_LIGHT_VISIBLE")):
+        assert re.search(r"\b%s = %d\b" % (name, k), header), name
+    rust = open(os.path.join(ROOT, "bindings", "rust", "ffi.rs")).read()
+    for name in ENTRY_POINTS + ("rl_scene_emitters",):
+        assert hasattr(_lib.lib, name) and name in _lib.SIGNATURES and re.search(r"pub fn %s\(" % name, rust), name
+    for name in ("rl_debug_light_launches", "rl_debug_light_sample", "rl_debug_scene_emitters"):
+        assert hasattr(_lib.lib, name) and name in _lib.DEBUG_SIGNATURES, name
+    assert len(R.light_launches()) == 6 and _lib.lib.rl_debug_light_launches(None) == RL_E_INVALID
+    assert "block 2^31 + s" in open(os.path.join(ROOT, "robigo_luculenta_amd", "csrc", "rl_rng.h")).read()
+
+
+class _FakeScene:
+    """A scene handle for the checks that come before the handle is read or a device is touched."""
+
+    def __init__(self):
+        self.buf = (C.c_uint8 * 256)()
+        self.ptr = C.cast(self.buf, C.c_void_p)
+
+
+@pytest.mark.parametrize("name", ENTRY_POINTS)
+def test_bad_arguments_are_invalid_in_the_documented_order_with_no_device(name):
+    fn = getattr(_lib.lib, name)
+    st, hits, sm = np.zeros(4, R.PATH_STATE_DTYPE), np.zeros(4, R.HIT_DTYPE), np.full(4 * 8, 0xAAAAAAAA, np.uint32)
+    lst = np.arange(4, dtype=np.uint32)
+    sp, hp, mp, lp = (a.ctypes.data_as(C.c_void_p) for a in (st, hits, sm, lst))
+    fake = _FakeScene().ptr
+    LDS = R.FETCH_LDS
+    for scene in (None, fake):
+        assert fn(scene, 7, 1, 0, sp, 4, lp, 4, hp, mp) == RL_E_INVALID and b"fetch" in _err()
+        assert fn(scene, -1, 1, 0, None, 4, None, 5, None, None) == RL_E_INVALID and b"fetch" in _err()
+        for args in ((None, 4, lp, 4, hp, mp), (sp, 4, lp, 4, None, mp), (sp, 4, lp, 4, hp, None), (None, 0, lp, 1, None, None)):
+            assert fn(scene, LDS, 1, 0, *args) == RL_E_INVALID and b"buffer" in _err(), args
+    assert fn(None, LDS, 1, 0, sp, 4, lp, 4, hp, mp) == RL_E_INVALID and b"scene" in _err()
+    assert fn(None, LDS, 1, 0, None, 0, None, 0, None, None) == RL_E_INVALID and b"scene" in _err()
+    assert fn(fake, LDS, 1, 0, sp, 4, None, 5, hp, mp) == RL_E_INVALID and b"identity list" in _err()
+    # the documented order: fetch, buffers, scene, identity list
+    assert fn(None, 7, 1, 0, None, 4, None, 5, None, None) == RL_E_INVALID and b"fetch" in _err()
+    assert fn(None, LDS, 1, 0, None, 4, None, 5, hp, mp) == RL_E_INVALID and b"buffer" in _err()
+    assert fn(None, LDS, 1, 0, sp, 4, None, 5, hp, mp) == RL_E_INVALID and b"scene" in _err()
+    # an empty list does nothing, whatever else is given
+    for args in ((sp, 4, lp, 0, hp, mp), (None, 0, None, 0, None, None), (sp, 0, None, 0, None, mp)):
+        for fetch in (LDS, R.FETCH_GLOBAL):
+            assert fn(fake, fetch, 1, 0, *args) == 0, args
+    assert (sm == 0xAAAAAAAA).all() and st.tobytes() == bytes(st.nbytes) and hits.tobytes() == bytes(hits.nbytes) and (lst == np.arange(4)).all()
+
+
+def test_emitters_of_a_description():
+    objs, cam = R.builtin_scene_desc(R.SCENE_DEMO)
+    want = [i for i, o in enumerate(objs) if o["material_kind"] == 0 and o["surface_kind"] in (0, 2)]   # black body on a sphere or a circle
+    assert len(want) == 3 and [int(objs["surface_kind"][i]) for i in want] == [0, 2, 2]                  # the sun and the two sky discs
+    assert R.description_emitters(objs).tolist() == want == LO.emitters(objs.view(O.OBJECT_DTYPE)).tolist()
+    # the capacity protocol
+    n, out = C.c_uint32(77), np.full(4, 0xAAAAAAAA, np.uint32)
+    op = objs.ctypes.data_as(C.c_void_p)
+    fn = _lib.lib.rl_debug_scene_emitters
+    assert fn(op, len(objs), out.ctypes.data_as(C.c_void_p), 2, C.byref(n)) == RL_E_INVALID and n.value == 3 and b"too small" in _err()
+    assert fn(op, len(objs), None, 0, C.byref(n)) == RL_E_INVALID and n.value == 3 and (out == 0xAAAAAAAA).all()
+    assert fn(op, len(objs), out.ctypes.data_as(C.c_void_p), 3, C.byref(n)) == 0 and out[:3].tolist() == want and out[3] == 0xAAAAAAAA
+    assert fn(op, len(objs), out.ctypes.data_as(C.c_void_p), 3, None) == RL_E_INVALID
+    assert _lib.lib.rl_scene_emitters(None, None, 0, C.byref(n)) == RL_E_INVALID and b"scene" in _err()
+    # what is not sampleable: a plane, a paraboloid, radii that are zero, negative or not finite, a disc whose normal is not a unit vector
+    odd = np.zeros(9, R.OBJECT_DTYPE)
+    odd["v0"] = (0, 0, 1)
+    odd["m"] = (5000.0, 1.0, 0.0)
+    odd["surface_kind"] = [1, 0, 0, 0, 0, 2, 2, 3, 2]
+    odd["f"][:, 0] = [0, 0.0, -1.0, np.inf, np.nan, 2.0, 2.0, 2.0, 0.0]
+    odd["v0"][5] = (0, 0, 1.001)
+    odd["v0"][6] = (0, 0, np.float32(1 + 2.0 ** -22))
+    assert R.description_emitters(odd).tolist() == [6] == LO.emitters(odd.view(O.OBJECT_DTYPE)).tolist()
+    odd["material_kind"] = 1
+    assert R.description_emitters(odd).tolist() == []
+    assert fn(odd.ctypes.data_as(C.c_void_p), 9, None, 0, C.byref(n)) == 0 and n.value == 0
+
+
+def _camera_rays(objs, cam, n, seed, stream, first):
+    import _mirror as M
+    ms = M.Scene(objs, cam)
+    dump = M.lib().mirror_dump_rays
+    dump.restype = C.c_uint64
+    dump.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64]
+    rays6 = np.zeros((n, 6), np.float32)
+    for i in range(n):
+        assert dump(ms.h, W, H, seed, stream, first + i, 1, rays6[i].ctypes.data, 1) == 1
+    rays = np.zeros(n, R.SPECTRAL_RAY_DTYPE)
+    rays["origin"], rays["direction"] = rays6[:, :3], rays6[:, 3:]
+    rays["wavelength"] = np.random.default_rng(seed).uniform(380.0, 780.0, n).astype(np.float32)
+    return rays
+
+
+def _with_lights(objs, rng):
+    """A description with a few more black-body spheres and discs appended, discs with normals next to +z and -z among them."""
+    extra = np.zeros(6, objs.dtype)
+    extra["material_kind"] = 0
+    extra["m"] = [(rng.uniform(3000, 9000), rng.uniform(0.3, 1.0), 0) for _ in range(6)]
+    extra["surface_kind"] = [0, 0, 2, 2, 2, 2]
+    extra["f"][:, 0] = rng.uniform(1.0, 5.0, 6)
+    for k in range(2):
+        extra["v0"][k] = rng.normal(0, 14, 3)
+    for k, nrm in ((2, rng.normal(size=3)), (3, (3e-3, 2e-3, 1.0)), (4, (-2e-3, 4e-3, -1.0)), (5, (0.02, 0.0, 1.0))):
+        nrm = np.asarray(nrm, np.float64)
+        extra["v0"][k] = (nrm / np.linalg.norm(nrm)).astype(np.float32)
+        extra["v1"][k] = rng.normal(0, 16, 3)
+    assert (np.abs(extra["v0"][3:5, 2]) > 0.9999).all() and abs(extra["v0"][5, 2]) < 0.9999
+    return np.concatenate([objs, extra])
+
+
+# path indices whose block 0x80000001 under (seed 11, stream 2) has all-zero / all-one top 24 bits in word 0: u = 0 and u = 1
+EDGE_SEED, EDGE_STREAM = 11, 2
+
+
+def _edge_paths():
+    """Searches the first 2^25 path indices for u = 0 and u = 1 at segments = 1 (each has probability 2^-24 per index)."""
+    found = {}
+    step = 1 << 21
+    w = np.zeros((step, 4), np.uint32)
+    blocks = np.full(step, 0x80000001, np.uint32)
+    for lo in range(0, 1 << 27, step):
+        paths = np.arange(lo, lo + step, dtype=np.uint64)
+        O.lib().oracle_rng_blocks(EDGE_SEED, EDGE_STREAM, O.ptr(paths), O.ptr(blocks), O.ptr(w), step)
+        top = w[:, 0] >> 8
+        for want in (0, 0xffffff):
+            hit = np.flatnonzero(top == want)
+            if len(hit) and want not in found:
+                found[want] = int(paths[hit[0]])
+        if len(found) == 2:
+            break
+    return found
+
+
+@pytest.mark.parametrize("name", ["demo", "random"])
+def test_host_compile_of_the_sampling_function_is_the_oracle_bit_for_bit(name):
+    rng = np.random.default_rng(len(name))
+    if name == "demo":
+        objs, cam = R.builtin_scene_desc(R.SCENE_DEMO)
+    else:
+        objs, cam = RS.random_scene(3, n_spheres=150, n_prisms=4, n_circles=4)
+        objs = _with_lights(objs.view(R.OBJECT_DTYPE), rng)
+    objs = np.ascontiguousarray(objs).view(R.OBJECT_DTYPE)
+    seed, stream, first, n = EDGE_SEED, EDGE_STREAM, 4000, 1200
+    so = S.StepOracle(objs, cam)
+    states = S.begin(_camera_rays(objs.view(O.OBJECT_DTYPE), cam, n, seed, stream, first), first)
+    hits = np.zeros(n, S.HIT_DTYPE)
+    all_states, all_hits = [], []
+    for step in range(3):
+        so.step(states, seed, stream, hits=hits)
+        all_states.append(states.copy())
+        all_hits.append(hits.copy())
+    st, ht = np.concatenate(all_states), np.concatenate(all_hits)
+    # vertices a camera path of this scene may not reach: anywhere among the objects, facing anywhere, on every diffuse object
+    m = 1500
+    diffuse = np.flatnonzero((objs["material_kind"] == 1) | (objs["material_kind"] == 2))
+    f_st, f_ht = np.zeros(m, S.STATE_DTYPE), np.zeros(m, S.HIT_DTYPE)
+    unit = lambda v: (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32)
+    f_ht["position"], f_ht["normal"], f_ht["object"] = rng.normal(0, 15, (m, 3)), unit(rng.normal(size=(m, 3))), rng.choice(diffuse, m)
+    f_st["direction"], f_st["wavelength"], f_st["intensity"] = unit(rng.normal(size=(m, 3))), rng.uniform(380, 780, m), rng.uniform(0.05, 1, m)
+    f_st["segments"], f_st["path_index"] = rng.integers(1, 9, m), rng.integers(0, 1 << 62, m, dtype=np.uint64)
+    f_st["end"] = np.where(rng.random(m) < 0.5, S.LIVE, 2)
+    st, ht = np.concatenate([st, f_st]), np.concatenate([ht, f_ht])
+    # a vertex lying on the emitter: the hit moved onto the point the sample will draw (d2 == 0), and one next to it
+    base, _ = LO.draw(objs, st, ht, seed, stream)
+    some = np.flatnonzero(base["status"] != LO.SKIPPED)[-40:]
+    assert len(some) == 40
+    on = ht[some].copy()
+    on["position"] = (ht["position"][some] + base["direction"][some] * base["distance"][some][:, None]).astype(np.float32)
+    st, ht = np.concatenate([st, st[some]]), np.concatenate([ht, on])
+    # u = 0 and u = 1: states whose path index draws them, at every sampled vertex kind
+    edges = _edge_paths()
+    assert sorted(edges) == [0, 0xffffff], edges
+    for path in edges.values():
+        e_st, e_ht = st[some].copy(), ht[some].copy()
+        e_st["path_index"], e_st["segments"] = path, 1
+        st, ht = np.concatenate([st, e_st]), np.concatenate([ht, e_ht])
+    # hit records a step never writes: a miss, an object out of range, NaN positions and normals
+    w_st, w_ht = st[some].copy(), ht[some].copy()
+    w_ht["object"][:10] = 0xffffffff
+    w_ht["object"][10:20] = len(objs)
+    w_ht["position"][20:30] = np.nan
+    w_ht["normal"][30:40] = (np.inf, 0, 0)
+    st, ht = np.concatenate([st, w_st]), np.concatenate([ht, w_ht])
+    assert len(st) > 5000
+
+    want, want_rays = LO.draw(objs, st, ht, seed, stream)
+    got, got_rays = R.light_sample_host(objs, st.view(R.PATH_STATE_DTYPE), ht.view(R.HIT_DTYPE), seed, stream)
+    bad = [i for i in range(len(st)) if got[i].tobytes() != want[i].tobytes() or got_rays[i].tobytes() != want_rays[i].tobytes()]
+    assert not bad, (name, len(bad), bad[:5], got[bad[0]], want[bad[0]], got_rays[bad[0]], want_rays[bad[0]])
+    # the classes are not vacuous, and the edge cases are what they claim to be
+    status = want["status"]
+    for s in (LO.SKIPPED, LO.BACKFACING, LO.VISIBLE):
+        assert (status == s).sum() >= 40, (name, s, np.bincount(status, minlength=4))
+    zero_d = (status == LO.BACKFACING) & (want["distance"] == 0)
+    assert zero_d.any() and (want["direction"][zero_d] == 0).all()
+    em = LO.emitters(objs.view(O.OBJECT_DTYPE))
+    kinds = set(int(objs["surface_kind"][e]) for e in np.unique(want["emitter"][status != LO.SKIPPED]))
+    assert kinds == {0, 2}, kinds
+    assert set(np.unique(want["emitter"][status != LO.SKIPPED]).tolist()) <= set(em.tolist())
+    if name == "random":
+        steep = [int(e) for e in em if objs["surface_kind"][e] == 2 and abs(objs["v0"][e][2]) > 0.9999]
+        assert len(steep) >= 2 and all((want["emitter"][status == LO.VISIBLE] == e).any() for e in steep), steep
+    skipped = want[status == LO.SKIPPED]
+    assert (skipped["emitter"] == 0xffffffff).all() and not skipped["direction"].any() and not skipped["weight"].any()
+    assert np.isfinite(want["weight"]).all() and (want["weight"][status == LO.VISIBLE] >= 0).all()
+
+
+def test_nearest_hit_occlusion_is_the_linear_scan():
+    objs, cam = R.builtin_scene_desc(R.SCENE_DEMO)
+    objs = objs.view(O.OBJECT_DTYPE)
+    seed, stream, first, n = 5, 1, 0, 150
+    so = S.StepOracle(objs, cam)
+    states, hits = S.begin(_camera_rays(objs, cam, n, seed, stream, first), first), np.zeros(n, S.HIT_DTYPE)
+    so.step(states, seed, stream, hits=hits)
+    so.step(states, seed, stream, hits=hits)
+    _, rays = LO.draw(objs, states, hits, seed, stream)
+    rays = rays[rays["t_max"] > 0]
+    occ = LO.Occluder(objs, cam)
+    fast = occ.occluded(rays)
+    assert fast.tolist() == occ.occluded_linear(rays).tolist() and 0 < fast.sum() < len(rays)
+
+
+def closed_scene(occluder):
+    """A diffuse-grey floor z = 0 under a black ceiling, one sphere light, one disc light and, optionally, a sphere between the
+    floor's origin and the lights."""
+    rows = [
+        (1, 1, (0, 0, 1), (0, 0, 0), 0.0, (0.7, 0, 0)),                 # the floor: a diffuse-grey plane
+        (0, 0, (1.5, 0.5, 4.0), (0, 0, 0), 0.8, (6000.0, 1.0, 0)),      # a sphere light
+        (2, 0, (0, 0, -1), (-2.0, 1.0, 5.0), 1.5, (4500.0, 0.8, 0)),    # a disc light facing down
+        (0, 1, (0, 0, 0), (0, 0, 0), 40.0, (0.0, 0, 0)),                # a black (reflectance 0) shell around everything
+    ]
+    if occluder:
+        rows.append((0, 1, (0.6, 0.3, 2.0), (0, 0, 0), 0.5, (0.0, 0, 0)))   # a black sphere in front of part of both lights
+    objs = np.zeros(len(rows), R.OBJECT_DTYPE)
+    for o, (sk, mk, v0, v1, f0, m) in zip(objs, rows):
+        o["surface_kind"], o["material_kind"], o["v0"], o["v1"], o["m"] = sk, mk, v0, v1, m
+        o["f"][0] = f0
+    return objs, O.demo_scene_desc()[1]
+
+
+def vertex_states(n, first=0):
+    """n states at one vertex: the floor's origin, reached by a segment from above, about to leave in the direction the NEXT bounce
+    draws (the estimator does not read it but for its side), intensity 0.7 (the floor's reflectance), distinct path indices."""
+    st = np.zeros(n, R.PATH_STATE_DTYPE)
+    st["origin"], st["direction"] = (0, 0, 1e-5), (0, 0, 1)
+    st["wavelength"], st["intensity"], st["continue_chance"] = 550.0, 0.7, 0.96
+    st["segments"], st["end"], st["object"] = 1, R.RL_PATH_LIVE, R.RL_OBJECT_NONE
+    st["path_index"] = first + np.arange(n, dtype=np.uint64)
+    ht = np.zeros(n, R.HIT_DTYPE)
+    ht["normal"], ht["distance"], ht["object"] = (0, 0, 1), 1.0, 0
+    return st, ht
+
+
+def bounce_directions(st, seed, stream):
+    """The cosine-weighted direction the reference's diffuse bounce draws at the vertex for each state's path, from block
+    2 + segments (monte_carlo.rs:47-58 on a z-up normal: no rotation): what the path itself does next."""
+    n = len(st)
+    w = np.zeros((n, 4), np.uint32)
+    paths = np.ascontiguousarray(st["path_index"], dtype=np.uint64)
+    blocks = (st["segments"] + 2).astype(np.uint32)
+    O.lib().oracle_rng_blocks(seed, stream, O.ptr(paths), O.ptr(blocks), O.ptr(w), n)
+    phi = (w[:, 0] >> 8).astype(np.float64) * 2.0 ** -24 * 2 * np.pi
+    rq = (w[:, 1] >> 8).astype(np.float64) * 2.0 ** -24 * (16777216.0 / 16777215.0)
+    r = np.sqrt(rq)
+    return np.stack([np.cos(phi) * r, np.sin(phi) * r, np.sqrt(1 - rq)], axis=1).astype(np.float32)
+
+
+def assert_means_agree(light_values, path_values, what):
+    """|mean a - mean b| <= 5 combined standard errors, each from the samples themselves."""
+    a, b = np.asarray(light_values, np.float64), np.asarray(path_values, np.float64)
+    se = np.sqrt(a.var(ddof=1) / len(a) + b.var(ddof=1) / len(b))
+    print("%s: light %.6g path %.6g diff %.3g se %.3g" % (what, a.mean(), b.mean(), a.mean() - b.mean(), se))
+    assert a.mean() > 0 and b.mean() > 0, what
+    assert abs(a.mean() - b.mean()) <= 5 * se, (what, a.mean(), b.mean(), se)
+
+
+@pytest.mark.parametrize("occluder", [True, False])
+def test_the_sample_estimates_what_the_next_segment_finds_on_the_cpu_oracle(occluder):
+    """The mean of `value` over states at one vertex against the mean of what those states carry after one more segment that ends
+    on one of the two lights: both estimate the light the vertex reflects towards the path.  On the oracle alone."""
+    objs, cam = closed_scene(occluder)
+    n, seed, stream = 1 << 13, 17, 3
+    st, ht = vertex_states(n)
+    occ = LO.Occluder(objs, cam)
+    light = LO.light_paths(occ, st, ht, seed, stream)
+    assert set(np.unique(light["status"])) >= ({LO.BACKFACING, LO.VISIBLE} | ({LO.OCCLUDED} if occluder else set()))
+    # the path's own next segment: the diffuse bounce, then Scene::intersect, counting ends on the lights
+    d = bounce_directions(st, seed, stream)
+    o = (ht["position"] + d * np.float32(1e-5)).astype(np.float32)
+    value = np.zeros(n)
+    isect = np.zeros(10, np.float32)
+    L = O.lib()
+    lights = set(LO.emitters(objs.view(O.OBJECT_DTYPE)).tolist())
+    assert lights == {1, 2}
+    for i in range(n):
+        idx = L.oracle_scene_intersect(occ.scene.h, O.ptr(o[i]), O.ptr(d[i]), O.ptr(isect))
+        if idx in lights:
+            value[i] = st["intensity"][i] * L.oracle_black_body(float(objs["m"][idx][0]), float(objs["m"][idx][1]), float(st["wavelength"][i]), None)
+    assert_means_agree(light["value"], value, "occluder %s" % occluder)
+
+
+@pytest.fixture(scope="module")
+def kernels():
+    return device_build()[1]
+
+
+def test_light_kernels_compile_without_scratch_and_within_the_register_bound(kernels):
+    light = {n: k for n, k in kernels.items() if "rl_light_kernel" in n}
+    assert sorted(re.search(r"rl_light_kernelILi([012])ELb([01])E", n).groups() for n in light) == [(s, c) for s in "012" for c in "01"]
+    steps = {re.search(r"rl_step_kernelILi([012])ELb([01])E", n).groups(): k for n, k in kernels.items() if "rl_step_kernel" in n}
+    for name, k in light.items():
+        assert k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0 and k["dynamic_stack"] == 0, (name, k)
+        assert k["vgpr_count"] <= 128 and k.get("agpr_count", 0) == 0, (name, k)
+        v = re.search(r"rl_light_kernelILi([012])ELb([01])E", name).groups()
+        assert k["sgpr_spill_count"] <= steps[v]["sgpr_spill_count"], (name, k["sgpr_spill_count"], steps[v]["sgpr_spill_count"])
+        if v[0] == "2":
+            assert k["sgpr_spill_count"] == 0, (name, k)
+    make = open(os.path.join(ROOT, "robigo_luculenta_amd", "csrc", "Makefile")).read()
+    assert "rl_light.hip.h" in re.search(r"^HDRS = (.*)$", make, re.M).group(1).split()
