@@ -151,6 +151,19 @@ extern "C" {
     pub fn rl_plot_unit_render_samples_device(u: *mut RlPlotUnit, scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32,
                                               first_path_index: u64, max_segments: u32, device_samples: *const RlCameraSample, n: u32,
                                               device_results: *mut RlPathResult) -> c_int;
+    pub fn rl_plot_unit_light_paths(u: *mut RlPlotUnit, scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32,
+                                    states: *const RlPathState, n_states: u32, list: *const u32, n_list: u32, hits: *const RlRayHit,
+                                    camera: *const RlCameraSample, sampled: *mut u8, samples: *mut RlLightSample) -> c_int;
+    pub fn rl_plot_unit_light_paths_device(u: *mut RlPlotUnit, scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32,
+                                           device_states: *const RlPathState, n_states: u32, device_list: *const u32, n_list: u32,
+                                           device_hits: *const RlRayHit, device_camera: *const RlCameraSample, device_sampled: *mut u8,
+                                           device_samples: *mut RlLightSample) -> c_int;
+    pub fn rl_plot_unit_render_samples_direct(u: *mut RlPlotUnit, scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32,
+                                              first_path_index: u64, max_segments: u32, samples: *const RlCameraSample, n: u32,
+                                              results: *mut RlPathResult) -> c_int;
+    pub fn rl_plot_unit_render_samples_direct_device(u: *mut RlPlotUnit, scene: *const RlScene, primitive_fetch: c_int, seed: u64,
+                                                     stream: u32, first_path_index: u64, max_segments: u32,
+                                                     device_samples: *const RlCameraSample, n: u32, device_results: *mut RlPathResult) -> c_int;
 
     pub fn rl_gather_unit_create(device: c_int, w: u32, h: u32, out: *mut *mut RlGatherUnit) -> c_int;
     pub fn rl_gather_unit_destroy(u: *mut RlGatherUnit) -> c_int;

@@ -605,6 +605,58 @@ int rl_plot_unit_render_samples_device(RlPlotUnit* unit, const RlScene* scene, i
                                        uint64_t first_path_index, uint32_t max_segments, const RlCameraSample* device_samples,
                                        uint32_t n, RlPathResult* device_results);
 
+/* rl_plot_unit_light_paths: rl_scene_light_paths with a film.  Everything that call says about the list, the states that get a
+ * sample, the draws, the arithmetic and the shadow ray holds unchanged; what it writes into a sample record this call splats into
+ * `unit` in the same kernel, and it splats the value of a path that has just ended on a light unless that light was already
+ * counted at the vertex before.  camera, sampled and samples are indexed by STATE and have room for n_states records (bytes);
+ * only camera[i].x and .y are read.
+ *   samples may be NULL.  Otherwise samples[i] receives, for every listed state i < n_states, exactly what rl_scene_light_paths
+ *   writes, bit for bit; the record of a state that is not listed is not touched.
+ *   Vertex splat.  A listed state whose sample is RL_LIGHT_VISIBLE with value != 0 is splatted: get_tristimulus(state.wavelength)
+ *   * value onto the four pixels of plot_pixel(camera[i].x, camera[i].y), by rl_plot_unit_plot_photons' arithmetic.  The image
+ *   size and aspect ratio are the plot unit's.  A state whose x or y is not finite is sampled, not splatted.
+ *   Ending splat.  A listed state with end == RL_PATH_END_EMITTER and value != 0 is splatted with state.value in the same way,
+ *   unless sampled != NULL, sampled[i] != 0 and state.object is one of rl_scene_emitters' objects: then the vertex before was
+ *   sampled, that light is counted already and the ending is dropped.  Endings on emitters that are never sampled (planes,
+ *   paraboloids, prisms) and endings reached from the camera or from a glossy, glass or soap vertex are always splatted.
+ *   sampled may be NULL: then nothing is dropped and nothing is recorded.  Otherwise, for every listed state i < n_states, the
+ *   byte is read (for the rule above) and then written: 1 if the state got a sample with a status other than RL_LIGHT_SKIPPED,
+ *   else 0.  The caller zeroes the bytes when the paths begin; bytes of states that are not listed are not touched.
+ *   The caller's part.  Each state is listed exactly once per step, in the call that follows the step that moved it: pass the list
+ *   that rl_scene_step_path_list was GIVEN, not its live_list, so that the states that have just ended are seen once.  A state
+ *   listed again after its end is splatted again; the library does not track it.
+ *   Determinism as rl_scene_light_paths'; the film differs by the order of the float atomics.
+ * Arguments, checked in this order, each failure RL_E_INVALID with a message before any device work: a NULL unit; a NULL scene;
+ *   an unknown fetch mode; NULL states, hits or camera with n_list > 0; list == NULL with n_list > n_states.  `unit` and `scene`
+ *   on different devices is RL_E_STATE.  n_list == 0 does nothing.
+ * Ordering is rl_plot_unit_render_samples': the call ends a fused render begun into `unit`, runs after everything queued into the
+ *   unit, returns when the splats are in the buffer, and orders against open launches as rl_scene_light_paths does.
+ * The host form is NOT chunked, like rl_scene_light_paths.  The _device form takes device pointers on the unit's device -- states,
+ *   samples and camera 16-byte aligned, list 4-byte aligned -- and refuses pageable host memory.
+ *
+ * rl_plot_unit_render_samples_direct: rl_plot_unit_render_samples with direct light.  For chunks of at most 2^20 samples the call
+ * begins the paths of samples[i].ray (path first_path_index + i), zeroes their `sampled` bytes and loops: rl_scene_step_path_list
+ * with hits, rl_plot_unit_light_paths over the list that step was given, and the step's live list becomes the next list; until no
+ * path is live or max_segments segments are made.  The film receives what that loop of public calls puts there: a path at the
+ * segment limit contributes the samples of its vertices and nothing more.  `results`, if given, equals rl_scene_render_rays'
+ * output for samples[i].ray bit for bit -- direct light does not change the paths -- RL_PATH_END_INVALID and RL_PATH_END_LIMIT
+ * included.  Argument checks and ordering are rl_plot_unit_render_samples'; the _device form wants device_samples 16-byte aligned.
+ *   Scratch memory.  The loop's states, hits, bytes and two lists, 121 bytes per sample of the largest chunk seen (127 MB at
+ *   2^20), live with the query context the call runs on (one per concurrent caller and device), grow on demand and are reused. */
+int rl_plot_unit_light_paths(RlPlotUnit* unit, const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream,
+                             const RlPathState* states, uint32_t n_states, const uint32_t* list, uint32_t n_list,
+                             const RlRayHit* hits, const RlCameraSample* camera, uint8_t* sampled, RlLightSample* samples);
+int rl_plot_unit_light_paths_device(RlPlotUnit* unit, const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream,
+                                    const RlPathState* device_states, uint32_t n_states, const uint32_t* device_list, uint32_t n_list,
+                                    const RlRayHit* device_hits, const RlCameraSample* device_camera, uint8_t* device_sampled,
+                                    RlLightSample* device_samples);
+int rl_plot_unit_render_samples_direct(RlPlotUnit* unit, const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream,
+                                       uint64_t first_path_index, uint32_t max_segments, const RlCameraSample* samples, uint32_t n,
+                                       RlPathResult* results);
+int rl_plot_unit_render_samples_direct_device(RlPlotUnit* unit, const RlScene* scene, int primitive_fetch, uint64_t seed,
+                                              uint32_t stream, uint64_t first_path_index, uint32_t max_segments,
+                                              const RlCameraSample* device_samples, uint32_t n, RlPathResult* device_results);
+
 /* ---- GatherUnit (gather_unit.rs:24-92) ----------------------------------------------------- */
 
 /* GatherUnit::new(width, height) WITHOUT the implicit read() of ./buffer.raw

@@ -499,6 +499,78 @@ class PlotUnit(_Handle):
                                                      C.c_void_p(results.data_ptr()) if results is not None else None))
 
 
+    def light_paths(self, scene, states, hits, camera, seed, stream, list=None, n_list=None, fetch=FETCH_LDS, sampled=None, samples=None):
+        """Scene.light_paths with a film (rl_plot_unit_light_paths): the states of an (n,) PATH_STATE_DTYPE array that `list`
+        names (or states 0 .. n_list - 1) are sampled as Scene.light_paths samples them, and a visible sample's value, or the
+        value of a state that ended on a light that was not counted at the vertex before, is splatted at camera[i]["x"], ["y"] of
+        an (n,) CAMERA_SAMPLE_DTYPE array, complete on return.  sampled: None (nothing is dropped or recorded) or an (n,) uint8
+        array, read and rewritten in place for the listed states.  samples: None, or an (n,) LIGHT_SAMPLE_DTYPE array that receives
+        the listed states' records.  Returns `samples`."""
+        if states.dtype != PATH_STATE_DTYPE or not states.flags.c_contiguous:
+            raise ValueError("states must be a contiguous PATH_STATE_DTYPE array")
+        n = len(states)
+        if hits.dtype != HIT_DTYPE or not hits.flags.c_contiguous or len(hits) < n:
+            raise ValueError("hits must be a contiguous HIT_DTYPE array with room for every state")
+        if camera.dtype != CAMERA_SAMPLE_DTYPE or not camera.flags.c_contiguous or len(camera) < n:
+            raise ValueError("camera must be a contiguous CAMERA_SAMPLE_DTYPE array with a record for every state")
+        if sampled is not None and (sampled.dtype != np.uint8 or not sampled.flags.c_contiguous or not sampled.flags.writeable or len(sampled) < n):
+            raise ValueError("sampled must be a contiguous, writeable uint8 array with a byte for every state")
+        if samples is not None and (samples.dtype != LIGHT_SAMPLE_DTYPE or not samples.flags.c_contiguous or not samples.flags.writeable or len(samples) < n):
+            raise ValueError("samples must be a contiguous, writeable LIGHT_SAMPLE_DTYPE array with room for every state")
+        lp = None
+        if list is not None:
+            list = np.ascontiguousarray(list, dtype=np.uint32)
+            if n_list is None:
+                n_list = len(list)
+            if list.ndim != 1 or n_list > len(list):
+                raise ValueError("list must be a one-dimensional array of at least n_list indices")
+            lp = list.ctypes.data_as(C.c_void_p)
+        elif n_list is None:
+            n_list = n
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        check(lib.rl_plot_unit_light_paths(self._h, scene.handle, fetch, seed, stream, ptr(states), n, lp, n_list, ptr(hits), ptr(camera),
+                                           ptr(sampled), ptr(samples)))
+        return samples
+
+    def light_paths_device(self, scene, states, hits, camera, seed, stream, list=None, n_list=None, fetch=FETCH_LDS, sampled=None, samples=None):
+        """rl_plot_unit_light_paths_device: `states`, `hits` and `camera` (and `sampled`, `samples`, `list`, if given) are device
+        buffers on the unit's device with data_ptr() (e.g. torch tensors) holding n PATH_STATE_DTYPE, HIT_DTYPE and
+        CAMERA_SAMPLE_DTYPE records, n bytes, room for n LIGHT_SAMPLE_DTYPE records and at least n_list uint32 indices."""
+        n_bytes = lambda t: t.numel() * t.element_size()
+        n = n_bytes(states) // PATH_STATE_DTYPE.itemsize
+        if n_bytes(states) != n * PATH_STATE_DTYPE.itemsize or n_bytes(hits) < n * HIT_DTYPE.itemsize or n_bytes(camera) < n * CAMERA_SAMPLE_DTYPE.itemsize:
+            raise ValueError("states must hold whole 64-byte records, hits room for as many 48-byte ones and camera as many 48-byte ones")
+        if (sampled is not None and n_bytes(sampled) < n) or (samples is not None and n_bytes(samples) < n * LIGHT_SAMPLE_DTYPE.itemsize):
+            raise ValueError("sampled must have a byte and samples room for a 32-byte record for every state")
+        if n_list is None:
+            n_list = n if list is None else n_bytes(list) // 4
+        if list is not None and n_bytes(list) < 4 * n_list:
+            raise ValueError("list must have room for n_list 4-byte indices")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        check(lib.rl_plot_unit_light_paths_device(self._h, scene.handle, fetch, seed, stream, ptr(states), n, ptr(list), n_list, ptr(hits),
+                                                  ptr(camera), ptr(sampled), ptr(samples)))
+
+    def render_samples_direct(self, scene, samples, seed, stream, first=0, fetch=FETCH_LDS, max_segments=0, results=True):
+        """render_samples with direct light (rl_plot_unit_render_samples_direct): the same paths, and at every diffuse vertex one
+        direct-light sample is splatted as well, each light counted once.  Returns what render_samples returns."""
+        samples = np.ascontiguousarray(samples, dtype=CAMERA_SAMPLE_DTYPE)
+        out = np.empty(len(samples), dtype=PATH_RESULT_DTYPE) if results else None
+        check(lib.rl_plot_unit_render_samples_direct(self._h, scene.handle, fetch, seed, stream, first, max_segments,
+                                                     samples.ctypes.data_as(C.c_void_p), len(samples),
+                                                     out.ctypes.data_as(C.c_void_p) if results else None))
+        return out
+
+    def render_samples_direct_device(self, scene, samples, seed, stream, first=0, fetch=FETCH_LDS, max_segments=0, results=None):
+        """rl_plot_unit_render_samples_direct_device: the buffers of render_samples_device."""
+        n_bytes = lambda t: t.numel() * t.element_size()
+        n = n_bytes(samples) // CAMERA_SAMPLE_DTYPE.itemsize
+        if n_bytes(samples) != n * CAMERA_SAMPLE_DTYPE.itemsize or (results is not None and n_bytes(results) < n * PATH_RESULT_DTYPE.itemsize):
+            raise ValueError("samples must hold whole 48-byte records and results room for as many 16-byte ones")
+        check(lib.rl_plot_unit_render_samples_direct_device(self._h, scene.handle, fetch, seed, stream, first, max_segments,
+                                                            C.c_void_p(samples.data_ptr()), n,
+                                                            C.c_void_p(results.data_ptr()) if results is not None else None))
+
+
 class GatherUnit(_Handle):
     """gather_unit.rs:24-92 (resume is explicit: load())."""
     _destroy = lib.rl_gather_unit_destroy
@@ -750,6 +822,14 @@ def light_launches():
     out = (C.c_uint64 * 6)()
     check(lib.rl_debug_light_launches(out))
     return list(out)
+
+
+def light_film_launches():
+    """Launches per instantiation of the light kernel with a film (PlotUnit.light_paths*, PlotUnit.render_samples_direct*) since the
+    library was loaded (rl_debug_light_film_launches); index = 2 * stage + cylinders, as light_launches()."""
+    out = (C.c_uint64 * 6)()
+    check(lib.rl_debug_light_film_launches(out))
+    return [int(x) for x in out]
 
 
 def description_emitters(objects):

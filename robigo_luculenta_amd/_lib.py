@@ -179,6 +179,10 @@ SIGNATURES = {
     "rl_plot_unit_plot_photons_device": (_i, [_vp, _vp, _u64]),
     "rl_plot_unit_render_samples": (_i, [_vp, _vp, _i, _u64, _u32, _u64, _u32, _vp, _u32, _vp]),
     "rl_plot_unit_render_samples_device": (_i, [_vp, _vp, _i, _u64, _u32, _u64, _u32, _vp, _u32, _vp]),
+    "rl_plot_unit_light_paths": (_i, [_vp, _vp, _i, _u64, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "rl_plot_unit_light_paths_device": (_i, [_vp, _vp, _i, _u64, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "rl_plot_unit_render_samples_direct": (_i, [_vp, _vp, _i, _u64, _u32, _u64, _u32, _vp, _u32, _vp]),
+    "rl_plot_unit_render_samples_direct_device": (_i, [_vp, _vp, _i, _u64, _u32, _u64, _u32, _vp, _u32, _vp]),
     "rl_gather_unit_sync": (_i, [_vp]),
     "rl_gather_unit_create": (_i, [_i, _u32, _u32, _pp]),
     "rl_gather_unit_destroy": (_i, [_vp]),
@@ -211,6 +215,7 @@ DEBUG_SIGNATURES = {
     "rl_debug_step_launches": (_i, [_vp]),
     "rl_debug_path_list_launches": (_i, [_vp]),
     "rl_debug_light_launches": (_i, [_vp]),
+    "rl_debug_light_film_launches": (_i, [_vp]),
     "rl_debug_scene_emitters": (_i, [_vp, _u32, _vp, _u32, C.POINTER(_u32)]),
     "rl_debug_light_sample": (_i, [_vp, _u32, _u64, _u32, _vp, _vp, _u32, _vp, _vp]),
     "rl_debug_prism_probe": (_i, [_vp, _u32, _vp, _u32, _vp]),

@@ -48,6 +48,7 @@
 #include "rl_step.hip.h"
 #include "rl_path_list.hip.h"
 #include "rl_light.hip.h"
+#include "rl_light_film.hip.h"
 #include "rl_scene.h"
 
 namespace {
@@ -111,6 +112,9 @@ struct RlScene {
     // RL_EMITTER_STRIDE records each, and their object indices in scan order.  Null and empty for a scene without one.
     RlF4* emitters;
     std::vector<uint32_t> emitter_objects;
+    // One byte per object beside the table, 1 for the objects above (rl_plot_unit_light_paths*: whether a path ended on a light
+    // that is sampled is decided per lane without a search).  Null for a scene without one.
+    uint8_t* emitter_flags;
 };
 
 namespace {
@@ -341,7 +345,7 @@ int launch_trace(RlTraceUnit* u, const RlScene* scene, RlMappedPhoton* photons, 
 
 // ---- the persistent ray kernels beside the trace kernel (rl_query.hip.h, rl_occlusion.hip.h, rl_paths.hip.h, rl_step.hip.h, rl_path_list.hip.h) ----
 // A family is one kernel template's six instantiations, index = 2 * stage + cylinders, and the launches of each since the library
-// was loaded (rl_debug_{query,occlusion,path,film,step,path_list,light}_launches).  P: the kernel's parameters behind the scene blob and its layout.
+// was loaded (rl_debug_{query,occlusion,path,film,step,path_list,light,light_film}_launches).  P: the kernel's parameters behind the scene blob and its layout.
 template <class... P>
 struct KernelFamily {
     void (*variants[6])(const RlF4*, RlSceneLayout, P...);
@@ -355,6 +359,7 @@ KernelFamily<const RlCameraSample*, RlPathResult*, uint32_t, uint64_t, uint32_t,
 KernelFamily<RlPathState*, RlRayHit*, uint32_t, uint64_t, uint32_t, uint32_t, unsigned long long*> g_step_kernels = RL_VARIANTS(rl_step_kernel);
 KernelFamily<RlPathState*, RlRayHit*, unsigned long long*> g_list_step_kernels = RL_VARIANTS(rl_list_step_kernel);
 KernelFamily<unsigned long long*> g_light_kernels = RL_VARIANTS(rl_light_kernel);
+KernelFamily<unsigned long long*> g_light_film_kernels = RL_VARIANTS(rl_light_film_kernel);
 #undef RL_VARIANTS
 template <class... P>
 int family_launches(const KernelFamily<P...>& family, uint64_t* out) {
@@ -377,6 +382,8 @@ struct QueryCtx {
     unsigned long long* queue = nullptr; // path, film and step calls only (allocated on first use): the counter of an RlFilmQueue
     uint32_t* pack = nullptr;            // rl_scene_step_path_list* only: the compaction's counts and survivors (query_ctx_pack)
     size_t pack_bytes = 0;
+    void* direct = nullptr;              // rl_plot_unit_render_samples_direct* only: the loop's working buffers (query_ctx_direct)
+    size_t direct_bytes = 0;
 };
 static_assert(sizeof(RlSpectralRay) == sizeof(RlRay) && sizeof(RlMappedPhoton) <= sizeof(RlRay) && sizeof(RlCameraSample) == sizeof(RlRayHit) &&
                   sizeof(RlPathResult) <= sizeof(RlRay),
@@ -416,10 +423,11 @@ void query_ctx_release(int device, QueryCtx* q) {
     std::lock_guard<std::mutex> guard(d->lock);
     d->idle.push_back(q);
 }
-// The context's queue counter (an RlFilmQueue, an RlPathListQueue or an RlLightQueue: a launch's constants sit behind it), allocated on first use.
+// The context's queue counter (an RlFilmQueue, an RlPathListQueue, an RlLightQueue or an RlLightFilmQueue: a launch's constants sit behind it), allocated on first use.
 int query_ctx_queue(QueryCtx* q) {
     size_t bytes = sizeof(RlFilmQueue) > sizeof(RlPathListQueue) ? sizeof(RlFilmQueue) : sizeof(RlPathListQueue);
     if (sizeof(RlLightQueue) > bytes) bytes = sizeof(RlLightQueue);
+    if (sizeof(RlLightFilmQueue) > bytes) bytes = sizeof(RlLightFilmQueue);
     if (!q->queue) RL_HIP(hipMalloc((void**)&q->queue, bytes));
     return RL_OK;
 }
@@ -432,6 +440,18 @@ int query_ctx_pack(QueryCtx* q, size_t bytes) {
     q->pack_bytes = 0;
     RL_HIP(hipMalloc((void**)&q->pack, bytes));
     q->pack_bytes = bytes;
+    return RL_OK;
+}
+
+// The context's working buffers of the direct render's loop with room for `bytes`: grown on demand, never shrunk.  (Nothing of the
+// context runs.)
+int query_ctx_direct(QueryCtx* q, size_t bytes) {
+    if (q->direct_bytes >= bytes) return RL_OK;
+    if (q->direct) RL_HIP(hipFree(q->direct));
+    q->direct = nullptr;
+    q->direct_bytes = 0;
+    RL_HIP(hipMalloc(&q->direct, bytes));
+    q->direct_bytes = bytes;
     return RL_OK;
 }
 
@@ -937,13 +957,19 @@ int rl_scene_create(const RlSceneDesc* desc, int device, RlScene** out) {
     s->tables_bytes = (size_t)(lay.off_objects - lay.off_planes) * sizeof(RlF4);
     s->blob = nullptr;
     s->emitters = nullptr;
+    s->emitter_flags = nullptr;
     std::vector<RlF4> emitters;
     emitter_table(desc->objects, desc->n_objects, &emitters, &s->emitter_objects);
+    std::vector<uint8_t> flags(desc->n_objects, (uint8_t)0);
+    for (uint32_t object : s->emitter_objects) flags[object] = 1;
     hipError_t e = hipMalloc((void**)&s->blob, s->staged_bytes);
     if (e == hipSuccess) e = hipMemcpy(s->blob, blob.data(), s->staged_bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess && !emitters.empty()) e = hipMalloc((void**)&s->emitters, emitters.size() * sizeof(RlF4));
     if (e == hipSuccess && !emitters.empty()) e = hipMemcpy(s->emitters, emitters.data(), emitters.size() * sizeof(RlF4), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !emitters.empty()) e = hipMalloc((void**)&s->emitter_flags, flags.size());
+    if (e == hipSuccess && !emitters.empty()) e = hipMemcpy(s->emitter_flags, flags.data(), flags.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
+        if (s->emitter_flags) (void)hipFree(s->emitter_flags);
         if (s->emitters) (void)hipFree(s->emitters);
         if (s->blob) (void)hipFree(s->blob);
         delete s;
@@ -965,6 +991,7 @@ int rl_scene_destroy(RlScene* scene) {
     (void)sessions_quiesce(scene->device); // an open launch may still be reading the blob
     (void)hipFree(scene->blob);
     if (scene->emitters) (void)hipFree(scene->emitters);
+    if (scene->emitter_flags) (void)hipFree(scene->emitter_flags);
     delete scene;
     return RL_OK;
 }
@@ -1991,6 +2018,96 @@ int with_film_ctx(RlPlotUnit* u, Body body) {
     return RL_OK;
 }
 
+// The light kernel with a film for the states of device array states [0, n_states) that device array list [0, n_list) names
+// (n_list > 0; a null list: states 0 .. n_list - 1), splatted into u: on `stream`, the copy that zeroes the context's chunk counter
+// and writes the launch's block behind it (RlLightFilmQueue), then the kernel.  `samples` and `sampled` may be null.
+int launch_light_film(RlPlotUnit* u, const RlScene* scene, int fetch, int cu_count, QueryCtx* q, hipStream_t stream, uint64_t seed, uint32_t rng_stream,
+                      const RlPathState* states, uint32_t n_states, const uint32_t* list, uint32_t n_list, const RlRayHit* hits,
+                      const RlCameraSample* camera, uint8_t* sampled, RlLightSample* samples) {
+    const int rc = query_ctx_queue(q);
+    if (rc != RL_OK) return rc;
+    RlLightFilmQueue lq;
+    std::memset(&lq, 0, sizeof lq);
+    lq.job.states = states;
+    lq.job.hits = hits;
+    lq.job.list = list;
+    lq.job.emitters = scene->emitters;
+    lq.job.samples = samples;
+    lq.job.camera = camera;
+    lq.job.sampled = sampled;
+    lq.job.emitter_flags = scene->emitter_flags;
+    lq.job.n_list = n_list;
+    lq.job.n_states = n_states;
+    lq.job.n_emitters = (uint32_t)scene->emitter_objects.size();
+    lq.job.stream = rng_stream;
+    lq.job.seed = seed;
+    lq.job.n_objects = scene->emitter_flags ? scene->lay.n_objects : 0u;
+    lq.job.film.plot = u->xyz;
+    lq.job.film.width = u->width;
+    lq.job.film.height = u->height;
+    lq.job.film.wm1 = (float)(int)u->width - 1.0f;
+    lq.job.film.hm1 = (float)(int)u->height - 1.0f;
+    lq.job.film.aspect_ratio = (float)u->width / (float)u->height; // plot_unit.rs:48
+    lq.job.film.off_cie = scene->lay.off_cie;
+    // (from pageable memory: the copy has left `lq` when the call returns)
+    RL_HIP(hipMemcpyAsync(q->queue, &lq, sizeof lq, hipMemcpyHostToDevice, stream));
+    return launch_persistent(g_light_film_kernels, scene, fetch, cu_count, stream, n_list, q->queue);
+}
+
+int light_film_check(const RlPlotUnit* u, const RlScene* scene, int fetch, const void* states, uint32_t n_states, const void* list, uint32_t n_list,
+                     const void* hits, const void* camera) {
+    if (!u) return fail(RL_E_INVALID, "null plot unit");
+    if (!scene) return fail(RL_E_INVALID, "null scene");
+    if (fetch_check(fetch) != RL_OK) return RL_E_INVALID;
+    if (n_list > 0 && (!states || !hits || !camera)) return fail(RL_E_INVALID, "null state, hit or camera sample buffer");
+    if (!list && n_list > n_states) return fail(RL_E_INVALID, "the identity list (list = NULL) is longer than the state buffer");
+    return RL_OK;
+}
+
+// A query context whose launches go onto another stream for as long as this lives: the direct render runs the list step (which
+// queues on its context's stream) on the plot unit's stream.  The context is the call's alone.
+struct StreamLoan {
+    QueryCtx* q;
+    hipStream_t own;
+    StreamLoan(QueryCtx* ctx, hipStream_t stream) : q(ctx), own(ctx->stream) { q->stream = stream; }
+    ~StreamLoan() { q->stream = own; }
+};
+
+// rl_plot_unit_render_samples_direct* for device arrays camera, results [0, n) (0 < n <= RL_QUERY_CHUNK; results may be null) as
+// paths first_path .. first_path + n - 1, on u's stream, which has drained on return: begin, then step / light / swap until no
+// path is live or max_segments segments are made.  The working buffers are the context's: states | hits | two lists | sampled.
+int direct_chunk(RlPlotUnit* u, const RlScene* scene, int fetch, int cu_count, QueryCtx* q, const PathJob& job, uint64_t first_path,
+                 const RlCameraSample* camera, RlPathResult* results, uint32_t n) {
+    int rc = query_ctx_direct(q, (size_t)n * (sizeof(RlPathState) + sizeof(RlRayHit) + 2u * sizeof(uint32_t) + 1u));
+    if (rc != RL_OK) return rc;
+    StreamLoan loan(q, u->stream);
+    RlPathState* states = (RlPathState*)q->direct;
+    RlRayHit* hits = (RlRayHit*)(states + n);
+    uint32_t* lists[2] = {(uint32_t*)(hits + n), (uint32_t*)(hits + n) + n};
+    uint8_t* sampled = (uint8_t*)(lists[1] + n);
+    hipLaunchKernelGGL(rl_direct_begin_kernel, dim3(grid_for(n, cu_count)), dim3(RL_BLOCK), 0, u->stream, camera, first_path, states, sampled, n);
+    RL_HIP(hipGetLastError());
+    const uint32_t* list = nullptr; // the first round's: every state
+    uint32_t n_list = n;
+    for (uint32_t segment = 0; segment < job.max_segments && n_list > 0; ++segment) {
+        uint32_t n_live = 0; // (written by the step's copy, read behind the synchronise)
+        uint32_t* live = lists[segment & 1u];
+        if ((rc = launch_list_step(scene, fetch, cu_count, q, job.seed, job.stream, 0u, states, n, list, n_list, hits, live, &n_live)) != RL_OK) return rc;
+        // (the list the step was given: the states that have just ended are seen once)
+        if ((rc = launch_light_film(u, scene, fetch, cu_count, q, u->stream, job.seed, job.stream, states, n, list, n_list, hits, camera, sampled, nullptr)) != RL_OK)
+            return rc;
+        RL_HIP(hipStreamSynchronize(u->stream));
+        list = live;
+        n_list = n_live;
+    }
+    if (results) {
+        hipLaunchKernelGGL(rl_direct_results_kernel, dim3(grid_for(n, cu_count)), dim3(RL_BLOCK), 0, u->stream, (const RlPathState*)states, results, n);
+        RL_HIP(hipGetLastError());
+    }
+    RL_HIP(hipStreamSynchronize(u->stream));
+    return RL_OK;
+}
+
 int samples_check(const RlPlotUnit* u, const RlScene* scene, int fetch, uint32_t max_segments, uint64_t first_path, const void* samples,
                   uint32_t n, PathJob* job) {
     if (!u) return fail(RL_E_INVALID, "null plot unit");
@@ -2052,6 +2169,107 @@ int rl_plot_unit_render_samples_device(RlPlotUnit* u, const RlScene* scene, int 
         return rc;
     return with_film_ctx(u, [&](QueryCtx* q, int cus) -> int {
         return launch_film(u, scene, primitive_fetch, cus, q, job, first_path_index, device_samples, device_results, n);
+    });
+}
+
+int rl_plot_unit_light_paths_device(RlPlotUnit* u, const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream,
+                                    const RlPathState* device_states, uint32_t n_states, const uint32_t* device_list, uint32_t n_list,
+                                    const RlRayHit* device_hits, const RlCameraSample* device_camera, uint8_t* device_sampled,
+                                    RlLightSample* device_samples) {
+    int rc = light_film_check(u, scene, primitive_fetch, device_states, n_states, device_list, n_list, device_hits, device_camera);
+    if (rc != RL_OK) return rc;
+    if (scene->device != u->device) return fail(RL_E_STATE, "scene and plot unit live on different devices");
+    if (n_list == 0) return RL_OK;
+    const char* what = "rl_plot_unit_light_paths_device";
+    if ((rc = states_aligned(device_states, what)) != RL_OK) return rc;
+    if ((((uintptr_t)device_samples | (uintptr_t)device_camera) & 15u) != 0)
+        return fail(RL_E_INVALID, std::string(what) + ": the sample or camera sample buffer is not 16-byte aligned");
+    if ((uintptr_t)device_list & 3u) return fail(RL_E_INVALID, std::string(what) + ": the list is not 4-byte aligned");
+    if ((rc = use_device(u->device)) != RL_OK) return rc;
+    const char* host_form = "rl_plot_unit_light_paths";
+    if ((rc = device_buffers_check(u->device, "plot unit", device_states, device_hits, what, host_form)) != RL_OK) return rc;
+    if ((rc = device_buffers_check(u->device, "plot unit", device_list, device_samples, what, host_form)) != RL_OK) return rc;
+    if ((rc = device_buffers_check(u->device, "plot unit", device_camera, device_sampled, what, host_form)) != RL_OK) return rc;
+    return with_film_ctx(u, [&](QueryCtx* q, int cus) -> int {
+        return launch_light_film(u, scene, primitive_fetch, cus, q, u->stream, seed, stream, device_states, n_states, device_list, n_list, device_hits,
+                                 device_camera, device_sampled, device_samples);
+    });
+}
+
+// Not chunked, as rl_scene_light_paths: device buffers of the call's own for the whole arrays.  The caller's samples and `sampled`
+// bytes go in too: those of the states that are not listed come back as they were.
+int rl_plot_unit_light_paths(RlPlotUnit* u, const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, const RlPathState* states,
+                             uint32_t n_states, const uint32_t* list, uint32_t n_list, const RlRayHit* hits, const RlCameraSample* camera,
+                             uint8_t* sampled, RlLightSample* samples) {
+    int rc = light_film_check(u, scene, primitive_fetch, states, n_states, list, n_list, hits, camera);
+    if (rc != RL_OK) return rc;
+    if (scene->device != u->device) return fail(RL_E_STATE, "scene and plot unit live on different devices");
+    if (n_list == 0 || n_states == 0) return RL_OK; // (a given list of a state buffer without states: every entry is skipped)
+    if ((rc = use_device(u->device)) != RL_OK) return rc;
+    struct Buffers { // freed on every way out
+        void* p[6] = {};
+        ~Buffers() {
+            for (void* b : p)
+                if (b) (void)hipFree(b);
+        }
+    } dev;
+    enum { STATES, HITS, CAMERA, SAMPLES, SAMPLED, LIST };
+    const size_t bytes[6] = {(size_t)n_states * sizeof(RlPathState), (size_t)n_states * sizeof(RlRayHit), (size_t)n_states * sizeof(RlCameraSample),
+                             samples ? (size_t)n_states * sizeof(RlLightSample) : 0u, sampled ? (size_t)n_states : 0u,
+                             list ? (size_t)n_list * sizeof(uint32_t) : 0u};
+    for (int k = 0; k < 6; ++k)
+        if (bytes[k]) RL_HIP(hipMalloc(&dev.p[k], bytes[k]));
+    return with_film_ctx(u, [&](QueryCtx* q, int cus) -> int {
+        const void* in[6] = {states, hits, camera, samples, sampled, list};
+        for (int k = 0; k < 6; ++k)
+            if (bytes[k]) RL_HIP(hipMemcpyAsync(dev.p[k], in[k], bytes[k], hipMemcpyHostToDevice, u->stream));
+        const int r = launch_light_film(u, scene, primitive_fetch, cus, q, u->stream, seed, stream, (const RlPathState*)dev.p[STATES], n_states,
+                                        (const uint32_t*)dev.p[LIST], n_list, (const RlRayHit*)dev.p[HITS], (const RlCameraSample*)dev.p[CAMERA],
+                                        (uint8_t*)dev.p[SAMPLED], (RlLightSample*)dev.p[SAMPLES]);
+        if (r != RL_OK) return r;
+        if (bytes[SAMPLES]) RL_HIP(hipMemcpyAsync(samples, dev.p[SAMPLES], bytes[SAMPLES], hipMemcpyDeviceToHost, u->stream));
+        if (bytes[SAMPLED]) RL_HIP(hipMemcpyAsync(sampled, dev.p[SAMPLED], bytes[SAMPLED], hipMemcpyDeviceToHost, u->stream));
+        RL_HIP(hipStreamSynchronize(u->stream)); // (the buffers are freed when the call returns)
+        return RL_OK;
+    });
+}
+
+int rl_plot_unit_render_samples_direct(RlPlotUnit* u, const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream,
+                                       uint64_t first_path_index, uint32_t max_segments, const RlCameraSample* samples, uint32_t n,
+                                       RlPathResult* results) {
+    PathJob job{seed, stream, 0u};
+    const int rc = samples_check(u, scene, primitive_fetch, max_segments, first_path_index, samples, n, &job);
+    if (rc != RL_OK || n == 0) return rc;
+    if (scene->device != u->device) return fail(RL_E_STATE, "scene and plot unit live on different devices");
+    return with_film_ctx(u, [&](QueryCtx* q, int cus) -> int {
+        return staged_chunks(q, u->stream, n, {staged_in(STAGING_HITS, samples, sizeof(RlCameraSample)), staged_out(STAGING_RAYS, results, sizeof(RlPathResult))},
+                             [&](uint32_t first, uint32_t k) -> int {
+                                 return direct_chunk(u, scene, primitive_fetch, cus, q, job, first_path_index + first,
+                                                     (const RlCameraSample*)q->staging[STAGING_HITS], results ? (RlPathResult*)q->staging[STAGING_RAYS] : nullptr, k);
+                             });
+    });
+}
+
+int rl_plot_unit_render_samples_direct_device(RlPlotUnit* u, const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream,
+                                              uint64_t first_path_index, uint32_t max_segments, const RlCameraSample* device_samples,
+                                              uint32_t n, RlPathResult* device_results) {
+    PathJob job{seed, stream, 0u};
+    int rc = samples_check(u, scene, primitive_fetch, max_segments, first_path_index, device_samples, n, &job);
+    if (rc != RL_OK || n == 0) return rc;
+    if (scene->device != u->device) return fail(RL_E_STATE, "scene and plot unit live on different devices");
+    const char* what = "rl_plot_unit_render_samples_direct_device";
+    if (((uintptr_t)device_samples & 15u) != 0) return fail(RL_E_INVALID, std::string(what) + ": the sample buffer is not 16-byte aligned");
+    if ((rc = use_device(u->device)) != RL_OK) return rc;
+    if ((rc = device_buffers_check(u->device, "plot unit", device_samples, device_results, what, "rl_plot_unit_render_samples_direct")) != RL_OK) return rc;
+    return with_film_ctx(u, [&](QueryCtx* q, int cus) -> int {
+        for (uint32_t first = 0; first < n;) {
+            const uint32_t k = n - first < RL_QUERY_CHUNK ? n - first : (uint32_t)RL_QUERY_CHUNK;
+            const int r = direct_chunk(u, scene, primitive_fetch, cus, q, job, first_path_index + first, device_samples + first,
+                                       device_results ? device_results + first : nullptr, k);
+            if (r != RL_OK) return r;
+            first += k;
+        }
+        return RL_OK;
     });
 }
 
@@ -2575,6 +2793,7 @@ int rl_debug_film_launches(uint64_t* out) { return family_launches(g_film_kernel
 int rl_debug_step_launches(uint64_t* out) { return family_launches(g_step_kernels, out); }
 int rl_debug_path_list_launches(uint64_t* out) { return family_launches(g_list_step_kernels, out); }
 int rl_debug_light_launches(uint64_t* out) { return family_launches(g_light_kernels, out); }
+int rl_debug_light_film_launches(uint64_t* out) { return family_launches(g_light_film_kernels, out); }
 
 int rl_debug_scene_emitters(const RlObjectDesc* objects, uint32_t n_objects, uint32_t* out, uint32_t cap, uint32_t* n_emitters) {
     if ((!objects && n_objects) || !n_emitters) return fail(RL_E_INVALID, "null argument");
