@@ -88,6 +88,57 @@ def load_scene_desc(path):
     return objs, cam
 
 
+def _n_bytes(t):
+    """Size in bytes of a device buffer: anything with numel(), element_size() and data_ptr(), e.g. a torch tensor."""
+    return t.numel() * t.element_size()
+
+
+def _device_ptr(t):
+    """The address of a device buffer, or None for a buffer that is not given."""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _host_ptr(a):
+    """The address of a numpy array, or None for an array that is not given."""
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _has_room(n, *rooms):
+    """Whether each (device buffer, record size) of `rooms` whose buffer is given holds at least n records."""
+    return all(t is None or _n_bytes(t) >= n * size for t, size in rooms)
+
+
+def _record_count(buf, dtype, message, *rooms):
+    """n, when device buffer `buf` holds n whole records of `dtype` and there is room for n in each of `rooms` (_has_room);
+    ValueError(message) otherwise."""
+    n = _n_bytes(buf) // dtype.itemsize
+    if _n_bytes(buf) != n * dtype.itemsize or not _has_room(n, *rooms):
+        raise ValueError(message)
+    return n
+
+
+def _host_list(list, n_list, n_states):
+    """A host call's `list` and `n_list` as (None or a contiguous uint32 array, the number of entries): n_list defaults to the
+    list's length, or to n_states for the identity list."""
+    if list is None:
+        return None, n_states if n_list is None else n_list
+    list = np.ascontiguousarray(list, dtype=np.uint32)
+    if n_list is None:
+        n_list = len(list)
+    if list.ndim != 1 or n_list > len(list):
+        raise ValueError("list must be a one-dimensional array of at least n_list indices")
+    return list, n_list
+
+
+def _device_list(list, n_list, n_states):
+    """n_list of a device call: by default what the device buffer `list` holds, or n_states for the identity list."""
+    if n_list is None:
+        n_list = n_states if list is None else _n_bytes(list) // 4
+    if not _has_room(n_list, (list, 4)):
+        raise ValueError("list must have room for n_list 4-byte indices")
+    return n_list
+
+
 class _Handle:
     _destroy = None
 
@@ -146,10 +197,8 @@ class Scene(_Handle):
     def intersect_device(self, rays, hits, fetch=FETCH_LDS):
         """rl_scene_intersect_device: `rays` and `hits` are device buffers on the scene's device with data_ptr() (e.g. torch
         tensors) holding n RAY_DTYPE records and room for n HIT_DTYPE records; n is taken from the sizes in bytes."""
-        n_bytes = lambda t: t.numel() * t.element_size()
-        n = n_bytes(rays) // RAY_DTYPE.itemsize
-        if n_bytes(rays) != n * RAY_DTYPE.itemsize or n_bytes(hits) < n * HIT_DTYPE.itemsize:
-            raise ValueError("rays must hold whole 32-byte records and hits room for as many 48-byte ones")
+        n = _record_count(rays, RAY_DTYPE, "rays must hold whole 32-byte records and hits room for as many 48-byte ones",
+                          (hits, HIT_DTYPE.itemsize))
         check(lib.rl_scene_intersect_device(self._h, fetch, C.c_void_p(rays.data_ptr()), n, C.c_void_p(hits.data_ptr())))
 
     def occluded(self, origins, directions, t_max=np.inf, fetch=FETCH_LDS):
@@ -170,10 +219,7 @@ class Scene(_Handle):
     def occluded_device(self, rays, occluded, fetch=FETCH_LDS):
         """rl_scene_occluded_device: `rays` and `occluded` are device buffers on the scene's device with data_ptr() (e.g. torch
         tensors) holding n RAY_DTYPE records and room for n bytes; n is taken from the rays' size in bytes."""
-        n_bytes = lambda t: t.numel() * t.element_size()
-        n = n_bytes(rays) // RAY_DTYPE.itemsize
-        if n_bytes(rays) != n * RAY_DTYPE.itemsize or n_bytes(occluded) < n:
-            raise ValueError("rays must hold whole 32-byte records and occluded room for as many bytes")
+        n = _record_count(rays, RAY_DTYPE, "rays must hold whole 32-byte records and occluded room for as many bytes", (occluded, 1))
         check(lib.rl_scene_occluded_device(self._h, fetch, C.c_void_p(rays.data_ptr()), n, C.c_void_p(occluded.data_ptr())))
 
     def camera_rays(self, width, height, seed, stream, first, n):
@@ -187,7 +233,7 @@ class Scene(_Handle):
     def camera_rays_device(self, width, height, seed, stream, first, samples):
         """rl_scene_camera_rays_device: fills a device buffer with data_ptr() (e.g. a torch tensor) with as many
         CAMERA_SAMPLE_DTYPE records as it holds whole."""
-        n = samples.numel() * samples.element_size() // CAMERA_SAMPLE_DTYPE.itemsize
+        n = _n_bytes(samples) // CAMERA_SAMPLE_DTYPE.itemsize
         check(lib.rl_scene_camera_rays_device(self._h, width, height, seed, stream, first, n, C.c_void_p(samples.data_ptr())))
 
     def render_rays(self, origins, directions, wavelengths, seed, stream, first=0, fetch=FETCH_LDS, max_segments=0):
@@ -216,10 +262,8 @@ class Scene(_Handle):
     def render_rays_device(self, rays, results, seed, stream, first=0, fetch=FETCH_LDS, max_segments=0):
         """rl_scene_render_rays_device: `rays` and `results` are device buffers on the scene's device with data_ptr() (e.g. torch
         tensors) holding n SPECTRAL_RAY_DTYPE records and room for n PATH_RESULT_DTYPE records; n is taken from the sizes in bytes."""
-        n_bytes = lambda t: t.numel() * t.element_size()
-        n = n_bytes(rays) // SPECTRAL_RAY_DTYPE.itemsize
-        if n_bytes(rays) != n * SPECTRAL_RAY_DTYPE.itemsize or n_bytes(results) < n * PATH_RESULT_DTYPE.itemsize:
-            raise ValueError("rays must hold whole 32-byte records and results room for as many 16-byte ones")
+        n = _record_count(rays, SPECTRAL_RAY_DTYPE, "rays must hold whole 32-byte records and results room for as many 16-byte ones",
+                          (results, PATH_RESULT_DTYPE.itemsize))
         check(lib.rl_scene_render_rays_device(self._h, fetch, seed, stream, first, max_segments, C.c_void_p(rays.data_ptr()), n,
                                               C.c_void_p(results.data_ptr())))
 
@@ -234,10 +278,8 @@ class Scene(_Handle):
     def begin_paths_device(self, rays, states, first=0):
         """rl_scene_begin_paths_device: `rays` and `states` are device buffers on the scene's device with data_ptr() (e.g. torch
         tensors) holding n SPECTRAL_RAY_DTYPE records and room for n PATH_STATE_DTYPE records; n is taken from the sizes in bytes."""
-        n_bytes = lambda t: t.numel() * t.element_size()
-        n = n_bytes(rays) // SPECTRAL_RAY_DTYPE.itemsize
-        if n_bytes(rays) != n * SPECTRAL_RAY_DTYPE.itemsize or n_bytes(states) < n * PATH_STATE_DTYPE.itemsize:
-            raise ValueError("rays must hold whole 32-byte records and states room for as many 64-byte ones")
+        n = _record_count(rays, SPECTRAL_RAY_DTYPE, "rays must hold whole 32-byte records and states room for as many 64-byte ones",
+                          (states, PATH_STATE_DTYPE.itemsize))
         check(lib.rl_scene_begin_paths_device(self._h, first, C.c_void_p(rays.data_ptr()), n, C.c_void_p(states.data_ptr())))
 
     def step_paths(self, states, seed, stream, fetch=FETCH_LDS, flags=0, hits=None):
@@ -246,23 +288,17 @@ class Scene(_Handle):
         RL_STEP_NO_ROULETTE.  Returns `states`."""
         if states.dtype != PATH_STATE_DTYPE or not states.flags.c_contiguous or not states.flags.writeable:
             raise ValueError("states must be a contiguous, writeable PATH_STATE_DTYPE array")
-        hp = None
-        if hits is not None:
-            if hits.dtype != HIT_DTYPE or not hits.flags.c_contiguous or len(hits) < len(states):
-                raise ValueError("hits must be a contiguous HIT_DTYPE array with room for every state")
-            hp = hits.ctypes.data_as(C.c_void_p)
-        check(lib.rl_scene_step_paths(self._h, fetch, seed, stream, flags, states.ctypes.data_as(C.c_void_p), len(states), hp))
+        if hits is not None and (hits.dtype != HIT_DTYPE or not hits.flags.c_contiguous or len(hits) < len(states)):
+            raise ValueError("hits must be a contiguous HIT_DTYPE array with room for every state")
+        check(lib.rl_scene_step_paths(self._h, fetch, seed, stream, flags, _host_ptr(states), len(states), _host_ptr(hits)))
         return states
 
     def step_paths_device(self, states, seed, stream, fetch=FETCH_LDS, flags=0, hits=None):
         """rl_scene_step_paths_device: `states` is a device buffer on the scene's device with data_ptr() (e.g. a torch tensor)
         holding n PATH_STATE_DTYPE records, stepped in place; `hits` None or a device buffer with room for n HIT_DTYPE records."""
-        n_bytes = lambda t: t.numel() * t.element_size()
-        n = n_bytes(states) // PATH_STATE_DTYPE.itemsize
-        if n_bytes(states) != n * PATH_STATE_DTYPE.itemsize or (hits is not None and n_bytes(hits) < n * HIT_DTYPE.itemsize):
-            raise ValueError("states must hold whole 64-byte records and hits room for as many 48-byte ones")
-        check(lib.rl_scene_step_paths_device(self._h, fetch, seed, stream, flags, C.c_void_p(states.data_ptr()), n,
-                                             C.c_void_p(hits.data_ptr()) if hits is not None else None))
+        n = _record_count(states, PATH_STATE_DTYPE, "states must hold whole 64-byte records and hits room for as many 48-byte ones",
+                          (hits, HIT_DTYPE.itemsize))
+        check(lib.rl_scene_step_paths_device(self._h, fetch, seed, stream, flags, _device_ptr(states), n, _device_ptr(hits)))
 
     def step_path_list(self, states, seed, stream, list=None, n_list=None, fetch=FETCH_LDS, flags=0, hits=None):
         """rl_scene_step_path_list: one segment, in place, for the live states of an (n,) PATH_STATE_DTYPE array that `list` names
@@ -271,24 +307,13 @@ class Scene(_Handle):
         that are live after the step, in the list's order, as a uint32 array."""
         if states.dtype != PATH_STATE_DTYPE or not states.flags.c_contiguous or not states.flags.writeable:
             raise ValueError("states must be a contiguous, writeable PATH_STATE_DTYPE array")
-        hp = lp = None
-        if hits is not None:
-            if hits.dtype != HIT_DTYPE or not hits.flags.c_contiguous or len(hits) < len(states):
-                raise ValueError("hits must be a contiguous HIT_DTYPE array with room for every state")
-            hp = hits.ctypes.data_as(C.c_void_p)
-        if list is not None:
-            list = np.ascontiguousarray(list, dtype=np.uint32)
-            if n_list is None:
-                n_list = len(list)
-            if list.ndim != 1 or n_list > len(list):
-                raise ValueError("list must be a one-dimensional array of at least n_list indices")
-            lp = list.ctypes.data_as(C.c_void_p)
-        elif n_list is None:
-            n_list = len(states)
+        if hits is not None and (hits.dtype != HIT_DTYPE or not hits.flags.c_contiguous or len(hits) < len(states)):
+            raise ValueError("hits must be a contiguous HIT_DTYPE array with room for every state")
+        list, n_list = _host_list(list, n_list, len(states))
         live = np.empty(n_list, dtype=np.uint32)
         n_live = C.c_uint32(0)
-        check(lib.rl_scene_step_path_list(self._h, fetch, seed, stream, flags, states.ctypes.data_as(C.c_void_p), len(states), lp, n_list, hp,
-                                          live.ctypes.data_as(C.c_void_p), C.byref(n_live)))
+        check(lib.rl_scene_step_path_list(self._h, fetch, seed, stream, flags, _host_ptr(states), len(states), _host_ptr(list), n_list,
+                                          _host_ptr(hits), _host_ptr(live), C.byref(n_live)))
         return live[:n_live.value].copy()
 
     def step_path_list_device(self, states, seed, stream, list, n_list, live_list, fetch=FETCH_LDS, flags=0, hits=None):
@@ -296,18 +321,14 @@ class Scene(_Handle):
         holding n PATH_STATE_DTYPE records; `list` None (states 0 .. n_list - 1) or a device buffer of at least n_list uint32
         indices; `live_list` None or a device buffer with room for n_list of them (it may be `list`); `hits` None or a device buffer
         with room for n HIT_DTYPE records.  Returns n_live."""
-        n_bytes = lambda t: t.numel() * t.element_size()
-        n = n_bytes(states) // PATH_STATE_DTYPE.itemsize
-        if n_bytes(states) != n * PATH_STATE_DTYPE.itemsize or (hits is not None and n_bytes(hits) < n * HIT_DTYPE.itemsize):
-            raise ValueError("states must hold whole 64-byte records and hits room for as many 48-byte ones")
-        if any(t is not None and n_bytes(t) < 4 * n_list for t in (list, live_list)):
+        n = _record_count(states, PATH_STATE_DTYPE, "states must hold whole 64-byte records and hits room for as many 48-byte ones",
+                          (hits, HIT_DTYPE.itemsize))
+        if not _has_room(n_list, (list, 4), (live_list, 4)):
             raise ValueError("list and live_list must have room for n_list 4-byte indices")
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         n_live = C.c_uint32(0)
-        check(lib.rl_scene_step_path_list_device(self._h, fetch, seed, stream, flags, ptr(states), n, ptr(list), n_list, ptr(hits), ptr(live_list),
-                                                 C.byref(n_live)))
+        check(lib.rl_scene_step_path_list_device(self._h, fetch, seed, stream, flags, _device_ptr(states), n, _device_ptr(list), n_list,
+                                                 _device_ptr(hits), _device_ptr(live_list), C.byref(n_live)))
         return n_live.value
-
 
     def emitters(self):
         """rl_scene_emitters: the object indices of the scene's sampleable emitters (black-body spheres and circles), in scan
@@ -331,35 +352,21 @@ class Scene(_Handle):
             samples = np.zeros(len(states), dtype=LIGHT_SAMPLE_DTYPE)
         if samples.dtype != LIGHT_SAMPLE_DTYPE or not samples.flags.c_contiguous or not samples.flags.writeable or len(samples) < len(states):
             raise ValueError("samples must be a contiguous, writeable LIGHT_SAMPLE_DTYPE array with room for every state")
-        lp = None
-        if list is not None:
-            list = np.ascontiguousarray(list, dtype=np.uint32)
-            if n_list is None:
-                n_list = len(list)
-            if list.ndim != 1 or n_list > len(list):
-                raise ValueError("list must be a one-dimensional array of at least n_list indices")
-            lp = list.ctypes.data_as(C.c_void_p)
-        elif n_list is None:
-            n_list = len(states)
-        check(lib.rl_scene_light_paths(self._h, fetch, seed, stream, states.ctypes.data_as(C.c_void_p), len(states), lp, n_list,
-                                       hits.ctypes.data_as(C.c_void_p), samples.ctypes.data_as(C.c_void_p)))
+        list, n_list = _host_list(list, n_list, len(states))
+        check(lib.rl_scene_light_paths(self._h, fetch, seed, stream, _host_ptr(states), len(states), _host_ptr(list), n_list, _host_ptr(hits),
+                                       _host_ptr(samples)))
         return samples
 
     def light_paths_device(self, states, hits, samples, seed, stream, list=None, n_list=None, fetch=FETCH_LDS):
         """rl_scene_light_paths_device: `states`, `hits` and `samples` are device buffers on the scene's device with data_ptr()
         (e.g. torch tensors) holding n PATH_STATE_DTYPE records, n HIT_DTYPE records and room for n LIGHT_SAMPLE_DTYPE records;
         `list` None (states 0 .. n_list - 1, n_list defaults to n) or a device buffer of at least n_list uint32 indices."""
-        n_bytes = lambda t: t.numel() * t.element_size()
-        n = n_bytes(states) // PATH_STATE_DTYPE.itemsize
-        if n_bytes(states) != n * PATH_STATE_DTYPE.itemsize or n_bytes(hits) < n * HIT_DTYPE.itemsize or n_bytes(samples) < n * LIGHT_SAMPLE_DTYPE.itemsize:
-            raise ValueError("states must hold whole 64-byte records, hits room for as many 48-byte ones and samples for as many 32-byte ones")
-        if n_list is None:
-            n_list = n if list is None else n_bytes(list) // 4
-        if list is not None and n_bytes(list) < 4 * n_list:
-            raise ValueError("list must have room for n_list 4-byte indices")
-        check(lib.rl_scene_light_paths_device(self._h, fetch, seed, stream, C.c_void_p(states.data_ptr()), n,
-                                              C.c_void_p(list.data_ptr()) if list is not None else None, n_list, C.c_void_p(hits.data_ptr()),
-                                              C.c_void_p(samples.data_ptr())))
+        n = _record_count(states, PATH_STATE_DTYPE,
+                          "states must hold whole 64-byte records, hits room for as many 48-byte ones and samples for as many 32-byte ones",
+                          (hits, HIT_DTYPE.itemsize), (samples, LIGHT_SAMPLE_DTYPE.itemsize))
+        n_list = _device_list(list, n_list, n)
+        check(lib.rl_scene_light_paths_device(self._h, fetch, seed, stream, _device_ptr(states), n, _device_ptr(list), n_list, _device_ptr(hits),
+                                              _device_ptr(samples)))
 
 
 class TraceUnit(_Handle):
@@ -471,7 +478,7 @@ class PlotUnit(_Handle):
     def plot_photons_device(self, photons):
         """rl_plot_unit_plot_photons_device: `photons` is a device buffer on the unit's device with data_ptr() (e.g. a torch tensor);
         as many PHOTON_DTYPE records as it holds whole are plotted."""
-        n = photons.numel() * photons.element_size() // PHOTON_DTYPE.itemsize
+        n = _n_bytes(photons) // PHOTON_DTYPE.itemsize
         check(lib.rl_plot_unit_plot_photons_device(self._h, C.c_void_p(photons.data_ptr()), n))
 
     def render_samples(self, scene, samples, seed, stream, first=0, fetch=FETCH_LDS, max_segments=0, results=True):
@@ -490,13 +497,10 @@ class PlotUnit(_Handle):
         """rl_plot_unit_render_samples_device: `samples` (and `results`, if given) are device buffers on the unit's device with
         data_ptr() (e.g. torch tensors) holding n CAMERA_SAMPLE_DTYPE records and room for n PATH_RESULT_DTYPE records; n is taken
         from the sizes in bytes."""
-        n_bytes = lambda t: t.numel() * t.element_size()
-        n = n_bytes(samples) // CAMERA_SAMPLE_DTYPE.itemsize
-        if n_bytes(samples) != n * CAMERA_SAMPLE_DTYPE.itemsize or (results is not None and n_bytes(results) < n * PATH_RESULT_DTYPE.itemsize):
-            raise ValueError("samples must hold whole 48-byte records and results room for as many 16-byte ones")
-        check(lib.rl_plot_unit_render_samples_device(self._h, scene.handle, fetch, seed, stream, first, max_segments,
-                                                     C.c_void_p(samples.data_ptr()), n,
-                                                     C.c_void_p(results.data_ptr()) if results is not None else None))
+        n = _record_count(samples, CAMERA_SAMPLE_DTYPE, "samples must hold whole 48-byte records and results room for as many 16-byte ones",
+                          (results, PATH_RESULT_DTYPE.itemsize))
+        check(lib.rl_plot_unit_render_samples_device(self._h, scene.handle, fetch, seed, stream, first, max_segments, _device_ptr(samples), n,
+                                                     _device_ptr(results)))
 
 
     def light_paths(self, scene, states, hits, camera, seed, stream, list=None, n_list=None, fetch=FETCH_LDS, sampled=None, samples=None):
@@ -517,38 +521,23 @@ class PlotUnit(_Handle):
             raise ValueError("sampled must be a contiguous, writeable uint8 array with a byte for every state")
         if samples is not None and (samples.dtype != LIGHT_SAMPLE_DTYPE or not samples.flags.c_contiguous or not samples.flags.writeable or len(samples) < n):
             raise ValueError("samples must be a contiguous, writeable LIGHT_SAMPLE_DTYPE array with room for every state")
-        lp = None
-        if list is not None:
-            list = np.ascontiguousarray(list, dtype=np.uint32)
-            if n_list is None:
-                n_list = len(list)
-            if list.ndim != 1 or n_list > len(list):
-                raise ValueError("list must be a one-dimensional array of at least n_list indices")
-            lp = list.ctypes.data_as(C.c_void_p)
-        elif n_list is None:
-            n_list = n
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
-        check(lib.rl_plot_unit_light_paths(self._h, scene.handle, fetch, seed, stream, ptr(states), n, lp, n_list, ptr(hits), ptr(camera),
-                                           ptr(sampled), ptr(samples)))
+        list, n_list = _host_list(list, n_list, n)
+        check(lib.rl_plot_unit_light_paths(self._h, scene.handle, fetch, seed, stream, _host_ptr(states), n, _host_ptr(list), n_list, _host_ptr(hits),
+                                           _host_ptr(camera), _host_ptr(sampled), _host_ptr(samples)))
         return samples
 
     def light_paths_device(self, scene, states, hits, camera, seed, stream, list=None, n_list=None, fetch=FETCH_LDS, sampled=None, samples=None):
         """rl_plot_unit_light_paths_device: `states`, `hits` and `camera` (and `sampled`, `samples`, `list`, if given) are device
         buffers on the unit's device with data_ptr() (e.g. torch tensors) holding n PATH_STATE_DTYPE, HIT_DTYPE and
         CAMERA_SAMPLE_DTYPE records, n bytes, room for n LIGHT_SAMPLE_DTYPE records and at least n_list uint32 indices."""
-        n_bytes = lambda t: t.numel() * t.element_size()
-        n = n_bytes(states) // PATH_STATE_DTYPE.itemsize
-        if n_bytes(states) != n * PATH_STATE_DTYPE.itemsize or n_bytes(hits) < n * HIT_DTYPE.itemsize or n_bytes(camera) < n * CAMERA_SAMPLE_DTYPE.itemsize:
-            raise ValueError("states must hold whole 64-byte records, hits room for as many 48-byte ones and camera as many 48-byte ones")
-        if (sampled is not None and n_bytes(sampled) < n) or (samples is not None and n_bytes(samples) < n * LIGHT_SAMPLE_DTYPE.itemsize):
+        n = _record_count(states, PATH_STATE_DTYPE,
+                          "states must hold whole 64-byte records, hits room for as many 48-byte ones and camera as many 48-byte ones",
+                          (hits, HIT_DTYPE.itemsize), (camera, CAMERA_SAMPLE_DTYPE.itemsize))
+        if not _has_room(n, (sampled, 1), (samples, LIGHT_SAMPLE_DTYPE.itemsize)):
             raise ValueError("sampled must have a byte and samples room for a 32-byte record for every state")
-        if n_list is None:
-            n_list = n if list is None else n_bytes(list) // 4
-        if list is not None and n_bytes(list) < 4 * n_list:
-            raise ValueError("list must have room for n_list 4-byte indices")
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        check(lib.rl_plot_unit_light_paths_device(self._h, scene.handle, fetch, seed, stream, ptr(states), n, ptr(list), n_list, ptr(hits),
-                                                  ptr(camera), ptr(sampled), ptr(samples)))
+        n_list = _device_list(list, n_list, n)
+        check(lib.rl_plot_unit_light_paths_device(self._h, scene.handle, fetch, seed, stream, _device_ptr(states), n, _device_ptr(list), n_list,
+                                                  _device_ptr(hits), _device_ptr(camera), _device_ptr(sampled), _device_ptr(samples)))
 
     def render_samples_direct(self, scene, samples, seed, stream, first=0, fetch=FETCH_LDS, max_segments=0, results=True):
         """render_samples with direct light (rl_plot_unit_render_samples_direct): the same paths, and at every diffuse vertex one
@@ -562,13 +551,10 @@ class PlotUnit(_Handle):
 
     def render_samples_direct_device(self, scene, samples, seed, stream, first=0, fetch=FETCH_LDS, max_segments=0, results=None):
         """rl_plot_unit_render_samples_direct_device: the buffers of render_samples_device."""
-        n_bytes = lambda t: t.numel() * t.element_size()
-        n = n_bytes(samples) // CAMERA_SAMPLE_DTYPE.itemsize
-        if n_bytes(samples) != n * CAMERA_SAMPLE_DTYPE.itemsize or (results is not None and n_bytes(results) < n * PATH_RESULT_DTYPE.itemsize):
-            raise ValueError("samples must hold whole 48-byte records and results room for as many 16-byte ones")
-        check(lib.rl_plot_unit_render_samples_direct_device(self._h, scene.handle, fetch, seed, stream, first, max_segments,
-                                                            C.c_void_p(samples.data_ptr()), n,
-                                                            C.c_void_p(results.data_ptr()) if results is not None else None))
+        n = _record_count(samples, CAMERA_SAMPLE_DTYPE, "samples must hold whole 48-byte records and results room for as many 16-byte ones",
+                          (results, PATH_RESULT_DTYPE.itemsize))
+        check(lib.rl_plot_unit_render_samples_direct_device(self._h, scene.handle, fetch, seed, stream, first, max_segments, _device_ptr(samples), n,
+                                                            _device_ptr(results)))
 
 
 class GatherUnit(_Handle):

@@ -22,6 +22,7 @@
 #include <dlfcn.h>
 #include <unistd.h> // fsync
 
+#include <algorithm>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -376,14 +377,24 @@ int family_launches(const KernelFamily<P...>& family, uint64_t* out) {
 // through STAGING_RAYS, 48-byte ones (hits, camera samples; the path results) through STAGING_HITS, path states through STAGING_STATES.
 enum { STAGING_RAYS, STAGING_HITS, STAGING_STATES, STAGING_COUNT };
 const size_t staging_record_bytes[STAGING_COUNT] = {sizeof(RlRay), sizeof(RlRayHit), sizeof(RlPathState)};
+// A device buffer that is grown on demand and never shrunk (device_reserve).
+struct GrowBuffer {
+    void* p = nullptr;
+    size_t bytes = 0;
+};
 struct QueryCtx {
     hipStream_t stream = nullptr;
     void* staging[STAGING_COUNT] = {};   // host path only (allocated on first use, RL_QUERY_CHUNK records each)
     unsigned long long* queue = nullptr; // path, film and step calls only (allocated on first use): the counter of an RlFilmQueue
-    uint32_t* pack = nullptr;            // rl_scene_step_path_list* only: the compaction's counts and survivors (query_ctx_pack)
-    size_t pack_bytes = 0;
-    void* direct = nullptr;              // rl_plot_unit_render_samples_direct* only: the loop's working buffers (query_ctx_direct)
-    size_t direct_bytes = 0;
+    GrowBuffer pack;                     // rl_scene_step_path_list* only: the compaction's counts and survivors (launch_list_step)
+    GrowBuffer direct;                   // rl_plot_unit_render_samples_direct* only: the loop's working buffers (direct_chunk)
+};
+// What a call's helpers run on: a query context borrowed for the call, the stream that every copy and launch of the call goes on
+// (the context's own for a scene call, the plot unit's for a film call) and the device's CU count.
+struct CallCtx {
+    QueryCtx* q;
+    hipStream_t stream;
+    int cus;
 };
 static_assert(sizeof(RlSpectralRay) == sizeof(RlRay) && sizeof(RlMappedPhoton) <= sizeof(RlRay) && sizeof(RlCameraSample) == sizeof(RlRayHit) &&
                   sizeof(RlPathResult) <= sizeof(RlRay),
@@ -425,33 +436,19 @@ void query_ctx_release(int device, QueryCtx* q) {
 }
 // The context's queue counter (an RlFilmQueue, an RlPathListQueue, an RlLightQueue or an RlLightFilmQueue: a launch's constants sit behind it), allocated on first use.
 int query_ctx_queue(QueryCtx* q) {
-    size_t bytes = sizeof(RlFilmQueue) > sizeof(RlPathListQueue) ? sizeof(RlFilmQueue) : sizeof(RlPathListQueue);
-    if (sizeof(RlLightQueue) > bytes) bytes = sizeof(RlLightQueue);
-    if (sizeof(RlLightFilmQueue) > bytes) bytes = sizeof(RlLightFilmQueue);
+    const size_t bytes = std::max({sizeof(RlFilmQueue), sizeof(RlPathListQueue), sizeof(RlLightQueue), sizeof(RlLightFilmQueue)});
     if (!q->queue) RL_HIP(hipMalloc((void**)&q->queue, bytes));
     return RL_OK;
 }
 
-// The context's compaction scratch (launch_list_step) with room for `bytes`: grown on demand, never shrunk.  (q's stream is idle.)
-int query_ctx_pack(QueryCtx* q, size_t bytes) {
-    if (q->pack_bytes >= bytes) return RL_OK;
-    if (q->pack) RL_HIP(hipFree(q->pack));
-    q->pack = nullptr;
-    q->pack_bytes = 0;
-    RL_HIP(hipMalloc((void**)&q->pack, bytes));
-    q->pack_bytes = bytes;
-    return RL_OK;
-}
-
-// The context's working buffers of the direct render's loop with room for `bytes`: grown on demand, never shrunk.  (Nothing of the
-// context runs.)
-int query_ctx_direct(QueryCtx* q, size_t bytes) {
-    if (q->direct_bytes >= bytes) return RL_OK;
-    if (q->direct) RL_HIP(hipFree(q->direct));
-    q->direct = nullptr;
-    q->direct_bytes = 0;
-    RL_HIP(hipMalloc(&q->direct, bytes));
-    q->direct_bytes = bytes;
+// Room for `bytes` in one of a context's scratch buffers.  (Nothing that uses the buffer runs.)
+int device_reserve(GrowBuffer* b, size_t bytes) {
+    if (b->bytes >= bytes) return RL_OK;
+    if (b->p) RL_HIP(hipFree(b->p));
+    b->p = nullptr;
+    b->bytes = 0;
+    RL_HIP(hipMalloc(&b->p, bytes));
+    b->bytes = bytes;
     return RL_OK;
 }
 
@@ -470,11 +467,11 @@ int resident_per_cu(int device, const void* kernel, size_t dyn, int* out) {
     return RL_OK;
 }
 
-// One launch of a family's kernel on `stream` for n (> 0) records of device arrays: the instantiation for what the scene stages
+// One launch of a family's kernel on c's stream for n (> 0) records of device arrays: the instantiation for what the scene stages
 // and how its prisms are bound, as many workgroups as stay resident (or as the records need), args... behind the blob and the layout.
 // What a family's queue needs before the launch is the caller's.
 template <class... P, class... A>
-int launch_persistent(KernelFamily<P...>& family, const RlScene* scene, int fetch, int cu_count, hipStream_t stream, uint32_t n, A... args) {
+int launch_persistent(const CallCtx& c, KernelFamily<P...>& family, const RlScene* scene, int fetch, uint32_t n, A... args) {
     const size_t scratch_bytes = (RL_TRACE_BLOCK / 64) * sizeof(RlWaveScratch) + ring_t_bytes(scene);
     size_t blob_bytes = 0;
     const int stage = stage_of(scene, fetch, scratch_bytes, &blob_bytes);
@@ -485,10 +482,10 @@ int launch_persistent(KernelFamily<P...>& family, const RlScene* scene, int fetc
     int per_cu = 0;
     const int rc = resident_per_cu(scene->device, (const void*)kernel, dyn, &per_cu);
     if (rc != RL_OK) return rc;
-    uint64_t blocks = (uint64_t)cu_count * (uint64_t)per_cu;
+    uint64_t blocks = (uint64_t)c.cus * (uint64_t)per_cu;
     const uint64_t needed = ((uint64_t)n + RL_TRACE_BLOCK - 1) / RL_TRACE_BLOCK;
     if (blocks > needed) blocks = needed;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(RL_TRACE_BLOCK), dyn, stream, scene->blob, scene->lay, args...);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(RL_TRACE_BLOCK), dyn, c.stream, scene->blob, scene->lay, args...);
     RL_HIP(hipGetLastError());
     return RL_OK;
 }
@@ -503,27 +500,67 @@ struct Staged {
 Staged staged_in(int slot, const void* host, size_t record_bytes) { return Staged{slot, const_cast<void*>(host), record_bytes, true, false}; }
 Staged staged_out(int slot, void* host, size_t record_bytes) { return Staged{slot, host, record_bytes, false, true}; }
 Staged staged_inout(int slot, void* host, size_t record_bytes) { return Staged{slot, host, record_bytes, true, true}; }
-// The host forms: records [0, n) in chunks of RL_QUERY_CHUNK through q's staging buffers (allocated here on first use) -- copy in,
-// launch(first, k) for records [first, first + k), copy out, synchronise (the next chunk overwrites the buffers).
+// The host forms: records [0, n) in chunks of RL_QUERY_CHUNK through the context's staging buffers (allocated here on first use) --
+// copy in, launch(first, k) for records [first, first + k), copy out, synchronise (the next chunk overwrites the buffers).
 template <class N, class Launch>
-int staged_chunks(QueryCtx* q, hipStream_t stream, N n, std::initializer_list<Staged> arrays, Launch launch) {
+int staged_chunks(const CallCtx& c, N n, std::initializer_list<Staged> arrays, Launch launch) {
     for (const Staged& a : arrays)
-        if (a.host && !q->staging[a.slot]) RL_HIP(hipMalloc(&q->staging[a.slot], (size_t)RL_QUERY_CHUNK * staging_record_bytes[a.slot]));
+        if (a.host && !c.q->staging[a.slot]) RL_HIP(hipMalloc(&c.q->staging[a.slot], (size_t)RL_QUERY_CHUNK * staging_record_bytes[a.slot]));
     for (N first = 0; first < n;) {
         const N k = n - first < RL_QUERY_CHUNK ? n - first : (N)RL_QUERY_CHUNK;
         for (const Staged& a : arrays)
             if (a.host && a.in)
-                RL_HIP(hipMemcpyAsync(q->staging[a.slot], (const char*)a.host + (size_t)first * a.record_bytes, (size_t)k * a.record_bytes, hipMemcpyHostToDevice, stream));
+                RL_HIP(hipMemcpyAsync(c.q->staging[a.slot], (const char*)a.host + (size_t)first * a.record_bytes, (size_t)k * a.record_bytes, hipMemcpyHostToDevice, c.stream));
         const int r = launch(first, k);
         if (r != RL_OK) return r;
         for (const Staged& a : arrays)
             if (a.host && a.out)
-                RL_HIP(hipMemcpyAsync((char*)a.host + (size_t)first * a.record_bytes, q->staging[a.slot], (size_t)k * a.record_bytes, hipMemcpyDeviceToHost, stream));
-        RL_HIP(hipStreamSynchronize(stream));
+                RL_HIP(hipMemcpyAsync((char*)a.host + (size_t)first * a.record_bytes, c.q->staging[a.slot], (size_t)k * a.record_bytes, hipMemcpyDeviceToHost, c.stream));
+        RL_HIP(hipStreamSynchronize(c.stream));
         first += k;
     }
     return RL_OK;
 }
+
+// One array of a whole-array host call: the caller's records (null: the call does without this array), their size, which way
+// run() copies them, and the call's own device buffer for them (null: not given, or empty).
+struct Whole {
+    void* host;
+    size_t bytes;
+    bool in, out;
+    void* dev = nullptr;
+};
+Whole whole_in(const void* host, size_t bytes) { return Whole{const_cast<void*>(host), bytes, true, false}; }
+Whole whole_inout(void* host, size_t bytes) { return Whole{host, bytes, true, true}; }
+Whole whole_scratch(void* host, size_t bytes) { return Whole{host, bytes, false, false}; } // (the caller copies what it needs of it)
+// The host forms that are not chunked (the context's staging buffers hold 2^20 records, and a list names states anywhere in the
+// array): device buffers of the call's own for the whole arrays, freed on every way out.  The arrays are the caller's named ones.
+struct WholeArrays {
+    Whole* arrays[6] = {};
+    template <class... W>
+    explicit WholeArrays(W*... w) : arrays{w...} {}
+    WholeArrays(const WholeArrays&) = delete;
+    ~WholeArrays() {
+        for (Whole* a : arrays)
+            if (a && a->dev) (void)hipFree(a->dev);
+    }
+    int allocate() {
+        for (Whole* a : arrays)
+            if (a && a->host && a->bytes) RL_HIP(hipMalloc(&a->dev, a->bytes));
+        return RL_OK;
+    }
+    // On `stream`: the copies in, launch(), the copies out.  Not synchronised.
+    template <class Launch>
+    int run(hipStream_t stream, Launch launch) {
+        for (Whole* a : arrays)
+            if (a && a->dev && a->in) RL_HIP(hipMemcpyAsync(a->dev, a->host, a->bytes, hipMemcpyHostToDevice, stream));
+        const int r = launch();
+        if (r != RL_OK) return r;
+        for (Whole* a : arrays)
+            if (a && a->dev && a->out) RL_HIP(hipMemcpyAsync(a->host, a->dev, a->bytes, hipMemcpyDeviceToHost, stream));
+        return RL_OK;
+    }
+};
 
 int query_check(const RlScene* scene, int fetch, const void* rays, uint32_t n_rays, const void* hits) {
     if (fetch_check(fetch) != RL_OK) return RL_E_INVALID;
@@ -532,11 +569,18 @@ int query_check(const RlScene* scene, int fetch, const void* rays, uint32_t n_ra
     return RL_OK;
 }
 
-// Both arrays of a _device call must be memory the scene's device can address: a pageable host pointer there would fault the
-// device.  Accepted: device memory of the scene's device, managed memory, and pinned host memory mapped at the same address.  (The
+// The arrays of a _device call, in the order they are checked (null: the call does without that one), and the names its messages
+// use: the entry point and its form for host arrays.  A host form has none.
+struct DeviceArrays {
+    const char* what = nullptr;
+    const char* host_form = nullptr;
+    const void* pointers[6] = {};
+};
+// Every array of a _device call must be memory the owner's device can address: a pageable host pointer there would fault the
+// device.  Accepted: device memory of that device, managed memory, and pinned host memory mapped at the same address.  (The
 // runtime reports pageable host memory as hipMemoryTypeUnregistered, or fails.)
-int device_buffers_check(int device, const char* owner, const void* a, const void* b, const char* what, const char* host_form) {
-    for (const void* p : {a, b}) {
+int device_buffers_check(int device, const char* owner, const DeviceArrays& arrays) {
+    for (const void* p : arrays.pointers) {
         if (!p) continue;
         hipPointerAttribute_t attr;
         std::memset(&attr, 0, sizeof attr);
@@ -547,12 +591,23 @@ int device_buffers_check(int device, const char* owner, const void* a, const voi
         const bool ok = (attr.type == hipMemoryTypeDevice && attr.device == device) || attr.type == hipMemoryTypeManaged ||
                         (attr.type == hipMemoryTypeHost && attr.devicePointer == p);
         if (!ok)
-            return fail(RL_E_INVALID, std::string(what) + ": a buffer is not device memory of the " + owner + "'s device (host arrays: " + host_form + ")");
+            return fail(RL_E_INVALID, std::string(arrays.what) + ": a buffer is not device memory of the " + owner + "'s device (host arrays: " +
+                                          arrays.host_form + ")");
     }
     return RL_OK;
 }
-int device_buffers_check(const RlScene* scene, const void* a, const void* b, const char* what, const char* host_form) {
-    return device_buffers_check(scene->device, "scene", a, b, what, host_form);
+// The alignment a _device call asks of its arrays: `which` names the one (or the ones, their addresses or-ed) in the message.
+int aligned_check(const char* what, const char* which, unsigned alignment, std::initializer_list<const void*> pointers) {
+    uintptr_t bits = 0;
+    for (const void* p : pointers) bits |= (uintptr_t)p;
+    if ((bits & (alignment - 1u)) == 0) return RL_OK;
+    return fail(RL_E_INVALID, std::string(what) + ": " + which + " is not " + std::to_string(alignment) + "-byte aligned");
+}
+int states_aligned(const void* states, const char* what) { return aligned_check(what, "the state buffer", 16, {states}); }
+// A null list names states 0 .. n_list - 1.
+int identity_list_check(const void* list, uint32_t n_list, uint32_t n_states) {
+    if (!list && n_list > n_states) return fail(RL_E_INVALID, "the identity list (list = NULL) is longer than the state buffer");
+    return RL_OK;
 }
 
 // ---- caller-supplied paths (rl_scene_camera_rays*, rl_scene_render_rays*, rl_paths.hip.h) -----------------------------------
@@ -562,24 +617,23 @@ struct PathJob {
     uint32_t max_segments; // resolved: 1 .. RL_PATH_MAX_SEGMENTS_CAP
 };
 
-// rays [0, n) of device arrays as paths first_path .. first_path + n - 1 (n > 0): one launch of the path kernel on q's stream,
+// rays [0, n) of device arrays as paths first_path .. first_path + n - 1 (n > 0): one launch of the path kernel on c's stream,
 // behind the zeroing of its queue.
-int launch_paths(const RlScene* scene, int fetch, int cu_count, QueryCtx* q, const PathJob& job, uint64_t first_path,
-                 const RlSpectralRay* rays, RlPathResult* results, uint32_t n) {
-    const int rc = query_ctx_queue(q);
+int launch_paths(const CallCtx& c, const RlScene* scene, int fetch, const PathJob& job, uint64_t first_path, const RlSpectralRay* rays,
+                 RlPathResult* results, uint32_t n) {
+    const int rc = query_ctx_queue(c.q);
     if (rc != RL_OK) return rc;
-    RL_HIP(hipMemsetAsync(q->queue, 0, sizeof(unsigned long long), q->stream));
-    return launch_persistent(g_path_kernels, scene, fetch, cu_count, q->stream, n, rays, results, n, job.seed, job.stream, first_path, job.max_segments,
-                             q->queue);
+    RL_HIP(hipMemsetAsync(c.q->queue, 0, sizeof(unsigned long long), c.stream));
+    return launch_persistent(c, g_path_kernels, scene, fetch, n, rays, results, n, job.seed, job.stream, first_path, job.max_segments, c.q->queue);
 }
 
 unsigned grid_for(uint64_t work_items, int cu_count);
 
-// The camera kernel for paths first_path .. first_path + n - 1 into device array `samples` (n > 0), on q's stream.
-int launch_camera(const RlScene* scene, int cu_count, QueryCtx* q, uint32_t width, uint32_t height, uint64_t seed, uint32_t stream,
-                  uint64_t first_path, RlCameraSample* samples, uint32_t n) {
+// The camera kernel for paths first_path .. first_path + n - 1 into device array `samples` (n > 0), on c's stream.
+int launch_camera(const CallCtx& c, const RlScene* scene, uint32_t width, uint32_t height, uint64_t seed, uint32_t stream, uint64_t first_path,
+                  RlCameraSample* samples, uint32_t n) {
     const float aspect_ratio = (float)width / (float)height; // trace_unit.rs:73, as launch_trace has it
-    hipLaunchKernelGGL(rl_camera_rays_kernel, dim3(grid_for(n, cu_count)), dim3(RL_BLOCK), 0, q->stream, scene->blob, scene->lay, aspect_ratio,
+    hipLaunchKernelGGL(rl_camera_rays_kernel, dim3(grid_for(n, c.cus)), dim3(RL_BLOCK), 0, c.stream, scene->blob, scene->lay, aspect_ratio,
                        seed, stream, first_path, samples, n);
     RL_HIP(hipGetLastError());
     return RL_OK;
@@ -632,51 +686,74 @@ int cu_count_of(int device, int* out) {
     return RL_OK;
 }
 
-// Runs body(q, cu_count) on a query context of the scene's device and hands the context back once nothing of the call runs.
+int plot_settle(RlPlotUnit* plot);
+
+// Runs body(c) on `device` with a query context borrowed, and returns when the call's stream has drained (also after a failure:
+// nothing of the call may still run when the context's buffers are handed on).  The stream is the context's own, or that of the
+// plot unit `film`, whose tail is every write into its buffer so far: a render begun into that unit ends first.  A _device form's
+// arrays are checked once the device is current.
 template <class Body>
-int with_query_ctx(const RlScene* scene, Body body) {
-    int rc = use_device(scene->device);
+int with_call_ctx(int device, const char* owner, RlPlotUnit* film, const DeviceArrays& arrays, Body body) {
+    int rc = use_device(device);
     if (rc != RL_OK) return rc;
+    if ((rc = device_buffers_check(device, owner, arrays)) != RL_OK) return rc;
+    if (film && (rc = plot_settle(film)) != RL_OK) return rc;
     int cus = 256;
-    if ((rc = cu_count_of(scene->device, &cus)) != RL_OK) return rc;
+    if ((rc = cu_count_of(device, &cus)) != RL_OK) return rc;
     QueryCtx* q = nullptr;
-    if ((rc = query_ctx_acquire(scene->device, &q)) != RL_OK) return rc;
-    rc = body(q, cus);
-    const hipError_t e = hipStreamSynchronize(q->stream); // (nothing of this call may still run when its buffers are handed on)
-    query_ctx_release(scene->device, q);
+    if ((rc = query_ctx_acquire(device, &q)) != RL_OK) return rc;
+    const CallCtx c{q, film ? film->stream : q->stream, cus};
+    rc = body(c);
+    const hipError_t e = hipStreamSynchronize(c.stream);
+    query_ctx_release(device, q);
     if (rc != RL_OK) return rc;
     RL_HIP(e);
     return RL_OK;
 }
+// A scene call: on a stream of the call's own.  A host form has no arrays to check.
+template <class Body>
+int with_query_ctx(const RlScene* scene, const DeviceArrays& arrays, Body body) {
+    return with_call_ctx(scene->device, "scene", nullptr, arrays, body);
+}
+template <class Body>
+int with_query_ctx(const RlScene* scene, Body body) { return with_query_ctx(scene, DeviceArrays{}, body); }
+// A film call: everything is queued on the plot unit's stream; the context lends its buffers and its queue counter, and its own
+// stream stays idle.
+template <class Body>
+int with_film_ctx(RlPlotUnit* u, const DeviceArrays& arrays, Body body) {
+    return with_call_ctx(u->device, "plot unit", u, arrays, body);
+}
+template <class Body>
+int with_film_ctx(RlPlotUnit* u, Body body) { return with_film_ctx(u, DeviceArrays{}, body); }
 
 // ---- caller-held path states (rl_scene_begin_paths*, rl_scene_step_paths*, rl_step.hip.h) -----------------------------------
-// One segment for the live states of device array states [0, n) (n > 0): one launch of the step kernel on q's stream, behind the
+// One segment for the live states of device array states [0, n) (n > 0): one launch of the step kernel on c's stream, behind the
 // zeroing of its chunk counter.  `hits` may be null.
-int launch_step(const RlScene* scene, int fetch, int cu_count, QueryCtx* q, uint64_t seed, uint32_t stream, uint32_t flags,
-                RlPathState* states, RlRayHit* hits, uint32_t n) {
-    const int rc = query_ctx_queue(q);
+int launch_step(const CallCtx& c, const RlScene* scene, int fetch, uint64_t seed, uint32_t stream, uint32_t flags, RlPathState* states,
+                RlRayHit* hits, uint32_t n) {
+    const int rc = query_ctx_queue(c.q);
     if (rc != RL_OK) return rc;
-    RL_HIP(hipMemsetAsync(q->queue, 0, sizeof(unsigned long long), q->stream));
-    return launch_persistent(g_step_kernels, scene, fetch, cu_count, q->stream, n, states, hits, n, seed, stream, flags, q->queue);
+    RL_HIP(hipMemsetAsync(c.q->queue, 0, sizeof(unsigned long long), c.stream));
+    return launch_persistent(c, g_step_kernels, scene, fetch, n, states, hits, n, seed, stream, flags, c.q->queue);
 }
 
 // One segment for the states of device array states [0, n_states) that device array list [0, n_list) names (n_list > 0; a null
 // list: states 0 .. n_list - 1), then the indices of the listed states that are still live to device array live_list, in the
-// list's order, and their number to host word *n_live when q's stream is next synchronised.  hits, live_list and n_live may be
-// null; live_list may be list.  On q's stream: the copy that zeroes the chunk counter and writes the list's block behind it
+// list's order, and their number to host word *n_live when c's stream is next synchronised.  hits, live_list and n_live may be
+// null; live_list may be list.  On c's stream: the copy that zeroes the chunk counter and writes the list's block behind it
 // (RlPathListQueue), the list-step kernel and, when live_list or n_live is given, the scan of the chunks' counts, the pack into live_list and the 4-byte copy of the last running total.  The
 // scratch of the compaction is the context's: one count per chunk of 64 list positions, then one survivor slot per list position.
-int launch_list_step(const RlScene* scene, int fetch, int cu_count, QueryCtx* q, uint64_t seed, uint32_t stream, uint32_t flags,
-                     RlPathState* states, uint32_t n_states, const uint32_t* list, uint32_t n_list, RlRayHit* hits, uint32_t* live_list,
-                     uint32_t* n_live) {
+int launch_list_step(const CallCtx& c, const RlScene* scene, int fetch, uint64_t seed, uint32_t stream, uint32_t flags, RlPathState* states,
+                     uint32_t n_states, const uint32_t* list, uint32_t n_list, RlRayHit* hits, uint32_t* live_list, uint32_t* n_live) {
+    QueryCtx* q = c.q;
     int rc = query_ctx_queue(q);
     if (rc != RL_OK) return rc;
     const uint32_t n_chunks = (uint32_t)(((uint64_t)n_list + 63u) / 64u);
     uint32_t *counts = nullptr, *survivors = nullptr;
     if (live_list || n_live) {
-        if ((rc = query_ctx_pack(q, ((size_t)n_chunks + n_list) * sizeof(uint32_t))) != RL_OK) return rc;
-        counts = q->pack;
-        survivors = q->pack + n_chunks;
+        if ((rc = device_reserve(&q->pack, ((size_t)n_chunks + n_list) * sizeof(uint32_t))) != RL_OK) return rc;
+        counts = (uint32_t*)q->pack.p;
+        survivors = counts + n_chunks;
     }
     RlPathListQueue lq;
     lq.next = 0;
@@ -688,26 +765,26 @@ int launch_list_step(const RlScene* scene, int fetch, int cu_count, QueryCtx* q,
     lq.job.stream = stream;
     lq.job.flags = flags;
     // (from pageable memory: the copy has left `lq` when the call returns)
-    RL_HIP(hipMemcpyAsync(q->queue, &lq, sizeof lq, hipMemcpyHostToDevice, q->stream));
-    rc = launch_persistent(g_list_step_kernels, scene, fetch, cu_count, q->stream, n_list, states, hits, q->queue);
+    RL_HIP(hipMemcpyAsync(q->queue, &lq, sizeof lq, hipMemcpyHostToDevice, c.stream));
+    rc = launch_persistent(c, g_list_step_kernels, scene, fetch, n_list, states, hits, q->queue);
     if (rc != RL_OK || !counts) return rc;
-    hipLaunchKernelGGL(rl_list_scan_kernel, dim3(1), dim3(RL_LIST_SCAN_BLOCK), 0, q->stream, counts, n_chunks);
+    hipLaunchKernelGGL(rl_list_scan_kernel, dim3(1), dim3(RL_LIST_SCAN_BLOCK), 0, c.stream, counts, n_chunks);
     RL_HIP(hipGetLastError());
     if (live_list) {
-        hipLaunchKernelGGL(rl_list_pack_kernel, dim3(grid_for((uint64_t)n_chunks * 64u, cu_count)), dim3(RL_BLOCK), 0, q->stream, (const uint32_t*)counts,
+        hipLaunchKernelGGL(rl_list_pack_kernel, dim3(grid_for((uint64_t)n_chunks * 64u, c.cus)), dim3(RL_BLOCK), 0, c.stream, (const uint32_t*)counts,
                            (const uint32_t*)survivors, n_chunks, live_list);
         RL_HIP(hipGetLastError());
     }
-    if (n_live) RL_HIP(hipMemcpyAsync(n_live, counts + (n_chunks - 1u), sizeof(uint32_t), hipMemcpyDeviceToHost, q->stream));
+    if (n_live) RL_HIP(hipMemcpyAsync(n_live, counts + (n_chunks - 1u), sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
     return RL_OK;
 }
 
 // One direct-light sample for the states of device array states [0, n_states) that device array list [0, n_list) names (n_list > 0;
-// a null list: states 0 .. n_list - 1), from device array hits into device array samples, both indexed by state.  On q's stream: the
+// a null list: states 0 .. n_list - 1), from device array hits into device array samples, both indexed by state.  On c's stream: the
 // copy that zeroes the chunk counter and writes the launch's block behind it (RlLightQueue), then the light kernel.
-int launch_light(const RlScene* scene, int fetch, int cu_count, QueryCtx* q, uint64_t seed, uint32_t stream, const RlPathState* states,
-                 uint32_t n_states, const uint32_t* list, uint32_t n_list, const RlRayHit* hits, RlLightSample* samples) {
-    const int rc = query_ctx_queue(q);
+int launch_light(const CallCtx& c, const RlScene* scene, int fetch, uint64_t seed, uint32_t stream, const RlPathState* states, uint32_t n_states,
+                 const uint32_t* list, uint32_t n_list, const RlRayHit* hits, RlLightSample* samples) {
+    const int rc = query_ctx_queue(c.q);
     if (rc != RL_OK) return rc;
     RlLightQueue lq;
     std::memset(&lq, 0, sizeof lq);
@@ -722,8 +799,8 @@ int launch_light(const RlScene* scene, int fetch, int cu_count, QueryCtx* q, uin
     lq.job.stream = stream;
     lq.job.seed = seed;
     // (from pageable memory: the copy has left `lq` when the call returns)
-    RL_HIP(hipMemcpyAsync(q->queue, &lq, sizeof lq, hipMemcpyHostToDevice, q->stream));
-    return launch_persistent(g_light_kernels, scene, fetch, cu_count, q->stream, n_list, q->queue);
+    RL_HIP(hipMemcpyAsync(c.q->queue, &lq, sizeof lq, hipMemcpyHostToDevice, c.stream));
+    return launch_persistent(c, g_light_kernels, scene, fetch, n_list, c.q->queue);
 }
 
 int light_check(const RlScene* scene, int fetch, const void* states, uint32_t n_states, const void* list, uint32_t n_list, const void* hits,
@@ -731,8 +808,7 @@ int light_check(const RlScene* scene, int fetch, const void* states, uint32_t n_
     if (fetch_check(fetch) != RL_OK) return RL_E_INVALID;
     if (n_list > 0 && (!states || !hits || !samples)) return fail(RL_E_INVALID, "null state, hit or sample buffer");
     if (!scene) return fail(RL_E_INVALID, "null scene");
-    if (!list && n_list > n_states) return fail(RL_E_INVALID, "the identity list (list = NULL) is longer than the state buffer");
-    return RL_OK;
+    return identity_list_check(list, n_list, n_states);
 }
 
 // The sampleable emitters of a description, in scan order (include/robigo_luculenta.h: rl_scene_emitters): their table as
@@ -763,9 +839,9 @@ void emitter_table(const RlObjectDesc* objects, uint32_t n_objects, std::vector<
     }
 }
 
-// The begin kernel for device arrays rays, states [0, n) (n > 0) as paths first_path .. first_path + n - 1, on q's stream.
-int launch_begin(int cu_count, QueryCtx* q, uint64_t first_path, const RlSpectralRay* rays, RlPathState* states, uint32_t n) {
-    hipLaunchKernelGGL(rl_begin_paths_kernel, dim3(grid_for(n, cu_count)), dim3(RL_BLOCK), 0, q->stream, rays, first_path, states, n);
+// The begin kernel for device arrays rays, states [0, n) (n > 0) as paths first_path .. first_path + n - 1, on c's stream.
+int launch_begin(const CallCtx& c, uint64_t first_path, const RlSpectralRay* rays, RlPathState* states, uint32_t n) {
+    hipLaunchKernelGGL(rl_begin_paths_kernel, dim3(grid_for(n, c.cus)), dim3(RL_BLOCK), 0, c.stream, rays, first_path, states, n);
     RL_HIP(hipGetLastError());
     return RL_OK;
 }
@@ -780,20 +856,13 @@ int step_check(const RlScene* scene, int fetch, uint32_t flags, const void* stat
 
 int path_list_check(const RlScene* scene, int fetch, uint32_t flags, const void* states, uint32_t n_states, const void* list, uint32_t n_list) {
     const int rc = step_check(scene, fetch, flags, states, n_list);
-    if (rc != RL_OK) return rc;
-    if (!list && n_list > n_states) return fail(RL_E_INVALID, "the identity list (list = NULL) is longer than the state buffer");
-    return RL_OK;
+    return rc != RL_OK ? rc : identity_list_check(list, n_list, n_states);
 }
 
 int begin_check(const RlScene* scene, uint64_t first_path, const void* rays, uint32_t n, const void* states) {
     if (n > 0 && (!rays || !states)) return fail(RL_E_INVALID, "null ray or state buffer");
     if (!scene) return fail(RL_E_INVALID, "null scene");
     return path_range_check(first_path, n);
-}
-
-int states_aligned(const void* states, const char* what) {
-    if (((uintptr_t)states & 15u) != 0) return fail(RL_E_INVALID, std::string(what) + ": the state buffer is not 16-byte aligned");
-    return RL_OK;
 }
 
 } // namespace
@@ -982,7 +1051,6 @@ int rl_scene_create(const RlSceneDesc* desc, int device, RlScene** out) {
 namespace {
 int sessions_quiesce(int device);
 int render_end(RlTraceUnit* u);
-int plot_settle(RlPlotUnit* plot);
 }
 
 int rl_scene_destroy(RlScene* scene) {
@@ -999,22 +1067,20 @@ int rl_scene_destroy(RlScene* scene) {
 int rl_scene_intersect(const RlScene* scene, int primitive_fetch, const RlRay* rays, uint32_t n_rays, RlRayHit* hits) {
     const int rc = query_check(scene, primitive_fetch, rays, n_rays, hits);
     if (rc != RL_OK || n_rays == 0) return rc;
-    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
-        return staged_chunks(q, q->stream, n_rays, {staged_in(STAGING_RAYS, rays, sizeof(RlRay)), staged_out(STAGING_HITS, hits, sizeof(RlRayHit))},
+    return with_query_ctx(scene, [&](const CallCtx& c) -> int {
+        return staged_chunks(c, n_rays, {staged_in(STAGING_RAYS, rays, sizeof(RlRay)), staged_out(STAGING_HITS, hits, sizeof(RlRayHit))},
                              [&](uint32_t, uint32_t k) -> int {
-                                 return launch_persistent(g_query_kernels, scene, primitive_fetch, cus, q->stream, k, (const RlRay*)q->staging[STAGING_RAYS],
-                                                          (RlRayHit*)q->staging[STAGING_HITS], k);
+                                 return launch_persistent(c, g_query_kernels, scene, primitive_fetch, k, (const RlRay*)c.q->staging[STAGING_RAYS],
+                                                          (RlRayHit*)c.q->staging[STAGING_HITS], k);
                              });
     });
 }
 
 int rl_scene_intersect_device(const RlScene* scene, int primitive_fetch, const RlRay* device_rays, uint32_t n_rays, RlRayHit* device_hits) {
-    int rc = query_check(scene, primitive_fetch, device_rays, n_rays, device_hits);
+    const int rc = query_check(scene, primitive_fetch, device_rays, n_rays, device_hits);
     if (rc != RL_OK || n_rays == 0) return rc;
-    if ((rc = use_device(scene->device)) != RL_OK) return rc;
-    if ((rc = device_buffers_check(scene, device_rays, device_hits, "rl_scene_intersect_device", "rl_scene_intersect")) != RL_OK) return rc;
-    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
-        return launch_persistent(g_query_kernels, scene, primitive_fetch, cus, q->stream, n_rays, device_rays, device_hits, n_rays);
+    return with_query_ctx(scene, {"rl_scene_intersect_device", "rl_scene_intersect", {device_rays, device_hits}}, [&](const CallCtx& c) -> int {
+        return launch_persistent(c, g_query_kernels, scene, primitive_fetch, n_rays, device_rays, device_hits, n_rays);
     });
 }
 
@@ -1022,22 +1088,20 @@ int rl_scene_intersect_device(const RlScene* scene, int primitive_fetch, const R
 int rl_scene_occluded(const RlScene* scene, int primitive_fetch, const RlRay* rays, uint32_t n_rays, uint8_t* occluded) {
     const int rc = query_check(scene, primitive_fetch, rays, n_rays, occluded);
     if (rc != RL_OK || n_rays == 0) return rc;
-    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
-        return staged_chunks(q, q->stream, n_rays, {staged_in(STAGING_RAYS, rays, sizeof(RlRay)), staged_out(STAGING_HITS, occluded, sizeof(uint8_t))},
+    return with_query_ctx(scene, [&](const CallCtx& c) -> int {
+        return staged_chunks(c, n_rays, {staged_in(STAGING_RAYS, rays, sizeof(RlRay)), staged_out(STAGING_HITS, occluded, sizeof(uint8_t))},
                              [&](uint32_t, uint32_t k) -> int {
-                                 return launch_persistent(g_occlusion_kernels, scene, primitive_fetch, cus, q->stream, k, (const RlRay*)q->staging[STAGING_RAYS],
-                                                          (uint8_t*)q->staging[STAGING_HITS], k);
+                                 return launch_persistent(c, g_occlusion_kernels, scene, primitive_fetch, k, (const RlRay*)c.q->staging[STAGING_RAYS],
+                                                          (uint8_t*)c.q->staging[STAGING_HITS], k);
                              });
     });
 }
 
 int rl_scene_occluded_device(const RlScene* scene, int primitive_fetch, const RlRay* device_rays, uint32_t n_rays, uint8_t* device_occluded) {
-    int rc = query_check(scene, primitive_fetch, device_rays, n_rays, device_occluded);
+    const int rc = query_check(scene, primitive_fetch, device_rays, n_rays, device_occluded);
     if (rc != RL_OK || n_rays == 0) return rc;
-    if ((rc = use_device(scene->device)) != RL_OK) return rc;
-    if ((rc = device_buffers_check(scene, device_rays, device_occluded, "rl_scene_occluded_device", "rl_scene_occluded")) != RL_OK) return rc;
-    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
-        return launch_persistent(g_occlusion_kernels, scene, primitive_fetch, cus, q->stream, n_rays, device_rays, device_occluded, n_rays);
+    return with_query_ctx(scene, {"rl_scene_occluded_device", "rl_scene_occluded", {device_rays, device_occluded}}, [&](const CallCtx& c) -> int {
+        return launch_persistent(c, g_occlusion_kernels, scene, primitive_fetch, n_rays, device_rays, device_occluded, n_rays);
     });
 }
 
@@ -1045,21 +1109,19 @@ int rl_scene_camera_rays(const RlScene* scene, uint32_t width, uint32_t height, 
                          uint32_t n, RlCameraSample* samples) {
     const int rc = camera_check(scene, width, height, first_path_index, n, samples);
     if (rc != RL_OK || n == 0) return rc;
-    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
-        return staged_chunks(q, q->stream, n, {staged_out(STAGING_HITS, samples, sizeof(RlCameraSample))}, [&](uint32_t first, uint32_t k) -> int {
-            return launch_camera(scene, cus, q, width, height, seed, stream, first_path_index + first, (RlCameraSample*)q->staging[STAGING_HITS], k);
+    return with_query_ctx(scene, [&](const CallCtx& c) -> int {
+        return staged_chunks(c, n, {staged_out(STAGING_HITS, samples, sizeof(RlCameraSample))}, [&](uint32_t first, uint32_t k) -> int {
+            return launch_camera(c, scene, width, height, seed, stream, first_path_index + first, (RlCameraSample*)c.q->staging[STAGING_HITS], k);
         });
     });
 }
 
 int rl_scene_camera_rays_device(const RlScene* scene, uint32_t width, uint32_t height, uint64_t seed, uint32_t stream,
                                 uint64_t first_path_index, uint32_t n, RlCameraSample* device_samples) {
-    int rc = camera_check(scene, width, height, first_path_index, n, device_samples);
+    const int rc = camera_check(scene, width, height, first_path_index, n, device_samples);
     if (rc != RL_OK || n == 0) return rc;
-    if ((rc = use_device(scene->device)) != RL_OK) return rc;
-    if ((rc = device_buffers_check(scene, device_samples, nullptr, "rl_scene_camera_rays_device", "rl_scene_camera_rays")) != RL_OK) return rc;
-    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
-        return launch_camera(scene, cus, q, width, height, seed, stream, first_path_index, device_samples, n);
+    return with_query_ctx(scene, {"rl_scene_camera_rays_device", "rl_scene_camera_rays", {device_samples}}, [&](const CallCtx& c) -> int {
+        return launch_camera(c, scene, width, height, seed, stream, first_path_index, device_samples, n);
     });
 }
 
@@ -1068,12 +1130,11 @@ int rl_scene_render_rays(const RlScene* scene, int primitive_fetch, uint64_t see
     PathJob job{seed, stream, 0u};
     const int rc = paths_check(scene, primitive_fetch, rays, n_rays, results, first_path_index, max_segments, &job);
     if (rc != RL_OK || n_rays == 0) return rc;
-    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
-        return staged_chunks(q, q->stream, n_rays,
-                             {staged_in(STAGING_RAYS, rays, sizeof(RlSpectralRay)), staged_out(STAGING_HITS, results, sizeof(RlPathResult))},
+    return with_query_ctx(scene, [&](const CallCtx& c) -> int {
+        return staged_chunks(c, n_rays, {staged_in(STAGING_RAYS, rays, sizeof(RlSpectralRay)), staged_out(STAGING_HITS, results, sizeof(RlPathResult))},
                              [&](uint32_t first, uint32_t k) -> int {
-                                 return launch_paths(scene, primitive_fetch, cus, q, job, first_path_index + first,
-                                                     (const RlSpectralRay*)q->staging[STAGING_RAYS], (RlPathResult*)q->staging[STAGING_HITS], k);
+                                 return launch_paths(c, scene, primitive_fetch, job, first_path_index + first, (const RlSpectralRay*)c.q->staging[STAGING_RAYS],
+                                                     (RlPathResult*)c.q->staging[STAGING_HITS], k);
                              });
     });
 }
@@ -1081,23 +1142,21 @@ int rl_scene_render_rays(const RlScene* scene, int primitive_fetch, uint64_t see
 int rl_scene_render_rays_device(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, uint64_t first_path_index,
                                 uint32_t max_segments, const RlSpectralRay* device_rays, uint32_t n_rays, RlPathResult* device_results) {
     PathJob job{seed, stream, 0u};
-    int rc = paths_check(scene, primitive_fetch, device_rays, n_rays, device_results, first_path_index, max_segments, &job);
+    const int rc = paths_check(scene, primitive_fetch, device_rays, n_rays, device_results, first_path_index, max_segments, &job);
     if (rc != RL_OK || n_rays == 0) return rc;
-    if ((rc = use_device(scene->device)) != RL_OK) return rc;
-    if ((rc = device_buffers_check(scene, device_rays, device_results, "rl_scene_render_rays_device", "rl_scene_render_rays")) != RL_OK) return rc;
-    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
-        return launch_paths(scene, primitive_fetch, cus, q, job, first_path_index, device_rays, device_results, n_rays);
+    return with_query_ctx(scene, {"rl_scene_render_rays_device", "rl_scene_render_rays", {device_rays, device_results}}, [&](const CallCtx& c) -> int {
+        return launch_paths(c, scene, primitive_fetch, job, first_path_index, device_rays, device_results, n_rays);
     });
 }
 
 int rl_scene_begin_paths(const RlScene* scene, uint64_t first_path_index, const RlSpectralRay* rays, uint32_t n, RlPathState* states) {
     const int rc = begin_check(scene, first_path_index, rays, n, states);
     if (rc != RL_OK || n == 0) return rc;
-    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
-        return staged_chunks(q, q->stream, n, {staged_in(STAGING_RAYS, rays, sizeof(RlSpectralRay)), staged_out(STAGING_STATES, states, sizeof(RlPathState))},
+    return with_query_ctx(scene, [&](const CallCtx& c) -> int {
+        return staged_chunks(c, n, {staged_in(STAGING_RAYS, rays, sizeof(RlSpectralRay)), staged_out(STAGING_STATES, states, sizeof(RlPathState))},
                              [&](uint32_t first, uint32_t k) -> int {
-                                 return launch_begin(cus, q, first_path_index + first, (const RlSpectralRay*)q->staging[STAGING_RAYS],
-                                                     (RlPathState*)q->staging[STAGING_STATES], k);
+                                 return launch_begin(c, first_path_index + first, (const RlSpectralRay*)c.q->staging[STAGING_RAYS],
+                                                     (RlPathState*)c.q->staging[STAGING_STATES], k);
                              });
     });
 }
@@ -1107,10 +1166,8 @@ int rl_scene_begin_paths_device(const RlScene* scene, uint64_t first_path_index,
     int rc = begin_check(scene, first_path_index, device_rays, n, device_states);
     if (rc != RL_OK || n == 0) return rc;
     if ((rc = states_aligned(device_states, "rl_scene_begin_paths_device")) != RL_OK) return rc;
-    if ((rc = use_device(scene->device)) != RL_OK) return rc;
-    if ((rc = device_buffers_check(scene, device_rays, device_states, "rl_scene_begin_paths_device", "rl_scene_begin_paths")) != RL_OK) return rc;
-    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
-        return launch_begin(cus, q, first_path_index, device_rays, device_states, n);
+    return with_query_ctx(scene, {"rl_scene_begin_paths_device", "rl_scene_begin_paths", {device_rays, device_states}}, [&](const CallCtx& c) -> int {
+        return launch_begin(c, first_path_index, device_rays, device_states, n);
     });
 }
 
@@ -1118,12 +1175,12 @@ int rl_scene_step_paths(const RlScene* scene, int primitive_fetch, uint64_t seed
                         uint32_t n, RlRayHit* hits) {
     const int rc = step_check(scene, primitive_fetch, flags, states, n);
     if (rc != RL_OK || n == 0) return rc;
-    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
+    return with_query_ctx(scene, [&](const CallCtx& c) -> int {
         // (the caller's hits go in too: the slots of the states that are not stepped come back as they were)
-        return staged_chunks(q, q->stream, n, {staged_inout(STAGING_STATES, states, sizeof(RlPathState)), staged_inout(STAGING_HITS, hits, sizeof(RlRayHit))},
+        return staged_chunks(c, n, {staged_inout(STAGING_STATES, states, sizeof(RlPathState)), staged_inout(STAGING_HITS, hits, sizeof(RlRayHit))},
                              [&](uint32_t, uint32_t k) -> int {
-                                 return launch_step(scene, primitive_fetch, cus, q, seed, stream, flags, (RlPathState*)q->staging[STAGING_STATES],
-                                                    hits ? (RlRayHit*)q->staging[STAGING_HITS] : nullptr, k);
+                                 return launch_step(c, scene, primitive_fetch, seed, stream, flags, (RlPathState*)c.q->staging[STAGING_STATES],
+                                                    hits ? (RlRayHit*)c.q->staging[STAGING_HITS] : nullptr, k);
                              });
     });
 }
@@ -1133,10 +1190,8 @@ int rl_scene_step_paths_device(const RlScene* scene, int primitive_fetch, uint64
     int rc = step_check(scene, primitive_fetch, flags, device_states, n);
     if (rc != RL_OK || n == 0) return rc;
     if ((rc = states_aligned(device_states, "rl_scene_step_paths_device")) != RL_OK) return rc;
-    if ((rc = use_device(scene->device)) != RL_OK) return rc;
-    if ((rc = device_buffers_check(scene, device_states, device_hits, "rl_scene_step_paths_device", "rl_scene_step_paths")) != RL_OK) return rc;
-    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
-        return launch_step(scene, primitive_fetch, cus, q, seed, stream, flags, device_states, device_hits, n);
+    return with_query_ctx(scene, {"rl_scene_step_paths_device", "rl_scene_step_paths", {device_states, device_hits}}, [&](const CallCtx& c) -> int {
+        return launch_step(c, scene, primitive_fetch, seed, stream, flags, device_states, device_hits, n);
     });
 }
 
@@ -1149,21 +1204,17 @@ int rl_scene_step_path_list_device(const RlScene* scene, int primitive_fetch, ui
     if (n_list == 0) return RL_OK;
     const char* what = "rl_scene_step_path_list_device";
     if ((rc = states_aligned(device_states, what)) != RL_OK) return rc;
-    if (((uintptr_t)device_list | (uintptr_t)device_live_list) & 3u) return fail(RL_E_INVALID, std::string(what) + ": a list is not 4-byte aligned");
-    if ((rc = use_device(scene->device)) != RL_OK) return rc;
-    if ((rc = device_buffers_check(scene, device_states, device_hits, what, "rl_scene_step_path_list")) != RL_OK) return rc;
-    if ((rc = device_buffers_check(scene, device_list, device_live_list, what, "rl_scene_step_path_list")) != RL_OK) return rc;
+    if ((rc = aligned_check(what, "a list", 4, {device_list, device_live_list})) != RL_OK) return rc;
     uint32_t total = 0; // (written by the call's copy, read behind with_query_ctx's synchronise)
-    rc = with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
-        return launch_list_step(scene, primitive_fetch, cus, q, seed, stream, flags, device_states, n_states, device_list, n_list, device_hits,
+    rc = with_query_ctx(scene, {what, "rl_scene_step_path_list", {device_states, device_hits, device_list, device_live_list}}, [&](const CallCtx& c) -> int {
+        return launch_list_step(c, scene, primitive_fetch, seed, stream, flags, device_states, n_states, device_list, n_list, device_hits,
                                 device_live_list, n_live ? &total : nullptr);
     });
     if (rc == RL_OK && n_live) *n_live = total;
     return rc;
 }
 
-// Not chunked: device buffers of the call's own for the whole arrays (the context's staging buffers hold 2^20 records, and a
-// list names states anywhere in the array).
+// Not chunked (WholeArrays).
 int rl_scene_step_path_list(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, uint32_t flags, RlPathState* states,
                             uint32_t n_states, const uint32_t* list, uint32_t n_list, RlRayHit* hits, uint32_t* live_list, uint32_t* n_live) {
     int rc = path_list_check(scene, primitive_fetch, flags, states, n_states, list, n_list);
@@ -1171,32 +1222,20 @@ int rl_scene_step_path_list(const RlScene* scene, int primitive_fetch, uint64_t 
     if (n_live) *n_live = 0u;
     if (n_list == 0) return RL_OK;
     if ((rc = use_device(scene->device)) != RL_OK) return rc;
-    struct Buffers { // freed on every way out
-        void* p[4] = {};
-        ~Buffers() {
-            for (void* b : p)
-                if (b) (void)hipFree(b);
-        }
-    } dev;
-    enum { STATES, HITS, LIST, LIVE };
-    const size_t bytes[4] = {(size_t)n_states * sizeof(RlPathState), hits ? (size_t)n_states * sizeof(RlRayHit) : 0u,
-                             list ? (size_t)n_list * sizeof(uint32_t) : 0u, live_list ? (size_t)n_list * sizeof(uint32_t) : 0u};
-    for (int k = 0; k < 4; ++k)
-        if (bytes[k]) RL_HIP(hipMalloc(&dev.p[k], bytes[k]));
+    // (the caller's hits go in too: the slots of the states that are not stepped come back as they were)
+    Whole d_states = whole_inout(states, (size_t)n_states * sizeof(RlPathState)), d_hits = whole_inout(hits, (size_t)n_states * sizeof(RlRayHit));
+    Whole d_list = whole_in(list, (size_t)n_list * sizeof(uint32_t)), d_live = whole_scratch(live_list, (size_t)n_list * sizeof(uint32_t));
+    WholeArrays dev(&d_states, &d_hits, &d_list, &d_live);
+    if ((rc = dev.allocate()) != RL_OK) return rc;
     uint32_t total = 0;
-    rc = with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
-        // (the caller's hits go in too: the slots of the states that are not stepped come back as they were)
-        const void* in[3] = {states, hits, list};
-        for (int k = 0; k < 3; ++k)
-            if (bytes[k]) RL_HIP(hipMemcpyAsync(dev.p[k], in[k], bytes[k], hipMemcpyHostToDevice, q->stream));
-        const int r = launch_list_step(scene, primitive_fetch, cus, q, seed, stream, flags, (RlPathState*)dev.p[STATES], n_states,
-                                       (const uint32_t*)dev.p[LIST], n_list, (RlRayHit*)dev.p[HITS], (uint32_t*)dev.p[LIVE],
-                                       live_list || n_live ? &total : nullptr);
+    rc = with_query_ctx(scene, [&](const CallCtx& c) -> int {
+        const int r = dev.run(c.stream, [&]() -> int {
+            return launch_list_step(c, scene, primitive_fetch, seed, stream, flags, (RlPathState*)d_states.dev, n_states, (const uint32_t*)d_list.dev,
+                                    n_list, (RlRayHit*)d_hits.dev, (uint32_t*)d_live.dev, live_list || n_live ? &total : nullptr);
+        });
         if (r != RL_OK) return r;
-        if (bytes[STATES]) RL_HIP(hipMemcpyAsync(states, dev.p[STATES], bytes[STATES], hipMemcpyDeviceToHost, q->stream));
-        if (bytes[HITS]) RL_HIP(hipMemcpyAsync(hits, dev.p[HITS], bytes[HITS], hipMemcpyDeviceToHost, q->stream));
-        RL_HIP(hipStreamSynchronize(q->stream)); // (`total` is known from here)
-        if (live_list && total) RL_HIP(hipMemcpyAsync(live_list, dev.p[LIVE], (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, q->stream));
+        RL_HIP(hipStreamSynchronize(c.stream)); // (`total` is known from here)
+        if (live_list && total) RL_HIP(hipMemcpyAsync(live_list, d_live.dev, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
         return RL_OK;
     });
     if (rc == RL_OK && n_live) *n_live = total;
@@ -1221,45 +1260,29 @@ int rl_scene_light_paths_device(const RlScene* scene, int primitive_fetch, uint6
     if (rc != RL_OK || n_list == 0) return rc;
     const char* what = "rl_scene_light_paths_device";
     if ((rc = states_aligned(device_states, what)) != RL_OK) return rc;
-    if (((uintptr_t)device_samples & 15u) != 0) return fail(RL_E_INVALID, std::string(what) + ": the sample buffer is not 16-byte aligned");
-    if ((uintptr_t)device_list & 3u) return fail(RL_E_INVALID, std::string(what) + ": the list is not 4-byte aligned");
-    if ((rc = use_device(scene->device)) != RL_OK) return rc;
-    if ((rc = device_buffers_check(scene, device_states, device_hits, what, "rl_scene_light_paths")) != RL_OK) return rc;
-    if ((rc = device_buffers_check(scene, device_list, device_samples, what, "rl_scene_light_paths")) != RL_OK) return rc;
-    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
-        return launch_light(scene, primitive_fetch, cus, q, seed, stream, device_states, n_states, device_list, n_list, device_hits, device_samples);
+    if ((rc = aligned_check(what, "the sample buffer", 16, {device_samples})) != RL_OK) return rc;
+    if ((rc = aligned_check(what, "the list", 4, {device_list})) != RL_OK) return rc;
+    return with_query_ctx(scene, {what, "rl_scene_light_paths", {device_states, device_hits, device_list, device_samples}}, [&](const CallCtx& c) -> int {
+        return launch_light(c, scene, primitive_fetch, seed, stream, device_states, n_states, device_list, n_list, device_hits, device_samples);
     });
 }
 
-// Not chunked, as rl_scene_step_path_list: device buffers of the call's own for the whole arrays.  The caller's samples go in too:
-// the records of the states that are not listed come back as they were.
+// Not chunked (WholeArrays).  The caller's samples go in too: the records of the states that are not listed come back as they were.
 int rl_scene_light_paths(const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, const RlPathState* states, uint32_t n_states,
                          const uint32_t* list, uint32_t n_list, const RlRayHit* hits, RlLightSample* samples) {
     int rc = light_check(scene, primitive_fetch, states, n_states, list, n_list, hits, samples);
     if (rc != RL_OK || n_list == 0) return rc;
     if (n_states == 0) return RL_OK; // (a given list of a state buffer without states: every entry is skipped)
     if ((rc = use_device(scene->device)) != RL_OK) return rc;
-    struct Buffers { // freed on every way out
-        void* p[4] = {};
-        ~Buffers() {
-            for (void* b : p)
-                if (b) (void)hipFree(b);
-        }
-    } dev;
-    enum { STATES, HITS, SAMPLES, LIST };
-    const size_t bytes[4] = {(size_t)n_states * sizeof(RlPathState), (size_t)n_states * sizeof(RlRayHit), (size_t)n_states * sizeof(RlLightSample),
-                             list ? (size_t)n_list * sizeof(uint32_t) : 0u};
-    for (int k = 0; k < 4; ++k)
-        if (bytes[k]) RL_HIP(hipMalloc(&dev.p[k], bytes[k]));
-    return with_query_ctx(scene, [&](QueryCtx* q, int cus) -> int {
-        const void* in[4] = {states, hits, samples, list};
-        for (int k = 0; k < 4; ++k)
-            if (bytes[k]) RL_HIP(hipMemcpyAsync(dev.p[k], in[k], bytes[k], hipMemcpyHostToDevice, q->stream));
-        const int r = launch_light(scene, primitive_fetch, cus, q, seed, stream, (const RlPathState*)dev.p[STATES], n_states, (const uint32_t*)dev.p[LIST],
-                                   n_list, (const RlRayHit*)dev.p[HITS], (RlLightSample*)dev.p[SAMPLES]);
-        if (r != RL_OK) return r;
-        RL_HIP(hipMemcpyAsync(samples, dev.p[SAMPLES], bytes[SAMPLES], hipMemcpyDeviceToHost, q->stream));
-        return RL_OK;
+    Whole d_states = whole_in(states, (size_t)n_states * sizeof(RlPathState)), d_hits = whole_in(hits, (size_t)n_states * sizeof(RlRayHit));
+    Whole d_samples = whole_inout(samples, (size_t)n_states * sizeof(RlLightSample)), d_list = whole_in(list, (size_t)n_list * sizeof(uint32_t));
+    WholeArrays dev(&d_states, &d_hits, &d_samples, &d_list);
+    if ((rc = dev.allocate()) != RL_OK) return rc;
+    return with_query_ctx(scene, [&](const CallCtx& c) -> int {
+        return dev.run(c.stream, [&]() -> int {
+            return launch_light(c, scene, primitive_fetch, seed, stream, (const RlPathState*)d_states.dev, n_states, (const uint32_t*)d_list.dev, n_list,
+                                (const RlRayHit*)d_hits.dev, (RlLightSample*)d_samples.dev);
+        });
     });
 }
 
@@ -1963,68 +1986,51 @@ int rl_plot_unit_download(RlPlotUnit* u, RlVector3* out) {
 
 // ---- film for caller-supplied photons and samples (rl_plot_unit_plot_photons*, rl_plot_unit_render_samples*, rl_film.hip.h) ----
 // Everything here is queued on the plot unit's own stream, whose tail is every write into the buffer so far, and the calls
-// return when that stream has drained.  The host forms borrow a query context for its staging buffers (and the film path kernel
-// its queue counter); the context's own stream stays idle.
+// return when that stream has drained (with_film_ctx).
 
 namespace {
-// samples [0, n) of device arrays as paths first_path .. first_path + n - 1 (n > 0), splatted into u: one launch of the film path
-// kernel on u's stream, behind the copy that zeroes the context's queue counter and writes the film's constants after it.
-// `results` may be null.
-int launch_film(RlPlotUnit* u, const RlScene* scene, int fetch, int cu_count, QueryCtx* q, const PathJob& job, uint64_t first_path,
-                const RlCameraSample* samples, RlPathResult* results, uint32_t n) {
-    const int rc = query_ctx_queue(q);
-    if (rc != RL_OK) return rc;
-    RlFilmQueue fq;
-    fq.next = 0;
-    fq.film.plot = u->xyz;
-    fq.film.width = u->width;
-    fq.film.height = u->height;
-    fq.film.wm1 = (float)(int)u->width - 1.0f;
-    fq.film.hm1 = (float)(int)u->height - 1.0f;
-    fq.film.aspect_ratio = (float)u->width / (float)u->height; // plot_unit.rs:48
-    fq.film.off_cie = scene->lay.off_cie;
-    // (from pageable memory: the copy has left `fq` when the call returns)
-    RL_HIP(hipMemcpyAsync(q->queue, &fq, sizeof fq, hipMemcpyHostToDevice, u->stream));
-    return launch_persistent(g_film_kernels, scene, fetch, cu_count, u->stream, n, samples, results, n, job.seed, job.stream, first_path, job.max_segments,
-                             q->queue);
+// The film's constants of a launch that splats into u what it traces in `scene`.
+RlFilm film_of(const RlPlotUnit* u, const RlScene* scene) {
+    RlFilm film;
+    film.plot = u->xyz;
+    film.width = u->width;
+    film.height = u->height;
+    film.wm1 = (float)(int)u->width - 1.0f;
+    film.hm1 = (float)(int)u->height - 1.0f;
+    film.aspect_ratio = (float)u->width / (float)u->height; // plot_unit.rs:48
+    film.off_cie = scene->lay.off_cie;
+    return film;
 }
 
-// The photon splat kernel for device array photons [0, n) (n > 0) on u's stream.
-int launch_film_photons(RlPlotUnit* u, int cu_count, const RlMappedPhoton* photons, uint64_t n) {
+// samples [0, n) of device arrays as paths first_path .. first_path + n - 1 (n > 0), splatted into u: one launch of the film path
+// kernel on c's stream, behind the copy that zeroes the context's queue counter and writes the film's constants after it.
+// `results` may be null.
+int launch_film(const CallCtx& c, RlPlotUnit* u, const RlScene* scene, int fetch, const PathJob& job, uint64_t first_path,
+                const RlCameraSample* samples, RlPathResult* results, uint32_t n) {
+    const int rc = query_ctx_queue(c.q);
+    if (rc != RL_OK) return rc;
+    const RlFilmQueue fq{0, film_of(u, scene)};
+    // (from pageable memory: the copy has left `fq` when the call returns)
+    RL_HIP(hipMemcpyAsync(c.q->queue, &fq, sizeof fq, hipMemcpyHostToDevice, c.stream));
+    return launch_persistent(c, g_film_kernels, scene, fetch, n, samples, results, n, job.seed, job.stream, first_path, job.max_segments, c.q->queue);
+}
+
+// The photon splat kernel for device array photons [0, n) (n > 0) on c's stream.
+int launch_film_photons(const CallCtx& c, RlPlotUnit* u, const RlMappedPhoton* photons, uint64_t n) {
     const float aspect = (float)u->width / (float)u->height; // plot_unit.rs:48
-    hipLaunchKernelGGL(rl_film_photons_kernel, dim3(grid_for(n, cu_count)), dim3(RL_BLOCK), 0, u->stream, photons, n, u->cie, u->width,
-                       u->height, aspect, u->xyz);
+    hipLaunchKernelGGL(rl_film_photons_kernel, dim3(grid_for(n, c.cus)), dim3(RL_BLOCK), 0, c.stream, photons, n, u->cie, u->width, u->height,
+                       aspect, u->xyz);
     RL_HIP(hipGetLastError());
     return RL_OK;
 }
 
-// Runs body(q, cu_count) on the plot unit's device with a query context borrowed, behind a render begun into the unit, and
-// returns when the unit's stream has drained (also after a failure: nothing of the call may still run when the context's
-// buffers are handed on).
-extern "C++" template <class Body>
-int with_film_ctx(RlPlotUnit* u, Body body) {
-    int rc = use_device(u->device);
-    if (rc != RL_OK) return rc;
-    if ((rc = plot_settle(u)) != RL_OK) return rc; // a fused render begun into this buffer ends first
-    int cus = 256;
-    if ((rc = cu_count_of(u->device, &cus)) != RL_OK) return rc;
-    QueryCtx* q = nullptr;
-    if ((rc = query_ctx_acquire(u->device, &q)) != RL_OK) return rc;
-    rc = body(q, cus);
-    const hipError_t e = hipStreamSynchronize(u->stream);
-    query_ctx_release(u->device, q);
-    if (rc != RL_OK) return rc;
-    RL_HIP(e);
-    return RL_OK;
-}
-
 // The light kernel with a film for the states of device array states [0, n_states) that device array list [0, n_list) names
-// (n_list > 0; a null list: states 0 .. n_list - 1), splatted into u: on `stream`, the copy that zeroes the context's chunk counter
+// (n_list > 0; a null list: states 0 .. n_list - 1), splatted into u: on c's stream, the copy that zeroes the context's chunk counter
 // and writes the launch's block behind it (RlLightFilmQueue), then the kernel.  `samples` and `sampled` may be null.
-int launch_light_film(RlPlotUnit* u, const RlScene* scene, int fetch, int cu_count, QueryCtx* q, hipStream_t stream, uint64_t seed, uint32_t rng_stream,
-                      const RlPathState* states, uint32_t n_states, const uint32_t* list, uint32_t n_list, const RlRayHit* hits,
-                      const RlCameraSample* camera, uint8_t* sampled, RlLightSample* samples) {
-    const int rc = query_ctx_queue(q);
+int launch_light_film(const CallCtx& c, RlPlotUnit* u, const RlScene* scene, int fetch, uint64_t seed, uint32_t rng_stream, const RlPathState* states,
+                      uint32_t n_states, const uint32_t* list, uint32_t n_list, const RlRayHit* hits, const RlCameraSample* camera, uint8_t* sampled,
+                      RlLightSample* samples) {
+    const int rc = query_ctx_queue(c.q);
     if (rc != RL_OK) return rc;
     RlLightFilmQueue lq;
     std::memset(&lq, 0, sizeof lq);
@@ -2042,16 +2048,10 @@ int launch_light_film(RlPlotUnit* u, const RlScene* scene, int fetch, int cu_cou
     lq.job.stream = rng_stream;
     lq.job.seed = seed;
     lq.job.n_objects = scene->emitter_flags ? scene->lay.n_objects : 0u;
-    lq.job.film.plot = u->xyz;
-    lq.job.film.width = u->width;
-    lq.job.film.height = u->height;
-    lq.job.film.wm1 = (float)(int)u->width - 1.0f;
-    lq.job.film.hm1 = (float)(int)u->height - 1.0f;
-    lq.job.film.aspect_ratio = (float)u->width / (float)u->height; // plot_unit.rs:48
-    lq.job.film.off_cie = scene->lay.off_cie;
+    lq.job.film = film_of(u, scene);
     // (from pageable memory: the copy has left `lq` when the call returns)
-    RL_HIP(hipMemcpyAsync(q->queue, &lq, sizeof lq, hipMemcpyHostToDevice, stream));
-    return launch_persistent(g_light_film_kernels, scene, fetch, cu_count, stream, n_list, q->queue);
+    RL_HIP(hipMemcpyAsync(c.q->queue, &lq, sizeof lq, hipMemcpyHostToDevice, c.stream));
+    return launch_persistent(c, g_light_film_kernels, scene, fetch, n_list, c.q->queue);
 }
 
 int light_film_check(const RlPlotUnit* u, const RlScene* scene, int fetch, const void* states, uint32_t n_states, const void* list, uint32_t n_list,
@@ -2060,51 +2060,39 @@ int light_film_check(const RlPlotUnit* u, const RlScene* scene, int fetch, const
     if (!scene) return fail(RL_E_INVALID, "null scene");
     if (fetch_check(fetch) != RL_OK) return RL_E_INVALID;
     if (n_list > 0 && (!states || !hits || !camera)) return fail(RL_E_INVALID, "null state, hit or camera sample buffer");
-    if (!list && n_list > n_states) return fail(RL_E_INVALID, "the identity list (list = NULL) is longer than the state buffer");
-    return RL_OK;
+    return identity_list_check(list, n_list, n_states);
 }
 
-// A query context whose launches go onto another stream for as long as this lives: the direct render runs the list step (which
-// queues on its context's stream) on the plot unit's stream.  The context is the call's alone.
-struct StreamLoan {
-    QueryCtx* q;
-    hipStream_t own;
-    StreamLoan(QueryCtx* ctx, hipStream_t stream) : q(ctx), own(ctx->stream) { q->stream = stream; }
-    ~StreamLoan() { q->stream = own; }
-};
-
 // rl_plot_unit_render_samples_direct* for device arrays camera, results [0, n) (0 < n <= RL_QUERY_CHUNK; results may be null) as
-// paths first_path .. first_path + n - 1, on u's stream, which has drained on return: begin, then step / light / swap until no
+// paths first_path .. first_path + n - 1, on c's stream, which has drained on return: begin, then step / light / swap until no
 // path is live or max_segments segments are made.  The working buffers are the context's: states | hits | two lists | sampled.
-int direct_chunk(RlPlotUnit* u, const RlScene* scene, int fetch, int cu_count, QueryCtx* q, const PathJob& job, uint64_t first_path,
+int direct_chunk(const CallCtx& c, RlPlotUnit* u, const RlScene* scene, int fetch, const PathJob& job, uint64_t first_path,
                  const RlCameraSample* camera, RlPathResult* results, uint32_t n) {
-    int rc = query_ctx_direct(q, (size_t)n * (sizeof(RlPathState) + sizeof(RlRayHit) + 2u * sizeof(uint32_t) + 1u));
+    int rc = device_reserve(&c.q->direct, (size_t)n * (sizeof(RlPathState) + sizeof(RlRayHit) + 2u * sizeof(uint32_t) + 1u));
     if (rc != RL_OK) return rc;
-    StreamLoan loan(q, u->stream);
-    RlPathState* states = (RlPathState*)q->direct;
+    RlPathState* states = (RlPathState*)c.q->direct.p;
     RlRayHit* hits = (RlRayHit*)(states + n);
     uint32_t* lists[2] = {(uint32_t*)(hits + n), (uint32_t*)(hits + n) + n};
     uint8_t* sampled = (uint8_t*)(lists[1] + n);
-    hipLaunchKernelGGL(rl_direct_begin_kernel, dim3(grid_for(n, cu_count)), dim3(RL_BLOCK), 0, u->stream, camera, first_path, states, sampled, n);
+    hipLaunchKernelGGL(rl_direct_begin_kernel, dim3(grid_for(n, c.cus)), dim3(RL_BLOCK), 0, c.stream, camera, first_path, states, sampled, n);
     RL_HIP(hipGetLastError());
     const uint32_t* list = nullptr; // the first round's: every state
     uint32_t n_list = n;
     for (uint32_t segment = 0; segment < job.max_segments && n_list > 0; ++segment) {
         uint32_t n_live = 0; // (written by the step's copy, read behind the synchronise)
         uint32_t* live = lists[segment & 1u];
-        if ((rc = launch_list_step(scene, fetch, cu_count, q, job.seed, job.stream, 0u, states, n, list, n_list, hits, live, &n_live)) != RL_OK) return rc;
+        if ((rc = launch_list_step(c, scene, fetch, job.seed, job.stream, 0u, states, n, list, n_list, hits, live, &n_live)) != RL_OK) return rc;
         // (the list the step was given: the states that have just ended are seen once)
-        if ((rc = launch_light_film(u, scene, fetch, cu_count, q, u->stream, job.seed, job.stream, states, n, list, n_list, hits, camera, sampled, nullptr)) != RL_OK)
-            return rc;
-        RL_HIP(hipStreamSynchronize(u->stream));
+        if ((rc = launch_light_film(c, u, scene, fetch, job.seed, job.stream, states, n, list, n_list, hits, camera, sampled, nullptr)) != RL_OK) return rc;
+        RL_HIP(hipStreamSynchronize(c.stream));
         list = live;
         n_list = n_live;
     }
     if (results) {
-        hipLaunchKernelGGL(rl_direct_results_kernel, dim3(grid_for(n, cu_count)), dim3(RL_BLOCK), 0, u->stream, (const RlPathState*)states, results, n);
+        hipLaunchKernelGGL(rl_direct_results_kernel, dim3(grid_for(n, c.cus)), dim3(RL_BLOCK), 0, c.stream, (const RlPathState*)states, results, n);
         RL_HIP(hipGetLastError());
     }
-    RL_HIP(hipStreamSynchronize(u->stream));
+    RL_HIP(hipStreamSynchronize(c.stream));
     return RL_OK;
 }
 
@@ -2123,9 +2111,9 @@ int rl_plot_unit_plot_photons(RlPlotUnit* u, const RlMappedPhoton* photons, uint
     if (!u) return fail(RL_E_INVALID, "null plot unit");
     if (n > 0 && !photons) return fail(RL_E_INVALID, "null photon buffer");
     if (n == 0) return RL_OK;
-    return with_film_ctx(u, [&](QueryCtx* q, int cus) -> int {
-        return staged_chunks(q, u->stream, n, {staged_in(STAGING_RAYS, photons, sizeof(RlMappedPhoton))}, [&](uint64_t, uint64_t k) -> int {
-            return launch_film_photons(u, cus, (const RlMappedPhoton*)q->staging[STAGING_RAYS], k);
+    return with_film_ctx(u, [&](const CallCtx& c) -> int {
+        return staged_chunks(c, n, {staged_in(STAGING_RAYS, photons, sizeof(RlMappedPhoton))}, [&](uint64_t, uint64_t k) -> int {
+            return launch_film_photons(c, u, (const RlMappedPhoton*)c.q->staging[STAGING_RAYS], k);
         });
     });
 }
@@ -2134,11 +2122,8 @@ int rl_plot_unit_plot_photons_device(RlPlotUnit* u, const RlMappedPhoton* device
     if (!u) return fail(RL_E_INVALID, "null plot unit");
     if (n > 0 && !device_photons) return fail(RL_E_INVALID, "null photon buffer");
     if (n == 0) return RL_OK;
-    int rc = use_device(u->device);
-    if (rc != RL_OK) return rc;
-    if ((rc = device_buffers_check(u->device, "plot unit", device_photons, nullptr, "rl_plot_unit_plot_photons_device", "rl_plot_unit_plot_photons")) != RL_OK)
-        return rc;
-    return with_film_ctx(u, [&](QueryCtx*, int cus) -> int { return launch_film_photons(u, cus, device_photons, n); });
+    return with_film_ctx(u, {"rl_plot_unit_plot_photons_device", "rl_plot_unit_plot_photons", {device_photons}},
+                         [&](const CallCtx& c) -> int { return launch_film_photons(c, u, device_photons, n); });
 }
 
 int rl_plot_unit_render_samples(RlPlotUnit* u, const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream,
@@ -2148,11 +2133,11 @@ int rl_plot_unit_render_samples(RlPlotUnit* u, const RlScene* scene, int primiti
     const int rc = samples_check(u, scene, primitive_fetch, max_segments, first_path_index, samples, n, &job);
     if (rc != RL_OK || n == 0) return rc;
     if (scene->device != u->device) return fail(RL_E_STATE, "scene and plot unit live on different devices");
-    return with_film_ctx(u, [&](QueryCtx* q, int cus) -> int {
-        return staged_chunks(q, u->stream, n, {staged_in(STAGING_HITS, samples, sizeof(RlCameraSample)), staged_out(STAGING_RAYS, results, sizeof(RlPathResult))},
+    return with_film_ctx(u, [&](const CallCtx& c) -> int {
+        return staged_chunks(c, n, {staged_in(STAGING_HITS, samples, sizeof(RlCameraSample)), staged_out(STAGING_RAYS, results, sizeof(RlPathResult))},
                              [&](uint32_t first, uint32_t k) -> int {
-                                 return launch_film(u, scene, primitive_fetch, cus, q, job, first_path_index + first,
-                                                    (const RlCameraSample*)q->staging[STAGING_HITS], results ? (RlPathResult*)q->staging[STAGING_RAYS] : nullptr, k);
+                                 return launch_film(c, u, scene, primitive_fetch, job, first_path_index + first, (const RlCameraSample*)c.q->staging[STAGING_HITS],
+                                                    results ? (RlPathResult*)c.q->staging[STAGING_RAYS] : nullptr, k);
                              });
     });
 }
@@ -2161,17 +2146,16 @@ int rl_plot_unit_render_samples_device(RlPlotUnit* u, const RlScene* scene, int 
                                        uint64_t first_path_index, uint32_t max_segments, const RlCameraSample* device_samples,
                                        uint32_t n, RlPathResult* device_results) {
     PathJob job{seed, stream, 0u};
-    int rc = samples_check(u, scene, primitive_fetch, max_segments, first_path_index, device_samples, n, &job);
+    const int rc = samples_check(u, scene, primitive_fetch, max_segments, first_path_index, device_samples, n, &job);
     if (rc != RL_OK || n == 0) return rc;
     if (scene->device != u->device) return fail(RL_E_STATE, "scene and plot unit live on different devices");
-    if ((rc = use_device(u->device)) != RL_OK) return rc;
-    if ((rc = device_buffers_check(u->device, "plot unit", device_samples, device_results, "rl_plot_unit_render_samples_device", "rl_plot_unit_render_samples")) != RL_OK)
-        return rc;
-    return with_film_ctx(u, [&](QueryCtx* q, int cus) -> int {
-        return launch_film(u, scene, primitive_fetch, cus, q, job, first_path_index, device_samples, device_results, n);
-    });
+    return with_film_ctx(u, {"rl_plot_unit_render_samples_device", "rl_plot_unit_render_samples", {device_samples, device_results}},
+                         [&](const CallCtx& c) -> int {
+                             return launch_film(c, u, scene, primitive_fetch, job, first_path_index, device_samples, device_results, n);
+                         });
 }
 
+// (The device mismatch is reported before the early-out on an empty list.)
 int rl_plot_unit_light_paths_device(RlPlotUnit* u, const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream,
                                     const RlPathState* device_states, uint32_t n_states, const uint32_t* device_list, uint32_t n_list,
                                     const RlRayHit* device_hits, const RlCameraSample* device_camera, uint8_t* device_sampled,
@@ -2182,22 +2166,17 @@ int rl_plot_unit_light_paths_device(RlPlotUnit* u, const RlScene* scene, int pri
     if (n_list == 0) return RL_OK;
     const char* what = "rl_plot_unit_light_paths_device";
     if ((rc = states_aligned(device_states, what)) != RL_OK) return rc;
-    if ((((uintptr_t)device_samples | (uintptr_t)device_camera) & 15u) != 0)
-        return fail(RL_E_INVALID, std::string(what) + ": the sample or camera sample buffer is not 16-byte aligned");
-    if ((uintptr_t)device_list & 3u) return fail(RL_E_INVALID, std::string(what) + ": the list is not 4-byte aligned");
-    if ((rc = use_device(u->device)) != RL_OK) return rc;
-    const char* host_form = "rl_plot_unit_light_paths";
-    if ((rc = device_buffers_check(u->device, "plot unit", device_states, device_hits, what, host_form)) != RL_OK) return rc;
-    if ((rc = device_buffers_check(u->device, "plot unit", device_list, device_samples, what, host_form)) != RL_OK) return rc;
-    if ((rc = device_buffers_check(u->device, "plot unit", device_camera, device_sampled, what, host_form)) != RL_OK) return rc;
-    return with_film_ctx(u, [&](QueryCtx* q, int cus) -> int {
-        return launch_light_film(u, scene, primitive_fetch, cus, q, u->stream, seed, stream, device_states, n_states, device_list, n_list, device_hits,
-                                 device_camera, device_sampled, device_samples);
-    });
+    if ((rc = aligned_check(what, "the sample or camera sample buffer", 16, {device_samples, device_camera})) != RL_OK) return rc;
+    if ((rc = aligned_check(what, "the list", 4, {device_list})) != RL_OK) return rc;
+    return with_film_ctx(u, {what, "rl_plot_unit_light_paths", {device_states, device_hits, device_list, device_samples, device_camera, device_sampled}},
+                         [&](const CallCtx& c) -> int {
+                             return launch_light_film(c, u, scene, primitive_fetch, seed, stream, device_states, n_states, device_list, n_list, device_hits,
+                                                      device_camera, device_sampled, device_samples);
+                         });
 }
 
-// Not chunked, as rl_scene_light_paths: device buffers of the call's own for the whole arrays.  The caller's samples and `sampled`
-// bytes go in too: those of the states that are not listed come back as they were.
+// Not chunked (WholeArrays).  The caller's samples and `sampled` bytes go in too: those of the states that are not listed come back
+// as they were.
 int rl_plot_unit_light_paths(RlPlotUnit* u, const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, const RlPathState* states,
                              uint32_t n_states, const uint32_t* list, uint32_t n_list, const RlRayHit* hits, const RlCameraSample* camera,
                              uint8_t* sampled, RlLightSample* samples) {
@@ -2206,30 +2185,18 @@ int rl_plot_unit_light_paths(RlPlotUnit* u, const RlScene* scene, int primitive_
     if (scene->device != u->device) return fail(RL_E_STATE, "scene and plot unit live on different devices");
     if (n_list == 0 || n_states == 0) return RL_OK; // (a given list of a state buffer without states: every entry is skipped)
     if ((rc = use_device(u->device)) != RL_OK) return rc;
-    struct Buffers { // freed on every way out
-        void* p[6] = {};
-        ~Buffers() {
-            for (void* b : p)
-                if (b) (void)hipFree(b);
-        }
-    } dev;
-    enum { STATES, HITS, CAMERA, SAMPLES, SAMPLED, LIST };
-    const size_t bytes[6] = {(size_t)n_states * sizeof(RlPathState), (size_t)n_states * sizeof(RlRayHit), (size_t)n_states * sizeof(RlCameraSample),
-                             samples ? (size_t)n_states * sizeof(RlLightSample) : 0u, sampled ? (size_t)n_states : 0u,
-                             list ? (size_t)n_list * sizeof(uint32_t) : 0u};
-    for (int k = 0; k < 6; ++k)
-        if (bytes[k]) RL_HIP(hipMalloc(&dev.p[k], bytes[k]));
-    return with_film_ctx(u, [&](QueryCtx* q, int cus) -> int {
-        const void* in[6] = {states, hits, camera, samples, sampled, list};
-        for (int k = 0; k < 6; ++k)
-            if (bytes[k]) RL_HIP(hipMemcpyAsync(dev.p[k], in[k], bytes[k], hipMemcpyHostToDevice, u->stream));
-        const int r = launch_light_film(u, scene, primitive_fetch, cus, q, u->stream, seed, stream, (const RlPathState*)dev.p[STATES], n_states,
-                                        (const uint32_t*)dev.p[LIST], n_list, (const RlRayHit*)dev.p[HITS], (const RlCameraSample*)dev.p[CAMERA],
-                                        (uint8_t*)dev.p[SAMPLED], (RlLightSample*)dev.p[SAMPLES]);
+    Whole d_states = whole_in(states, (size_t)n_states * sizeof(RlPathState)), d_hits = whole_in(hits, (size_t)n_states * sizeof(RlRayHit));
+    Whole d_camera = whole_in(camera, (size_t)n_states * sizeof(RlCameraSample)), d_samples = whole_inout(samples, (size_t)n_states * sizeof(RlLightSample));
+    Whole d_sampled = whole_inout(sampled, (size_t)n_states), d_list = whole_in(list, (size_t)n_list * sizeof(uint32_t));
+    WholeArrays dev(&d_states, &d_hits, &d_camera, &d_samples, &d_sampled, &d_list);
+    if ((rc = dev.allocate()) != RL_OK) return rc;
+    return with_film_ctx(u, [&](const CallCtx& c) -> int {
+        const int r = dev.run(c.stream, [&]() -> int {
+            return launch_light_film(c, u, scene, primitive_fetch, seed, stream, (const RlPathState*)d_states.dev, n_states, (const uint32_t*)d_list.dev, n_list,
+                                     (const RlRayHit*)d_hits.dev, (const RlCameraSample*)d_camera.dev, (uint8_t*)d_sampled.dev, (RlLightSample*)d_samples.dev);
+        });
         if (r != RL_OK) return r;
-        if (bytes[SAMPLES]) RL_HIP(hipMemcpyAsync(samples, dev.p[SAMPLES], bytes[SAMPLES], hipMemcpyDeviceToHost, u->stream));
-        if (bytes[SAMPLED]) RL_HIP(hipMemcpyAsync(sampled, dev.p[SAMPLED], bytes[SAMPLED], hipMemcpyDeviceToHost, u->stream));
-        RL_HIP(hipStreamSynchronize(u->stream)); // (the buffers are freed when the call returns)
+        RL_HIP(hipStreamSynchronize(c.stream)); // (the buffers are freed when the call returns)
         return RL_OK;
     });
 }
@@ -2241,11 +2208,11 @@ int rl_plot_unit_render_samples_direct(RlPlotUnit* u, const RlScene* scene, int 
     const int rc = samples_check(u, scene, primitive_fetch, max_segments, first_path_index, samples, n, &job);
     if (rc != RL_OK || n == 0) return rc;
     if (scene->device != u->device) return fail(RL_E_STATE, "scene and plot unit live on different devices");
-    return with_film_ctx(u, [&](QueryCtx* q, int cus) -> int {
-        return staged_chunks(q, u->stream, n, {staged_in(STAGING_HITS, samples, sizeof(RlCameraSample)), staged_out(STAGING_RAYS, results, sizeof(RlPathResult))},
+    return with_film_ctx(u, [&](const CallCtx& c) -> int {
+        return staged_chunks(c, n, {staged_in(STAGING_HITS, samples, sizeof(RlCameraSample)), staged_out(STAGING_RAYS, results, sizeof(RlPathResult))},
                              [&](uint32_t first, uint32_t k) -> int {
-                                 return direct_chunk(u, scene, primitive_fetch, cus, q, job, first_path_index + first,
-                                                     (const RlCameraSample*)q->staging[STAGING_HITS], results ? (RlPathResult*)q->staging[STAGING_RAYS] : nullptr, k);
+                                 return direct_chunk(c, u, scene, primitive_fetch, job, first_path_index + first, (const RlCameraSample*)c.q->staging[STAGING_HITS],
+                                                     results ? (RlPathResult*)c.q->staging[STAGING_RAYS] : nullptr, k);
                              });
     });
 }
@@ -2258,13 +2225,11 @@ int rl_plot_unit_render_samples_direct_device(RlPlotUnit* u, const RlScene* scen
     if (rc != RL_OK || n == 0) return rc;
     if (scene->device != u->device) return fail(RL_E_STATE, "scene and plot unit live on different devices");
     const char* what = "rl_plot_unit_render_samples_direct_device";
-    if (((uintptr_t)device_samples & 15u) != 0) return fail(RL_E_INVALID, std::string(what) + ": the sample buffer is not 16-byte aligned");
-    if ((rc = use_device(u->device)) != RL_OK) return rc;
-    if ((rc = device_buffers_check(u->device, "plot unit", device_samples, device_results, what, "rl_plot_unit_render_samples_direct")) != RL_OK) return rc;
-    return with_film_ctx(u, [&](QueryCtx* q, int cus) -> int {
+    if ((rc = aligned_check(what, "the sample buffer", 16, {device_samples})) != RL_OK) return rc;
+    return with_film_ctx(u, {what, "rl_plot_unit_render_samples_direct", {device_samples, device_results}}, [&](const CallCtx& c) -> int {
         for (uint32_t first = 0; first < n;) {
             const uint32_t k = n - first < RL_QUERY_CHUNK ? n - first : (uint32_t)RL_QUERY_CHUNK;
-            const int r = direct_chunk(u, scene, primitive_fetch, cus, q, job, first_path_index + first, device_samples + first,
+            const int r = direct_chunk(c, u, scene, primitive_fetch, job, first_path_index + first, device_samples + first,
                                        device_results ? device_results + first : nullptr, k);
             if (r != RL_OK) return r;
             first += k;

@@ -7,6 +7,8 @@ import ctypes as C
 
 import numpy as np
 
+import _query_rays as QR
+
 GUARD = 64    # bytes in front of and behind the payload; a multiple of every alignment the ABI asks for (16 bytes: RlPathState)
 FILL = 0xAA   # 0xAAAAAAAA is no value a kernel writes: a finite, tiny negative float (-3.0e-13), an object index beyond any scene
 
@@ -70,6 +72,11 @@ class Guarded:
         assert (lo == FILL).all(), "%s: %d guard bytes IN FRONT of the output were written, first at -%d" % (
             what, int((lo != FILL).sum()), self.front - int(np.flatnonzero(lo != FILL)[-1]))
         return image[self.front:self.front + self.nbytes].copy().view(dtype)
+
+
+def device_guarded(nbytes=None, initial=None):
+    """A Guarded buffer in device memory."""
+    return Guarded(QR.DeviceBuffer, nbytes=nbytes, initial=initial)
 
 
 def assert_written_as(got, want, what):

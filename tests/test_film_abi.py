@@ -10,6 +10,7 @@ import pytest
 
 import robigo_luculenta_amd as R
 from robigo_luculenta_amd import _lib
+from _boundary import _err, _Fake
 from _device_build import device_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,19 +39,6 @@ def test_every_entry_point_is_exported_bound_and_declared_for_rust():
     assert _lib.lib.rl_debug_film_launches(None) == RL_E_INVALID
     for method in ("plot_photons", "plot_photons_device", "render_samples", "render_samples_device"):
         assert callable(getattr(R.PlotUnit, method))
-
-
-def _err():
-    return _lib.lib.rl_last_error()
-
-
-class _Fake:
-    """A handle for the checks that come after the null checks: every one of them must refuse before the handle is read or a
-    device is touched (the pointer is never dereferenced when an argument is bad)."""
-
-    def __init__(self):
-        self.buf = (C.c_uint8 * 256)()
-        self.ptr = C.cast(self.buf, C.c_void_p)
 
 
 @pytest.mark.parametrize("name", ["rl_plot_unit_plot_photons", "rl_plot_unit_plot_photons_device"])

@@ -440,8 +440,7 @@ def test_step_on_poisoned_lds_and_in_another_order(name, pattern):
 
 # ---- 6. guarded, prefilled outputs of every _device form --------------------------------------------------------------------
 
-def _guarded(nbytes=None, initial=None):
-    return G.Guarded(QR.DeviceBuffer, nbytes=nbytes, initial=initial)
+_guarded = G.device_guarded
 
 
 @pytest.mark.parametrize("n", BATCHES)

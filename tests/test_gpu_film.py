@@ -9,10 +9,12 @@ import threading
 import numpy as np
 import pytest
 
+import _boundary as B
 import _image_cases as IC
 import _oracle as O
 import _path_oracle as P
 import _query_rays as QR
+from _boundary import _ocam
 from test_gpu_query import _scene
 
 pytestmark = pytest.mark.gpu
@@ -24,10 +26,6 @@ W, H = 320, 180
 # the least share of paths that must carry a value (tests/test_gpu_path_query.py: IDENTITY_SCENES)
 IDENTITY_SCENES = {"demo": 0.05, "glass": 0.05, "random-seed-1": 0.3, "demo-2500": 0.05}
 BATCH_SIZES = [0, 1, 63, 64, 65, (1 << 20) + 4097]
-
-
-def _ocam(cam):
-    return O.RlCameraDesc.from_buffer_copy(bytes(cam))
 
 
 def _photons(x, y, probability, wavelength):
@@ -56,9 +54,7 @@ def assert_film(got, w, h, photons, what=""):
 
 
 def _variant_of(before):
-    ran = [a - b for a, b in zip(R.film_launches(), before)]
-    assert sum(1 for r in ran if r) == 1, ran
-    return next(i for i, r in enumerate(ran) if r)
+    return B._variant_of(R.film_launches, before)
 
 
 def _upload(a):

@@ -10,12 +10,13 @@ import pytest
 
 import _guarded as G
 import _lds_poison as LP
+from _light_cases import _lit_scene, _prefilled
 import _light_oracle as LO
 import _oracle as O
 import _query_rays as QR
 from test_gpu_path_list import _Words, _rays, _slice_crossing_size
 from test_gpu_step import _Device, _scene, assert_same
-from test_light_abi import _with_lights, assert_means_agree, closed_scene, vertex_states
+from test_light_abi import assert_means_agree, closed_scene, vertex_states
 
 pytestmark = pytest.mark.gpu
 
@@ -27,13 +28,6 @@ FILL32 = 0xAAAAAAAA
 SAMPLE = R.LIGHT_SAMPLE_DTYPE
 
 
-def _lit_scene(name):
-    objs, cam = _scene(name)
-    if name.startswith("random") or name.endswith("prisms"):
-        objs = _with_lights(np.ascontiguousarray(objs).view(R.OBJECT_DTYPE), np.random.default_rng(len(name)))
-    return np.ascontiguousarray(objs).view(R.OBJECT_DTYPE), cam
-
-
 def _stepped(scene, n, seed, stream, first, steps):
     """(states, hits) of n camera paths after `steps` segments with hits; the hits of states that ended earlier stay as written."""
     st = scene.begin_paths(_rays(scene, n, seed, stream, first), first)
@@ -42,10 +36,6 @@ def _stepped(scene, n, seed, stream, first, steps):
     for _ in range(steps):
         scene.step_paths(st, seed, stream, hits=hits)
     return st, hits
-
-
-def _prefilled(n):
-    return np.frombuffer(bytes([G.FILL]) * (32 * n), dtype=SAMPLE).copy()
 
 
 def _light_device(scene, st, hits, seed, stream, lst=None, n_list=None, fetch=R.FETCH_LDS, samples=None):

@@ -10,11 +10,12 @@ import pytest
 
 import _guarded as G
 import _lds_poison as LP
+from _light_cases import _lit_scene, _prefilled
 import _light_film_oracle as FO
 import _query_rays as QR
 from test_gpu_path_list import _Words, _slice_crossing_size
 from test_gpu_step import _Device, _scene, assert_same
-from test_light_abi import _with_lights, assert_means_agree, closed_scene
+from test_light_abi import assert_means_agree, closed_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -27,13 +28,6 @@ FILMS = ((16, 9), (64, 36))
 W, H = 320, 180      # the camera the paths are drawn for; the films are smaller, which a plot unit is free to be
 
 
-def _lit_scene(name):
-    objs, cam = _scene(name)
-    if name.startswith("random") or name.endswith("prisms"):
-        objs = _with_lights(np.ascontiguousarray(objs).view(R.OBJECT_DTYPE), np.random.default_rng(len(name)))
-    return np.ascontiguousarray(objs).view(R.OBJECT_DTYPE), cam
-
-
 def _stepped(scene, n, seed, stream, first, steps):
     """(camera samples, states, hits) of n camera paths after `steps` segments with hits."""
     camera = scene.camera_rays(W, H, seed, stream, first, n)
@@ -43,10 +37,6 @@ def _stepped(scene, n, seed, stream, first, steps):
     for _ in range(steps):
         scene.step_paths(st, seed, stream, hits=hits)
     return camera, st, hits
-
-
-def _prefilled(n):
-    return np.frombuffer(bytes([G.FILL]) * (32 * n), dtype=SAMPLE).copy()
 
 
 def _some_bytes(n, rng):

@@ -12,6 +12,7 @@ import pytest
 
 import _image_cases as IC
 import _oracle as O
+from _boundary import _ocam
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,10 +23,6 @@ def R():
     import robigo_luculenta_amd as R
     assert R.device_count() > 0
     return R
-
-
-def _ocam(cam):
-    return O.RlCameraDesc.from_buffer_copy(bytes(cam))
 
 
 def test_black_image_tonemaps_to_black_like_the_reference(R):

@@ -10,6 +10,7 @@ import zlib
 import numpy as np
 import pytest
 
+import _boundary as B
 import _occlusion_cases as OC
 import _oracle as O
 import _query_rays as QR
@@ -47,9 +48,7 @@ def bounded_sets(objs, cam_o, cam_d, first_hits, rng, oscene=None):
 
 
 def _variant_of(before):
-    ran = [a - b for a, b in zip(R.occlusion_launches(), before)]
-    assert sum(1 for r in ran if r) == 1, ran
-    return next(i for i, r in enumerate(ran) if r)
+    return B._variant_of(R.occlusion_launches, before)
 
 
 @pytest.mark.parametrize("name", SCENES)

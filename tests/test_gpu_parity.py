@@ -11,14 +11,11 @@ import pytest
 import _image_cases as IC
 import _oracle as O
 from _lds_poison import _poison_lds
+from _boundary import _ocam
 
 pytestmark = pytest.mark.gpu
 
 import robigo_luculenta_amd as R  # a missing HIP library is a failure, never a skip
-
-
-def _ocam(cam):
-    return O.RlCameraDesc.from_buffer_copy(bytes(cam))
 
 
 @pytest.fixture(scope="module")

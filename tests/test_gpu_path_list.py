@@ -165,8 +165,7 @@ def scene_first_step_live(a, begun, scene, seed, stream, fetch):
 
 # ---- (c) a hostile list ------------------------------------------------------------------------------------------------------
 
-def _guarded(nbytes=None, initial=None):
-    return G.Guarded(QR.DeviceBuffer, nbytes=nbytes, initial=initial)
+_guarded = G.device_guarded
 
 
 @pytest.mark.parametrize("name", ["demo", "glass"])

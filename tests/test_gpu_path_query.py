@@ -10,9 +10,11 @@ import zlib
 import numpy as np
 import pytest
 
+import _boundary as B
 import _oracle as O
 import _path_oracle as P
 import _query_rays as QR
+from _boundary import _ocam
 from test_gpu_query import _scene, ray_sets
 
 pytestmark = pytest.mark.gpu
@@ -28,14 +30,8 @@ IDENTITY_SCENES = {"demo": 0.05, "glass": 0.05, "random-seed-1": 0.3, "random-se
                    "random-6000": 0.1}
 
 
-def _ocam(cam):
-    return O.RlCameraDesc.from_buffer_copy(bytes(cam))
-
-
 def _variant_of(before):
-    ran = [a - b for a, b in zip(R.path_launches(), before)]
-    assert sum(1 for r in ran if r) == 1, ran
-    return next(i for i, r in enumerate(ran) if r)
+    return B._variant_of(R.path_launches, before)
 
 
 def assert_same(got, want, what):

@@ -11,9 +11,11 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+import _boundary as B
 import _oracle as O
 import _query_rays as QR
 import _random_scene as RS
+from _boundary import _ocam
 
 pytestmark = pytest.mark.gpu
 
@@ -21,10 +23,6 @@ import robigo_luculenta_amd as R  # a missing HIP library is a failure, never a 
 
 NONE = R.RL_OBJECT_NONE
 FETCHES = (R.FETCH_LDS, R.FETCH_GLOBAL)
-
-
-def _ocam(cam):
-    return O.RlCameraDesc.from_buffer_copy(bytes(cam))
 
 
 def oracle_hits(oscene, origins, directions, t_max=None):
@@ -163,9 +161,7 @@ _ran = set()   # query variants seen by test_scene_queries_bit_exact (test_every
 
 
 def _variant_of(before):
-    ran = [a - b for a, b in zip(R.query_launches(), before)]
-    assert sum(1 for r in ran if r) == 1, ran
-    return next(i for i, r in enumerate(ran) if r)
+    return B._variant_of(R.query_launches, before)
 
 
 @pytest.mark.parametrize("name", SCENES)

@@ -15,16 +15,13 @@ import _light_oracle as LO
 import _oracle as O
 import _random_scene as RS
 import _step_oracle as S
+from _boundary import _err, _FakeScene
 from _device_build import device_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RL_E_INVALID = -1
 ENTRY_POINTS = ("rl_scene_light_paths", "rl_scene_light_paths_device")
 W, H = 320, 180
-
-
-def _err():
-    return _lib.lib.rl_last_error()
 
 
 def test_the_record_is_as_specified():
@@ -43,14 +40,6 @@ def test_the_record_is_as_specified():
         assert hasattr(_lib.lib, name) and name in _lib.DEBUG_SIGNATURES, name
     assert len(R.light_launches()) == 6 and _lib.lib.rl_debug_light_launches(None) == RL_E_INVALID
     assert "block 2^31 + s" in open(os.path.join(ROOT, "robigo_luculenta_amd", "csrc", "rl_rng.h")).read()
-
-
-class _FakeScene:
-    """A scene handle for the checks that come before the handle is read or a device is touched."""
-
-    def __init__(self):
-        self.buf = (C.c_uint8 * 256)()
-        self.ptr = C.cast(self.buf, C.c_void_p)
 
 
 @pytest.mark.parametrize("name", ENTRY_POINTS)

@@ -11,6 +11,7 @@ import pytest
 import robigo_luculenta_amd as R
 from robigo_luculenta_amd import _lib
 import _light_film_oracle as FO
+from _boundary import _err
 from _device_build import device_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,10 +20,6 @@ LIGHT = ("rl_plot_unit_light_paths", "rl_plot_unit_light_paths_device")
 DIRECT = ("rl_plot_unit_render_samples_direct", "rl_plot_unit_render_samples_direct_device")
 # rl_light_kernel's spilled SGPRs per variant (stage, cylinders), DESIGN.md section 4: the new kernel may not spill more
 LIGHT_KERNEL_SGPR_SPILLS = {("0", "0"): 22, ("0", "1"): 23, ("1", "0"): 14, ("1", "1"): 15, ("2", "0"): 0, ("2", "1"): 0}
-
-
-def _err():
-    return _lib.lib.rl_last_error()
 
 
 class _Fake:

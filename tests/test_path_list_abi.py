@@ -11,6 +11,7 @@ import pytest
 
 import robigo_luculenta_amd as R
 from robigo_luculenta_amd import _lib
+from _boundary import _err, _FakeScene
 from _device_build import device_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,18 +39,6 @@ def test_both_entry_points_are_exported_bound_and_in_the_rust_block():
     assert _lib.lib.rl_debug_path_list_launches(None) == RL_E_INVALID
     for method in ("step_path_list", "step_path_list_device"):
         assert callable(getattr(R.Scene, method))
-
-
-def _err():
-    return _lib.lib.rl_last_error()
-
-
-class _FakeScene:
-    """A scene handle for the checks that come before the handle is read or a device is touched."""
-
-    def __init__(self):
-        self.buf = (C.c_uint8 * 256)()
-        self.ptr = C.cast(self.buf, C.c_void_p)
 
 
 @pytest.mark.parametrize("name", ENTRY_POINTS)

@@ -11,6 +11,7 @@ import pytest
 
 import robigo_luculenta_amd as R
 from robigo_luculenta_amd import _lib
+from _boundary import _err, _FakeScene
 from _device_build import device_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -54,10 +55,6 @@ def test_every_entry_point_is_exported_and_bound():
     assert _lib.lib.rl_debug_path_launches(None) == RL_E_INVALID
 
 
-def _err():
-    return _lib.lib.rl_last_error()
-
-
 @pytest.mark.parametrize("name", ["rl_scene_render_rays", "rl_scene_render_rays_device"])
 def test_render_rays_bad_arguments_are_invalid_with_a_message(name):
     fn = getattr(_lib.lib, name)
@@ -80,15 +77,6 @@ def test_camera_rays_bad_arguments_are_invalid_with_a_message(name):
     assert fn(None, 64, 36, 1, 0, 0, 4, sp) == RL_E_INVALID and b"scene" in _err()
     assert fn(None, 64, 36, 1, 0, 0, 0, None) == RL_E_INVALID and b"scene" in _err()
     assert s.tobytes() == bytes(s.nbytes)
-
-
-class _FakeScene:
-    """A scene handle for the checks that come after the null-scene check: every one of them must refuse before the handle is
-    read or a device is touched (the pointer is never dereferenced when an argument is bad)."""
-
-    def __init__(self):
-        self.buf = (C.c_uint8 * 256)()
-        self.ptr = C.cast(self.buf, C.c_void_p)
 
 
 def test_bad_arguments_after_the_scene_check():
