@@ -779,6 +779,24 @@ int launch_list_step(const CallCtx& c, const RlScene* scene, int fetch, uint64_t
     return RL_OK;
 }
 
+// The words of a light launch's block that rl_light_kernel and rl_light_film_kernel share (`samples` may be null for the second).
+RlLightJob light_job(const RlScene* scene, uint64_t seed, uint32_t stream, const RlPathState* states, uint32_t n_states, const uint32_t* list,
+                     uint32_t n_list, const RlRayHit* hits, RlLightSample* samples) {
+    RlLightJob job;
+    std::memset(&job, 0, sizeof job);
+    job.states = states;
+    job.hits = hits;
+    job.list = list;
+    job.emitters = scene->emitters;
+    job.samples = samples;
+    job.n_list = n_list;
+    job.n_states = n_states;
+    job.n_emitters = (uint32_t)scene->emitter_objects.size();
+    job.stream = stream;
+    job.seed = seed;
+    return job;
+}
+
 // One direct-light sample for the states of device array states [0, n_states) that device array list [0, n_list) names (n_list > 0;
 // a null list: states 0 .. n_list - 1), from device array hits into device array samples, both indexed by state.  On c's stream: the
 // copy that zeroes the chunk counter and writes the launch's block behind it (RlLightQueue), then the light kernel.
@@ -788,16 +806,7 @@ int launch_light(const CallCtx& c, const RlScene* scene, int fetch, uint64_t see
     if (rc != RL_OK) return rc;
     RlLightQueue lq;
     std::memset(&lq, 0, sizeof lq);
-    lq.job.states = states;
-    lq.job.hits = hits;
-    lq.job.list = list;
-    lq.job.emitters = scene->emitters;
-    lq.job.samples = samples;
-    lq.job.n_list = n_list;
-    lq.job.n_states = n_states;
-    lq.job.n_emitters = (uint32_t)scene->emitter_objects.size();
-    lq.job.stream = stream;
-    lq.job.seed = seed;
+    lq.job = light_job(scene, seed, stream, states, n_states, list, n_list, hits, samples);
     // (from pageable memory: the copy has left `lq` when the call returns)
     RL_HIP(hipMemcpyAsync(c.q->queue, &lq, sizeof lq, hipMemcpyHostToDevice, c.stream));
     return launch_persistent(c, g_light_kernels, scene, fetch, n_list, c.q->queue);
@@ -2034,19 +2043,10 @@ int launch_light_film(const CallCtx& c, RlPlotUnit* u, const RlScene* scene, int
     if (rc != RL_OK) return rc;
     RlLightFilmQueue lq;
     std::memset(&lq, 0, sizeof lq);
-    lq.job.states = states;
-    lq.job.hits = hits;
-    lq.job.list = list;
-    lq.job.emitters = scene->emitters;
-    lq.job.samples = samples;
+    lq.job.light = light_job(scene, seed, rng_stream, states, n_states, list, n_list, hits, samples);
     lq.job.camera = camera;
     lq.job.sampled = sampled;
     lq.job.emitter_flags = scene->emitter_flags;
-    lq.job.n_list = n_list;
-    lq.job.n_states = n_states;
-    lq.job.n_emitters = (uint32_t)scene->emitter_objects.size();
-    lq.job.stream = rng_stream;
-    lq.job.seed = seed;
     lq.job.n_objects = scene->emitter_flags ? scene->lay.n_objects : 0u;
     lq.job.film = film_of(u, scene);
     // (from pageable memory: the copy has left `lq` when the call returns)

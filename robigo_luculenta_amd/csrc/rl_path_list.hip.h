@@ -1,6 +1,6 @@
 // rl_path_list.hip.h -- the kernels behind rl_scene_step_path_list*: one segment for the path states an index list names, in place,
 // and the list of those that are still live afterwards, in the order the list had them.  Included by rl_api.hip after
-// rl_step.hip.h (RlPathState as four 16-byte words), rl_paths.hip.h (rl_opaque) and rl_film.hip.h (RlFilmQueue).
+// rl_step.hip.h (rl_step_chunk), rl_paths.hip.h (rl_opaque, RlChunkCursor) and rl_film.hip.h (RlFilmQueue).
 //
 // Three launches on one stream: rl_list_step_kernel steps the listed states and leaves, per chunk of 64 list positions, the
 // chunk's survivors (compacted in list order) and their number; rl_list_scan_kernel turns the numbers into running totals, in
@@ -29,101 +29,51 @@ struct RlPathListQueue {
     RlPathList job;
 };
 
-// What rl_step_kernel does with one chunk, statement for statement (rl_step.hip.h: the loads, rl_intersect_segment, the hit record,
-// rl_bounce, the emitter term, the stores), for a state index that need not be the chunk's position: lane `lane` of the wave steps
-// states[i] when `in_range` and the state is live, and idles through the scan as a null ray otherwise, writing nothing.  Returns
-// whether the lane's state is live after the step.  seed, stream and flags come from the launch's block (`queue`).  A copy, not a function both kernels call: called from rl_step_kernel it
-// changed instructions in all six of its instantiations (profiles/path_list_isa_diff.txt).
-template <int STAGE, bool CYL>
-__device__ __forceinline__ bool rl_list_step_chunk(const RlStagedScene& staged, const RlSceneLayout& lay, RlWaveScratch* ws, uint32_t lane,
-                                              RlPathState* __restrict__ states, RlRayHit* __restrict__ hits, uint32_t i, bool in_range,
-                                              unsigned long long* queue RL_TACC_PARAM) {
-    const RlSceneView& sv = staged.sv;
-    RL_T0(t_load);
-    RlF4* rec = (RlF4*)(states + i);
-    RlF4 q0 = {0.0f, 0.0f, 0.0f, 0.0f}, q1 = q0, q2 = q0, q3 = q0;
-    bool live = false, live_after = false;
-    if (in_range) {
-        q0 = rec[0];
-        q1 = rec[1];
-        q2 = rec[2];
-        q3 = rec[3];
-        live = rl_f2u(q2.z) == RL_PATH_LIVE;
+// A launch's seed, stream and flags for rl_step_chunk (rl_step.hip.h): words of the block, loaded through an opaque copy of the
+// pointer where the body uses them, so that nothing of the block is held across the scan.
+struct RlPathListConsts {
+    unsigned long long* queue;
+    __device__ __forceinline__ const RlPathList* job() const { return &((const RlPathListQueue*)rl_opaque(queue))->job; }
+    // (the same in every lane: rl_rng.h wants the launch constants in scalar registers)
+    __device__ __forceinline__ uint64_t seed() const {
+        const uint64_t seed = job()->seed;
+        return ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(seed >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)seed);
     }
-    RL_T1(RL_ST_T_REFILL, t_load);
-    RL_STAT(RL_ST_ITER, 1);
-    RL_STAT(RL_ST_SCAN_LANES, __popcll(__builtin_amdgcn_ballot_w64(live)));
-    RlPath p;
-    p.origin = rl_f3(q0.x, q0.y, q0.z);
-    p.direction = rl_f3(q1.x, q1.y, q1.z);
-    p.wavelength = q0.w;
-    p.intensity = q1.w;
-    p.continue_chance = q2.x;
-    p.sx = p.sy = 0.0f;
-    p.ior = 1.0f;
-    p.bounce = rl_f2u(q2.y); // the bounce draws block 2 + segments
+    __device__ __forceinline__ uint32_t stream() const { return __builtin_amdgcn_readfirstlane(job()->stream); }
+    __device__ __forceinline__ uint32_t flags() const { return job()->flags; }
+};
 
-    // ---- Scene::intersect for every lane's segment ----
-    const RlHit hit = rl_intersect_segment<STAGE, CYL>(staged, lay, live, p.origin, p.direction, ws, lane RL_TACC_ARG);
-
-    // ---- the hit record, as rl_query_kernel writes it for t_max = INFINITY ----
-    RL_T0(t_camera);
-    if (live) {
-        if (RlRayHit* out_hits = rl_opaque(hits)) out_hits[i] = rl_ray_hit_of(sv, p.origin, p.direction, hit, hit.obj != RL_HIT_NONE);
+// A list position as a state index: `listed` when k is below n_list and the entry there (k itself when the list is null: the
+// identity list) is below n_states; i = 0 otherwise, so that no address is formed from an entry that was not checked.  `job` is
+// a launch's block with the words list, n_list and n_states (RlPathList, RlLightJob): each is loaded where it is tested, n_states
+// only under the lanes that are listed so far.  (Handed the three words as values the light kernels loaded them all up front and
+// ran 3.5 % slower: DESIGN.md section 4.)
+struct RlListed {
+    bool listed;
+    uint32_t i;
+};
+template <class JOB>
+__device__ __forceinline__ RlListed rl_listed_index(const JOB* job, uint32_t k) {
+    RlListed at;
+    at.i = k;
+    at.listed = k < job->n_list;
+    if (const uint32_t* entries = job->list) {
+        if (at.listed) at.i = entries[k];
     }
-    RL_T1(RL_ST_T_CAMERA, t_camera);
-
-    // ---- the rest of the loop body (trace_unit.rs:92-126) ----
-    RL_T0(t_shade);
-    int status = RL_PATH_CONTINUES;
-    uint32_t emitter = RL_OBJECT_NONE;
-    float value = 0.0f;
-    if (live) {
-        if (hit.obj != RL_HIT_NONE && rl_object_material(rl_f2u(sv.objects[hit.obj].w)) == RL_MATERIAL_SF10_GLASS)
-            p.ior = rl_sf10_ior(p.wavelength);
-        const uint64_t path = ((uint64_t)rl_f2u(q3.y) << 32) | rl_f2u(q3.x);
-        const RlPathList* job = &((const RlPathListQueue*)rl_opaque(queue))->job;
-        // (the same in every lane: rl_rng.h wants the launch constants in scalar registers)
-        const uint64_t seed = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(job->seed >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)job->seed);
-        status = rl_bounce(sv, seed, __builtin_amdgcn_readfirstlane(job->stream), path, &p, hit, &value, &emitter);
-    }
-    RL_T1(RL_ST_T_SHADE, t_shade);
-    RL_T0(t_emit);
-    const bool on_light = status == RL_PATH_ENDED_ON_EMITTER;
-    RL_STAT(RL_ST_END_EMITTER, __popcll(__builtin_amdgcn_ballot_w64(on_light)));
-    if (on_light) value = rl_emission(sv, p.intensity, p.wavelength, emitter);
-    if (live) {
-        uint32_t end = RL_PATH_LIVE;
-        if (on_light) end = RL_PATH_END_EMITTER;
-        else if (hit.obj == RL_HIT_NONE) end = RL_PATH_END_VOID;
-        else if (status == RL_PATH_ENDED && !(((const RlPathListQueue*)rl_opaque(queue))->job.flags & RL_STEP_NO_ROULETTE)) end = RL_PATH_END_ROULETTE;
-        q0.x = p.origin.x, q0.y = p.origin.y, q0.z = p.origin.z;
-        q1.x = p.direction.x, q1.y = p.direction.y, q1.z = p.direction.z;
-        q1.w = p.intensity;
-        q2.x = p.continue_chance;
-        q2.y = rl_u2f(rl_f2u(q2.y) + 1u);
-        q2.z = rl_u2f(end);
-        live_after = end == RL_PATH_LIVE;
-        q2.w = on_light ? value : 0.0f;
-        q3.z = rl_u2f(on_light ? emitter : RL_OBJECT_NONE);
-        q3.w = rl_u2f(0u);
-        rec[0] = q0;
-        rec[1] = q1;
-        rec[2] = q2;
-        rec[3] = q3;
-    }
-    RL_T1(RL_ST_T_EMIT, t_emit);
-    return live_after;
+    at.listed = at.listed && at.i < job->n_states;
+    if (!at.listed) at.i = 0u;
+    return at;
 }
 
 // rl_step_kernel on a list: chunk c is list positions c * 64 .. c * 64 + 63, lane l steps states[list[c * 64 + l]] (or state
 // c * 64 + l when the list is null: the identity list).  An entry that is not below n_states is skipped like a position past the
-// end of the list: the lane idles through the scan and touches no memory.  The chunk counter, the slice rule and the body of a
-// chunk are the step kernel's (rl_list_step_chunk).  `queue` is the counter of an RlPathListQueue, written before the launch and,
-// but for the counter, never by the kernel; its block is loaded through an opaque copy of the pointer where it is used, so that
-// nothing of it is held across the scan.  When `survivors` is not null: the lanes whose state is live after the step write its
-// index to survivors[c * 64 + rank], rank = the number of such lanes below (ballot + mbcnt), and the chunk's count of them goes to
-// counts[c].  Slot c * 64 + rank is below n_list: a chunk has no more survivors than list positions.
+// end of the list: the lane idles through the scan and touches no memory (rl_listed_index).  The chunk counter, the slice rule
+// and the body of a chunk are the step kernel's (RlChunkCursor, rl_step_chunk).  `queue` is the counter of an RlPathListQueue,
+// written before the launch and, but for the counter, never by the kernel; its block is loaded through an opaque copy of the
+// pointer where it is used, so that nothing of it is held across the scan.  When `survivors` is not null: the lanes whose state
+// is live after the step write its index to survivors[c * 64 + rank], rank = the number of such lanes below (ballot + mbcnt), and
+// the chunk's count of them goes to counts[c].  Slot c * 64 + rank is below n_list: a chunk has no more survivors than list
+// positions.
 template <int STAGE, bool CYL>
 __global__ __launch_bounds__(RL_TRACE_BLOCK, RL_TRACE_WPS) __attribute__((amdgpu_num_vgpr(RL_TRACE_VGPRS / 2))) void rl_list_step_kernel(
     const RlF4* __restrict__ scene, RlSceneLayout lay, RlPathState* __restrict__ states, RlRayHit* __restrict__ hits,
@@ -134,45 +84,23 @@ __global__ __launch_bounds__(RL_TRACE_BLOCK, RL_TRACE_WPS) __attribute__((amdgpu
 #ifdef RL_STATS
     unsigned long long st[RL_ST_COUNT] = {};
 #endif
-    const uint32_t n_list = __builtin_amdgcn_readfirstlane(((const RlPathListQueue*)queue)->job.n_list); // (used up before the loop)
-    const uint32_t n_chunks = (uint32_t)(((uint64_t)n_list + 63u) / 64u);
-    const uint32_t slice = (uint64_t)n_list >= (uint64_t)gridDim.x * (RL_TRACE_BLOCK * 16ull) ? (uint32_t)(RL_CHUNK / 64ull) : 1u;
-    uint32_t chunk_next = 0, chunk_left = 0; // wave-uniform: this wave's slice of the counter
+    RlChunkCursor chunks(__builtin_amdgcn_readfirstlane(((const RlPathListQueue*)queue)->job.n_list)); // (n_list: used up before the loop)
+    const RlPathListConsts consts = {queue};
     RL_T0(t_total);
     for (;;) {
         RL_T0(t_refill);
-        if (chunk_left == 0) {
-            unsigned long long taken = 0;
-            if (lane == 0) taken = atomicAdd(queue, (unsigned long long)slice);
-            chunk_next = __builtin_amdgcn_readfirstlane((uint32_t)taken);
-            chunk_left = slice;
-        }
-        const uint32_t c = chunk_next;
-        if (c >= n_chunks) break;
-        chunk_next += 1;
-        chunk_left -= 1;
-        const uint32_t k = c * 64u + lane; // the list position
-        uint32_t i = k;
-        bool listed;
-        {
-            const RlPathList* job = &((const RlPathListQueue*)rl_opaque(queue))->job;
-            listed = k < job->n_list;
-            if (const uint32_t* entries = job->list) {
-                if (listed) i = entries[k];
-            }
-            listed = listed && i < job->n_states;
-        }
-        if (!listed) i = 0u; // (no address is formed from an entry that was not checked)
+        uint32_t c;
+        if (!chunks.next(queue, lane, &c)) break;
+        const RlPathList* job = consts.job();
+        const RlListed at = rl_listed_index(job, c * 64u + lane);
         RL_T1(RL_ST_T_REFILL, t_refill);
-        const bool survives = rl_list_step_chunk<STAGE, CYL>(staged, lay, ws, lane, states, hits, i, listed, queue RL_TACC_ARG);
+        const bool survives = rl_step_chunk<STAGE, CYL>(staged, lay, ws, lane, states, hits, at.i, at.listed, consts RL_TACC_ARG);
         RL_T0(t_pack);
-        if (uint32_t* out = ((const RlPathListQueue*)rl_opaque(queue))->job.survivors) {
-            uint32_t done = chunk_next; // the chunk again, from the counter's copy: `c` itself would be one more register held across the scan
-            asm volatile("" : "+s"(done));
-            done -= 1u;
+        if (uint32_t* out = consts.job()->survivors) {
+            const uint32_t done = chunks.last(); // (`c` itself would be one more register held across the scan)
             const uint64_t m = __builtin_amdgcn_ballot_w64(survives);
-            if (survives) out[done * 64u + rl_mbcnt(m)] = i;
-            if (lane == 0) (out - n_chunks)[done] = (uint32_t)__popcll(m);
+            if (survives) out[done * 64u + rl_mbcnt(m)] = at.i;
+            if (lane == 0) (out - chunks.n_chunks)[done] = (uint32_t)__popcll(m);
         }
         RL_T1(RL_ST_T_TAIL, t_pack); // (the diagnostic build: the scan's tail-flush timer is free in this kernel)
         rl_wave_sync(); // (the next chunk's scan rewrites the wave's scratch)

@@ -39,6 +39,40 @@ __device__ __forceinline__ T* rl_opaque(T* p) {
     return p;
 }
 
+// How the step, list-step and light kernels hand out their work: chunks of 64 records (or list positions) from one counter
+// (`queue`, zero at launch), every wave taking a slice of them per atomic.  The counter is in chunks.  Large calls (16 records or
+// more per lane of the grid) take RL_CHUNK / 64 chunks per atomic, as the path kernel takes its ray indices: one atomic per chunk,
+// all on one address, cost more than the chunk's scan; small calls take one, so that every wave gets work.
+// Everything here is wave-uniform.
+struct RlChunkCursor {
+    uint32_t n_chunks;   // ceil(n / 64): chunk c is records c * 64 .. c * 64 + 63, and c * 64 + lane stays under 2^32
+    uint32_t slice;      // chunks per atomic
+    uint32_t first, left; // this wave's slice of the counter: `left` chunks from `first`
+    __device__ __forceinline__ explicit RlChunkCursor(uint32_t n)
+        : n_chunks((uint32_t)(((uint64_t)n + 63u) / 64u)),
+          slice((uint64_t)n >= (uint64_t)gridDim.x * (RL_TRACE_BLOCK * 16ull) ? (uint32_t)(RL_CHUNK / 64ull) : 1u), first(0), left(0) {}
+    // This wave's next chunk in *c; false when the call's chunks are used up (the counter only grows).
+    __device__ __forceinline__ bool next(unsigned long long* queue, uint32_t lane, uint32_t* c) {
+        if (left == 0) {
+            unsigned long long taken = 0;
+            if (lane == 0) taken = atomicAdd(queue, (unsigned long long)slice);
+            first = __builtin_amdgcn_readfirstlane((uint32_t)taken); // (the counter stays below n_chunks + slice x waves of the grid)
+            left = slice;
+        }
+        *c = first;
+        first += 1;
+        left -= 1;
+        return *c < n_chunks; // (past the end the cursor's state no longer matters: the caller leaves its loop)
+    }
+    // The chunk next() gave last, again, from the cursor's own copy: for use behind a scan, where the caller's `c` would be one
+    // more register held across it.
+    __device__ __forceinline__ uint32_t last() const {
+        uint32_t done = first;
+        asm volatile("" : "+s"(done));
+        return done - 1u;
+    }
+};
+
 __device__ __forceinline__ RlPathResult rl_path_result(float value, uint32_t segments, uint32_t object, uint32_t end) {
     RlPathResult out;
     out.value = value;
