@@ -350,6 +350,24 @@ def splat_violations(got, want, k, s, exact):
     return np.argwhere(bad), (float((d - bound)[bad].max()) if bad.any() else 0.0)
 
 
+def splat_leave_one_out(w, h, photons):
+    """For every photon, whether the film `splat` returns with that photon alone taken out would still pass: (by splat_violations
+    against the k, S and exact of the whole list, by np.allclose(rtol=2e-5, atol=1e-6 max) alone), two bool arrays (n,).
+    Vectorised: a photon changes only the components its four terms land on, so the film without it is, on each of those, the
+    float32 nearest to (image - the photon's terms on that pixel), and every other component is the image's own, which passes."""
+    idx, terms = splat_terms(w, h, photons)
+    img, k, s, exact = splat(w, h, photons)
+    t64 = terms.astype(np.float64)
+    same = idx[:, :, None] == idx[:, None, :]                           # (n, 4, 4): the slots of one photon that share a pixel
+    removed = (same[:, :, :, None] * t64[:, None, :, :]).sum(axis=2)    # (n, 4, 3): what the photon put on each slot's pixel
+    at = img[idx]                                                       # (n, 4, 3)
+    without = (at.astype(np.float64) - removed).astype(np.float32)
+    d = np.abs(without.astype(np.float64) - exact[idx])
+    bad = np.where(k[idx] <= 2, without.view(np.uint32) != at.view(np.uint32), ~(d <= splat_bound(k[idx], s[idx])))
+    scale = float(np.abs(img).max()) if img.size else 0.0
+    far = ~(np.abs(without.astype(np.float64) - at) <= 1e-6 * scale + 2e-5 * np.abs(at.astype(np.float64)))
+    return ~bad.any(axis=(1, 2)), ~far.any(axis=(1, 2))
+
 # ---- comparison -------------------------------------------------------------------------------------------------------
 
 def same_bits(got, want):

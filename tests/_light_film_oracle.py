@@ -1,7 +1,7 @@
 """What rl_plot_unit_light_paths puts on the film and into `sampled`, restated in numpy as a pure function of the states, the
 samples rl_scene_light_paths wrote for them, the scene's sampleable emitters, the camera samples and the `sampled` bytes the call
 was given (include/robigo_luculenta.h: the vertex splat, the ending splat and its drop rule, the byte protocol).  The GPU tests
-plot the photons this returns with rl_plot_unit_plot_photons and compare films."""
+plot the photons this returns with the CPU oracle, and with rl_plot_unit_plot_photons beside it, and compare films."""
 import numpy as np
 
 SKIPPED, VISIBLE = 0, 3
@@ -44,10 +44,17 @@ def kept_values(states, samples, emitters, sampled, list=None, n_list=None, drop
 def film_photons(states, samples, emitters, camera, sampled, list=None, n_list=None):
     """(photons, new_sampled): the photons rl_plot_unit_plot_photons is to plot for the film of one rl_plot_unit_light_paths call,
     in state order.  A state whose x or y is not finite is left out, as that call leaves it out."""
+    ph, _, new_sampled = film_photon_rows(states, samples, emitters, camera, sampled, list, n_list)
+    return ph, new_sampled
+
+
+def film_photon_rows(states, samples, emitters, camera, sampled, list=None, n_list=None):
+    """film_photons with, between the two, the state each photon comes from (a state gives at most one: a vertex splat where
+    its sample is visible, an ending splat otherwise)."""
     value, new_sampled = kept_values(states, samples, emitters, sampled, list, n_list)
     with np.errstate(invalid="ignore"):
         on = (value != 0) & np.isfinite(camera["x"][:len(states)]) & np.isfinite(camera["y"][:len(states)])
     ph = np.zeros(int(on.sum()), PHOTON_DTYPE)
     ph["x"], ph["y"] = camera["x"][:len(states)][on], camera["y"][:len(states)][on]
     ph["probability"], ph["wavelength"] = value[on], states["wavelength"][on]
-    return ph, new_sampled
+    return ph, np.flatnonzero(on), new_sampled

@@ -1,7 +1,10 @@
 """PlotUnit.light_paths* and PlotUnit.render_samples_direct* on the device (rl_plot_unit_light_paths*,
 rl_plot_unit_render_samples_direct*): the sample records against rl_scene_light_paths' byte for byte on all six variants; the film
-against rl_plot_unit_plot_photons of the photons the numpy statement of the rule (tests/_light_film_oracle.py) builds from those
-samples, by the film tests' bar for atomic summation order, and the `sampled` bytes exactly; the drop rule's corners on a scene
+against the CPU oracle's plot of the photons the numpy statement of the rule (tests/_light_film_oracle.py) builds from those
+samples, by the film tests' bar (tests/test_gpu_film.py::assert_film: the tolerance and the per-pixel bound, the oracle's bits where a
+component has at most two terms, which on the camera's own 320x180 film is nearly all of them -- tests/test_light_film_abi.py
+measures what that catches), with rl_plot_unit_plot_photons' film of the same photons beside it, and the `sampled` bytes exactly;
+the drop rule's corners on a scene
 built for them; a hostile list into guarded buffers; every variant on poisoned LDS; the direct render against the loop of public
 calls and rl_scene_render_rays; and the estimator's mean against the paths' own.  A GPU fault ends the run: nothing here provokes
 one."""
@@ -9,10 +12,14 @@ import numpy as np
 import pytest
 
 import _guarded as G
+import _image_cases as IC
 import _lds_poison as LP
 from _light_cases import _lit_scene, _prefilled
 import _light_film_oracle as FO
+import _oracle as O
 import _query_rays as QR
+from _boundary import _ocam
+from test_gpu_film import assert_film
 from test_gpu_path_list import _Words, _slice_crossing_size
 from test_gpu_step import _Device, _scene, assert_same
 from test_light_abi import assert_means_agree, closed_scene
@@ -24,8 +31,10 @@ import robigo_luculenta_amd as R  # a missing HIP library is a failure, never a 
 FETCHES = (R.FETCH_LDS, R.FETCH_GLOBAL)
 SCENES = ["demo", "many-prisms", "demo-2500", "tables-prisms", "random-6000"]   # whole scene / tables / third level, with and without CYL
 SAMPLE = R.LIGHT_SAMPLE_DTYPE
-FILMS = ((16, 9), (64, 36))
-W, H = 320, 180      # the camera the paths are drawn for; the films are smaller, which a plot unit is free to be
+W, H = 320, 180      # the camera the paths are drawn for
+# 16x9 and 64x36 are the contention cases for the atomics (a plot unit is free to be smaller than the camera's film); on the camera's
+# own film almost every component collects one or two terms, and the device must then give the oracle's bits
+FILMS = ((16, 9), (64, 36), (W, H))
 
 
 def _stepped(scene, n, seed, stream, first, steps):
@@ -50,18 +59,28 @@ def _plot_of(w, h, photons):
     return plot.tristimulus_buffer
 
 
-def assert_film_close(got, want, what):
-    """The film tests' bar for a different order of the float atomics."""
-    scale = float(np.abs(want).max())
-    print("%s: max |got - want| %.3e, image max %.3e" % (what, float(np.abs(got - want).max()), scale))
-    assert np.allclose(got, want, rtol=2e-5, atol=1e-6 * scale), what
+def assert_light_film(got, w, h, photons, what, beside=None):
+    """The film tests' bar (tests/test_gpu_film.py::assert_film): `got` against the CPU oracle's plot of `photons`, which the numpy
+    restatement reproduces bit for bit, by np.allclose(rtol=2e-5, atol=1e-6 max) AND the per-pixel bound against the exact sum,
+    the oracle's bits where a component has at most two terms.  `beside` is a film of the same photons made on the device by
+    other calls (rl_plot_unit_plot_photons, the loop of public calls), itself held to that bar where it is made: a second
+    comparison, by the tolerance for a different order of the float atomics."""
+    want = assert_film(got, w, h, photons, what)
+    if beside is not None:
+        scale = float(np.abs(beside).max())
+        print("%s: max |got - device film| %.3e, image max %.3e" % (what, float(np.abs(got - beside).max()), scale))
+        assert np.allclose(got, beside, rtol=2e-5, atol=1e-6 * scale), what
+    return want
 
 
 def _expected(scene, st, hits, camera, sampled, seed, stream, w, h, lst=None, n_list=None):
-    """(film, sampled bytes, samples) the call must produce on a cleared film: the composition of today's public calls."""
+    """(rl_plot_unit_plot_photons' film of the photons, sampled bytes, samples, photons) the call must produce on a cleared film:
+    the composition of today's public calls."""
     samples = scene.light_paths(st, hits, seed, stream, list=lst, n_list=n_list, samples=_prefilled(len(st)))
     photons, after = FO.film_photons(st, samples, scene.emitters(), camera, sampled, lst, n_list)
-    return _plot_of(w, h, photons), after, samples, photons
+    film = _plot_of(w, h, photons)
+    assert_film(film, w, h, photons, "plot_photons of the composition's %d photons" % len(photons))
+    return film, after, samples, photons
 
 
 def _call_device(scene, w, h, st, hits, camera, sampled, seed, stream, lst=None, n_list=None, fetch=R.FETCH_LDS, want_samples=True):
@@ -105,36 +124,59 @@ def test_samples_are_light_paths_in_every_byte_on_all_six_variants():
 
 # ---- 2. the film against the composition -------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("name", SCENES)
-def test_film_and_bytes_are_the_composition_after_one_two_and_three_steps(name):
-    scene = R.Scene(*_lit_scene(name))
-    n, seed, stream, first = 4097, 7, 1, 1 << 34
+def _composition(name, film_of_steps):
+    """The film, the bytes and the samples of every form of the call against the composition, after one, two and three steps onto
+    the film film_of_steps names."""
+    objs, cam = _lit_scene(name)
+    scene = R.Scene(objs, cam)
+    n, seed, stream, first = 4097, 7, 1, 1 << 34      # (tests/test_light_film_abi.py: FILM_PATHS)
     rng = np.random.default_rng(n)
     for steps in (1, 2, 3):
         camera, st, hits = _stepped(scene, n, seed, stream, first, steps)
         sampled = _some_bytes(n, rng)
-        w, h = FILMS[steps % 2]
+        w, h = film_of_steps(steps)
         film, after, samples, photons = _expected(scene, st, hits, camera, sampled, seed, stream, w, h)
         if name == "demo":      # on the composition alone: both kinds of splat and the drop are present
             ending = (st["end"] == R.RL_PATH_END_EMITTER) & (st["value"] != 0)
             dropped = ending & (sampled != 0) & np.isin(st["object"], scene.emitters())
             assert (samples["status"] == R.RL_LIGHT_VISIBLE).sum() > 50 and dropped.sum() > 10 and (ending & ~dropped).sum() > 10
+        if name == "demo" and steps == 1:
+            # the film positions and wavelengths the CPU test of the bound measured its shares on are these
+            drawn, _ = O.Scene(objs.view(O.OBJECT_DTYPE), _ocam(cam)).render(W, H, seed, stream, first, n, threads=16)
+            assert all(camera[a].tobytes() == drawn[a].tobytes() for a in "xy") and camera["ray"]["wavelength"].tobytes() == drawn["wavelength"].tobytes()
+        if (w, h) == (W, H):
+            k = IC.splat(w, h, photons)[1]
+            few = float((k[k > 0] <= 2).mean()) if len(photons) else 1.0      # (random-6000 lights nothing after one step)
+            print("%s steps %d: %d photons, %.1f %% of the non-empty components have k <= 2" % (name, steps, len(photons), 100 * few))
+            assert (name != "demo" or len(photons) > 1000) and few > 0.9
         for fetch in FETCHES:
             what = "%s steps %d fetch %d" % (name, steps, fetch)
             got, got_bytes, got_samples, _ = _call_device(scene, w, h, st, hits, camera, sampled, seed, stream, fetch=fetch)
-            assert_film_close(got, film, what)
+            assert_light_film(got, w, h, photons, what, film)
             assert got_bytes.tobytes() == after.tobytes(), what
             assert_same(got_samples, samples, what)
         # the host form, without a sample buffer, and with sampled = NULL
         plot = R.PlotUnit(0, w, h)
         mine = sampled.copy()
         assert plot.light_paths(scene, st, hits, camera, seed, stream, sampled=mine) is None
-        assert_film_close(plot.tristimulus_buffer, film, name + ": host form")
+        assert_light_film(plot.tristimulus_buffer, w, h, photons, "%s steps %d: host form" % (name, steps), film)
         assert mine.tobytes() == after.tobytes()
-        film0, none, _, _ = _expected(scene, st, hits, camera, None, seed, stream, w, h)
+        film0, none, _, photons0 = _expected(scene, st, hits, camera, None, seed, stream, w, h)
         got, got_bytes, _, _ = _call_device(scene, w, h, st, hits, camera, None, seed, stream, want_samples=False)
-        assert none is None and got_bytes is None
-        assert_film_close(got, film0, name + ": sampled = NULL")
+        assert none is None and got_bytes is None and len(photons0) >= len(photons)
+        assert_light_film(got, w, h, photons0, "%s steps %d: sampled = NULL" % (name, steps), film0)
+
+
+@pytest.mark.parametrize("name", SCENES)
+def test_film_and_bytes_are_the_composition_after_one_two_and_three_steps(name):
+    _composition(name, lambda steps: FILMS[steps % 2])
+
+
+@pytest.mark.parametrize("name", SCENES)
+def test_film_and_bytes_are_the_composition_on_the_cameras_own_film(name):
+    """320x180: about 1.1 to 1.8 thousand photons (demo) on 57,600 pixels, so almost every component the call writes collects one
+    or two terms and is held to the oracle's bits: one splat lost, doubled, misplaced or carrying the wrong field cannot hide."""
+    _composition(name, lambda steps: FILMS[2])
 
 
 @pytest.fixture(scope="module")
@@ -161,10 +203,10 @@ def test_list_sizes_identity_and_permuted(demo_paths, n):
         cases = [(st[:n], hits[:n], camera[:n], None), (st, hits, camera, rng.permutation(len(st))[:n].astype(np.uint32))]
     for s, ht, cm, lst in cases:
         sampled = _some_bytes(len(s), rng)
-        film, after, samples, _ = _expected(scene, s, ht, cm, sampled, seed, stream, w, h, lst)
+        film, after, samples, photons = _expected(scene, s, ht, cm, sampled, seed, stream, w, h, lst)
         got, got_bytes, got_samples, _ = _call_device(scene, w, h, s, ht, cm, sampled, seed, stream, lst)
         what = "n %s %s" % (n, "identity" if lst is None else "listed")
-        assert_film_close(got, film, what)
+        assert_light_film(got, w, h, photons, what, film)
         assert got_bytes.tobytes() == after.tobytes(), what
         assert_same(got_samples, samples, what)
 
@@ -182,7 +224,7 @@ def test_every_splat_on_one_pixel_and_positions_that_are_not_finite(demo_paths):
         film, after, samples, photons = _expected(scene, st, hits, cm, sampled, seed, stream, 16, 9)
         assert len(photons) > 100
         got, got_bytes, got_samples, _ = _call_device(scene, 16, 9, st, hits, cm, sampled, seed, stream)
-        assert_film_close(got, film, what)
+        assert_light_film(got, 16, 9, photons, what, film)
         assert np.isfinite(got).all() and got_bytes.tobytes() == after.tobytes()
         assert_same(got_samples, samples, what)      # a state that is not splatted is sampled all the same
     assert (np.count_nonzero(_expected(scene, st, hits, one, None, seed, stream, 16, 9)[0].any(axis=1))) <= 4
@@ -229,8 +271,12 @@ def test_the_drop_rules_corners():
         return camera, scene.begin_paths(rays, 100), np.zeros(n, R.HIT_DTYPE)
 
     def film_of(camera, st, hits, rows, sampled):
+        """The call's pixel sum; the whole film and the bytes it leaves are first held to the composition."""
+        _, after, _, photons = _expected(scene, st, hits, camera, sampled, seed, stream, w, h, rows)
         plot = R.PlotUnit(0, w, h)
         plot.light_paths(scene, st, hits, camera, seed, stream, list=rows, sampled=sampled)
+        assert_light_film(plot.tristimulus_buffer, w, h, photons, "corners: %d photons" % len(photons))
+        assert sampled is None or sampled.tobytes() == after.tobytes()
         return _pixel_sum(plot.tristimulus_buffer, w, h, camera["x"][0], camera["y"][0])
 
     # from above onto the floor beside the light (a diffuse vertex, which is sampled), then wherever the bounce goes
@@ -283,7 +329,7 @@ def test_hostile_list_into_guarded_prefilled_buffers():
     sampled = _some_bytes(n, rng)
     sampled[left_out] = G.FILL
     guard = lambda **kw: G.Guarded(QR.DeviceBuffer, **kw)
-    film, after, samples, _ = _expected(scene, st, hits, camera, sampled, seed, stream, w, h, once)
+    film, after, samples, photons = _expected(scene, st, hits, camera, sampled, seed, stream, w, h, once)
     for fetch in FETCHES:
         for lst, exact in ((once, True), (twice, False)):
             what = "fetch %d %s" % (fetch, "distinct" if exact else "with duplicates")
@@ -302,7 +348,7 @@ def test_hostile_list_into_guarded_prefilled_buffers():
             if exact:
                 G.assert_written_as(got, samples, what)
                 assert got_bytes.tobytes() == after.tobytes(), what
-                assert_film_close(got_film, film, what)
+                assert_light_film(got_film, w, h, photons, what, film)
             else:   # a state named twice: memory-safe, its own records unspecified; every other state's are as before
                 rest = np.ones(n, bool)
                 rest[listed[:100]] = False
@@ -339,7 +385,7 @@ def test_every_variant_on_poisoned_lds(pattern):
         n, seed, stream, first, w, h = 65, 5, 2, 12345, 16, 9
         camera, st, hits = _stepped(scene, n, seed, stream, first, 2)
         sampled = _some_bytes(n, np.random.default_rng(pattern & 0xff))
-        film, after, samples, _ = _expected(scene, st, hits, camera, sampled, seed, stream, w, h)
+        film, after, samples, photons = _expected(scene, st, hits, camera, sampled, seed, stream, w, h)
         for fetch in FETCHES:
             what = "%s pattern 0x%08X fetch %d" % (name, pattern, fetch)
             plot = R.PlotUnit(0, w, h)
@@ -354,7 +400,7 @@ def test_every_variant_on_poisoned_lds(pattern):
             ran.add(v)
             assert_same(mb.get(), samples, what)
             assert yb.get().tobytes() == after.tobytes(), what
-            assert_film_close(plot.tristimulus_buffer, film, what)
+            assert_light_film(plot.tristimulus_buffer, w, h, photons, what, film)
     assert ran == set(range(6)), sorted(ran)
 
 
@@ -362,22 +408,28 @@ def test_every_variant_on_poisoned_lds(pattern):
 
 def _loop_of_public_calls(scene, plot, camera, seed, stream, first, max_segments, fetch=R.FETCH_LDS):
     """The film of rl_plot_unit_render_samples_direct as its contract states it, from begin_paths, step_path_list and
-    PlotUnit.light_paths; returns the final states."""
+    PlotUnit.light_paths; returns the final states and the photons of that film in call order: per segment, the rule's photons
+    (tests/_light_film_oracle.py) for the states, the `sampled` bytes and rl_scene_light_paths' samples the segment's call had."""
     n = len(camera)
     st = scene.begin_paths(np.ascontiguousarray(camera["ray"]), first)
     hits, sampled = np.zeros(n, R.HIT_DTYPE), np.zeros(n, np.uint8)
     lst, n_list = None, n
+    photons = [np.zeros(0, FO.PHOTON_DTYPE)]
     for _ in range(max_segments or R.RL_PATH_MAX_SEGMENTS):
         if n_list == 0:
             break
         live = scene.step_path_list(st, seed, stream, list=lst, n_list=n_list, fetch=fetch, hits=hits)
+        samples = scene.light_paths(st, hits, seed, stream, list=lst, n_list=n_list, samples=_prefilled(n))
+        of_segment, after = FO.film_photons(st, samples, scene.emitters(), camera, sampled, lst, n_list)
         plot.light_paths(scene, st, hits, camera, seed, stream, list=lst, n_list=n_list, fetch=fetch, sampled=sampled)
+        assert sampled.tobytes() == after.tobytes()
+        photons.append(of_segment)
         lst, n_list = live, len(live)
-    return st
+    return st, np.concatenate(photons)
 
 
 @pytest.mark.parametrize("n,max_segments,film", [(1, 0, (64, 36)), (65, 0, (64, 36)), (65, 1, (16, 9)), (65, 2, (64, 36)), (4097, 3, (64, 36)),
-                                                 ((1 << 20) + 65, 2, (16, 9))])
+                                                 ((1 << 20) + 65, 2, (16, 9)), (4097, 3, (W, H))])
 def test_direct_render_is_render_rays_and_the_loop_of_public_calls(n, max_segments, film):
     scene = R.Scene(*_scene("demo"))
     seed, stream, first = 4, 2, 1 << 33
@@ -387,15 +439,19 @@ def test_direct_render_is_render_rays_and_the_loop_of_public_calls(n, max_segmen
     want = scene.render_spectral_rays(np.ascontiguousarray(camera["ray"]), seed, stream, first, max_segments=max_segments)
     assert n < 65 or ((want["end"] == R.RL_PATH_END_INVALID).any() and (max_segments == 0) != (want["end"] == R.RL_PATH_END_LIMIT).any())
     loop = R.PlotUnit(0, w, h)
-    _loop_of_public_calls(scene, loop, camera, seed, stream, first, max_segments)
+    _, photons = _loop_of_public_calls(scene, loop, camera, seed, stream, first, max_segments)
     film_want = loop.tristimulus_buffer
     assert n < 65 or film_want.any()
+    assert_light_film(film_want, w, h, photons, "the loop of public calls: film")
+    if film == (W, H):
+        k = IC.splat(w, h, photons)[1]
+        assert len(photons) > 1000 and (k[k > 0] <= 2).mean() > 0.9
     plot = R.PlotUnit(0, w, h)
     before = R.light_film_launches()
     got = plot.render_samples_direct(scene, camera, seed, stream, first, max_segments=max_segments)
     assert sum(R.light_film_launches()) > sum(before)
     assert_same(got, want, "host form: results")
-    assert_film_close(plot.tristimulus_buffer, film_want, "host form: film")
+    assert_light_film(plot.tristimulus_buffer, w, h, photons, "host form: film", film_want)
     # the device form under the other fetch mode, results poisoned first
     res = np.zeros(n, R.PATH_RESULT_DTYPE)
     res["end"] = 12345
@@ -406,11 +462,11 @@ def test_direct_render_is_render_rays_and_the_loop_of_public_calls(n, max_segmen
     plot.render_samples_direct_device(scene, cb, seed, stream, first, fetch=R.FETCH_GLOBAL, max_segments=max_segments, results=rb)
     rb.download(res)
     assert_same(res, want, "device form: results")
-    assert_film_close(plot.tristimulus_buffer, film_want, "device form: film")
+    assert_light_film(plot.tristimulus_buffer, w, h, photons, "device form: film", film_want)
     if n == 65:      # without results only the film is written
         plot = R.PlotUnit(0, w, h)
         assert plot.render_samples_direct(scene, camera, seed, stream, first, max_segments=max_segments, results=False) is None
-        assert_film_close(plot.tristimulus_buffer, film_want, "no results: film")
+        assert_light_film(plot.tristimulus_buffer, w, h, photons, "no results: film", film_want)
 
 
 # ---- 7. it is the right estimator --------------------------------------------------------------------------------------------
@@ -442,6 +498,7 @@ def test_direct_light_with_the_drop_rule_estimates_what_the_paths_find(occluder)
     plot = R.PlotUnit(0, 16, 9)
     D, twice = np.zeros(n), np.zeros(n)
     lst, n_list = None, n
+    splats = []
     while n_list:
         live = scene.step_path_list(st, seed, stream, list=lst, n_list=n_list, hits=hits)
         before = sampled.copy()
@@ -449,6 +506,7 @@ def test_direct_light_with_the_drop_rule_estimates_what_the_paths_find(occluder)
         kept, after = FO.kept_values(st, samples, emitters, before, lst, n_list)
         assert after.tobytes() == sampled.tobytes()
         D += kept
+        splats.append(FO.film_photons(st, samples, emitters, camera, before, lst, n_list)[0])
         twice += FO.kept_values(st, samples, emitters, before, lst, n_list, drop=False)[0]
         lst, n_list = live, len(live)
     assert (D != twice).any()
@@ -458,7 +516,10 @@ def test_direct_light_with_the_drop_rule_estimates_what_the_paths_find(occluder)
     se = np.sqrt(a.var(ddof=1) / n + b.var(ddof=1) / n)
     print("%s: every ending kept: mean %.6g against %.6g, %.2f standard errors apart" % (what, a.mean(), b.mean(), abs(a.mean() - b.mean()) / se))
     assert abs(a.mean() - b.mean()) > 5 * se, what + ": counting twice is not told apart from the rule"
-    # the film holds the same light: its Y total against the photons of D
+    # the film holds the same light: it is the plot of every round's splats, which carry D between them; beside it, as before,
+    # rl_plot_unit_plot_photons' film of one photon of value D per path
+    splats = np.concatenate(splats)
+    assert np.isclose(splats["probability"].sum(dtype=np.float64), D.sum(), rtol=1e-12, atol=0)
     photons = np.zeros(n, FO.PHOTON_DTYPE)
     photons["x"], photons["y"], photons["probability"], photons["wavelength"] = camera["x"], camera["y"], D, st["wavelength"]
-    assert_film_close(plot.tristimulus_buffer, _plot_of(16, 9, photons[D != 0]), what + ": film")
+    assert_light_film(plot.tristimulus_buffer, 16, 9, splats, what + ": film", _plot_of(16, 9, photons[D != 0]))

@@ -10,7 +10,11 @@ import pytest
 
 import robigo_luculenta_amd as R
 from robigo_luculenta_amd import _lib
+import _image_cases as IC
 import _light_film_oracle as FO
+import _light_oracle as LO
+import _oracle as O
+import _step_oracle as S
 from _boundary import _err
 from _device_build import device_build
 
@@ -124,6 +128,109 @@ def test_the_oracle_states_the_drop_rule_and_the_byte_protocol():
     # drop=False: the estimator that counts twice
     value, _ = FO.kept_values(st, sm, em, before, drop=False)
     assert value.tolist() == [0.5, 2.0, 3.0, 4.0, 0, 0]
+
+
+FILM_PATHS = dict(n=4097, seed=7, stream=1, first=1 << 34)     # the composition test's paths (tests/test_gpu_light_film.py)
+CAMERA_FILM = (320, 180)
+TEETH_FILMS = ((16, 9), (64, 36), CAMERA_FILM)
+
+
+def _oracle_camera_samples(objs, cam, n, seed, stream, first):
+    """rl_scene_camera_rays on the CPU: the first ray of each path from the host compile of the kernel's path header
+    (mirror_dump_rays), the wavelength and the film position from the oracle's render of the same paths, which records them
+    with every photon (trace_unit.rs:151-168)."""
+    import _mirror as M
+    ms = M.Scene(objs, cam)
+    dump = M.lib().mirror_dump_rays
+    dump.restype = C.c_uint64
+    dump.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64]
+    rays6 = np.zeros((n, 6), np.float32)
+    for i in range(n):
+        assert dump(ms.h, CAMERA_FILM[0], CAMERA_FILM[1], seed, stream, first + i, 1, rays6[i].ctypes.data, 1) == 1
+    drawn, _ = O.Scene(objs, cam).render(CAMERA_FILM[0], CAMERA_FILM[1], seed, stream, first, n, threads=16)
+    camera = np.zeros(n, R.CAMERA_SAMPLE_DTYPE)
+    camera["ray"]["origin"], camera["ray"]["direction"], camera["ray"]["wavelength"] = rays6[:, :3], rays6[:, 3:], drawn["wavelength"]
+    camera["x"], camera["y"] = drawn["x"], drawn["y"]
+    return camera
+
+
+@pytest.fixture(scope="module")
+def oracle_light_photons():
+    """{steps: (photons, is a vertex splat, the sample's weight)} of the demo scene's FILM_PATHS after one, two and three
+    segments, `sampled` all zero, on the oracles alone: _step_oracle, _light_oracle, _light_film_oracle."""
+    objs, cam = O.demo_scene_desc()
+    n, seed, stream, first = (FILM_PATHS[k] for k in ("n", "seed", "stream", "first"))
+    camera = _oracle_camera_samples(objs, cam, n, seed, stream, first)
+    stepper, occluder = S.StepOracle(objs, cam), LO.Occluder(objs, cam)
+    states, hits = S.begin(camera["ray"], first), np.zeros(n, S.HIT_DTYPE)
+    hits["object"] = S.NONE
+    out = {}
+    for steps in (1, 2, 3):
+        stepper.step(states, seed, stream, hits=hits)
+        samples = LO.light_paths(occluder, states, hits, seed, stream)
+        photons, rows, _ = FO.film_photon_rows(states, samples, LO.emitters(objs), camera, np.zeros(n, np.uint8))
+        out[steps] = (photons, samples["status"][rows] == LO.VISIBLE, samples["weight"][rows])
+    return out
+
+
+def test_the_per_pixel_bound_sees_one_lost_splat_where_allclose_did_not(oracle_light_photons):
+    """The share of photons that could be lost ONE AT A TIME without the film assertion noticing, and four mutants of the list.
+    No GPU: the photons rl_plot_unit_light_paths is to plot for the demo scene's 4097 paths (seed 7, stream 1, first 2^34: the
+    GPU composition test's) after one, two and three segments, from the step, light and film oracles; the film positions and
+    wavelengths are the camera's own, from the oracle's render of the same paths.
+
+    A photon is undetectable when the float32 film of IC.splat with that photon's terms taken out has no violation:
+      * new rule (tests/test_gpu_film.py::assert_film): IC.splat_violations against the k, S and exact of the whole list;
+      * old rule: np.allclose(rtol=2e-5, atol=1e-6 image max) alone.
+    Measured, undetectable photons (new rule; old rule):
+      steps 1, 1133 photons: 16x9  53 (4.7 %); 193 (17.0 %)   64x36  15 (1.3 %); 131 (11.6 %)   320x180 1 (0.1 %); 116 (10.2 %)
+      steps 2, 1441 photons: 16x9 353 (24.5 %); 619 (43.0 %)   64x36 142 (9.9 %); 515 (35.7 %)   320x180 2 (0.1 %); 486 (33.7 %)
+      steps 3, 1788 photons: 16x9 524 (29.3 %); 879 (49.2 %)   64x36 209 (11.7 %); 734 (41.1 %)  320x180 3 (0.2 %); 696 (38.9 %)
+    and 99.8 % of the 320x180 film's non-empty components collect at most two terms.
+    Asserted: at most 2 % under the new rule on 320x180 -- a condition on these inputs, which the GPU test then uses -- and at
+    least 15 % under the old rule on 16x9 after two steps, which is why the light films are held to the per-pixel bound.
+
+    The mutants, each plotted by the oracle and held to the unmutated list's k, S and exact on 320x180: the dimmest vertex photon
+    dropped, doubled, and carrying the sample's `weight` for its `value`; and the same photon one pixel further in x."""
+    w, h = CAMERA_FILM
+    for steps, (photons, vertex, weight) in oracle_light_photons.items():
+        assert len(photons) > 1000 and vertex.sum() > 50 and (~vertex).sum() > 50
+        share = {}
+        for film in TEETH_FILMS:
+            new, old = IC.splat_leave_one_out(film[0], film[1], photons)
+            share[film] = (new.mean(), old.mean())
+            print("steps %d, %d photons, %dx%d: undetectable one at a time: per-pixel bound %d (%.1f %%), allclose alone %d (%.1f %%)"
+                  % (steps, len(photons), film[0], film[1], new.sum(), 100 * new.mean(), old.sum(), 100 * old.mean()))
+        assert share[CAMERA_FILM][0] <= 0.02, (steps, share)
+        if steps == 2:
+            assert share[(16, 9)][1] >= 0.15, share
+
+        want = O.plot(w, h, photons)
+        img, k, s, exact = IC.splat(w, h, photons)
+        assert IC.same_bits(img, want) and not len(IC.splat_violations(want, want, k, s, exact)[0])
+        print("steps %d: %.1f %% of the film's non-empty components have k <= 2" % (steps, 100 * (k[k > 0] <= 2).mean()))
+        assert (k[k > 0] <= 2).mean() > 0.9
+        dim = np.flatnonzero(vertex & (photons["probability"] != weight))
+        dim = dim[np.argmin(np.abs(photons["probability"][dim]))]
+        assert photons["probability"][dim] != 0
+        one = photons[dim:dim + 1]
+        as_weight, moved = one.copy(), one.copy()
+        as_weight["probability"] = weight[dim]
+        step = np.float32(2.0 / (w - 1))
+        moved["x"] = one["x"] + (step if one["x"][0] + step <= 1 else -step)
+        rest = np.delete(photons, dim)
+        mutants = {"dropped": rest, "doubled": np.concatenate([photons, one]), "weight for value": np.concatenate([rest, as_weight]),
+                   "one pixel off in x": np.concatenate([rest, moved])}
+        old_passes = 0
+        for what, mutant in mutants.items():
+            got = O.plot(w, h, mutant)
+            bad, excess = IC.splat_violations(got, want, k, s, exact)
+            passes_allclose = bool(np.allclose(got, want, rtol=2e-5, atol=1e-6 * np.abs(want).max()))
+            old_passes += passes_allclose
+            print("steps %d, photon of value %.3e %s: %d per-pixel violations; allclose alone %s"
+                  % (steps, photons["probability"][dim], what, len(bad), "passes" if passes_allclose else "fails"))
+            assert len(bad), (steps, what)
+        assert old_passes == len(mutants), old_passes      # (what the tolerance alone let through)
 
 
 @pytest.fixture(scope="module")
