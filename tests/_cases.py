@@ -1,0 +1,241 @@
+"""Cases for the tests of the ray, path, light and film calls, and the answers they are held to: ray sets and t_max cases with the
+CPU oracle's hits and what follows from them by definition; wavelengths; camera rays with holes and the states and hits after a
+few segments; states at one vertex of _scenes.closed_scene with the direction the path itself takes next; photons no renderer
+makes.  Nothing is built at import."""
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+import robigo_luculenta_amd as R
+import _oracle as O
+import _query_rays as QR
+
+NONE = R.RL_OBJECT_NONE
+W, H = 320, 180      # the film the camera rays of _rays are drawn for
+KNOTS = [370.0, 374.99, 375.0, 377.5, 379.99, 380.0, 385.0, 555.0, 560.0, 775.0, 780.0, 782.5, 784.99, 785.0, 790.0, 1000.0, 0.0, -5.0]
+
+
+# ---- rays, t_max and the oracle's answers ---------------------------------------------------------------------------------------
+
+def _ray_records(o, d, t_max=np.inf):
+    """RAY_DTYPE records of origins, directions and a t_max (one for all, or one per ray)."""
+    rays = np.zeros(len(o), dtype=R.RAY_DTYPE)
+    rays["origin"], rays["direction"], rays["t_max"] = o, d, t_max
+    return rays
+
+
+def oracle_hits(oscene, origins, directions, t_max=None):
+    """HIT_DTYPE records of the oracle's Scene::intersect for every ray (per-ray calls on a thread pool: ctypes releases the
+    GIL), restricted to distance < t_max when t_max is given."""
+    o = np.ascontiguousarray(origins, dtype=np.float32)
+    d = np.ascontiguousarray(directions, dtype=np.float32)
+    n = len(o)
+    out10 = np.zeros((n, 10), dtype=np.float32)
+    idx = np.zeros(n, dtype=np.int64)
+    fn, h = O.lib().oracle_scene_intersect, oscene.h
+    po, pd, pv = o.ctypes.data, d.ctypes.data, out10.ctypes.data
+
+    def work(lo, hi):
+        for i in range(lo, hi):
+            idx[i] = fn(h, po + 12 * i, pd + 12 * i, pv + 40 * i)
+
+    step = max(1, (n + 63) // 64)
+    with ThreadPoolExecutor(16) as pool:
+        list(pool.map(lambda lo: work(lo, min(n, lo + step)), range(0, n, step)))
+    hits = np.zeros(n, dtype=R.HIT_DTYPE)
+    hit = idx >= 0
+    if t_max is not None:
+        hit &= out10[:, 9] < np.broadcast_to(np.asarray(t_max, np.float32), (n,))
+    hits["object"] = np.where(hit, idx, NONE).astype(np.uint32)
+    hits["position"][hit], hits["normal"][hit], hits["tangent"][hit] = out10[hit, 0:3], out10[hit, 3:6], out10[hit, 6:9]
+    hits["distance"][hit] = out10[hit, 9]
+    return hits
+
+
+def t_max_cases(want, rng):
+    """Per ray: +inf, random in (0, 2 distance), exactly the distance (a miss), nextafter(distance, inf) (a hit), 0, -1, NaN."""
+    n = len(want)
+    dist = np.where(want["object"] != NONE, want["distance"], np.float32(50.0)).astype(np.float32)
+    case = np.arange(n) % 7
+    t = np.full(n, np.inf, dtype=np.float32)
+    t[case == 1] = (dist * rng.uniform(0, 2, n).astype(np.float32))[case == 1]
+    t[case == 2] = dist[case == 2]
+    t[case == 3] = np.nextafter(dist, np.float32(np.inf))[case == 3]
+    t[case == 4], t[case == 5], t[case == 6] = 0.0, -1.0, np.nan
+    return t
+
+
+def ray_sets(scene, objs, cam, rng, n):
+    """{kind: (origins, directions)}: camera-like, bounce-like (from the camera rays' hits), uniform origins within 4x the scene's
+    bounding radius, non-unit directions (|d| in [0.25, 4]), rays tangent to spheres and degenerate rays."""
+    sets = {}
+    o, d = QR.camera_rays(cam, 1920, 1080, rng, n)
+    sets["camera"] = (o, d)
+    sets["bounce"] = QR.bounce_rays(o, d, scene.intersect(o, d), rng)
+    centres = np.concatenate([objs["v0"][objs["surface_kind"] == 0], objs["v1"][objs["surface_kind"] != 0]])
+    finite = np.isfinite(centres).all(axis=1) & (np.abs(centres).max(axis=1) < 1e4)
+    radius = float(np.linalg.norm(centres[finite], axis=1).max()) if finite.any() else 10.0
+    u = QR.uniform_directions(rng, n)
+    sets["uniform"] = ((u * (4.0 * radius * rng.random((n, 1)) ** (1 / 3))).astype(np.float32), QR.uniform_directions(rng, n))
+    o2 = (rng.normal(0, radius, (n, 3))).astype(np.float32)
+    sets["non_unit"] = (o2, (QR.uniform_directions(rng, n) * rng.uniform(0.25, 4.0, (n, 1))).astype(np.float32))
+    sph = objs[(objs["surface_kind"] == 0) & np.isfinite(objs["f"][:, 0]) & (objs["f"][:, 0] > 0)]
+    if len(sph):
+        k = rng.integers(0, len(sph), n // 4)
+        c, r = sph["v0"][k].astype(np.float64), sph["f"][k, 0].astype(np.float64)
+        a = QR.uniform_directions(rng, len(k)).astype(np.float64)
+        b = np.cross(a, QR.uniform_directions(rng, len(k)))
+        b /= np.linalg.norm(b, axis=1, keepdims=True)
+        # the line origin + s a passes at distance r from the centre: tangent (up to rounding, which either grazes or misses)
+        sets["tangent"] = ((c + r[:, None] * b - 3.0 * r[:, None] * a).astype(np.float32), a.astype(np.float32))
+    bad = np.array([np.nan, np.inf, -np.inf, 0.0], np.float32)
+    dg_o = np.repeat(o[:1], 48, axis=0).copy()
+    dg_d = np.repeat(d[:1], 48, axis=0).copy()
+    for j in range(48):
+        comp, val = j % 3, bad[(j // 3) % 4]
+        if j < 12:
+            dg_d[j] = 0.0                       # zero direction
+        elif j < 30:
+            dg_d[j, comp] = val                 # NaN / inf in the direction
+        else:
+            dg_o[j, comp] = val                 # ... in the origin
+    sets["degenerate"] = (dg_o, dg_d)
+    return sets
+
+
+def _filter(want, t_max):
+    out = want.copy()
+    miss = (want["object"] == NONE) | ~(want["distance"] < t_max)
+    out[miss] = np.zeros(1, dtype=R.HIT_DTYPE)
+    out["object"][miss] = NONE
+    return out
+
+
+def blocked(want, t_max):
+    """The definition: uint8 (the oracle's object != NONE) & (its distance < t_max) -- false for a NaN, zero or negative t_max."""
+    with np.errstate(invalid="ignore"):
+        return ((want["object"] != NONE) & (want["distance"] < np.broadcast_to(np.asarray(t_max, np.float32), (len(want),)))).astype(np.uint8)
+
+
+def _wavelengths(rng, n):
+    """Uniform in [380, 780] nm, with finite ones outside that range and non-finite ones mixed in."""
+    wl = rng.uniform(380.0, 780.0, n).astype(np.float32)
+    odd = np.array([200.0, 379.99, 780.01, 1000.0, 2500.0, 50.0, np.nan, np.inf, -np.inf, -500.0], np.float32)
+    k = rng.choice(n, min(n, n // 8), replace=False)
+    wl[k] = odd[np.arange(len(k)) % len(odd)]
+    return wl
+
+
+# ---- paths ------------------------------------------------------------------------------------------------------------------------
+
+def _rays(scene, n, seed, stream, first, holes=True):
+    rays = np.ascontiguousarray(scene.camera_rays(W, H, seed, stream, first, n)["ray"])
+    if holes:
+        bad = np.arange(n) % 11 == 3
+        rays["wavelength"][bad] = np.array([np.nan, np.inf, -np.inf], np.float32)[np.arange(int(bad.sum())) % 3]
+    return rays
+
+
+def _step_with_hits(scene, rays, seed, stream, first, steps):
+    st = scene.begin_paths(rays, first)
+    hits = np.zeros(len(st), R.HIT_DTYPE)
+    hits["object"] = R.RL_OBJECT_NONE
+    for _ in range(steps):
+        scene.step_paths(st, seed, stream, hits=hits)
+    return st, hits
+
+
+def _stepped(scene, n, seed, stream, first, steps):
+    """(states, hits) of n camera paths, some with wavelengths that are not finite (_rays), after `steps` segments with hits; the
+    hits of states that ended earlier stay as written."""
+    return _step_with_hits(scene, _rays(scene, n, seed, stream, first), seed, stream, first, steps)
+
+
+def _stepped_camera(scene, n, seed, stream, first, steps):
+    """(camera samples, states, hits) of n camera paths, every one of them valid, after `steps` segments with hits."""
+    camera = scene.camera_rays(W, H, seed, stream, first, n)
+    return (camera,) + _step_with_hits(scene, np.ascontiguousarray(camera["ray"]), seed, stream, first, steps)
+
+
+def _results(states):
+    """{value, segments, object, end} of final states as RlPathResult records."""
+    res = np.zeros(len(states), dtype=R.PATH_RESULT_DTYPE)
+    for f in res.dtype.names:
+        res[f] = states[f]
+    return res
+
+
+def vertex_states(n, first=0):
+    """n states at one vertex: the floor's origin, reached by a segment from above, about to leave in the direction the NEXT bounce
+    draws (the estimator does not read it but for its side), intensity 0.7 (the floor's reflectance), distinct path indices."""
+    st = np.zeros(n, R.PATH_STATE_DTYPE)
+    st["origin"], st["direction"] = (0, 0, 1e-5), (0, 0, 1)
+    st["wavelength"], st["intensity"], st["continue_chance"] = 550.0, 0.7, 0.96
+    st["segments"], st["end"], st["object"] = 1, R.RL_PATH_LIVE, R.RL_OBJECT_NONE
+    st["path_index"] = first + np.arange(n, dtype=np.uint64)
+    ht = np.zeros(n, R.HIT_DTYPE)
+    ht["normal"], ht["distance"], ht["object"] = (0, 0, 1), 1.0, 0
+    return st, ht
+
+
+def bounce_directions(st, seed, stream):
+    """The cosine-weighted direction the reference's diffuse bounce draws at the vertex for each state's path, from block
+    2 + segments (monte_carlo.rs:47-58 on a z-up normal: no rotation): what the path itself does next."""
+    n = len(st)
+    w = np.zeros((n, 4), np.uint32)
+    paths = np.ascontiguousarray(st["path_index"], dtype=np.uint64)
+    blocks = (st["segments"] + 2).astype(np.uint32)
+    O.lib().oracle_rng_blocks(seed, stream, O.ptr(paths), O.ptr(blocks), O.ptr(w), n)
+    phi = (w[:, 0] >> 8).astype(np.float64) * 2.0 ** -24 * 2 * np.pi
+    rq = (w[:, 1] >> 8).astype(np.float64) * 2.0 ** -24 * (16777216.0 / 16777215.0)
+    r = np.sqrt(rq)
+    return np.stack([np.cos(phi) * r, np.sin(phi) * r, np.sqrt(1 - rq)], axis=1).astype(np.float32)
+
+
+# ---- photons ----------------------------------------------------------------------------------------------------------------------
+
+def _photons(x, y, probability, wavelength):
+    ph = np.zeros(len(x), dtype=O.PHOTON_DTYPE)
+    ph["x"], ph["y"], ph["probability"], ph["wavelength"] = x, y, probability, wavelength
+    return ph
+
+
+def _photons_of(samples, results):
+    """The photons a renderer would have recorded for these samples: (x, y, value, wavelength)."""
+    return _photons(samples["x"], samples["y"], results["value"], samples["ray"]["wavelength"])
+
+
+def synthetic_photons(w, h, seed, n=20000):
+    """x, y beyond the screen on every side and exactly on its borders, wavelengths around both ends of the CIE table and on its
+    knots, zero and negative probabilities, and many photons on one pixel.
+    Beyond the screen means by up to two pixels, not further: a photon c pixels beyond a border is clamped onto the border pixel
+    with the weights (1 - c) and c of its two columns (plot_unit.rs:64-77), terms of opposite sign and |c| times the photon's size
+    that land on the SAME pixel.  Any order of f32 adds is then off by about c 2^-24 of the photon's size per term, so for photons
+    far outside, or a fixed share of a wide image outside, no summation order -- the oracle's included -- lies within rtol = 2e-5
+    of another.  Within two pixels the terms are at most 3 times the photon, and the comparison with the oracle's order holds."""
+    rng = np.random.default_rng([seed, w, h])
+    aspect = np.float32(w) / np.float32(h)
+    x = rng.uniform(-1.0, 1.0, n).astype(np.float32)
+    y = (rng.uniform(-1.0, 1.0, n) / aspect).astype(np.float32)
+    out = rng.choice(n, n // 4, replace=False)
+    side = np.where(rng.random(len(out)) < 0.5, -1.0, 1.0)
+    bx, by = out[: len(out) // 2], out[len(out) // 2:]   # (a quarter of each also lies beyond the other axis: the corners)
+    x[bx] = (side[: len(bx)] * (1.0 + rng.random(len(bx)) * 4.0 / max(w - 1, 1))).astype(np.float32)
+    y[by] = (side[len(bx):] * (1.0 + rng.random(len(by)) * 4.0 / max(h - 1, 1))).astype(np.float32) / aspect
+    corner = by[: len(by) // 4]
+    x[corner] = (np.where(rng.random(len(corner)) < 0.5, -1.0, 1.0) * (1.0 + rng.random(len(corner)) * 4.0 / max(w - 1, 1))).astype(np.float32)
+    edge = rng.choice(n, n // 10, replace=False)
+    x[edge[0::4]], x[edge[1::4]] = -1.0, 1.0
+    y[edge[2::4]], y[edge[3::4]] = np.float32(-1.0) / aspect, np.float32(1.0) / aspect
+    wl = rng.uniform(360.0, 800.0, n).astype(np.float32)
+    k = rng.choice(n, n // 8, replace=False)
+    wl[k] = np.array(KNOTS, np.float32)[np.arange(len(k)) % len(KNOTS)]
+    pr = rng.uniform(0.0, 1.0, n).astype(np.float32)
+    z = rng.choice(n, n // 5, replace=False)
+    pr[z[0::2]] = 0.0
+    pr[z[1::2]] *= -1.0
+    pile = rng.choice(n, n // 5, replace=False)   # a large k on one pixel (and its neighbours)
+    x[pile], y[pile] = np.float32(0.2137), np.float32(-0.1) / aspect
+    pr[pile] = rng.uniform(0.5, 1.0, len(pile)).astype(np.float32)
+    wl[pile] = rng.uniform(400.0, 700.0, len(pile)).astype(np.float32)
+    return _photons(x, y, pr, wl)

@@ -1,5 +1,6 @@
 """The device-only compile of rl_api.hip with the library's own flags (hipcc cross-compiles without a GPU), made once per pytest
-process and shared by the tests that read the kernels' resources or instructions: one compile takes about two minutes."""
+process and shared by the tests that read the kernels' resources or instructions: one compile takes about two minutes.  The
+*_abi.py modules import the fixture `kernels` and variant_of_name by name."""
 import os
 import re
 import shutil
@@ -50,3 +51,14 @@ def device_build():
             metadata[m.group(1)]["dynamic_stack"] = int(bool(re.search(r"^\s+\.uses_dynamic_stack:\s+true", entry, re.M)))
     _build = (text, metadata, remarks)
     return _build
+
+
+@pytest.fixture(scope="module")
+def kernels():
+    """Metadata of every kernel from the device-only -S compile with the library's own flags."""
+    return device_build()[1]
+
+
+def variant_of_name(name, kernel):
+    """(stage, cyl), each a one-digit string, of the instantiation kernel<stage, cyl> that the mangled `name` is."""
+    return re.search(kernel + r"ILi([012])ELb([01])E", name).groups()

@@ -1,4 +1,4 @@
-"""Ray sets for Scene.intersect (tests/test_gpu_query.py, tools/query_bench.py): camera-like rays through a jittered pixel grid
+"""Ray sets for Scene.intersect (tests/_cases.py, tools/query_bench.py): camera-like rays through a jittered pixel grid
 and bounce-like rays that leave the camera rays' hits in uniform directions.  Host arithmetic (numpy), and DeviceBuffer for the device path."""
 import ctypes as C
 

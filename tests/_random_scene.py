@@ -1,6 +1,7 @@
 """Random scenes for the parity tests: arbitrary mixes of every surface and material kind, including
 overlapping / nested / huge spheres and randomly oriented prisms, so the conservative culls (sphere
-clusters, prism bounds) are exercised far away from the demo scene's regular layout."""
+clusters, prism bounds) are exercised far away from the demo scene's regular layout; and sphere sets a cull table cannot do anything
+sensible with (degenerate_spheres).  numpy and the oracle alone: the tests that run without the HIP library use them too."""
 import numpy as np
 
 import _oracle as O
@@ -59,3 +60,30 @@ def random_scene(seed, n_spheres=120, n_prisms=6, n_planes=2, n_circles=2, n_par
             objs[i]["material_kind"], objs[i]["m"] = 0, (rng.uniform(4000, 8000), 0.5, 0.0)
     cam = O.demo_scene_desc()[1]
     return objs, cam
+
+
+DEGENERATE_LAYOUTS = ("same", "line", "zero_radius", "huge_spread", "infinite")
+
+
+def degenerate_spheres(proto, layout, n, rng):
+    """n copies of the sphere record `proto` (one record) laid out at random, then as `layout` says: all at one point, on a line, of
+    radius zero, spread over seven decades, one of infinite radius, or left as drawn ("random").  Draws from `rng` and advances
+    it: a caller that makes several sizes from one generator gets other spheres than one that starts a generator per size."""
+    if layout not in DEGENERATE_LAYOUTS + ("random",):
+        raise KeyError(layout)
+    o = np.repeat(proto, n)
+    o["v0"] = rng.normal(0, 8, (n, 3)).astype(np.float32)
+    o["v0"][:, 1] = np.abs(o["v0"][:, 1])
+    o["f"][:, 0] = rng.uniform(0.1, 1.0, n).astype(np.float32)
+    if layout == "same":
+        o["v0"] = np.array([1.0, 2.0, 3.0], np.float32)
+    elif layout == "line":
+        o["v0"] = np.stack([np.linspace(-20, 20, n), np.ones(n), np.ones(n)], 1).astype(np.float32)
+    elif layout == "zero_radius":
+        o["f"][:, 0] = 0.0
+    elif layout == "huge_spread":
+        o["v0"] = (rng.normal(0, 1, (n, 3)) * np.exp(rng.uniform(-5, 12, (n, 1)))).astype(np.float32)
+        o["f"][:, 0] = np.exp(rng.uniform(-8, 3, n)).astype(np.float32)
+    elif layout == "infinite":
+        o["f"][0, 0] = np.inf
+    return o

@@ -5,7 +5,7 @@ the emitter queue and the camera stash that this launch has not necessarily writ
 slots.  In a fresh process the LDS is zero or holds a benign earlier kernel's data, so a read of an unwritten slot passes by luck.
 Here every CU's LDS is filled with a pattern (tests/_lds_poison.py) IMMEDIATELY before each launch under test -- all ones, the
 quiet NaN, a plausible index -- and the results must still equal the family's own reference, bit for bit (the atomically summed
-film within exactly the tolerances of tests/test_gpu_film.py): all 24 instantiations of the trace kernel and every variant of the
+film within exactly the tolerances of tests/test_gpu_film.py, tests/_compare.py: assert_film): all 24 instantiations of the trace kernel and every variant of the
 query, occlusion, path, film and step kernels in both fetch modes, on few rays (partial rounds everywhere), with a tail wave
 (4,033 rays) and with lanes that have no work inside full waves (t_max 0 / negative / NaN, non-finite wavelengths, states that are
 not live).  A control test first proves that the pattern IS what the next kernel finds; without it the rest would prove nothing.
@@ -23,6 +23,7 @@ import zlib
 import numpy as np
 import pytest
 
+import _boundary as B
 import _guarded as G
 import _lds_poison as LP
 import _occlusion_cases as OC
@@ -31,11 +32,11 @@ import _path_oracle as P
 import _query_rays as QR
 import _random_scene as RS
 import _step_oracle as S
-from test_gpu_film import _photons_of, _upload, assert_film, synthetic_photons
-from test_gpu_occlusion import assert_same_bytes, blocked
-from test_gpu_path_query import _wavelengths, assert_consistent
-from test_gpu_query import _filter, _ocam, _scene, assert_same, oracle_hits, ray_sets, t_max_cases
-from test_gpu_step import _poison_hits, _results
+from _boundary import _ocam
+from _cases import _filter, _photons_of, _results, _wavelengths, blocked, oracle_hits, ray_sets, synthetic_photons, t_max_cases
+from _compare import assert_consistent, assert_film, assert_same, assert_same_bytes
+from _device_arrays import _poison_hits, _upload
+from _scenes import _scene
 
 pytestmark = pytest.mark.gpu
 
@@ -57,12 +58,6 @@ _wall = {"start": None}
 
 def _pid(p):
     return "0x%08X" % p
-
-
-def _one_variant(counters, before):
-    ran = [a - b for a, b in zip(counters(), before)]
-    assert sum(1 for r in ran if r) == 1, ran
-    return next(i for i, r in enumerate(ran) if r)
 
 
 def _check_variant(v, cyl, fetch, what):
@@ -247,7 +242,7 @@ def test_trace_kernel_every_instantiation_on_poisoned_lds(name, pattern):
                         t.sync()
                     assert_film(p.tristimulus_buffer, W, H, want, what)
                 assert t.stats()[:2] == (TRACE_N, segs), (what, t.stats()[:2], segs)
-                v = _one_variant(R.variant_launches, before)
+                v = B._variant_of(R.variant_launches, before)
                 low = (4 if fused else 0) | (2 if open_launch else 0) | cyl
                 if name == "random-6000":                # a third level: never the whole scene; the tables where they fit
                     assert v in (low, 16 | low) and (fetch == R.FETCH_LDS or v == low), (what, v)
@@ -269,7 +264,7 @@ def test_query_on_poisoned_lds_and_in_another_order(name, pattern):
             before = R.query_launches()
             LP.poison_lds(pattern)
             got = c.scene.intersect(c.o, c.d, t, fetch=fetch)
-            v = _one_variant(R.query_launches, before)
+            v = B._variant_of(R.query_launches, before)
             _check_variant(v, c.cyl, fetch, what)
             _ran["query"].add(v)
             assert_same(got, want, what)
@@ -288,7 +283,7 @@ def test_occlusion_on_poisoned_lds_and_in_another_order(name, pattern):
             before = R.occlusion_launches()
             LP.poison_lds(pattern)
             got = c.scene.occluded(c.o, c.d, t, fetch=fetch)
-            v = _one_variant(R.occlusion_launches, before)
+            v = B._variant_of(R.occlusion_launches, before)
             _check_variant(v, c.cyl, fetch, what)
             _ran["occlusion"].add(v)
             assert_same_bytes(got, want, what)
@@ -320,7 +315,7 @@ def test_paths_on_poisoned_lds(name, pattern):
         before = R.path_launches()
         LP.poison_lds(pattern)
         res = c.scene.render_spectral_rays(cam_rays, c.cam_seed, c.cam_stream, c.cam_first, fetch=fetch)
-        v = _one_variant(R.path_launches, before)
+        v = B._variant_of(R.path_launches, before)
         _check_variant(v, c.cyl, fetch, what)
         _ran["path"].add(v)
         assert res["value"].tobytes() == c.cam_want["probability"].tobytes(), what
@@ -378,7 +373,7 @@ def test_film_on_poisoned_lds(name, pattern):
             before = R.film_launches()
             LP.poison_lds(pattern)
             res = p.render_samples(c.scene, samples, c.seed, c.stream, c.first, fetch=fetch, results=results)
-            v = _one_variant(R.film_launches, before)
+            v = B._variant_of(R.film_launches, before)
             assert v % 2 == c.cyl and (fetch == R.FETCH_LDS or v // 2 == 0), (what, v)
             _ran["film"].add(v)
             if results:
@@ -421,7 +416,7 @@ def test_step_on_poisoned_lds_and_in_another_order(name, pattern):
             before = R.step_launches()
             LP.poison_lds(pattern)
             c.scene.step_paths(st, c.seed, c.stream, fetch=fetch, hits=hits)
-            v = _one_variant(R.step_launches, before)
+            v = B._variant_of(R.step_launches, before)
             _check_variant(v, c.cyl, fetch, what)
             _ran["step"].add(v)
             assert_same(st, want, "%s step %d: states" % (what, k))

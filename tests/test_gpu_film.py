@@ -15,7 +15,10 @@ import _oracle as O
 import _path_oracle as P
 import _query_rays as QR
 from _boundary import _ocam
-from test_gpu_query import _scene
+from _cases import _photons_of, synthetic_photons
+from _compare import assert_film
+from _device_arrays import _upload
+from _scenes import _scene
 
 pytestmark = pytest.mark.gpu
 
@@ -26,41 +29,6 @@ W, H = 320, 180
 # the least share of paths that must carry a value (tests/test_gpu_path_query.py: IDENTITY_SCENES)
 IDENTITY_SCENES = {"demo": 0.05, "glass": 0.05, "random-seed-1": 0.3, "demo-2500": 0.05}
 BATCH_SIZES = [0, 1, 63, 64, 65, (1 << 20) + 4097]
-
-
-def _photons(x, y, probability, wavelength):
-    ph = np.zeros(len(x), dtype=O.PHOTON_DTYPE)
-    ph["x"], ph["y"], ph["probability"], ph["wavelength"] = x, y, probability, wavelength
-    return ph
-
-
-def _photons_of(samples, results):
-    """The photons a renderer would have recorded for these samples: (x, y, value, wavelength)."""
-    return _photons(samples["x"], samples["y"], results["value"], samples["ray"]["wavelength"])
-
-
-def assert_film(got, w, h, photons, what=""):
-    """`got` is the plot of `photons` onto a cleared buffer, by the project's tolerance."""
-    want = O.plot(w, h, photons)
-    scale = np.abs(want).max()
-    img, k, s, exact = IC.splat(w, h, photons)
-    assert IC.same_bits(img, want), (what, IC.first_difference(img, want))   # the restatement is the oracle's plot
-    bad, excess = IC.splat_violations(got, want, k, s, exact)
-    print("%s: max |got - want| %.3e (image max %.3e), per-pixel violations %d, worst excess %.3e"
-          % (what, float(np.abs(got - want).max()) if got.size else 0.0, scale, len(bad), excess))
-    assert np.allclose(got, want, rtol=2e-5, atol=1e-6 * scale), what
-    assert not len(bad), (what, bad[:8], excess)
-    return want
-
-
-def _variant_of(before):
-    return B._variant_of(R.film_launches, before)
-
-
-def _upload(a):
-    b = QR.DeviceBuffer(a.nbytes)
-    b.upload(np.ascontiguousarray(a))
-    return b
 
 
 def _render_samples_device(plot, scene, samples, seed, stream, first, fetch=R.FETCH_LDS, max_segments=0, results=True):
@@ -106,45 +74,6 @@ def test_plot_of_the_renderers_own_photons(demo):
 # ---- 2. photons no renderer makes -------------------------------------------------------------------------------------------
 
 FILM_SHAPES = [s for s in IC.SMALL_SHAPES if min(s) >= 2] + [(1, 17), (17, 1), (1, 4097), (4097, 1), (1919, 1079)]
-KNOTS = [370.0, 374.99, 375.0, 377.5, 379.99, 380.0, 385.0, 555.0, 560.0, 775.0, 780.0, 782.5, 784.99, 785.0, 790.0, 1000.0, 0.0, -5.0]
-
-
-def synthetic_photons(w, h, seed, n=20000):
-    """x, y beyond the screen on every side and exactly on its borders, wavelengths around both ends of the CIE table and on its
-    knots, zero and negative probabilities, and many photons on one pixel.
-    Beyond the screen means by up to two pixels, not further: a photon c pixels beyond a border is clamped onto the border pixel
-    with the weights (1 - c) and c of its two columns (plot_unit.rs:64-77), terms of opposite sign and |c| times the photon's size
-    that land on the SAME pixel.  Any order of f32 adds is then off by about c 2^-24 of the photon's size per term, so for photons
-    far outside, or a fixed share of a wide image outside, no summation order -- the oracle's included -- lies within rtol = 2e-5
-    of another.  Within two pixels the terms are at most 3 times the photon, and the comparison with the oracle's order holds."""
-    rng = np.random.default_rng([seed, w, h])
-    aspect = np.float32(w) / np.float32(h)
-    x = rng.uniform(-1.0, 1.0, n).astype(np.float32)
-    y = (rng.uniform(-1.0, 1.0, n) / aspect).astype(np.float32)
-    out = rng.choice(n, n // 4, replace=False)
-    side = np.where(rng.random(len(out)) < 0.5, -1.0, 1.0)
-    bx, by = out[: len(out) // 2], out[len(out) // 2:]   # (a quarter of each also lies beyond the other axis: the corners)
-    x[bx] = (side[: len(bx)] * (1.0 + rng.random(len(bx)) * 4.0 / max(w - 1, 1))).astype(np.float32)
-    y[by] = (side[len(bx):] * (1.0 + rng.random(len(by)) * 4.0 / max(h - 1, 1))).astype(np.float32) / aspect
-    corner = by[: len(by) // 4]
-    x[corner] = (np.where(rng.random(len(corner)) < 0.5, -1.0, 1.0) * (1.0 + rng.random(len(corner)) * 4.0 / max(w - 1, 1))).astype(np.float32)
-    edge = rng.choice(n, n // 10, replace=False)
-    x[edge[0::4]], x[edge[1::4]] = -1.0, 1.0
-    y[edge[2::4]], y[edge[3::4]] = np.float32(-1.0) / aspect, np.float32(1.0) / aspect
-    wl = rng.uniform(360.0, 800.0, n).astype(np.float32)
-    k = rng.choice(n, n // 8, replace=False)
-    wl[k] = np.array(KNOTS, np.float32)[np.arange(len(k)) % len(KNOTS)]
-    pr = rng.uniform(0.0, 1.0, n).astype(np.float32)
-    z = rng.choice(n, n // 5, replace=False)
-    pr[z[0::2]] = 0.0
-    pr[z[1::2]] *= -1.0
-    pile = rng.choice(n, n // 5, replace=False)   # a large k on one pixel (and its neighbours)
-    x[pile], y[pile] = np.float32(0.2137), np.float32(-0.1) / aspect
-    pr[pile] = rng.uniform(0.5, 1.0, len(pile)).astype(np.float32)
-    wl[pile] = rng.uniform(400.0, 700.0, len(pile)).astype(np.float32)
-    return _photons(x, y, pr, wl)
-
-
 @pytest.mark.parametrize("shape", FILM_SHAPES, ids=IC.shape_id)
 def test_photons_no_renderer_makes(shape):
     w, h = shape
@@ -202,7 +131,7 @@ def test_camera_samples_rendered_onto_a_film_reproduce_the_renderer(name):
         p = R.PlotUnit(0, W, H)
         before = R.film_launches()
         res = p.render_samples(scene, samples, seed, stream, first, fetch=fetch)
-        v = _variant_of(before)
+        v = B._variant_of(R.film_launches, before)
         assert v % 2 == cyl and (fetch == R.FETCH_LDS or v // 2 == 0) and (fetch != R.FETCH_LDS or v // 2 == (1 if big else 2)), (name, fetch, v)
         assert res.tobytes() == rays.tobytes(), (name, fetch)
         assert res["value"].tobytes() == want_photons["probability"].tobytes() and int(res["segments"].sum(dtype=np.uint64)) == segs
@@ -210,7 +139,7 @@ def test_camera_samples_rendered_onto_a_film_reproduce_the_renderer(name):
         q = R.PlotUnit(1, W, H)
         before = R.film_launches()
         assert q.render_samples(scene, samples, seed, stream, first, fetch=fetch, results=False) is None
-        assert _variant_of(before) == v
+        assert B._variant_of(R.film_launches, before) == v
         assert_film(q.tristimulus_buffer, W, H, want_photons, "%s fetch %d, no results" % (name, fetch))
 
 
@@ -230,7 +159,7 @@ def test_every_film_variant_ran():
                 p = R.PlotUnit(0, W, H)
                 before = R.film_launches()
                 res = p.render_samples(scene, samples, 1, 0, 0, fetch=fetch, results=results)
-                ran.add(_variant_of(before))
+                ran.add(B._variant_of(R.film_launches, before))
                 assert res is None or res.tobytes() == rays.tobytes(), (name, fetch)
                 assert_film(p.tristimulus_buffer, W, H, _photons_of(samples, rays), "%s fetch %d" % (name, fetch))
     assert ran == set(range(6)), sorted(ran)

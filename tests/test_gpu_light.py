@@ -10,13 +10,13 @@ import pytest
 
 import _guarded as G
 import _lds_poison as LP
-from _light_cases import _lit_scene, _prefilled
 import _light_oracle as LO
 import _oracle as O
 import _query_rays as QR
-from test_gpu_path_list import _Words, _rays, _slice_crossing_size
-from test_gpu_step import _Device, _scene, assert_same
-from test_light_abi import assert_means_agree, closed_scene, vertex_states
+from _cases import _rays, _stepped, bounce_directions, vertex_states
+from _compare import assert_means_agree, assert_same
+from _device_arrays import _Device, _Words, _prefilled, _slice_crossing_size
+from _scenes import _lit_scene, _scene, closed_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -26,16 +26,6 @@ FETCHES = (R.FETCH_LDS, R.FETCH_GLOBAL)
 SCENES = ["demo", "many-prisms", "demo-2500", "tables-prisms", "random-6000"]   # whole scene / tables / third level, with and without CYL
 FILL32 = 0xAAAAAAAA
 SAMPLE = R.LIGHT_SAMPLE_DTYPE
-
-
-def _stepped(scene, n, seed, stream, first, steps):
-    """(states, hits) of n camera paths after `steps` segments with hits; the hits of states that ended earlier stay as written."""
-    st = scene.begin_paths(_rays(scene, n, seed, stream, first), first)
-    hits = np.zeros(n, R.HIT_DTYPE)
-    hits["object"] = R.RL_OBJECT_NONE
-    for _ in range(steps):
-        scene.step_paths(st, seed, stream, hits=hits)
-    return st, hits
 
 
 def _light_device(scene, st, hits, seed, stream, lst=None, n_list=None, fetch=R.FETCH_LDS, samples=None):
@@ -187,9 +177,8 @@ def test_the_mean_of_the_samples_is_the_mean_of_the_paths_own_emitter_hits(occlu
     seen = set(np.unique(light["status"]).tolist())
     assert seen >= ({R.RL_LIGHT_BACKFACING, R.RL_LIGHT_VISIBLE} | ({R.RL_LIGHT_OCCLUDED} if occluder else set())), seen
     # the path's own next segment leaves the vertex in the direction its diffuse bounce draws: the step before this vertex made it
-    import test_light_abi as T
     nxt = st.copy()
-    nxt["direction"] = T.bounce_directions(st, seed, stream)
+    nxt["direction"] = bounce_directions(st, seed, stream)
     nxt["origin"] = (ht["position"] + nxt["direction"] * np.float32(1e-5)).astype(np.float32)
     scene.step_paths(nxt, seed, stream, flags=R.RL_STEP_NO_ROULETTE)
     lights = scene.emitters()

@@ -1,7 +1,7 @@
 """PlotUnit.light_paths* and PlotUnit.render_samples_direct* on the device (rl_plot_unit_light_paths*,
 rl_plot_unit_render_samples_direct*): the sample records against rl_scene_light_paths' byte for byte on all six variants; the film
 against the CPU oracle's plot of the photons the numpy statement of the rule (tests/_light_film_oracle.py) builds from those
-samples, by the film tests' bar (tests/test_gpu_film.py::assert_film: the tolerance and the per-pixel bound, the oracle's bits where a
+samples, by the film tests' bar (tests/_compare.py: assert_film: the tolerance and the per-pixel bound, the oracle's bits where a
 component has at most two terms, which on the camera's own 320x180 film is nearly all of them -- tests/test_light_film_abi.py
 measures what that catches), with rl_plot_unit_plot_photons' film of the same photons beside it, and the `sampled` bytes exactly;
 the drop rule's corners on a scene
@@ -14,15 +14,14 @@ import pytest
 import _guarded as G
 import _image_cases as IC
 import _lds_poison as LP
-from _light_cases import _lit_scene, _prefilled
 import _light_film_oracle as FO
 import _oracle as O
 import _query_rays as QR
 from _boundary import _ocam
-from test_gpu_film import assert_film
-from test_gpu_path_list import _Words, _slice_crossing_size
-from test_gpu_step import _Device, _scene, assert_same
-from test_light_abi import assert_means_agree, closed_scene
+from _cases import _stepped_camera
+from _compare import assert_film, assert_means_agree, assert_same
+from _device_arrays import _Device, _Words, _prefilled, _slice_crossing_size
+from _scenes import _lit_scene, _scene, closed_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -37,17 +36,6 @@ W, H = 320, 180      # the camera the paths are drawn for
 FILMS = ((16, 9), (64, 36), (W, H))
 
 
-def _stepped(scene, n, seed, stream, first, steps):
-    """(camera samples, states, hits) of n camera paths after `steps` segments with hits."""
-    camera = scene.camera_rays(W, H, seed, stream, first, n)
-    st = scene.begin_paths(np.ascontiguousarray(camera["ray"]), first)
-    hits = np.zeros(n, R.HIT_DTYPE)
-    hits["object"] = R.RL_OBJECT_NONE
-    for _ in range(steps):
-        scene.step_paths(st, seed, stream, hits=hits)
-    return camera, st, hits
-
-
 def _some_bytes(n, rng):
     """`sampled` as a caller may hold it: zero, one, and other non-zero values."""
     return rng.choice(np.array([0, 0, 1, 1, 0xAA], np.uint8), n)
@@ -60,7 +48,7 @@ def _plot_of(w, h, photons):
 
 
 def assert_light_film(got, w, h, photons, what, beside=None):
-    """The film tests' bar (tests/test_gpu_film.py::assert_film): `got` against the CPU oracle's plot of `photons`, which the numpy
+    """The film tests' bar (tests/_compare.py: assert_film): `got` against the CPU oracle's plot of `photons`, which the numpy
     restatement reproduces bit for bit, by np.allclose(rtol=2e-5, atol=1e-6 max) AND the per-pixel bound against the exact sum,
     the oracle's bits where a component has at most two terms.  `beside` is a film of the same photons made on the device by
     other calls (rl_plot_unit_plot_photons, the loop of public calls), itself held to that bar where it is made: a second
@@ -109,7 +97,7 @@ def test_samples_are_light_paths_in_every_byte_on_all_six_variants():
         scene = R.Scene(objs, cam)
         cyl = int((objs["surface_kind"] == 4).sum() >= 40)
         n, seed, stream, first = 4097, 7, 1, 1 << 34
-        camera, st, hits = _stepped(scene, n, seed, stream, first, 2)
+        camera, st, hits = _stepped_camera(scene, n, seed, stream, first, 2)
         want = scene.light_paths(st, hits, seed, stream, samples=_prefilled(n))
         for fetch in FETCHES:
             what = "%s fetch %d" % (name, fetch)
@@ -132,7 +120,7 @@ def _composition(name, film_of_steps):
     n, seed, stream, first = 4097, 7, 1, 1 << 34      # (tests/test_light_film_abi.py: FILM_PATHS)
     rng = np.random.default_rng(n)
     for steps in (1, 2, 3):
-        camera, st, hits = _stepped(scene, n, seed, stream, first, steps)
+        camera, st, hits = _stepped_camera(scene, n, seed, stream, first, steps)
         sampled = _some_bytes(n, rng)
         w, h = film_of_steps(steps)
         film, after, samples, photons = _expected(scene, st, hits, camera, sampled, seed, stream, w, h)
@@ -184,7 +172,7 @@ def demo_paths():
     """One reference shared by the size cases: 4033 demo paths after two steps."""
     scene = R.Scene(*_scene("demo"))
     seed, stream, first = 9, 0, 5
-    return (scene, seed, stream) + _stepped(scene, 4033, seed, stream, first, 2)
+    return (scene, seed, stream) + _stepped_camera(scene, 4033, seed, stream, first, 2)
 
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 4033, "slice"])
@@ -319,7 +307,7 @@ def test_hostile_list_into_guarded_prefilled_buffers():
     scene = R.Scene(*_scene("demo"))
     n, seed, stream, first, w, h = 2113, 21, 3, 1 << 35, 16, 9
     rng = np.random.default_rng(n)
-    camera, st, hits = _stepped(scene, n, seed, stream, first, 2)
+    camera, st, hits = _stepped_camera(scene, n, seed, stream, first, 2)
     left_out = np.arange(n) % 3 == 1
     listed = np.flatnonzero(~left_out)
     wild = np.concatenate([[n, n + 1, 0xffffffff, 0x80000000, 0xfffffffe, n + 63, n + 64], rng.integers(n, 1 << 32, 200)]).astype(np.uint32)
@@ -383,7 +371,7 @@ def test_every_variant_on_poisoned_lds(pattern):
         scene = R.Scene(objs, cam)
         cyl = int((objs["surface_kind"] == 4).sum() >= 40)
         n, seed, stream, first, w, h = 65, 5, 2, 12345, 16, 9
-        camera, st, hits = _stepped(scene, n, seed, stream, first, 2)
+        camera, st, hits = _stepped_camera(scene, n, seed, stream, first, 2)
         sampled = _some_bytes(n, np.random.default_rng(pattern & 0xff))
         film, after, samples, photons = _expected(scene, st, hits, camera, sampled, seed, stream, w, h)
         for fetch in FETCHES:

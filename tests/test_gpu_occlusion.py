@@ -1,6 +1,6 @@
 """Scene.occluded on the device (rl_scene_occluded / rl_scene_occluded_device) against its definition: one byte per ray, 1 where
 Scene::intersect reports an object nearer than t_max.  Bit for bit against the CPU oracle over every scene, ray set and t_max case of
-tests/test_gpu_query.py plus shadow rays and short rays (whose bound the kernel's scan starts from), both fetch modes and every
+tests/test_gpu_query.py (tests/_scenes.py, tests/_cases.py) plus shadow rays and short rays (whose bound the kernel's scan starts from), both fetch modes and every
 kernel variant; against rl_scene_intersect_device at scale; batch sizes with guard bytes behind the output; pageable memory refused;
 concurrent callers; a call made while a render is open."""
 import ctypes as C
@@ -14,7 +14,10 @@ import _boundary as B
 import _occlusion_cases as OC
 import _oracle as O
 import _query_rays as QR
-from test_gpu_query import SCENES, _ocam, _scene, oracle_hits, ray_sets, t_max_cases
+from _boundary import _ocam
+from _cases import _ray_records, blocked, oracle_hits, ray_sets, t_max_cases
+from _compare import assert_same_bytes
+from _scenes import SCENES, _scene
 
 pytestmark = pytest.mark.gpu
 
@@ -26,29 +29,11 @@ BOTH_OUTCOMES = ("demo", "demo-2500", "random-6000")   # the shadow and short se
 _ran = set()   # occlusion variants seen by test_scene_occlusion_bit_exact (test_every_occlusion_variant_ran reads it)
 
 
-def blocked(want, t_max):
-    """The definition: uint8 (the oracle's object != NONE) & (its distance < t_max) -- false for a NaN, zero or negative t_max."""
-    with np.errstate(invalid="ignore"):
-        return ((want["object"] != NONE) & (want["distance"] < np.broadcast_to(np.asarray(t_max, np.float32), (len(want),)))).astype(np.uint8)
-
-
-def assert_same_bytes(got, want, what):
-    assert got.dtype == np.uint8 and got.shape == want.shape, (what, got.dtype, got.shape)
-    if got.tobytes() != want.tobytes():
-        rows = np.flatnonzero(got != want)
-        raise AssertionError("%s: %d of %d rays differ, first %d: got %d want %d" % (what, len(rows), len(got), rows[0], got[rows[0]],
-                                                                                       want[rows[0]]))
-
-
 def bounded_sets(objs, cam_o, cam_d, first_hits, rng, oscene=None):
     """{kind: (origins, directions, t_max)}: the shadow and the short set from the camera rays' first hits.  With the CPU oracle's
     scene, a quarter of the shadow rays aim at emitter points the oracle says they see."""
     oracle = None if oscene is None else (lambda o, d: oracle_hits(oscene, o, d))
     return {"shadow": OC.shadow_rays(objs, cam_d, first_hits, rng, oracle), "short": OC.short_rays(cam_d, first_hits, rng)}
-
-
-def _variant_of(before):
-    return B._variant_of(R.occlusion_launches, before)
 
 
 @pytest.mark.parametrize("name", SCENES)
@@ -79,7 +64,7 @@ def test_scene_occlusion_bit_exact(name):
                 before = R.occlusion_launches()
                 got = scene.occluded(o, d, t, fetch=fetch)
                 if len(o):
-                    v = _variant_of(before)
+                    v = B._variant_of(R.occlusion_launches, before)
                     assert v % 2 == cyl and (fetch == R.FETCH_LDS or v // 2 == 0), (name, fetch, v)
                     _ran.add(v)
                 assert_same_bytes(got, answer, "%s %s fetch %d t_max %s" % (name, kind, fetch, "inf" if np.ndim(t) == 0 else "per ray"))
@@ -95,14 +80,8 @@ def test_every_occlusion_variant_ran():
         for fetch in FETCHES:
             before = R.occlusion_launches()
             scene.occluded(o, d, fetch=fetch)
-            _ran.add(_variant_of(before))
+            _ran.add(B._variant_of(R.occlusion_launches, before))
     assert _ran == set(range(6)), sorted(_ran)
-
-
-def _rays(o, d, t_max=np.inf):
-    rays = np.zeros(len(o), dtype=R.RAY_DTYPE)
-    rays["origin"], rays["direction"], rays["t_max"] = o, d, t_max
-    return rays
 
 
 GUARD = 64
@@ -148,14 +127,14 @@ def test_device_against_device_at_scale(name):
     n = 1 << 22
     rng = np.random.default_rng(zlib.crc32(name.encode()) + 1)
     cam_o, cam_d = QR.camera_rays(cam, 1920, 1080, rng, n)
-    first = _device_objects(scene, _rays(cam_o, cam_d), R.FETCH_LDS)
+    first = _device_objects(scene, _ray_records(cam_o, cam_d), R.FETCH_LDS)
     assert (first["object"] != NONE).any()
     sets = {"camera": (cam_o, cam_d, np.float32(np.inf))}
     for kind, (o, d, t) in bounded_sets(objs, cam_o, cam_d, first, rng).items():
         pad = rng.integers(0, len(o), n - len(o))   # (misses dropped: filled up to 2^22 with repeats)
         sets[kind] = (np.concatenate([o, o[pad]]), np.concatenate([d, d[pad]]), np.concatenate([t, t[pad]]))
     for kind, (o, d, t) in sets.items():
-        rays = _rays(o, d, t)
+        rays = _ray_records(o, d, t)
         assert len(rays) == n
         for fetch in FETCHES:
             want = (_device_objects(scene, rays, fetch)["object"] != NONE).astype(np.uint8)
@@ -175,7 +154,7 @@ def test_batch_sizes_host_and_device_forms_agree(demo, n):
     for fetch in FETCHES:
         host = scene.occluded(o, d, t, fetch=fetch)
         assert host.dtype == np.uint8 and len(host) == n
-        dev = _device_occluded(scene, _rays(o, d, t), fetch)
+        dev = _device_occluded(scene, _ray_records(o, d, t), fetch)
         assert_same_bytes(dev, host, "device vs host form, n=%d fetch %d" % (n, fetch))
         pick = rng.choice(n, min(n, 4096), replace=False) if n else np.zeros(0, np.int64)
         assert_same_bytes(host[pick], blocked(oracle_hits(oscene, o[pick], d[pick]), t[pick]), "n=%d fetch %d" % (n, fetch))
@@ -207,7 +186,7 @@ def test_four_threads_query_one_scene_concurrently(demo):
             barrier.wait()
             for rep in range(20):
                 o, d, t = sets[k]
-                got = scene.occluded(o, d, t, fetch=FETCHES[(k + rep) % 2]) if rep % 2 else _device_occluded(scene, _rays(o, d, t), FETCHES[k % 2])
+                got = scene.occluded(o, d, t, fetch=FETCHES[(k + rep) % 2]) if rep % 2 else _device_occluded(scene, _ray_records(o, d, t), FETCHES[k % 2])
                 assert got.tobytes() == wants[k].tobytes(), (k, rep)
         except Exception as e:  # noqa: BLE001 -- reported below
             errors.append(e)

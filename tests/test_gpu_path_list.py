@@ -12,9 +12,11 @@ import pytest
 import _guarded as G
 import _lds_poison as LP
 import _path_list_oracle as L
-import _query_rays as QR
 import _step_oracle as S
-from test_gpu_step import _Device, _begin_device, _poison_hits, _results, _scene, assert_same
+from _cases import _rays, _results
+from _compare import assert_same
+from _device_arrays import _Device, _Words, _begin_device, _poison_hits, _slice_crossing_size
+from _scenes import _scene
 
 pytestmark = pytest.mark.gpu
 
@@ -25,29 +27,6 @@ FETCHES = (R.FETCH_LDS, R.FETCH_GLOBAL)
 W, H = 320, 180
 BUDGET = R.RL_PATH_MAX_SEGMENTS
 FILL32 = 0xAAAAAAAA
-
-
-def _rays(scene, n, seed, stream, first, holes=True):
-    rays = np.ascontiguousarray(scene.camera_rays(W, H, seed, stream, first, n)["ray"])
-    if holes:
-        bad = np.arange(n) % 11 == 3
-        rays["wavelength"][bad] = np.array([np.nan, np.inf, -np.inf], np.float32)[np.arange(int(bad.sum())) % 3]
-    return rays
-
-
-class _Words:
-    """n uint32 in device memory."""
-
-    def __init__(self, a):
-        self.host = np.ascontiguousarray(a, dtype=np.uint32).copy()
-        self.buf = QR.DeviceBuffer(max(self.host.nbytes, 64))
-        if self.host.nbytes:
-            self.buf.upload(self.host)
-
-    def get(self):
-        if self.host.nbytes:
-            self.buf.download(self.host)
-        return self.host
 
 
 def _step(scene, sb, seed, stream, lst, n_list, live, fetch=R.FETCH_LDS, flags=0, hb=None):
@@ -108,12 +87,6 @@ def test_listed_loop_is_render_rays_and_every_step_is_the_oracle(name):
 
 
 # ---- (b) one step against rl_scene_step_paths_device, (g) sizes -------------------------------------------------------------
-
-def _slice_crossing_size():
-    """A list longer than the slice rule's threshold whatever the residency (16 states per lane of a grid of at most two
-    workgroups of 1,024 threads per CU), and not a multiple of 64 or of the slice."""
-    return LP.cu_count() * 2 * 1024 * 16 + 4097
-
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 4033, "slice"])
 def test_identity_list_equals_step_paths_device_in_every_byte(n):

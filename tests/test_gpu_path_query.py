@@ -15,7 +15,9 @@ import _oracle as O
 import _path_oracle as P
 import _query_rays as QR
 from _boundary import _ocam
-from test_gpu_query import _scene, ray_sets
+from _cases import _wavelengths, ray_sets
+from _compare import assert_consistent, assert_same
+from _scenes import _scene
 
 pytestmark = pytest.mark.gpu
 
@@ -28,26 +30,6 @@ W, H = 320, 180
 # scene), so that a kernel which zeroed most emitter hits would fail here even before the bit-for-bit comparison
 IDENTITY_SCENES = {"demo": 0.05, "glass": 0.05, "random-seed-1": 0.3, "random-seed-2": 0.4, "many-prisms": 0.4, "demo-2500": 0.05,
                    "random-6000": 0.1}
-
-
-def _variant_of(before):
-    return B._variant_of(R.path_launches, before)
-
-
-def assert_same(got, want, what):
-    if got.tobytes() != want.tobytes():
-        rows = [i for i in range(len(got)) if got[i].tobytes() != want[i].tobytes()]
-        raise AssertionError("%s: %d of %d records differ, first %d: got %r want %r" % (what, len(rows), len(got), rows[0],
-                                                                                          got[rows[0]], want[rows[0]]))
-
-
-def assert_consistent(res):
-    """end and object agree with value: only a path that ended on a light carries a value, and only it names an object."""
-    emit = res["end"] == R.RL_PATH_END_EMITTER
-    assert ((res["object"] != NONE) == emit).all()
-    assert (res["value"][~emit] == 0).all()
-    assert np.isin(res["end"], [R.RL_PATH_END_VOID, R.RL_PATH_END_EMITTER, R.RL_PATH_END_ROULETTE]).all()
-    assert (res["segments"] >= 1).all()
 
 
 @pytest.mark.parametrize("name", sorted(IDENTITY_SCENES))
@@ -65,7 +47,7 @@ def test_camera_rays_fed_back_reproduce_the_renderer(name):
     for fetch in FETCHES:
         before = R.path_launches()
         res = scene.render_spectral_rays(samples["ray"], seed, stream, first, fetch=fetch)
-        v = _variant_of(before)
+        v = B._variant_of(R.path_launches, before)
         assert v % 2 == cyl and (fetch == R.FETCH_LDS or v // 2 == 0), (name, fetch, v)
         assert res["value"].tobytes() == want["probability"].tobytes(), (name, fetch)
         assert int(res["segments"].sum(dtype=np.uint64)) == segs, (name, fetch)
@@ -91,15 +73,6 @@ def test_path_oracle_on_device_camera_rays(name):
     got = P.PathOracle(objs, cam).render_rays(r["origin"], r["direction"], r["wavelength"], seed, stream, first)
     assert got["value"].tobytes() == want["probability"].tobytes()
     assert int(got["segments"].sum()) == segs
-
-
-def _wavelengths(rng, n):
-    """Uniform in [380, 780] nm, with finite ones outside that range and non-finite ones mixed in."""
-    wl = rng.uniform(380.0, 780.0, n).astype(np.float32)
-    odd = np.array([200.0, 379.99, 780.01, 1000.0, 2500.0, 50.0, np.nan, np.inf, -np.inf, -500.0], np.float32)
-    k = rng.choice(n, min(n, n // 8), replace=False)
-    wl[k] = odd[np.arange(len(k)) % len(odd)]
-    return wl
 
 
 @pytest.mark.parametrize("name", ["demo", "glass", "random-seed-1"])
@@ -225,7 +198,7 @@ def test_every_path_variant_ran():
         for fetch in FETCHES:
             before = R.path_launches()
             scene.render_spectral_rays(r, 1, 0, 0, fetch=fetch)
-            ran.add(_variant_of(before))
+            ran.add(B._variant_of(R.path_launches, before))
     assert ran == set(range(6)), sorted(ran)
 
 

@@ -12,8 +12,11 @@ import pytest
 
 import _oracle as O
 import _query_rays as QR
-import _random_scene as RS
 import _step_oracle as S
+from _cases import _results
+from _compare import assert_same
+from _device_arrays import _Device, _begin_device, _poison_hits
+from _scenes import _scene
 
 pytestmark = pytest.mark.gpu
 
@@ -28,68 +31,10 @@ IDENTITY_SCENES = ("demo", "glass", "random-seed-1", "random-seed-2", "many-pris
 BUDGET = R.RL_PATH_MAX_SEGMENTS
 
 
-def _scene(name):
-    if name == "demo":
-        return R.builtin_scene_desc(R.SCENE_DEMO)
-    if name == "demo-2500":
-        return R.builtin_scene_desc(R.SCENE_DEMO, 2500)
-    if name == "glass":
-        return R.builtin_scene_desc(R.SCENE_GLASS_STRESS)
-    if name.startswith("random-seed-"):
-        seed = int(name.rsplit("-", 1)[1])
-        return RS.random_scene(seed, n_spheres=[40, 300, 700][seed % 3], n_prisms=6 + seed % 5)
-    if name == "many-prisms":
-        return RS.random_scene(22, n_spheres=60, n_prisms=70)
-    if name == "tables-prisms":
-        return RS.random_scene(77, n_spheres=3000, n_prisms=48, n_planes=2, n_circles=3, n_parabs=1)
-    if name == "random-6000":
-        return RS.random_scene(41, n_spheres=6000, n_prisms=12, n_planes=2, n_circles=3, n_parabs=1)
-    raise KeyError(name)
-
-
 def _identity_case(name):
     objs, cam = _scene(name)
     n, seed, stream, first = (8192 if len(objs) > 2000 else 65536), 3 + len(name), 1, 1000
     return objs, cam, n, seed, stream, first
-
-
-def assert_same(got, want, what):
-    if got.tobytes() != want.tobytes():
-        rows = [i for i in range(len(got)) if got[i].tobytes() != want[i].tobytes()]
-        raise AssertionError("%s: %d of %d records differ, first %d: got %r want %r" % (what, len(rows), len(got), rows[0],
-                                                                                          got[rows[0]], want[rows[0]]))
-
-
-def _results(states):
-    """{value, segments, object, end} of final states as RlPathResult records."""
-    res = np.zeros(len(states), dtype=R.PATH_RESULT_DTYPE)
-    for f in res.dtype.names:
-        res[f] = states[f]
-    return res
-
-
-class _Device:
-    """An (n,) record array in device memory."""
-
-    def __init__(self, a):
-        self.host = np.ascontiguousarray(a).copy()
-        self.buf = QR.DeviceBuffer(max(self.host.nbytes, 64))
-        if self.host.nbytes:
-            self.buf.upload(self.host)
-
-    def get(self):
-        if self.host.nbytes:
-            self.buf.download(self.host)
-        return self.host
-
-
-def _begin_device(scene, rays, first):
-    rb = _Device(np.ascontiguousarray(rays))
-    poison = np.zeros(len(rays), R.PATH_STATE_DTYPE)
-    poison["end"] = 12345   # every record must be written
-    sb = _Device(poison)
-    R.check(R.lib.rl_scene_begin_paths_device(scene.handle, first, C.c_void_p(rb.buf.data_ptr()), len(rays), C.c_void_p(sb.buf.data_ptr())))
-    return sb
 
 
 def _step_device(scene, sb, seed, stream, fetch=R.FETCH_LDS, flags=0, hb=None):
@@ -179,10 +124,6 @@ def _mixed_states(name, rng):
     rays["origin"], rays["direction"] = origins, directions
     rays["wavelength"] = rng.uniform(380.0, 780.0, len(rays)).astype(np.float32)
     return objs, cam, scene, rays
-
-
-def _poison_hits(n):
-    return np.frombuffer(bytes([0xa5]) * (48 * n), dtype=R.HIT_DTYPE).copy()
 
 
 @pytest.mark.parametrize("name", ["demo", "glass"])

@@ -16,7 +16,10 @@ import _oracle as O
 import _random_scene as RS
 import _step_oracle as S
 from _boundary import _err, _FakeScene
-from _device_build import device_build
+from _cases import bounce_directions, vertex_states
+from _compare import assert_means_agree
+from _device_build import kernels, variant_of_name  # noqa: F401  (kernels is a fixture)
+from _scenes import _with_lights, closed_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RL_E_INVALID = -1
@@ -110,23 +113,6 @@ def _camera_rays(objs, cam, n, seed, stream, first):
     rays["origin"], rays["direction"] = rays6[:, :3], rays6[:, 3:]
     rays["wavelength"] = np.random.default_rng(seed).uniform(380.0, 780.0, n).astype(np.float32)
     return rays
-
-
-def _with_lights(objs, rng):
-    """A description with a few more black-body spheres and discs appended, discs with normals next to +z and -z among them."""
-    extra = np.zeros(6, objs.dtype)
-    extra["material_kind"] = 0
-    extra["m"] = [(rng.uniform(3000, 9000), rng.uniform(0.3, 1.0), 0) for _ in range(6)]
-    extra["surface_kind"] = [0, 0, 2, 2, 2, 2]
-    extra["f"][:, 0] = rng.uniform(1.0, 5.0, 6)
-    for k in range(2):
-        extra["v0"][k] = rng.normal(0, 14, 3)
-    for k, nrm in ((2, rng.normal(size=3)), (3, (3e-3, 2e-3, 1.0)), (4, (-2e-3, 4e-3, -1.0)), (5, (0.02, 0.0, 1.0))):
-        nrm = np.asarray(nrm, np.float64)
-        extra["v0"][k] = (nrm / np.linalg.norm(nrm)).astype(np.float32)
-        extra["v1"][k] = rng.normal(0, 16, 3)
-    assert (np.abs(extra["v0"][3:5, 2]) > 0.9999).all() and abs(extra["v0"][5, 2]) < 0.9999
-    return np.concatenate([objs, extra])
 
 
 # path indices whose block 0x80000001 under (seed 11, stream 2) has all-zero / all-one top 24 bits in word 0: u = 0 and u = 1
@@ -241,60 +227,6 @@ def test_nearest_hit_occlusion_is_the_linear_scan():
     assert fast.tolist() == occ.occluded_linear(rays).tolist() and 0 < fast.sum() < len(rays)
 
 
-def closed_scene(occluder):
-    """A diffuse-grey floor z = 0 under a black ceiling, one sphere light, one disc light and, optionally, a sphere between the
-    floor's origin and the lights."""
-    rows = [
-        (1, 1, (0, 0, 1), (0, 0, 0), 0.0, (0.7, 0, 0)),                 # the floor: a diffuse-grey plane
-        (0, 0, (1.5, 0.5, 4.0), (0, 0, 0), 0.8, (6000.0, 1.0, 0)),      # a sphere light
-        (2, 0, (0, 0, -1), (-2.0, 1.0, 5.0), 1.5, (4500.0, 0.8, 0)),    # a disc light facing down
-        (0, 1, (0, 0, 0), (0, 0, 0), 40.0, (0.0, 0, 0)),                # a black (reflectance 0) shell around everything
-    ]
-    if occluder:
-        rows.append((0, 1, (0.6, 0.3, 2.0), (0, 0, 0), 0.5, (0.0, 0, 0)))   # a black sphere in front of part of both lights
-    objs = np.zeros(len(rows), R.OBJECT_DTYPE)
-    for o, (sk, mk, v0, v1, f0, m) in zip(objs, rows):
-        o["surface_kind"], o["material_kind"], o["v0"], o["v1"], o["m"] = sk, mk, v0, v1, m
-        o["f"][0] = f0
-    return objs, O.demo_scene_desc()[1]
-
-
-def vertex_states(n, first=0):
-    """n states at one vertex: the floor's origin, reached by a segment from above, about to leave in the direction the NEXT bounce
-    draws (the estimator does not read it but for its side), intensity 0.7 (the floor's reflectance), distinct path indices."""
-    st = np.zeros(n, R.PATH_STATE_DTYPE)
-    st["origin"], st["direction"] = (0, 0, 1e-5), (0, 0, 1)
-    st["wavelength"], st["intensity"], st["continue_chance"] = 550.0, 0.7, 0.96
-    st["segments"], st["end"], st["object"] = 1, R.RL_PATH_LIVE, R.RL_OBJECT_NONE
-    st["path_index"] = first + np.arange(n, dtype=np.uint64)
-    ht = np.zeros(n, R.HIT_DTYPE)
-    ht["normal"], ht["distance"], ht["object"] = (0, 0, 1), 1.0, 0
-    return st, ht
-
-
-def bounce_directions(st, seed, stream):
-    """The cosine-weighted direction the reference's diffuse bounce draws at the vertex for each state's path, from block
-    2 + segments (monte_carlo.rs:47-58 on a z-up normal: no rotation): what the path itself does next."""
-    n = len(st)
-    w = np.zeros((n, 4), np.uint32)
-    paths = np.ascontiguousarray(st["path_index"], dtype=np.uint64)
-    blocks = (st["segments"] + 2).astype(np.uint32)
-    O.lib().oracle_rng_blocks(seed, stream, O.ptr(paths), O.ptr(blocks), O.ptr(w), n)
-    phi = (w[:, 0] >> 8).astype(np.float64) * 2.0 ** -24 * 2 * np.pi
-    rq = (w[:, 1] >> 8).astype(np.float64) * 2.0 ** -24 * (16777216.0 / 16777215.0)
-    r = np.sqrt(rq)
-    return np.stack([np.cos(phi) * r, np.sin(phi) * r, np.sqrt(1 - rq)], axis=1).astype(np.float32)
-
-
-def assert_means_agree(light_values, path_values, what):
-    """|mean a - mean b| <= 5 combined standard errors, each from the samples themselves."""
-    a, b = np.asarray(light_values, np.float64), np.asarray(path_values, np.float64)
-    se = np.sqrt(a.var(ddof=1) / len(a) + b.var(ddof=1) / len(b))
-    print("%s: light %.6g path %.6g diff %.3g se %.3g" % (what, a.mean(), b.mean(), a.mean() - b.mean(), se))
-    assert a.mean() > 0 and b.mean() > 0, what
-    assert abs(a.mean() - b.mean()) <= 5 * se, (what, a.mean(), b.mean(), se)
-
-
 @pytest.mark.parametrize("occluder", [True, False])
 def test_the_sample_estimates_what_the_next_segment_finds_on_the_cpu_oracle(occluder):
     """The mean of `value` over states at one vertex against the mean of what those states carry after one more segment that ends
@@ -320,19 +252,14 @@ def test_the_sample_estimates_what_the_next_segment_finds_on_the_cpu_oracle(occl
     assert_means_agree(light["value"], value, "occluder %s" % occluder)
 
 
-@pytest.fixture(scope="module")
-def kernels():
-    return device_build()[1]
-
-
 def test_light_kernels_compile_without_scratch_and_within_the_register_bound(kernels):
     light = {n: k for n, k in kernels.items() if "rl_light_kernel" in n}
-    assert sorted(re.search(r"rl_light_kernelILi([012])ELb([01])E", n).groups() for n in light) == [(s, c) for s in "012" for c in "01"]
-    steps = {re.search(r"rl_step_kernelILi([012])ELb([01])E", n).groups(): k for n, k in kernels.items() if "rl_step_kernel" in n}
+    assert sorted(variant_of_name(n, "rl_light_kernel") for n in light) == [(s, c) for s in "012" for c in "01"]
+    steps = {variant_of_name(n, "rl_step_kernel"): k for n, k in kernels.items() if "rl_step_kernel" in n}
     for name, k in light.items():
         assert k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0 and k["dynamic_stack"] == 0, (name, k)
         assert k["vgpr_count"] <= 128 and k.get("agpr_count", 0) == 0, (name, k)
-        v = re.search(r"rl_light_kernelILi([012])ELb([01])E", name).groups()
+        v = variant_of_name(name, "rl_light_kernel")
         assert k["sgpr_spill_count"] <= steps[v]["sgpr_spill_count"], (name, k["sgpr_spill_count"], steps[v]["sgpr_spill_count"])
         if v[0] == "2":
             assert k["sgpr_spill_count"] == 0, (name, k)

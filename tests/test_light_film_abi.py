@@ -16,7 +16,7 @@ import _light_oracle as LO
 import _oracle as O
 import _step_oracle as S
 from _boundary import _err
-from _device_build import device_build
+from _device_build import kernels, variant_of_name  # noqa: F401  (kernels is a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RL_E_INVALID = -1
@@ -180,7 +180,7 @@ def test_the_per_pixel_bound_sees_one_lost_splat_where_allclose_did_not(oracle_l
     wavelengths are the camera's own, from the oracle's render of the same paths.
 
     A photon is undetectable when the float32 film of IC.splat with that photon's terms taken out has no violation:
-      * new rule (tests/test_gpu_film.py::assert_film): IC.splat_violations against the k, S and exact of the whole list;
+      * new rule (tests/_compare.py: assert_film): IC.splat_violations against the k, S and exact of the whole list;
       * old rule: np.allclose(rtol=2e-5, atol=1e-6 image max) alone.
     Measured, undetectable photons (new rule; old rule):
       steps 1, 1133 photons: 16x9  53 (4.7 %); 193 (17.0 %)   64x36  15 (1.3 %); 131 (11.6 %)   320x180 1 (0.1 %); 116 (10.2 %)
@@ -233,14 +233,8 @@ def test_the_per_pixel_bound_sees_one_lost_splat_where_allclose_did_not(oracle_l
         assert old_passes == len(mutants), old_passes      # (what the tolerance alone let through)
 
 
-@pytest.fixture(scope="module")
-def kernels():
-    return device_build()[1]
-
-
 def test_light_film_kernels_compile_without_scratch_and_within_the_light_kernels_registers(kernels):
-    pattern = r"rl_light_film_kernelILi([012])ELb([01])E"
-    film = {re.search(pattern, n).groups(): k for n, k in kernels.items() if "rl_light_film_kernel" in n}
+    film = {variant_of_name(n, "rl_light_film_kernel"): k for n, k in kernels.items() if "rl_light_film_kernel" in n}
     assert sorted(film) == [(s, c) for s in "012" for c in "01"]
     for v, k in film.items():
         print("rl_light_film_kernel<%s, %s>: %d VGPRs, %d SGPRs spilled" % (v[0], v[1], k["vgpr_count"], k["sgpr_spill_count"]))

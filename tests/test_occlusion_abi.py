@@ -12,7 +12,7 @@ import pytest
 
 import robigo_luculenta_amd as R
 from robigo_luculenta_amd import _lib
-from _device_build import device_build
+from _device_build import kernels, variant_of_name  # noqa: F401  (kernels is a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RL_E_INVALID = -1
@@ -53,22 +53,11 @@ def test_bad_arguments_are_invalid_with_a_message(name):
     assert _lib.lib.rl_debug_occlusion_launches(None) == RL_E_INVALID
 
 
-@pytest.fixture(scope="module")
-def kernels():
-    """Metadata of every kernel from the device-only -S compile with the library's own flags."""
-    _, metadata, _ = device_build()
-    return metadata
-
-
-def _stage_and_cyl(name, kernel):
-    return re.search(r"%sILi([012])ELb([01])E" % kernel, name).groups()
-
-
 def test_six_occlusion_kernels_free_of_scratch_and_vector_spills(kernels):
     mine = {n: k for n, k in kernels.items() if "rl_occlusion_kernel" in n}
     assert len(mine) == VARIANTS, sorted(mine)
-    assert sorted(_stage_and_cyl(n, "rl_occlusion_kernel") for n in mine) == [(s, c) for s in "012" for c in "01"]
-    query = {_stage_and_cyl(n, "rl_query_kernel"): k for n, k in kernels.items() if "rl_query_kernel" in n}
+    assert sorted(variant_of_name(n, "rl_occlusion_kernel") for n in mine) == [(s, c) for s in "012" for c in "01"]
+    query = {variant_of_name(n, "rl_query_kernel"): k for n, k in kernels.items() if "rl_query_kernel" in n}
     for name, k in mine.items():
         # the other *_abi.py tests count their kernels by these substrings
         for other in ("rl_query_kernel", "rl_step_kernel", "rl_ray_paths_kernel", "rl_film_", "rl_trace_kernel"):
@@ -76,7 +65,7 @@ def test_six_occlusion_kernels_free_of_scratch_and_vector_spills(kernels):
         assert k["private_segment_fixed_size"] == 0 and k["dynamic_stack"] == 0, (name, k)   # no scratch memory
         assert k["vgpr_spill_count"] == 0, (name, k)
         assert k["vgpr_count"] <= 128 and k.get("agpr_count", 0) == 0, (name, k)             # four waves per SIMD, no AGPRs
-        q = query[_stage_and_cyl(name, "rl_occlusion_kernel")]
+        q = query[variant_of_name(name, "rl_occlusion_kernel")]
         assert k["sgpr_spill_count"] <= q["sgpr_spill_count"], (name, k["sgpr_spill_count"], q["sgpr_spill_count"])
 
 

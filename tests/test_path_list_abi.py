@@ -12,7 +12,7 @@ import pytest
 import robigo_luculenta_amd as R
 from robigo_luculenta_amd import _lib
 from _boundary import _err, _FakeScene
-from _device_build import device_build
+from _device_build import kernels, variant_of_name  # noqa: F401  (kernels is a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "robigo_luculenta_amd", "csrc")
@@ -95,21 +95,12 @@ def test_an_empty_list_does_nothing_but_report_zero(name):
     assert st.tobytes() == before and (live == 0xAAAAAAAA).all()
 
 
-@pytest.fixture(scope="module")
-def kernels():
-    return device_build()[1]
-
-
-def _variant(name, kernel):
-    return re.search(kernel + r"ILi([012])ELb([01])E", name).groups()
-
-
 def test_list_kernels_resources_names_and_the_existing_families(kernels):
     lists = {n: k for n, k in kernels.items() if "rl_list_step_kernel" in n}
     pack = {n: k for n, k in kernels.items() if "rl_list_scan_kernel" in n or "rl_list_pack_kernel" in n}
     steps = {n: k for n, k in kernels.items() if "rl_step_kernel" in n}
     assert len(lists) == 6 and len(pack) == 2 and len(steps) == 6, sorted(kernels)
-    assert sorted(_variant(n, "rl_list_step_kernel") for n in lists) == [(s, c) for s in "012" for c in "01"]
+    assert sorted(variant_of_name(n, "rl_list_step_kernel") for n in lists) == [(s, c) for s in "012" for c in "01"]
     new = {n: k for n, k in kernels.items() if "rl_list_" in n}
     assert len(new) == 8
     for name, k in new.items():
@@ -118,9 +109,9 @@ def test_list_kernels_resources_names_and_the_existing_families(kernels):
         assert k["private_segment_fixed_size"] == 0, (name, k)          # no scratch memory
         assert k["vgpr_spill_count"] == 0 and k["dynamic_stack"] == 0, (name, k)
         assert k["vgpr_count"] <= 128 and k.get("agpr_count", 0) == 0, (name, k)
-    step_spills = {_variant(n, "rl_step_kernel"): k["sgpr_spill_count"] for n, k in steps.items()}
+    step_spills = {variant_of_name(n, "rl_step_kernel"): k["sgpr_spill_count"] for n, k in steps.items()}
     for name, k in lists.items():
-        v = _variant(name, "rl_list_step_kernel")
+        v = variant_of_name(name, "rl_list_step_kernel")
         assert k["sgpr_spill_count"] <= step_spills[v], (name, k["sgpr_spill_count"], step_spills[v])
         if v[0] == "2":                                                   # the whole scene staged
             assert k["sgpr_spill_count"] == 0, (name, k)
