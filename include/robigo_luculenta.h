@@ -297,7 +297,8 @@ typedef struct RlPathState {
     RlVector3 direction;    /* used as given, not normalised */
     float intensity;        /* trace_unit.rs:88 */
     float continue_chance;  /* trace_unit.rs:84 */
-    uint32_t segments;      /* Scene::intersect calls made so far; the next bounce draws RNG block 2 + segments */
+    uint32_t segments;      /* Scene::intersect calls made so far; the next bounce draws RNG block 2 + segments.  That sum, the
+                               light sample's 2^31 + segments and the step's segments + 1 are 32-bit: they wrap. */
     uint32_t end;           /* RL_PATH_LIVE, or an enum RlPathEnd value */
     float value;            /* RlPathResult::value once the path has ended, 0 while it is live */
     uint64_t path_index;    /* the RNG path of this state: it travels with the record */

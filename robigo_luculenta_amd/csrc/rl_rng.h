@@ -7,7 +7,9 @@
 // authors report the generator Crush-resistant (their Table 2; 10 is their default with a safety margin, and what rounds
 // 1-3 of this build used: the three rounds less are 1.2 % of the trace kernel's time).  The round function is pinned by
 // Random123's published 10-round vectors (rl_philox4x32_10, tests/test_oracle_kat.py), the 7-round words by an independent
-// numpy implementation over a million tuples (tests/test_independent.py).
+// numpy implementation over a million tuples (tests/test_independent.py); tests/test_rng_width.py holds the oracle to that
+// implementation where the seed's, the stream's and the path's upper halves are set and a launch's path range carries into the
+// high counter word, and tests/test_gpu_rng_width.py holds every kernel to the oracle there.
 //
 //   block 0        : slot 0 wavelength, slot 1 screen x, slot 2 screen y, slot 3 camera time
 //                    (trace_unit.rs:154-158,138)
@@ -20,6 +22,8 @@
 //                    the reference): slot 0 the point's first coordinate (closed unit), slot 1 its longitude (half-open),
 //                    slot 2 which emitter, slot 3 unused.  Disjoint from the bounces' blocks for every path of fewer than
 //                    2^31 - 2 segments.
+//   The block is one 32-bit counter word: 2 + b and 2^31 + s are 32-bit sums and wrap for a caller-held state whose `segments`
+//   is that large.
 //
 // Every lane of a wave therefore makes exactly one Philox call per bounce regardless of which
 // material it hit -- no divergence and no cached words live across the intersection scan.

@@ -58,8 +58,8 @@ class StepOracle:
         wl = f32(state["wavelength"])
         isect = np.zeros(10, np.float32)
         idx = L.oracle_scene_intersect(self.scene.h, O.ptr(o), O.ptr(d), O.ptr(isect))
-        block = 2 + int(state["segments"])
-        state["segments"] = int(state["segments"]) + 1
+        block = (2 + int(state["segments"])) & 0xffffffff          # 32-bit sums, as RlPathState::segments says: they wrap
+        state["segments"] = (int(state["segments"]) + 1) & 0xffffffff
         state["value"], state["object"], state["reserved"] = f32(0), NONE, 0
         if hit is not None:
             hit["position"], hit["normal"], hit["tangent"] = (isect[0:3], isect[3:6], isect[6:9]) if idx >= 0 else (0, 0, 0)

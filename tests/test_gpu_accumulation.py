@@ -117,14 +117,14 @@ def test_film_at_depth_is_the_f64_sum_of_its_photons(R, scenes, reference, shape
 
 @pytest.fixture(scope="module")
 def oracle_film(scenes):
-    """The oracle's photons of paths [0, count) of `ranks` streams (stream = rank): k, S and the exact sum of the whole list (the
-    partition into gathers is the scheduler's), and the segment total; once per configuration."""
+    """The oracle's photons of paths [first, first + count) of `ranks` streams (stream = stream0 + rank): k, S and the exact sum of
+    the whole list (the partition into gathers is the scheduler's), and the segment total; once per configuration."""
     cache = {}
 
-    def get(w, h, seed, ranks, count):
-        key = (w, h, seed, ranks, count)
+    def get(w, h, seed, ranks, count, first=0, stream0=0):
+        key = (w, h, seed, ranks, count, first, stream0)
         if key not in cache:
-            rendered = [scenes[1].render(w, h, seed, r, 0, count, threads=8) for r in range(ranks)]
+            rendered = [scenes[1].render(w, h, seed, stream0 + r, first, count, threads=8) for r in range(ranks)]
             ph = np.concatenate([p for p, _ in rendered])
             k, s, exact = A.film_terms(w, h, ph, np.zeros(len(ph), np.int64), 1)
             cache[key] = (exact[0], A.accumulation_bound(k[0], s[0], ranks), sum(segs for _, segs in rendered))
@@ -182,3 +182,18 @@ def test_resumed_run_accumulates_all_twelve_batches(R, oracle_film, tmp_path, fu
     assert st2["next_batch"] == 2 * batches
     both = {"paths": st1["paths"] + st2["paths"], "segments": st1["segments"] + st2["segments"]}
     _assert_app_film(both, _raw_film(raw, w, h), oracle_film(w, h, 9, 1, 2 * batches * n), 1, 2 * batches * n)
+
+
+@pytest.mark.parametrize("fused", [False, True], ids=["unfused", "fused"])
+def test_app_batches_across_2_32_paths_under_a_wide_seed_and_the_last_two_streams(R, oracle_film, tmp_path, fused):
+    """12 batches of 4,096 paths from batch 2^20 - 6 on: the path indices [2^32 - 24576, 2^32 + 24576), so batch * photons_per_batch
+    carries into the high counter word half way; a seed with a high word; two ranks on one GPU on streams 0xFFFFFFFE and
+    0xFFFFFFFF.  buffer.raw is the sum of the oracle's photons of exactly those ranges and streams."""
+    w, h, n, batches, first_batch = 64, 36, 1 << 12, 12, (1 << 20) - 6
+    seed, stream = 0xA5A5A5A500000009, 0xFFFFFFFE
+    assert first_batch * n == (1 << 32) - 24576 and (first_batch + batches) * n == (1 << 32) + 24576
+    raw = str(tmp_path / "buffer.raw")
+    _, st = R.app_run(w, h, batches, concurrency=3, photons_per_batch=n, seed=seed, stream=stream, fused=fused, devices=[0, 0],
+                      checkpoint=raw, first_batch=first_batch)
+    assert st["batches"] == batches and st["next_batch"] == (1 << 20) + 6
+    _assert_app_film(st, _raw_film(raw, w, h), oracle_film(w, h, seed, 2, batches * n, first_batch * n, stream), 2, batches * n)

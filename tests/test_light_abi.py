@@ -14,6 +14,7 @@ from robigo_luculenta_amd import _lib
 import _light_oracle as LO
 import _oracle as O
 import _random_scene as RS
+import _rng_width as RW
 import _step_oracle as S
 from _boundary import _err, _FakeScene
 from _cases import bounce_directions, vertex_states
@@ -188,7 +189,19 @@ def test_host_compile_of_the_sampling_function_is_the_oracle_bit_for_bit(name):
     w_ht["position"][20:30] = np.nan
     w_ht["normal"][30:40] = (np.inf, 0, 0)
     st, ht = np.concatenate([st, w_st]), np.concatenate([ht, w_ht])
-    assert len(st) > 5000
+    # path indices over all 64 bits (neighbours that share one word and differ in the other, words that are float NaN, -0 and
+    # infinity patterns) and `segments` at the edges of 32 bits: the block is (2^31 + segments) mod 2^32 (tests/_rng_width.py)
+    mixed = RW.mixed_path_indices(320)
+    p_st, p_ht = st[some][np.arange(320) % 40].copy(), ht[some][np.arange(320) % 40].copy()
+    p_st["path_index"] = mixed
+    edges = np.array([s for s in RW.SEGMENT_EDGES if s >= 1], np.uint32)
+    s_st, s_ht = st[some][np.arange(8 * len(edges)) % 40].copy(), ht[some][np.arange(8 * len(edges)) % 40].copy()
+    s_st["segments"] = edges[np.arange(len(s_st)) % len(edges)]
+    b_st, b_ht = p_st.copy(), p_ht.copy()
+    b_st["segments"] = edges[np.arange(len(b_st)) % len(edges)]
+    assert set(RW.SPECIAL_PATHS) <= set(mixed.tolist()) and (mixed >> np.uint64(32) != 0).mean() > 0.9
+    st, ht = np.concatenate([st, p_st, s_st, b_st]), np.concatenate([ht, p_ht, s_ht, b_ht])
+    assert len(st) > 5700
 
     want, want_rays = LO.draw(objs, st, ht, seed, stream)
     got, got_rays = R.light_sample_host(objs, st.view(R.PATH_STATE_DTYPE), ht.view(R.HIT_DTYPE), seed, stream)
