@@ -52,6 +52,24 @@ def oracle_hits(oscene, origins, directions, t_max=None):
     return hits
 
 
+def tied_hits(oscene, want, origins, directions, among=None):
+    """Per ray: does an object other than the one the oracle reports (of `among`, a list of object numbers, or of all) lie at exactly
+    the reported distance?  From the oracle's per-object intersection alone; false where the ray hits nothing."""
+    o = np.ascontiguousarray(origins, dtype=np.float32)
+    d = np.ascontiguousarray(directions, dtype=np.float32)
+    others = [int(j) for j in (range(len(oscene.objs)) if among is None else among)]
+    fn, h = O.lib().oracle_intersect_object, oscene.h
+    tied = np.zeros(len(want), dtype=bool)
+    out = np.zeros((len(others), 10), dtype=np.float32)
+    slots = [(j, out.ctypes.data + 40 * k) for k, j in enumerate(others)]
+    numbers = np.array(others, dtype=np.int64)
+    for i in np.flatnonzero(want["object"] != NONE):   # (one thread: the calls are too short to share the interpreter over)
+        po, pd = o.ctypes.data + 12 * int(i), d.ctypes.data + 12 * int(i)
+        hit = np.array([fn(h, j, po, pd, pv) for j, pv in slots], dtype=bool)
+        tied[i] = (hit & (out[:, 9] == want["distance"][i]) & (numbers != want["object"][i])).any()
+    return tied
+
+
 def t_max_cases(want, rng):
     """Per ray: +inf, random in (0, 2 distance), exactly the distance (a miss), nextafter(distance, inf) (a hit), 0, -1, NaN."""
     n = len(want)
@@ -67,7 +85,8 @@ def t_max_cases(want, rng):
 
 def ray_sets(scene, objs, cam, rng, n):
     """{kind: (origins, directions)}: camera-like, bounce-like (from the camera rays' hits), uniform origins within 4x the scene's
-    bounding radius, non-unit directions (|d| in [0.25, 4]), rays tangent to spheres and degenerate rays."""
+    bounding radius, non-unit directions (|d| in [0.25, 4]), rays tangent to spheres, degenerate rays and rays from far away
+    (far_rays)."""
     sets = {}
     o, d = QR.camera_rays(cam, 1920, 1080, rng, n)
     sets["camera"] = (o, d)
@@ -100,7 +119,35 @@ def ray_sets(scene, objs, cam, rng, n):
         else:
             dg_o[j, comp] = val                 # ... in the origin
     sets["degenerate"] = (dg_o, dg_d)
+    if len(sph):
+        sets["far"] = far_rays(objs, n)
     return sets
+
+
+def far_rays(objs, n):
+    """(origins, directions) of up to n unit rays aimed at the spheres of `objs` from 1e3 to 1e8 scene units away (log-uniform),
+    passing the centre at up to 1.05 radii, half of them within radius * 10^-U(0, 8) of grazing.  At these distances the reference's
+    f32 distance is coarse and distinct spheres tie; the origin is rounded to f32 first and the direction re-aimed from it,
+    normalised in f64 and rounded, and a ray whose f32 |d|^2 is further than 2^-20 from 1 is dropped, so every ray takes the culled
+    scan.  Drawn from a generator of its own: ray_sets' goes on as it did before this family."""
+    rng = np.random.default_rng([len(objs), n])
+    sph = objs[(objs["surface_kind"] == 0) & np.isfinite(objs["f"][:, 0]) & (objs["f"][:, 0] > 0)]
+    k = rng.integers(0, len(sph), n)
+    c, r = sph["v0"][k].astype(np.float64), sph["f"][k, 0].astype(np.float64)
+    u = QR.uniform_directions(rng, n).astype(np.float64)
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    b = np.cross(u, QR.uniform_directions(rng, n))
+    b /= np.linalg.norm(b, axis=1, keepdims=True)
+    lateral = r * rng.uniform(0.0, 1.05, n)
+    graze = r * (1.0 + rng.choice([-1.0, 1.0], n) * 10.0 ** -rng.uniform(0.0, 8.0, n))
+    lateral = np.where(rng.random(n) < 0.5, graze, lateral)
+    target = c + lateral[:, None] * b
+    o = (target - (10.0 ** rng.uniform(3.0, 8.0, n))[:, None] * u).astype(np.float32)
+    d = target - o.astype(np.float64)
+    d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+    d2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]
+    keep = np.abs(d2 - np.float32(1.0)) <= np.float32(2.0 ** -20)
+    return o[keep], d[keep]
 
 
 def _filter(want, t_max):

@@ -117,6 +117,27 @@ def small_axis_z(scene):
     return bool(L.mirror_small_axis_z(scene.h))
 
 
+def small_counts(scene):
+    """(paraboloids, planes and circles) in `scene`'s flattened tables: the n_parabs and n_planes the kernel's scan branches on."""
+    L = lib()
+    L.mirror_small_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    a, b = C.c_uint32(0), C.c_uint32(0)
+    L.mirror_small_counts(scene.h, C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+def super_bounds(scene, cap=4096):
+    """The third level of `scene`'s cull table: ((n, 4) floats {centre, radius^2} per super, cluster groups per super); n = 0 for a
+    two-level table."""
+    L = lib()
+    L.mirror_super_bounds.restype = C.c_uint32
+    L.mirror_super_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    sup, sg = np.zeros((cap, 4), np.float32), C.c_uint32(0)
+    n = L.mirror_super_bounds(scene.h, O.ptr(sup), cap, C.byref(sg))
+    assert n <= cap
+    return sup[:n], sg.value
+
+
 def axis_z_check(seed, n):
     """rl_paraboloid_t<AXIS_Z> / rl_plane_t<AXIS_Z> against the general forms: (cases, hits compared, differences, cases with a zero n.d / n.o)."""
     L = lib()

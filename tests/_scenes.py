@@ -12,8 +12,79 @@ SCENES = ["demo", "demo-2500", "glass", "random-seed-1", "random-seed-2", "rando
           "random-6000", "random-20000"]
 
 
+# The shapes of a description that rl_scan_wave's code paths depend on and no scene above has (tests/test_scene_shapes.py holds each
+# to the shape named here): the built-in room with one normal off z / a seventh small primitive / a plane in front of its
+# paraboloids, random scenes under a permutation of the whole description at the sizes of the four table shapes, and permuted scenes
+# whose objects coincide across the kernel's tables.
+SHAPE_SCENES = ["room-tilted", "room-plus-disc", "room-reordered", "shuffled-40", "shuffled-300", "shuffled-3000", "shuffled-6000",
+                "coincident-300", "coincident-3000"]
+
+
+def _room(change):
+    """The built-in scene with its small primitives changed: "tilted" (the second circle's normal a hair off z), "plus-disc" (a
+    seventh small primitive, a circle in the first circle's own plane and overlapping it, appended behind everything) or
+    "reordered" (the first plane in the place of the first paraboloid, then the paraboloids last to first, then the rest)."""
+    objs, cam = R.builtin_scene_desc(R.SCENE_DEMO)
+    objs = np.ascontiguousarray(objs).view(R.OBJECT_DTYPE).copy()
+    kinds = objs["surface_kind"]
+    circles = np.flatnonzero(kinds == 2)
+    if change == "tilted":
+        k = int(circles[1])
+        nrm = np.array((3e-3, 2e-3, 1.0), np.float64) * (-1.0 if objs["v0"][k, 2] < 0 else 1.0)
+        objs["v0"][k] = (nrm / np.linalg.norm(nrm)).astype(np.float32)
+    elif change == "plus-disc":
+        disc = objs[circles[:1]].copy()       # coplanar with the first circle and overlapping it: the ordered loop meets exact ties
+        disc["v1"][0, :2] += disc["f"][0, 0] * np.float32(0.75)
+        disc["material_kind"], disc["m"] = 3, (0.1, 0.0, 0.0)
+        objs = np.concatenate([objs, disc])
+    elif change == "reordered":
+        small = np.flatnonzero((kinds >= 1) & (kinds <= 3))
+        parabs, plane = np.flatnonzero(kinds == 3), int(np.flatnonzero(kinds == 1)[0])
+        order = [plane] + list(parabs[::-1]) + [int(k) for k in small if kinds[k] != 3 and k != plane]
+        objs[small] = objs[order]
+    else:
+        raise KeyError(change)
+    return objs, cam
+
+
+def _shuffled(n_spheres):
+    """A random scene of n_spheres spheres and its light under a seeded permutation of the whole description: surface kinds
+    interleave, planes precede paraboloids, the light stands anywhere."""
+    objs, cam = RS.random_scene(500 + n_spheres, n_spheres=n_spheres, n_prisms=12, n_planes=2, n_circles=3, n_parabs=2)
+    return objs[np.random.default_rng([n_spheres, 1]).permutation(len(objs))], cam
+
+
+def _coincident(n_spheres):
+    """A random scene with a coincident copy, of another material kind, of every plane, circle, paraboloid and prism and of a
+    tenth of its spheres, and a circle of radius 30 in each plane's own plane, permuted: equal distances to objects of different
+    tables, which only the object numbers decide (scene.rs:51) and whose winner shows in the path that follows.
+    The seeds are ones at which a copied sphere stands in the camera's view (it sees a handful of the large ones): at least a
+    tenth of the camera rays' first hits tie exactly, which tests/test_scene_shapes.py holds them to."""
+    objs, cam = RS.random_scene({300: 1201, 3000: 3908}[n_spheres], n_spheres=n_spheres, n_prisms=12, n_planes=2, n_circles=3, n_parabs=2)
+    rng = np.random.default_rng([n_spheres, 2])
+    kinds = objs["surface_kind"]
+    spheres = np.flatnonzero(kinds == 0)
+    copies = objs[np.concatenate([np.flatnonzero(kinds != 0), rng.choice(spheres, len(spheres) // 10, replace=False)])].copy()
+    diffuse = copies["material_kind"] != 1     # a copy is diffuse, a diffuse object's copy a mirror
+    copies["material_kind"] = np.where(diffuse, 1, 3)
+    copies["m"] = 0.0
+    copies["m"][:, 0] = np.where(diffuse, 0.8, 0.1)
+    discs = objs[kinds == 1].copy()            # same normal (v0) and offset point (v1) as the plane
+    discs["surface_kind"], discs["material_kind"], discs["m"] = 2, 3, (0.2, 0.0, 0.0)
+    discs["f"][:, 0] = 30.0
+    everything = np.concatenate([objs, copies, discs])
+    return everything[rng.permutation(len(everything))], cam
+
+
 def _scene(name):
     """(objects, camera) of the scene `name`; KeyError for a name that is none."""
+    if name in SHAPE_SCENES:
+        family, what = name.split("-", 1)
+        if family == "room":
+            return _room(what)
+        if family == "shuffled":
+            return _shuffled(38 if what == "40" else int(what))   # 38 and the light: 39 spheres, the most that get no clusters
+        return _coincident(int(what))
     if name == "demo":
         return R.builtin_scene_desc(R.SCENE_DEMO)
     if name == "demo-2500":

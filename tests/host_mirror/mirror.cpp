@@ -491,6 +491,13 @@ static bool mirror_reach(RlF4 b, RlF3 o, RlF3 dir, double far_t) {
 extern "C" int mirror_small_ordered(void* scene) { return ((MirrorScene*)scene)->flat.small_ordered ? 1 : 0; }
 // RlFlatScene::small_axis_z: every paraboloid's, plane's and circle's normal lies along z (the kernel then takes n.v as n.z v.z)
 extern "C" int mirror_small_axis_z(void* scene) { return ((MirrorScene*)scene)->flat.small_axis_z ? 1 : 0; }
+// The record counts of the flattened small-primitive tables, as rl_api.hip hands them to the kernel (RlSceneLayout::n_parabs, n_planes:
+// planes and circles share a table): what rl_scan_wave's choice of the straight-line block is made on.
+extern "C" void mirror_small_counts(void* scene, uint32_t* n_parabs, uint32_t* n_planes) {
+    const RlFlatScene& fs = ((MirrorScene*)scene)->flat;
+    *n_parabs = (uint32_t)(fs.parabs.size() / 3);
+    *n_planes = (uint32_t)(fs.planes.size() / 2);
+}
 
 extern "C" void mirror_cull_counts(void* scene, uint32_t w, uint32_t h, uint64_t seed, uint32_t stream, uint64_t first, uint64_t n,
                                    uint64_t* counts) {

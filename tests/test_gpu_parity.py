@@ -590,11 +590,8 @@ def test_third_table_level_scenes_bit_exact_in_every_launch_kind(which):
         objs, cam = RS.random_scene(35, n_spheres=20000, n_prisms=12, n_planes=2, n_circles=3, n_parabs=1)
     else:
         objs, cam = R.builtin_scene_desc(R.SCENE_DEMO, 2500)
-    L = M.lib()
-    L.mirror_super_bounds.restype = C.c_uint32
-    L.mirror_super_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-    sup, sg = np.zeros((1024, 4), np.float32), C.c_uint32(0)
-    assert L.mirror_super_bounds(M.Scene(objs, _ocam(cam)).h, O.ptr(sup), len(sup), C.byref(sg)) >= 14 and sg.value == 8
+    sup, super_g = M.super_bounds(M.Scene(objs, _ocam(cam)))
+    assert len(sup) >= 14 and super_g == 8
     scene, oscene = R.Scene(objs, cam), O.Scene(objs, _ocam(cam))
     W, H, N = 160, 90, 1 << 12
     want, segs = oscene.render(W, H, 9, 3, 128, N, threads=8)

@@ -1,6 +1,6 @@
 """Scene.intersect on the device (rl_scene_intersect / rl_scene_intersect_device) against the CPU oracle's Scene::intersect,
 bit for bit: the object index and the raw bits of position, normal, tangent and distance of every ray, over the built-in, glass,
-random, many-prism, degenerate and third-level scenes, camera-like, bounce-like, random, non-unit, tangent and degenerate rays,
+random, many-prism, degenerate and third-level scenes, camera-like, bounce-like, random, non-unit, tangent, degenerate and far rays,
 every t_max case, both fetch modes, every query variant, the host and device paths, concurrent callers and a query made while a
 render is open."""
 import ctypes as C

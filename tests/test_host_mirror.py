@@ -172,8 +172,6 @@ def test_third_level_of_the_cull_table_is_conservative_and_only_for_large_scenes
     L = M.lib()
     L.mirror_group_bounds.restype = C.c_uint32
     L.mirror_group_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-    L.mirror_super_bounds.restype = C.c_uint32
-    L.mirror_super_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     small = [M.builtin_desc(0, 0), M.builtin_desc(1, 0), M.builtin_desc(0, 158), random_scene(3, n_spheres=400, n_prisms=5)]
     small.append(M.builtin_desc(0, 600))    # 46 groups: two levels (the planner prices the third level: rl_scene.cpp, plan_cost)
     large = [M.builtin_desc(0, 1500), M.builtin_desc(0, 2500), random_scene(31, n_spheres=5000, n_prisms=12, n_planes=2, n_circles=3, n_parabs=1)]
@@ -185,16 +183,15 @@ def test_third_level_of_the_cull_table_is_conservative_and_only_for_large_scenes
         ng = L.mirror_group_bounds(sc.h, O.ptr(g), len(g), sizes)
         ncg = sizes[2]
         g = g[:ncg].astype(np.float64)
-        sup = np.zeros((1024, 4), np.float32)
-        sg = C.c_uint32(0)
-        ns = L.mirror_super_bounds(sc.h, O.ptr(sup), len(sup), C.byref(sg))
+        sup, super_g = M.super_bounds(sc)
+        ns = len(sup)
         if which < len(small):
             assert ns == 0
             continue
-        assert ns >= 14 and sg.value == 8 and ncg == ns * sg.value
-        sup = sup[:ns].astype(np.float64)
+        assert ns >= 14 and super_g == 8 and ncg == ns * super_g
+        sup = sup.astype(np.float64)
         for s in range(ns):
-            members = g[sg.value * s: sg.value * (s + 1)]
+            members = g[super_g * s: super_g * (s + 1)]
             real = members[np.isfinite(members[:, 3]) & (members[:, 3] > 0)]
             assert len(real) >= 1                                  # a super is never all padding
             reach = np.sqrt(((real[:, :3] - sup[s, :3]) ** 2).sum(1)) + np.sqrt(real[:, 3])

@@ -1,0 +1,133 @@
+"""The scene shapes of tests/_scenes.py's SHAPE_SCENES, on the host: each description reaches the branch of rl_scan_wave it was made
+for, the host mirror renders the oracle's photons on it, and the exact ties it was made for are really there.  No GPU:
+tests/test_gpu_scene_shapes.py runs the kernels on the same scenes.
+
+The flags and tables this module holds the scenes to (n_parabs + n_planes are the record counts of the FLATTENED tables, planes and
+circles together, read from the host mirror: M.small_counts):
+
+    scene            small_ordered  small_axis_z  small primitives  sphere table
+    room-tilted      true           false         3 + 3             clusters, two levels
+    room-plus-disc   true           true          3 + 4             clusters, two levels
+    room-reordered   false          true          3 + 3             clusters, two levels
+    shuffled-40      false          false         2 + 5             direct list only (39 spheres)
+    shuffled-300     false          false         2 + 5             clusters, two levels
+    shuffled-3000    false          false         2 + 5             clusters, two levels
+    shuffled-6000    false          false         2 + 5             clusters, three levels (supers)
+    coincident-300   false          false         4 + 12            clusters, two levels
+    coincident-3000  false          false         4 + 12            clusters, two levels
+
+The two tie conditions, from the oracle's per-object intersection alone: on each coincident-* scene at least 10 % of the camera
+rays' hits have a second object at exactly the same distance; on the built-in scene at least 5 % of the far family's hits
+(tests/_cases.py: far_rays) tie exactly with a different sphere."""
+import numpy as np
+import pytest
+
+import _mirror as M
+import _oracle as O
+import _query_rays as QR
+from _boundary import _ocam
+from _cases import far_rays, oracle_hits, tied_hits
+from _scenes import SCENES, SHAPE_SCENES, _scene
+
+NONE = 0xffffffff
+#            name: (small_ordered, small_axis_z, paraboloids, planes and circles, table)
+SHAPES = {"room-tilted": (True, False, 3, 3, "clusters"), "room-plus-disc": (True, True, 3, 4, "clusters"),
+          "room-reordered": (False, True, 3, 3, "clusters"), "shuffled-40": (False, False, 2, 5, "direct"),
+          "shuffled-300": (False, False, 2, 5, "clusters"), "shuffled-3000": (False, False, 2, 5, "clusters"),
+          "shuffled-6000": (False, False, 2, 5, "supers"), "coincident-300": (False, False, 4, 12, "clusters"),
+          "coincident-3000": (False, False, 4, 12, "clusters")}
+
+
+def _described(name):
+    objs, cam = _scene(name)
+    return np.ascontiguousarray(objs).view(O.OBJECT_DTYPE), _ocam(cam)
+
+
+def test_the_table_above_names_every_shape_scene():
+    assert sorted(SHAPES) == sorted(SHAPE_SCENES) and not set(SHAPE_SCENES) & set(SCENES)
+
+
+@pytest.mark.parametrize("name", SHAPE_SCENES)
+def test_mirror_renders_the_oracles_photons_and_the_planner_gives_the_shape_claimed(name):
+    objs, cam = _described(name)
+    ordered, axis_z, n_parabs, n_planes, table = SHAPES[name]
+    so, sm = O.Scene(objs, cam), M.Scene(objs, cam)
+    n = 30000 if len(objs) < 1000 else (4096 if len(objs) < 5000 else 2048)
+    want, segs = so.render(320, 180, 7, 1, 12345, n, threads=16)
+    got, segs2 = sm.render(320, 180, 7, 1, 12345, n)
+    assert segs == segs2 and got.tobytes() == want.tobytes(), name
+    assert (want["probability"] > 0).any(), name
+    kinds = objs["surface_kind"]
+    assert (M.small_ordered(sm), M.small_axis_z(sm)) == (ordered, axis_z), name
+    assert M.small_counts(sm) == (n_parabs, n_planes), name                      # the flattened tables' counts, which the scan branches on
+    assert (int((kinds == 3).sum()), int(((kinds == 1) | (kinds == 2)).sum())) == (n_parabs, n_planes), name   # ... no record lost or made
+    counts, supers = M.cull_counts(sm, 320, 180, 3, 0, 0, 64), len(M.super_bounds(sm)[0])
+    if table == "direct":
+        assert counts["clusters"] == 0 and counts["groups"] == 0 and supers == 0, (name, counts)
+        assert int((kinds == 0).sum()) == 39        # one more sphere and rl_flatten_scene builds clusters
+    else:
+        assert counts["clusters"] > 0 and counts["members_per_cluster"] in (10, 14) and counts["clusters_per_group"] in (3, 4), (name, counts)
+        assert (supers >= 14 and M.super_bounds(sm)[1] == 8) if table == "supers" else supers == 0, (name, supers)
+
+
+def test_a_permutation_changes_what_the_oracle_renders():
+    """The ties decide something: the same objects in two orders give other segment counts and other photons."""
+    renders = []
+    for name in ("coincident-300", "shuffled-300"):
+        objs, cam = _described(name)
+        back = objs[::-1].copy()
+        a, b = O.Scene(objs, cam).render(320, 180, 7, 1, 0, 30000, threads=16), O.Scene(back, cam).render(320, 180, 7, 1, 0, 30000, threads=16)
+        renders.append((name, a[1], b[1], a[0].tobytes() != b[0].tobytes()))
+    print(renders)
+    assert renders[0][3] and renders[0][1] != renders[0][2], renders   # (shuffled-300 has its two coincident paraboloids alone: printed, not held)
+
+
+def test_every_flag_mix_and_both_cluster_and_group_sizes_occur_over_the_named_scenes():
+    """Over SCENES and SHAPE_SCENES all four values of (small_ordered, small_axis_z) occur.  The plans (members per cluster,
+    clusters per group) the named scenes get are printed; at the time of writing they are (10, 3), (10, 4) and (14, 4), and the
+    shape scenes add none: (14, 3) does not occur.  The planner CAN produce it -- rl_flatten_scene prices all four of
+    {10, 14} x {3, 4} and keeps the cheapest (test_host_mirror.py holds the built-in scene to 14 members and 3 OR 4 clusters a
+    group) -- but no named scene's cost estimate prefers it, and an RL_PLAN override is what reaches it.  Held here: both cluster
+    sizes and both group sizes occur, so every unrolled member loop and both forms of the group round run under the GPU tests."""
+    flags, plans = {}, {}
+    for name in SCENES + SHAPE_SCENES:
+        objs, cam = _described(name)
+        sm = M.Scene(objs, cam)
+        flags.setdefault((M.small_ordered(sm), M.small_axis_z(sm)), []).append(name)
+        counts = M.cull_counts(sm, 320, 180, 3, 0, 0, 16)
+        if counts["clusters"]:
+            plans.setdefault((counts["members_per_cluster"], counts["clusters_per_group"]), []).append(name)
+    print(flags)
+    print(plans)
+    assert sorted(flags) == [(False, False), (False, True), (True, False), (True, True)], flags
+    assert set(plans) <= {(10, 3), (10, 4), (14, 3), (14, 4)}, plans
+    assert {k for k, g in plans} == {10, 14} and {g for k, g in plans} == {3, 4}, plans
+
+
+@pytest.mark.parametrize("name", ["coincident-300", "coincident-3000"])
+def test_a_tenth_of_the_camera_rays_hits_on_a_coincident_scene_tie_exactly(name):
+    objs, cam = _described(name)
+    so = O.Scene(objs, cam)
+    o, d = QR.camera_rays(cam, 1920, 1080, np.random.default_rng(len(name)), 2048 if len(objs) < 1000 else 512)
+    want = oracle_hits(so, o, d)
+    hit = want["object"] != NONE
+    tied = tied_hits(so, want, o, d)
+    share = float(tied[hit].mean())
+    kinds = objs["surface_kind"][want["object"][hit & tied]]
+    print("%s: %d hits, %.1f %% tied; winners of a tie by surface kind %s" % (name, hit.sum(), 100 * share, np.bincount(kinds, minlength=5)))
+    assert hit.sum() >= 256 and share >= 0.10, (name, share)
+
+
+def test_a_twentieth_of_the_far_rays_hits_on_the_built_in_scene_tie_with_another_sphere():
+    objs, cam = _described("demo")
+    so = O.Scene(objs, cam)
+    o, d = far_rays(objs, 4096)
+    assert len(o) >= 4000                                   # (the |d|^2 test drops next to nothing)
+    dist = np.linalg.norm(o.astype(np.float64), axis=1)
+    assert dist.min() < 3e3 and dist.max() > 3e7
+    want = oracle_hits(so, o, d)
+    hit = want["object"] != NONE
+    tied = tied_hits(so, want, o, d, among=np.flatnonzero(objs["surface_kind"] == 0))
+    share = float(tied[hit].mean())
+    print("demo far: %d of %d rays hit, %.1f %% of the hits tied with another sphere" % (hit.sum(), len(o), 100 * share))
+    assert hit.mean() > 0.3 and share >= 0.05, share
