@@ -45,6 +45,10 @@ pub const RL_STEP_NO_ROULETTE: u32 = 1;
     pub direction: RlVector3, pub distance: f32, pub value: f32, pub weight: f32, pub emitter: u32,
     pub status: u32,    // 0 skipped, 1 backfacing, 2 occluded, 3 visible
 } // 32 bytes
+#[repr(C)] #[derive(Copy, Clone, Default)] pub struct RlDirectStats {      // rl_plot_unit_render_direct: what one call did, exact counts
+    pub paths: u64, pub segments: u64, pub light_samples: u64, pub shadow_rays: u64, pub visible: u64,
+    pub endings_kept: u64, pub endings_dropped: u64,
+} // 56 bytes
 
 pub const RL_MAX_PIXELS: usize = 2147483647;
 pub const RL_TASK_MAX_UNITS: usize = 256;
@@ -164,6 +168,9 @@ extern "C" {
     pub fn rl_plot_unit_render_samples_direct_device(u: *mut RlPlotUnit, scene: *const RlScene, primitive_fetch: c_int, seed: u64,
                                                      stream: u32, first_path_index: u64, max_segments: u32,
                                                      device_samples: *const RlCameraSample, n: u32, device_results: *mut RlPathResult) -> c_int;
+    pub fn rl_plot_unit_render_direct(u: *mut RlPlotUnit, scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32,
+                                      first_path_index: u64, n_paths: u64, max_segments: u32, device_results: *mut RlPathResult,
+                                      stats: *mut RlDirectStats) -> c_int;
 
     pub fn rl_gather_unit_create(device: c_int, w: u32, h: u32, out: *mut *mut RlGatherUnit) -> c_int;
     pub fn rl_gather_unit_destroy(u: *mut RlGatherUnit) -> c_int;

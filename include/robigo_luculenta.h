@@ -658,6 +658,49 @@ int rl_plot_unit_render_samples_direct_device(RlPlotUnit* unit, const RlScene* s
                                               uint32_t stream, uint64_t first_path_index, uint32_t max_segments,
                                               const RlCameraSample* device_samples, uint32_t n, RlPathResult* device_results);
 
+/* What one rl_plot_unit_render_direct call did; every field an exact count. */
+typedef struct RlDirectStats {
+    uint64_t paths;           /* n_paths */
+    uint64_t segments;        /* Scene::intersect calls: the sum of RlPathResult::segments */
+    uint64_t light_samples;   /* vertices at which a point was drawn: status != RL_LIGHT_SKIPPED */
+    uint64_t shadow_rays;     /* of those, rays cast: RL_LIGHT_OCCLUDED or RL_LIGHT_VISIBLE */
+    uint64_t visible;         /* of those, RL_LIGHT_VISIBLE */
+    uint64_t endings_kept;    /* paths that ended on an emitter with value != 0 and were splatted */
+    uint64_t endings_dropped; /* ... and were dropped because the vertex before was sampled ("counting light once") */
+} RlDirectStats;              /* 56 bytes */
+
+/* rl_plot_unit_render_direct: direct light over paths of the RNG, into a film, in one persistent launch -- what
+ * rl_scene_camera_rays followed by rl_plot_unit_render_samples_direct does, without the samples, the loop of launches or its
+ * per-path buffers.
+ *   Paths.  Path first_path_index + i, for i < n_paths, is the camera path of that index of stream `stream` under `seed`.  The
+ *   image size is the plot unit's, unit.width x unit.height.  The camera sample is the one rl_scene_camera_rays returns; the path
+ *   from that sample is rl_scene_render_rays' under every one of its rules, max_segments and RL_PATH_END_LIMIT included.
+ *   Film.  The film receives exactly what rl_scene_camera_rays followed by rl_plot_unit_render_samples_direct puts there for the
+ *   same arguments, up to the order of the float atomics: the vertex after every segment gets rl_scene_light_paths' sample (the
+ *   state as rl_scene_step_path_list leaves it, a state the roulette has just ended included); a visible sample with value != 0
+ *   is splatted at the path's screen position, and so is an ending on an emitter under rl_plot_unit_light_paths' drop rule.  A
+ *   path at the segment limit contributes the samples of its vertices and nothing more.
+ *   Results.  device_results may be NULL.  Otherwise it is a device pointer on the unit's device, 16-byte aligned, with room for
+ *   n_paths records; pageable host memory is refused as in the other _device forms.  device_results[i] is bit for bit what
+ *   rl_scene_render_rays writes for that path: direct light does not change the paths.
+ *   Stats.  `stats` may be NULL and is a HOST pointer, written on return.  It depends only on the scene, seed, stream, path range,
+ *   image size and max_segments -- not on the fetch mode, the kernel variant, how the work is handed out or how a range is split
+ *   into calls: each field of [a, b) plus the same field of [b, c) equals that field of [a, c).
+ *   Determinism.  Results and stats are exact; the film differs only by the order of the atomics.
+ *   Arguments, checked in this order, each failure RL_E_INVALID with a message before any device work: a NULL unit; a NULL scene;
+ *   an unknown fetch mode; max_segments > RL_PATH_MAX_SEGMENTS_CAP; path indices that reach 2^64 - 1; device_results not 16-byte
+ *   aligned.  `unit` and `scene` on different devices is RL_E_STATE.  With n_paths == 0 the call does nothing, except that *stats
+ *   becomes all zero.
+ *   n_paths.  Any n_paths is accepted: the host may split the range into several launches, which it queues back to back without
+ *   a synchronise between them, and it reads the counters once at the end.
+ *   Ordering is rl_plot_unit_render_samples': the call first ends a fused render begun into `unit`, runs after everything queued
+ *   into the unit, returns when the splats are in the buffer, and waits for an open launch to drain, as a query does.  One user
+ *   per plot unit at a time; several threads may render into different plot units on one scene at once.
+ *   No scratch memory that grows with n_paths: the call keeps no per-path buffer. */
+int rl_plot_unit_render_direct(RlPlotUnit* unit, const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream,
+                               uint64_t first_path_index, uint64_t n_paths, uint32_t max_segments, RlPathResult* device_results,
+                               RlDirectStats* stats);
+
 /* ---- GatherUnit (gather_unit.rs:24-92) ----------------------------------------------------- */
 
 /* GatherUnit::new(width, height) WITHOUT the implicit read() of ./buffer.raw

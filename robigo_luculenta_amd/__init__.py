@@ -11,7 +11,7 @@ import numpy as np
 from ._lib import (RlAppConfig, RlAppStats, RlCameraDesc, RlCameraSample, RlError, RlIntersection, RlMappedPhoton, RlObjectDesc, RlPathResult,
                    RlPathState, RL_PATH_LIVE, RL_STEP_NO_ROULETTE, RlRay, RlRayHit, RlSceneDesc, RlSpectralRay, RlTask, RlVector3, check, lib, RL_OBJECT_NONE, RL_PATH_END_EMITTER,
                    RL_PATH_END_INVALID, RL_PATH_END_LIMIT, RL_PATH_END_ROULETTE, RL_PATH_END_VOID, RL_PATH_MAX_SEGMENTS,
-                   RL_PATH_MAX_SEGMENTS_CAP, RL_TASK_MAX_UNITS, RlLightSample, RL_LIGHT_SKIPPED, RL_LIGHT_BACKFACING, RL_LIGHT_OCCLUDED,
+                   RL_PATH_MAX_SEGMENTS_CAP, RL_TASK_MAX_UNITS, RlLightSample, RlDirectStats, RL_LIGHT_SKIPPED, RL_LIGHT_BACKFACING, RL_LIGHT_OCCLUDED,
                    RL_LIGHT_VISIBLE)
 
 PHOTON_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("probability", "<f4"), ("wavelength", "<f4")])
@@ -556,6 +556,18 @@ class PlotUnit(_Handle):
         check(lib.rl_plot_unit_render_samples_direct_device(self._h, scene.handle, fetch, seed, stream, first, max_segments, _device_ptr(samples), n,
                                                             _device_ptr(results)))
 
+    def render_direct(self, scene, seed, stream, first_path_index, n_paths, max_segments=0, fetch=FETCH_LDS, results=None):
+        """Direct light over paths of the RNG in one launch (rl_plot_unit_render_direct): camera paths first_path_index ..
+        first_path_index + n_paths - 1 of `stream` under `seed`, on this unit's image size, with render_samples_direct's film.
+        `results`, if given, is a device buffer on the unit's device with data_ptr() (e.g. a torch tensor) with room for n_paths
+        PATH_RESULT_DTYPE records.  Returns the call's RlDirectStats as a dict of exact counts."""
+        if results is not None and not _has_room(n_paths, (results, PATH_RESULT_DTYPE.itemsize)):
+            raise ValueError("results must have room for a 16-byte record for every path")
+        stats = RlDirectStats()
+        check(lib.rl_plot_unit_render_direct(self._h, scene.handle, fetch, seed, stream, first_path_index, n_paths, max_segments,
+                                             _device_ptr(results), C.byref(stats)))
+        return {name: int(getattr(stats, name)) for name, _ in RlDirectStats._fields_}
+
 
 class GatherUnit(_Handle):
     """gather_unit.rs:24-92 (resume is explicit: load())."""
@@ -815,6 +827,14 @@ def light_film_launches():
     library was loaded (rl_debug_light_film_launches); index = 2 * stage + cylinders, as light_launches()."""
     out = (C.c_uint64 * 6)()
     check(lib.rl_debug_light_film_launches(out))
+    return [int(x) for x in out]
+
+
+def direct_launches():
+    """Launches per instantiation of the direct path kernel (PlotUnit.render_direct) since the library was loaded
+    (rl_debug_direct_launches); index = 2 * stage + cylinders, as light_launches()."""
+    out = (C.c_uint64 * 6)()
+    check(lib.rl_debug_direct_launches(out))
     return [int(x) for x in out]
 
 

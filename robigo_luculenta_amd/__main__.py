@@ -1,11 +1,15 @@
 """`python -m robigo_luculenta_amd` -- the reference's main.rs (main.rs:45-67) on one MI355X: renders the
-built-in scene with the App worker pool and writes output.ppm (+ buffer.raw) when the batch budget is done."""
+built-in scene with the App worker pool and writes output.ppm (+ buffer.raw) when the batch budget is done.
+With --direct the image is rendered with direct light (PlotUnit.render_direct), batch by batch over the unit API."""
 import argparse
+import struct
+import time
+import zlib
 
 from . import SCENE_DEMO, SCENE_GLASS_STRESS, app_run
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog="python -m robigo_luculenta_amd")
     ap.add_argument("--width", type=int, default=1280)    # main.rs:47
     ap.add_argument("--height", type=int, default=720)    # main.rs:48
@@ -13,7 +17,7 @@ def main():
     ap.add_argument("--photons-per-batch", type=int, default=64 * 1024 * 512,
                     help="paths per trace task; the reference's 524288 (trace_unit.rs:67) keeps an MI355X busy for "
                          "0.2 ms only, so the default is 64 of those")
-    ap.add_argument("--concurrency", type=int, default=2)
+    ap.add_argument("--concurrency", type=int, default=None, help="default 2")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--scene", choices=["demo", "glass"], default="demo")
@@ -22,8 +26,71 @@ def main():
     ap.add_argument("--checkpoint", default=None, help="buffer.raw to write (and to resume from with --resume)")
     ap.add_argument("--resume", action="store_true")
     ap.add_argument("--quiet", action="store_true")
-    a = ap.parse_args()
+    ap.add_argument("--direct", action="store_true",
+                    help="render with direct light: one PlotUnit.render_direct call per batch, not the App worker pool")
+    ap.add_argument("--max-segments", type=int, default=None, help="with --direct: segments per path (default: the library's)")
+    a = ap.parse_args(argv)
+    if a.direct:
+        for given, flag in ((a.unfused, "--unfused"), (a.concurrency is not None, "--concurrency"), (a.resume, "--resume")):
+            if given:
+                ap.error("%s cannot be combined with --direct: the direct mode makes one render_direct call per batch" % flag)
+    elif a.max_segments is not None:
+        ap.error("--max-segments needs --direct")
+    if a.concurrency is None:
+        a.concurrency = 2
+    return a
+
+
+def write_image(path, rgb, width, height):
+    """(height * width, 3) uint8 as binary PPM, or as PNG for a name that ends in .png."""
+    data = rgb.tobytes()
+    if path.lower().endswith(".png"):
+        def chunk(kind, body):
+            return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xffffffff)
+        rows = b"".join(b"\x00" + data[y * width * 3:(y + 1) * width * 3] for y in range(height))
+        blob = (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", width, height, 8, 2, 0, 0, 0)) +
+                chunk(b"IDAT", zlib.compress(rows, 6)) + chunk(b"IEND", b""))
+    else:
+        blob = b"P6\n%d %d\n255\n" % (width, height) + data
+    with open(path, "wb") as f:
+        f.write(blob)
+
+
+def render_direct(a):
+    """--direct: batch b is paths [b * photons_per_batch, (b + 1) * photons_per_batch) of stream 0, one render_direct call into a
+    plot unit and one GatherUnit.accumulate each; one tonemap at the end."""
+    from . import GatherUnit, PlotUnit, Scene, TonemapUnit
+    scene = Scene.builtin(SCENE_DEMO if a.scene == "demo" else SCENE_GLASS_STRESS, device=a.device)
+    plot = PlotUnit(0, a.width, a.height, device=a.device)
+    gather = GatherUnit(a.width, a.height, device=a.device)
+    total = {}
+    t0 = time.perf_counter()
+    for b in range(a.batches):
+        stats = plot.render_direct(scene, a.seed, 0, b * a.photons_per_batch, a.photons_per_batch, max_segments=a.max_segments or 0)
+        gather.accumulate(plot)
+        for k, v in stats.items():
+            total[k] = total.get(k, 0) + v
+        if not a.quiet:
+            print("batch %d: %s" % (b, ", ".join("%s %d" % kv for kv in stats.items())))
+    tonemap = TonemapUnit(a.width, a.height, device=a.device)
+    tonemap.tonemap(gather)
+    rgb = tonemap.rgb_buffer
+    seconds = time.perf_counter() - t0
+    write_image(a.output, rgb, a.width, a.height)
+    if a.checkpoint:
+        gather.save(a.checkpoint)
+    print("direct light: %s" % ", ".join("%s %d" % kv for kv in total.items()))
+    print("%d batches, %.1f Mpaths, %.1f Mrays and %.1f M shadow rays in %.2f s; wrote %s"
+          % (a.batches, total.get("paths", 0) / 1e6, total.get("segments", 0) / 1e6, total.get("shadow_rays", 0) / 1e6, seconds, a.output))
+    return rgb, total
+
+
+def main(argv=None):
+    a = parse_args(argv)
     print("rendering %d batches at %dx%d" % (a.batches, a.width, a.height))
+    if a.direct:
+        render_direct(a)
+        return
     rgb, st = app_run(a.width, a.height, a.batches, concurrency=a.concurrency, device=a.device, seed=a.seed,
                       photons_per_batch=a.photons_per_batch,
                       scene=SCENE_DEMO if a.scene == "demo" else SCENE_GLASS_STRESS, fused=not a.unfused,

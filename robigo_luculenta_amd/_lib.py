@@ -90,6 +90,11 @@ class RlLightSample(C.Structure):
                 ("emitter", C.c_uint32), ("status", C.c_uint32)]
 
 
+class RlDirectStats(C.Structure):
+    _fields_ = [("paths", C.c_uint64), ("segments", C.c_uint64), ("light_samples", C.c_uint64), ("shadow_rays", C.c_uint64),
+                ("visible", C.c_uint64), ("endings_kept", C.c_uint64), ("endings_dropped", C.c_uint64)]
+
+
 class RlTask(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("unit", C.c_uint32), ("n_units", C.c_uint32),
                 ("units", C.c_uint32 * RL_TASK_MAX_UNITS)]
@@ -183,6 +188,7 @@ SIGNATURES = {
     "rl_plot_unit_light_paths_device": (_i, [_vp, _vp, _i, _u64, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
     "rl_plot_unit_render_samples_direct": (_i, [_vp, _vp, _i, _u64, _u32, _u64, _u32, _vp, _u32, _vp]),
     "rl_plot_unit_render_samples_direct_device": (_i, [_vp, _vp, _i, _u64, _u32, _u64, _u32, _vp, _u32, _vp]),
+    "rl_plot_unit_render_direct": (_i, [_vp, _vp, _i, _u64, _u32, _u64, _u64, _u32, _vp, C.POINTER(RlDirectStats)]),
     "rl_gather_unit_sync": (_i, [_vp]),
     "rl_gather_unit_create": (_i, [_i, _u32, _u32, _pp]),
     "rl_gather_unit_destroy": (_i, [_vp]),
@@ -216,6 +222,7 @@ DEBUG_SIGNATURES = {
     "rl_debug_path_list_launches": (_i, [_vp]),
     "rl_debug_light_launches": (_i, [_vp]),
     "rl_debug_light_film_launches": (_i, [_vp]),
+    "rl_debug_direct_launches": (_i, [_vp]),
     "rl_debug_scene_emitters": (_i, [_vp, _u32, _vp, _u32, C.POINTER(_u32)]),
     "rl_debug_light_sample": (_i, [_vp, _u32, _u64, _u32, _vp, _vp, _u32, _vp, _vp]),
     "rl_debug_prism_probe": (_i, [_vp, _u32, _vp, _u32, _vp]),

@@ -50,6 +50,7 @@
 #include "rl_path_list.hip.h"
 #include "rl_light.hip.h"
 #include "rl_light_film.hip.h"
+#include "rl_direct.hip.h"
 #include "rl_scene.h"
 
 namespace {
@@ -346,7 +347,7 @@ int launch_trace(RlTraceUnit* u, const RlScene* scene, RlMappedPhoton* photons, 
 
 // ---- the persistent ray kernels beside the trace kernel (rl_query.hip.h, rl_occlusion.hip.h, rl_paths.hip.h, rl_step.hip.h, rl_path_list.hip.h) ----
 // A family is one kernel template's six instantiations, index = 2 * stage + cylinders, and the launches of each since the library
-// was loaded (rl_debug_{query,occlusion,path,film,step,path_list,light,light_film}_launches).  P: the kernel's parameters behind the scene blob and its layout.
+// was loaded (rl_debug_{query,occlusion,path,film,step,path_list,light,light_film,direct}_launches).  P: the kernel's parameters behind the scene blob and its layout.
 template <class... P>
 struct KernelFamily {
     void (*variants[6])(const RlF4*, RlSceneLayout, P...);
@@ -361,6 +362,7 @@ KernelFamily<RlPathState*, RlRayHit*, uint32_t, uint64_t, uint32_t, uint32_t, un
 KernelFamily<RlPathState*, RlRayHit*, unsigned long long*> g_list_step_kernels = RL_VARIANTS(rl_list_step_kernel);
 KernelFamily<unsigned long long*> g_light_kernels = RL_VARIANTS(rl_light_kernel);
 KernelFamily<unsigned long long*> g_light_film_kernels = RL_VARIANTS(rl_light_film_kernel);
+KernelFamily<unsigned long long*> g_direct_kernels = RL_VARIANTS(rl_direct_paths_kernel);
 #undef RL_VARIANTS
 template <class... P>
 int family_launches(const KernelFamily<P...>& family, uint64_t* out) {
@@ -434,9 +436,9 @@ void query_ctx_release(int device, QueryCtx* q) {
     std::lock_guard<std::mutex> guard(d->lock);
     d->idle.push_back(q);
 }
-// The context's queue counter (an RlFilmQueue, an RlPathListQueue, an RlLightQueue or an RlLightFilmQueue: a launch's constants sit behind it), allocated on first use.
+// The context's queue counter (an RlFilmQueue, an RlPathListQueue, an RlLightQueue, an RlLightFilmQueue or an RlDirectQueue: a launch's constants sit behind it), allocated on first use.
 int query_ctx_queue(QueryCtx* q) {
-    const size_t bytes = std::max({sizeof(RlFilmQueue), sizeof(RlPathListQueue), sizeof(RlLightQueue), sizeof(RlLightFilmQueue)});
+    const size_t bytes = std::max({sizeof(RlFilmQueue), sizeof(RlPathListQueue), sizeof(RlLightQueue), sizeof(RlLightFilmQueue), sizeof(RlDirectQueue)});
     if (!q->queue) RL_HIP(hipMalloc((void**)&q->queue, bytes));
     return RL_OK;
 }
@@ -2096,6 +2098,43 @@ int direct_chunk(const CallCtx& c, RlPlotUnit* u, const RlScene* scene, int fetc
     return RL_OK;
 }
 
+// rl_plot_unit_render_direct for paths first_path .. first_path + n_paths - 1 (n_paths > 0) on c's stream: the counters behind the
+// context's queue counter zeroed once, then launches of at most RL_DIRECT_LAUNCH paths back to back -- each behind the copy that
+// zeroes the queue counter and writes the launch's block after it (RlDirectQueue, up to its counters) -- and the copy of the
+// counters into `counters`, which holds them when the stream has drained.  `results` may be null.
+#define RL_DIRECT_LAUNCH (1ull << 30)
+int launch_direct(const CallCtx& c, RlPlotUnit* u, const RlScene* scene, int fetch, const PathJob& job, uint64_t first_path, uint64_t n_paths,
+                  RlPathResult* results, unsigned long long* counters) {
+    const int rc = query_ctx_queue(c.q);
+    if (rc != RL_OK) return rc;
+    RlDirectQueue* dq = (RlDirectQueue*)c.q->queue;
+    RL_HIP(hipMemsetAsync(dq->stats, 0, sizeof dq->stats, c.stream));
+    for (uint64_t done = 0; done < n_paths;) {
+        const uint32_t k = (uint32_t)std::min<uint64_t>(n_paths - done, RL_DIRECT_LAUNCH);
+        RlDirectQueue q;
+        std::memset(&q, 0, sizeof q);
+        q.job.results = results ? results + done : nullptr;
+        q.job.emitters = scene->emitters;
+        q.job.emitter_flags = scene->emitter_flags;
+        q.job.seed = job.seed;
+        q.job.first_path = first_path + done;
+        q.job.n_paths = k;
+        q.job.stream = job.stream;
+        q.job.max_segments = job.max_segments;
+        q.job.n_emitters = (uint32_t)scene->emitter_objects.size();
+        q.job.n_objects = scene->emitter_flags ? scene->lay.n_objects : 0u;
+        q.job.aspect_ratio = (float)u->width / (float)u->height; // trace_unit.rs:73, as launch_camera has it
+        q.job.film = film_of(u, scene);
+        // (from pageable memory: the copy has left `q` when the call returns)
+        RL_HIP(hipMemcpyAsync(dq, &q, offsetof(RlDirectQueue, stats), hipMemcpyHostToDevice, c.stream));
+        const int r = launch_persistent(c, g_direct_kernels, scene, fetch, k, c.q->queue);
+        if (r != RL_OK) return r;
+        done += k;
+    }
+    RL_HIP(hipMemcpyAsync(counters, dq->stats, sizeof dq->stats, hipMemcpyDeviceToHost, c.stream));
+    return RL_OK;
+}
+
 int samples_check(const RlPlotUnit* u, const RlScene* scene, int fetch, uint32_t max_segments, uint64_t first_path, const void* samples,
                   uint32_t n, PathJob* job) {
     if (!u) return fail(RL_E_INVALID, "null plot unit");
@@ -2236,6 +2275,35 @@ int rl_plot_unit_render_samples_direct_device(RlPlotUnit* u, const RlScene* scen
         }
         return RL_OK;
     });
+}
+
+int rl_plot_unit_render_direct(RlPlotUnit* u, const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream,
+                               uint64_t first_path_index, uint64_t n_paths, uint32_t max_segments, RlPathResult* device_results,
+                               RlDirectStats* stats) {
+    PathJob job{seed, stream, 0u};
+    if (!u) return fail(RL_E_INVALID, "null plot unit");
+    if (!scene) return fail(RL_E_INVALID, "null scene");
+    if (fetch_check(primitive_fetch) != RL_OK || max_segments_resolve(max_segments, &job.max_segments) != RL_OK) return RL_E_INVALID;
+    if (path_range_check(first_path_index, n_paths) != RL_OK) return RL_E_INVALID;
+    const char* what = "rl_plot_unit_render_direct";
+    int rc = aligned_check(what, "the result buffer", 16, {device_results});
+    if (rc != RL_OK) return rc;
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n_paths == 0) return RL_OK;
+    if (scene->device != u->device) return fail(RL_E_STATE, "scene and plot unit live on different devices");
+    unsigned long long counters[RL_DIRECT_COUNTERS] = {};
+    rc = with_film_ctx(u, {what, "rl_scene_render_rays", {device_results}}, [&](const CallCtx& c) -> int {
+        return launch_direct(c, u, scene, primitive_fetch, job, first_path_index, n_paths, device_results, counters);
+    });
+    if (rc != RL_OK || !stats) return rc;
+    stats->paths = n_paths;
+    stats->segments = counters[RL_DIRECT_SEGMENTS];
+    stats->light_samples = counters[RL_DIRECT_LIGHT_SAMPLES];
+    stats->shadow_rays = counters[RL_DIRECT_SHADOW_RAYS];
+    stats->visible = counters[RL_DIRECT_SHADOW_RAYS] - counters[RL_DIRECT_VISIBLE]; // (the kernel counts the blocked ones)
+    stats->endings_kept = counters[RL_DIRECT_KEPT];
+    stats->endings_dropped = counters[RL_DIRECT_DROPPED];
+    return RL_OK;
 }
 
 // ---- GatherUnit ---------------------------------------------------------------------------------
@@ -2759,6 +2827,7 @@ int rl_debug_step_launches(uint64_t* out) { return family_launches(g_step_kernel
 int rl_debug_path_list_launches(uint64_t* out) { return family_launches(g_list_step_kernels, out); }
 int rl_debug_light_launches(uint64_t* out) { return family_launches(g_light_kernels, out); }
 int rl_debug_light_film_launches(uint64_t* out) { return family_launches(g_light_film_kernels, out); }
+int rl_debug_direct_launches(uint64_t out[6]) { return family_launches(g_direct_kernels, out); }
 
 int rl_debug_scene_emitters(const RlObjectDesc* objects, uint32_t n_objects, uint32_t* out, uint32_t cap, uint32_t* n_emitters) {
     if ((!objects && n_objects) || !n_emitters) return fail(RL_E_INVALID, "null argument");
