@@ -34,6 +34,11 @@ pub const RL_PATH_END_LIMIT: u32 = 3;
 pub const RL_PATH_END_INVALID: u32 = 4;
 pub const RL_PATH_MAX_SEGMENTS: u32 = 4096;
 pub const RL_PATH_MAX_SEGMENTS_CAP: u32 = 65536;
+pub const RL_FEATURE_VOID: u32 = 0;
+pub const RL_FEATURE_EMITTER: u32 = 1;
+pub const RL_FEATURE_DIFFUSE: u32 = 2;
+pub const RL_FEATURE_LIMIT: u32 = 3;
+pub const RL_FEATURE_MAX_SEGMENTS: u32 = 64;
 // one turn of render_ray's loop at a time on states the caller holds (rl_scene_begin_paths*, rl_scene_step_paths*)
 #[repr(C)] #[derive(Copy, Clone)] pub struct RlPathState {
     pub origin: RlVector3, pub wavelength: f32, pub direction: RlVector3, pub intensity: f32, pub continue_chance: f32,
@@ -49,6 +54,15 @@ pub const RL_STEP_NO_ROULETTE: u32 = 1;
     pub paths: u64, pub segments: u64, pub light_samples: u64, pub shadow_rays: u64, pub visible: u64,
     pub endings_kept: u64, pub endings_dropped: u64,
 } // 56 bytes
+#[repr(C)] #[derive(Copy, Clone)] pub struct RlFeatureSample {             // rl_scene_render_features: the guide record of one path
+    pub x: f32, pub y: f32, pub wavelength: f32, pub albedo: f32, pub normal: RlVector3, pub depth: f32,
+    pub object: u32, pub segments: u32,
+    pub kind: u32,      // RL_FEATURE_*
+    pub reserved: u32,
+} // 48 bytes
+#[repr(C)] #[derive(Copy, Clone, Default)] pub struct RlFeatureStats {     // rl_scene_render_features: what one call did, exact counts
+    pub paths: u64, pub segments: u64, pub kinds: [u64; 4],
+} // 48 bytes
 
 pub const RL_MAX_PIXELS: usize = 2147483647;
 pub const RL_TASK_MAX_UNITS: usize = 256;
@@ -171,6 +185,10 @@ extern "C" {
     pub fn rl_plot_unit_render_direct(u: *mut RlPlotUnit, scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32,
                                       first_path_index: u64, n_paths: u64, max_segments: u32, device_results: *mut RlPathResult,
                                       stats: *mut RlDirectStats) -> c_int;
+    pub fn rl_scene_render_features(scene: *const RlScene, primitive_fetch: c_int, width: u32, height: u32, seed: u64, stream: u32,
+                                    first_path_index: u64, n_paths: u64, max_segments: u32, albedo: *mut RlPlotUnit,
+                                    normal: *mut RlPlotUnit, aux: *mut RlPlotUnit, device_records: *mut RlFeatureSample,
+                                    stats: *mut RlFeatureStats) -> c_int;
 
     pub fn rl_gather_unit_create(device: c_int, w: u32, h: u32, out: *mut *mut RlGatherUnit) -> c_int;
     pub fn rl_gather_unit_destroy(u: *mut RlGatherUnit) -> c_int;

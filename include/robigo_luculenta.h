@@ -701,6 +701,84 @@ int rl_plot_unit_render_direct(RlPlotUnit* unit, const RlScene* scene, int primi
                                uint64_t first_path_index, uint64_t n_paths, uint32_t max_segments, RlPathResult* device_results,
                                RlDirectStats* stats);
 
+/* ---- denoising guides: albedo, shading normal and depth films (rl_scene_render_features) ---- */
+
+enum RlFeatureKind {
+    RL_FEATURE_VOID = 0,    /* the feature path left the scene */
+    RL_FEATURE_EMITTER = 1, /* it reached a light */
+    RL_FEATURE_DIFFUSE = 2, /* it reached a diffuse surface */
+    RL_FEATURE_LIMIT = 3    /* it was still in mirrors, glass or bubbles after max_segments segments */
+};
+
+typedef struct RlFeatureSample {
+    float x, y;          /* screen position: RlCameraSample x, y of the path */
+    float wavelength;    /* nm */
+    float albedo;        /* below; 0 for VOID and LIMIT */
+    RlVector3 normal;    /* below; zero for VOID and LIMIT */
+    float depth;         /* distance of the path's FIRST segment's hit (the camera ray is unit length); 0 if it hit nothing */
+    uint32_t object;     /* the object at the feature vertex (EMITTER, DIFFUSE); RL_OBJECT_NONE otherwise */
+    uint32_t segments;   /* Scene::intersect calls made for this record */
+    uint32_t kind;       /* enum RlFeatureKind */
+    uint32_t reserved;   /* written 0 */
+} RlFeatureSample;       /* 48 bytes */
+
+/* What one rl_scene_render_features call did; every field an exact count. */
+typedef struct RlFeatureStats {
+    uint64_t paths, segments, kinds[4]; /* n_paths; the sum of RlFeatureSample::segments; records per RlFeatureKind */
+} RlFeatureStats;                       /* 48 bytes */
+
+#define RL_FEATURE_MAX_SEGMENTS 64 /* max_segments = 0 */
+
+/* rl_scene_render_features: the per-pixel guide images a denoiser or an edge-aware filter wants beside a noisy image -- the
+ * albedo, the shading normal and the depth of what each pixel shows -- for paths of the RNG, accumulated with the image's own
+ * reconstruction, in one persistent launch.  A guide taken at the first hit would show glass, so the guide follows the path
+ * through mirrors, glass and bubbles to the first diffuse surface or light.
+ *   The feature path of path first_path_index + i, for i < n_paths, is defined by public calls: take the sample
+ *   rl_scene_camera_rays(scene, width, height, seed, stream, ...) returns for that index, pass it through rl_scene_begin_paths,
+ *   then call rl_scene_step_paths with RL_STEP_NO_ROULETTE and hits, one segment at a time.  After each step, the first rule that
+ *   applies ends the feature path:
+ *     state.end == RL_PATH_END_VOID: VOID.
+ *     state.end == RL_PATH_END_EMITTER: EMITTER; albedo = state.intensity, the throughput that reached the light (the step leaves
+ *       it as it was); object = hits.object.
+ *     the hit object's material is RL_MATERIAL_DIFFUSE_GREY or RL_MATERIAL_DIFFUSE_COLOURED: DIFFUSE; albedo = state.intensity
+ *       after that step, the product of every `probability` factor from the camera up to and including the diffuse bounce;
+ *       object = hits.object.
+ *     state.segments == max_segments: LIMIT.
+ *     otherwise (glossy mirror, SF10 glass, soap bubble) the path goes on.
+ *   The path follows the true path's RNG blocks, 2 + segments: the feature vertex is a vertex of the path the renderer traces for
+ *   that index, up to the roulette.
+ *   The normal is hits.normal of the feature vertex, turned to face the ray that arrived: with d the state's direction before
+ *   that step, normal = dot(d, n) < 0 ? n : -n (strict; -n flips each component's sign bit, so +0 becomes -0).
+ *   max_segments = 0 means RL_FEATURE_MAX_SEGMENTS; otherwise it is 1 .. RL_PATH_MAX_SEGMENTS_CAP.
+ *   The films.  Any of the three plot units may be NULL; that film is not written.  Each film takes rl_plot_unit_plot_photons'
+ *   splat: the four pixels and weights of x, y under the unit's width, height and aspect ratio, each colour component times each
+ *   weight added with f32 atomics onto what the buffer holds.
+ *     albedo: colour get_tristimulus(wavelength) * albedo, only if albedo != 0 -- exactly rl_plot_unit_plot_photons of the photon
+ *       {x, y, albedo, wavelength}.
+ *     normal: colour (normal.x, normal.y, normal.z), for EMITTER and DIFFUSE.
+ *     aux: colour (1, depth, (float)segments), for every path.
+ *   Consumers normalise: aux.x is the reconstruction weight, aux.y / aux.x the mean depth, normal / |normal| the mean normal.
+ *   Given units must be three distinct handles, else RL_E_INVALID; they must be width x height and on the scene's device, else
+ *   RL_E_STATE and nothing is written.  They are plot units so that rl_gather_unit_accumulate, rl_plot_unit_reduce / _add,
+ *   _download and _clear work on guides unchanged.
+ *   Records.  device_records may be NULL.  Otherwise it is device memory on the scene's device, 16-byte aligned, with room for
+ *   n_paths records; pageable host memory is refused as in the other _device forms.  All 48 bytes of every record are written.
+ *   Stats.  `stats` may be NULL and is a HOST pointer, written on return; all zero for n_paths == 0.  It is exact, additive over
+ *   any split of a range ([a, b) plus [b, c) equals [a, c)), and independent of the fetch mode, the kernel variant and how the work
+ *   is handed out.
+ *   Determinism.  Records and stats are exact; the films differ only by the order of the atomics.
+ *   Arguments, checked in this order, each failure RL_E_INVALID with a message before any device work: a NULL scene; an unknown
+ *   fetch mode; width or height 0, or width * height > RL_MAX_PIXELS; max_segments > RL_PATH_MAX_SEGMENTS_CAP; path indices that
+ *   reach 2^64 - 1; device_records not 16-byte aligned; two given units that are the same handle.
+ *   Ordering is rl_plot_unit_render_direct's, for each given unit: the call ends a fused render begun into the unit, runs after
+ *   everything queued into it, returns when the splats are in the buffers, and waits for an open launch to drain, as a query
+ *   does.  Any n_paths is accepted: launches of at most 2^30 paths queued back to back, the counters read once.  No scratch
+ *   memory that grows with n_paths. */
+int rl_scene_render_features(const RlScene* scene, int primitive_fetch, uint32_t width, uint32_t height, uint64_t seed,
+                             uint32_t stream, uint64_t first_path_index, uint64_t n_paths, uint32_t max_segments,
+                             RlPlotUnit* albedo, RlPlotUnit* normal, RlPlotUnit* aux, RlFeatureSample* device_records,
+                             RlFeatureStats* stats);
+
 /* ---- GatherUnit (gather_unit.rs:24-92) ----------------------------------------------------- */
 
 /* GatherUnit::new(width, height) WITHOUT the implicit read() of ./buffer.raw

@@ -62,6 +62,9 @@ int rl_debug_light_film_launches(uint64_t* out);
 /* out[v], v = 0..5: launches of instantiation v of the direct path kernel (rl_plot_unit_render_direct) since the library was
  * loaded, indexed as rl_debug_query_launches is. */
 int rl_debug_direct_launches(uint64_t out[6]);
+/* out[v], v = 0..5: launches of instantiation v of the feature path kernel (rl_scene_render_features) since the library was
+ * loaded, indexed as rl_debug_query_launches is. */
+int rl_debug_feature_launches(uint64_t out[6]);
 /* rl_scene_emitters for a description instead of a scene: the sampleable emitters' object indices in scan order, by the function
  * rl_scene_create builds a scene's table with.  Host arithmetic only: callable without a GPU.  The same capacity protocol. */
 int rl_debug_scene_emitters(const RlObjectDesc* objects, uint32_t n_objects, uint32_t* out, uint32_t cap, uint32_t* n_emitters);

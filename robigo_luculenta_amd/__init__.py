@@ -12,7 +12,8 @@ from ._lib import (RlAppConfig, RlAppStats, RlCameraDesc, RlCameraSample, RlErro
                    RlPathState, RL_PATH_LIVE, RL_STEP_NO_ROULETTE, RlRay, RlRayHit, RlSceneDesc, RlSpectralRay, RlTask, RlVector3, check, lib, RL_OBJECT_NONE, RL_PATH_END_EMITTER,
                    RL_PATH_END_INVALID, RL_PATH_END_LIMIT, RL_PATH_END_ROULETTE, RL_PATH_END_VOID, RL_PATH_MAX_SEGMENTS,
                    RL_PATH_MAX_SEGMENTS_CAP, RL_TASK_MAX_UNITS, RlLightSample, RlDirectStats, RL_LIGHT_SKIPPED, RL_LIGHT_BACKFACING, RL_LIGHT_OCCLUDED,
-                   RL_LIGHT_VISIBLE)
+                   RL_LIGHT_VISIBLE, RlFeatureSample, RlFeatureStats, RL_FEATURE_VOID, RL_FEATURE_EMITTER, RL_FEATURE_DIFFUSE, RL_FEATURE_LIMIT,
+                   RL_FEATURE_MAX_SEGMENTS)
 
 PHOTON_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("probability", "<f4"), ("wavelength", "<f4")])
 OBJECT_DTYPE = np.dtype([("surface_kind", "<u4"), ("material_kind", "<u4"), ("v0", "<f4", 3), ("v1", "<f4", 3),
@@ -32,9 +33,13 @@ PATH_STATE_DTYPE = np.dtype([("origin", "<f4", 3), ("wavelength", "<f4"), ("dire
 # Scene.light_paths records: RlLightSample (32 bytes)
 LIGHT_SAMPLE_DTYPE = np.dtype([("direction", "<f4", 3), ("distance", "<f4"), ("value", "<f4"), ("weight", "<f4"), ("emitter", "<u4"),
                                ("status", "<u4")])
+# Scene.render_features records: RlFeatureSample (48 bytes)
+FEATURE_SAMPLE_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("wavelength", "<f4"), ("albedo", "<f4"), ("normal", "<f4", 3), ("depth", "<f4"),
+                                 ("object", "<u4"), ("segments", "<u4"), ("kind", "<u4"), ("reserved", "<u4")])
 NUMBER_OF_PHOTONS = 1024 * 512  # trace_unit.rs:67
 
 SCENE_DEMO, SCENE_GLASS_STRESS = 0, 1
+FEATURE_VOID, FEATURE_EMITTER, FEATURE_DIFFUSE, FEATURE_LIMIT = RL_FEATURE_VOID, RL_FEATURE_EMITTER, RL_FEATURE_DIFFUSE, RL_FEATURE_LIMIT
 FETCH_LDS, FETCH_GLOBAL = 0, 1
 TASK_SLEEP, TASK_TRACE, TASK_PLOT, TASK_GATHER, TASK_TONEMAP = range(5)
 
@@ -367,6 +372,21 @@ class Scene(_Handle):
         n_list = _device_list(list, n_list, n)
         check(lib.rl_scene_light_paths_device(self._h, fetch, seed, stream, _device_ptr(states), n, _device_ptr(list), n_list, _device_ptr(hits),
                                               _device_ptr(samples)))
+
+    def render_features(self, width, height, seed, stream, first, n, max_segments=0, fetch=FETCH_LDS, albedo=None, normal=None, aux=None,
+                        records=None):
+        """rl_scene_render_features: the denoising guides of camera paths first .. first + n - 1 of `stream` under `seed` for a
+        width x height image, in one launch.  `albedo`, `normal` and `aux` are None or three distinct PlotUnits of that size on
+        the scene's device; each receives its film's splats on top of what it holds.  `records`, if given, is a device buffer on
+        the scene's device with data_ptr() (e.g. a torch tensor) with room for n FEATURE_SAMPLE_DTYPE records.  Returns the call's
+        RlFeatureStats as a dict of exact counts: paths, segments and kinds (a list indexed by FEATURE_VOID .. FEATURE_LIMIT)."""
+        if records is not None and not _has_room(n, (records, FEATURE_SAMPLE_DTYPE.itemsize)):
+            raise ValueError("records must have room for a 48-byte record for every path")
+        stats = RlFeatureStats()
+        check(lib.rl_scene_render_features(self._h, fetch, width, height, seed, stream, first, n, max_segments,
+                                           *[u.handle if u is not None else None for u in (albedo, normal, aux)], _device_ptr(records),
+                                           C.byref(stats)))
+        return {"paths": int(stats.paths), "segments": int(stats.segments), "kinds": [int(k) for k in stats.kinds]}
 
 
 class TraceUnit(_Handle):
@@ -835,6 +855,14 @@ def direct_launches():
     (rl_debug_direct_launches); index = 2 * stage + cylinders, as light_launches()."""
     out = (C.c_uint64 * 6)()
     check(lib.rl_debug_direct_launches(out))
+    return [int(x) for x in out]
+
+
+def feature_launches():
+    """Launches per instantiation of the feature path kernel (Scene.render_features) since the library was loaded
+    (rl_debug_feature_launches); index = 2 * stage + cylinders, as light_launches()."""
+    out = (C.c_uint64 * 6)()
+    check(lib.rl_debug_feature_launches(out))
     return [int(x) for x in out]
 
 

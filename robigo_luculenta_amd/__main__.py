@@ -1,6 +1,7 @@
 """`python -m robigo_luculenta_amd` -- the reference's main.rs (main.rs:45-67) on one MI355X: renders the
 built-in scene with the App worker pool and writes output.ppm (+ buffer.raw) when the batch budget is done.
-With --direct the image is rendered with direct light (PlotUnit.render_direct), batch by batch over the unit API."""
+With --direct the image is rendered with direct light (PlotUnit.render_direct), batch by batch over the unit API.
+With --features PREFIX the denoising guides of the same paths (Scene.render_features) are written beside the image."""
 import argparse
 import struct
 import time
@@ -28,14 +29,18 @@ def parse_args(argv=None):
     ap.add_argument("--quiet", action="store_true")
     ap.add_argument("--direct", action="store_true",
                     help="render with direct light: one PlotUnit.render_direct call per batch, not the App worker pool")
-    ap.add_argument("--max-segments", type=int, default=None, help="with --direct: segments per path (default: the library's)")
+    ap.add_argument("--max-segments", type=int, default=None,
+                    help="with --direct or --features: segments per path (default: the library's)")
+    ap.add_argument("--features", metavar="PREFIX", default=None,
+                    help="after the image, write the denoising guides of the same paths: PREFIX.npz (albedo_xyz, normal, aux: raw sums), "
+                         "PREFIX-normal.png and PREFIX-depth.png")
     a = ap.parse_args(argv)
     if a.direct:
         for given, flag in ((a.unfused, "--unfused"), (a.concurrency is not None, "--concurrency"), (a.resume, "--resume")):
             if given:
                 ap.error("%s cannot be combined with --direct: the direct mode makes one render_direct call per batch" % flag)
-    elif a.max_segments is not None:
-        ap.error("--max-segments needs --direct")
+    elif a.max_segments is not None and a.features is None:
+        ap.error("--max-segments needs --direct or --features")
     if a.concurrency is None:
         a.concurrency = 2
     return a
@@ -85,11 +90,46 @@ def render_direct(a):
     return rgb, total
 
 
+def render_features(a):
+    """--features PREFIX: batch b is paths [b * photons_per_batch, (b + 1) * photons_per_batch) of stream 0, one render_features
+    call into three plot units and one GatherUnit.accumulate for each; PREFIX.npz holds the raw sums as float32 (h, w, 3) arrays,
+    PREFIX-normal.png the mean normal and PREFIX-depth.png the mean depth over its maximum."""
+    import numpy as np
+    from . import GatherUnit, PlotUnit, Scene
+    scene = Scene.builtin(SCENE_DEMO if a.scene == "demo" else SCENE_GLASS_STRESS, device=a.device)
+    names = ("albedo_xyz", "normal", "aux")
+    plots = [PlotUnit(k, a.width, a.height, device=a.device) for k in range(3)]
+    gathers = [GatherUnit(a.width, a.height, device=a.device) for _ in range(3)]
+    total = {"paths": 0, "segments": 0, "kinds": [0, 0, 0, 0]}
+    for b in range(a.batches):
+        stats = scene.render_features(a.width, a.height, a.seed, 0, b * a.photons_per_batch, a.photons_per_batch,
+                                      max_segments=a.max_segments or 0, albedo=plots[0], normal=plots[1], aux=plots[2])
+        for gather, plot in zip(gathers, plots):
+            gather.accumulate(plot)
+        total["paths"] += stats["paths"]
+        total["segments"] += stats["segments"]
+        total["kinds"] = [x + y for x, y in zip(total["kinds"], stats["kinds"])]
+    films = {name: gather.tristimulus_buffer.reshape(a.height, a.width, 3) for name, gather in zip(names, gathers)}
+    np.savez(a.features + ".npz", **films)
+    normal, aux = films["normal"].astype(np.float64), films["aux"].astype(np.float64)
+    length = np.sqrt((normal * normal).sum(axis=2, keepdims=True))
+    unit = np.divide(normal, length, out=np.zeros_like(normal), where=length > 0)
+    write_image(a.features + "-normal.png", np.clip((unit * 0.5 + 0.5) * 255.0 + 0.5, 0, 255).astype(np.uint8).reshape(-1, 3), a.width, a.height)
+    depth = np.divide(aux[:, :, 1], aux[:, :, 0], out=np.zeros(aux.shape[:2]), where=aux[:, :, 0] > 0)
+    grey = np.clip(depth / (depth.max() if depth.max() > 0 else 1.0) * 255.0 + 0.5, 0, 255).astype(np.uint8)
+    write_image(a.features + "-depth.png", np.repeat(grey.reshape(-1, 1), 3, axis=1), a.width, a.height)
+    print("features: paths %d, segments %d, void %d, emitter %d, diffuse %d, limit %d; wrote %s.npz"
+          % ((total["paths"], total["segments"]) + tuple(total["kinds"]) + (a.features,)))
+    return films, total
+
+
 def main(argv=None):
     a = parse_args(argv)
     print("rendering %d batches at %dx%d" % (a.batches, a.width, a.height))
     if a.direct:
         render_direct(a)
+        if a.features is not None:
+            render_features(a)
         return
     rgb, st = app_run(a.width, a.height, a.batches, concurrency=a.concurrency, device=a.device, seed=a.seed,
                       photons_per_batch=a.photons_per_batch,
@@ -98,6 +138,8 @@ def main(argv=None):
     print("%d trace tasks, %.1f Mpaths, %.1f Mrays in %.2f s (%.1f Mrays/s, %.1f reference batches/sec); wrote %s"
           % (st["batches"], st["paths"] / 1e6, st["segments"] / 1e6, st["seconds"], st["segments"] / st["seconds"] / 1e6,
              st["paths"] / 524288.0 / st["seconds"], a.output))
+    if a.features is not None:
+        render_features(a)
 
 
 if __name__ == "__main__":

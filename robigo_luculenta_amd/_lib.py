@@ -95,6 +95,19 @@ class RlDirectStats(C.Structure):
                 ("visible", C.c_uint64), ("endings_kept", C.c_uint64), ("endings_dropped", C.c_uint64)]
 
 
+RL_FEATURE_VOID, RL_FEATURE_EMITTER, RL_FEATURE_DIFFUSE, RL_FEATURE_LIMIT = range(4)
+RL_FEATURE_MAX_SEGMENTS = 64
+
+
+class RlFeatureSample(C.Structure):
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("wavelength", C.c_float), ("albedo", C.c_float), ("normal", RlVector3),
+                ("depth", C.c_float), ("object", C.c_uint32), ("segments", C.c_uint32), ("kind", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RlFeatureStats(C.Structure):
+    _fields_ = [("paths", C.c_uint64), ("segments", C.c_uint64), ("kinds", C.c_uint64 * 4)]
+
+
 class RlTask(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("unit", C.c_uint32), ("n_units", C.c_uint32),
                 ("units", C.c_uint32 * RL_TASK_MAX_UNITS)]
@@ -189,6 +202,7 @@ SIGNATURES = {
     "rl_plot_unit_render_samples_direct": (_i, [_vp, _vp, _i, _u64, _u32, _u64, _u32, _vp, _u32, _vp]),
     "rl_plot_unit_render_samples_direct_device": (_i, [_vp, _vp, _i, _u64, _u32, _u64, _u32, _vp, _u32, _vp]),
     "rl_plot_unit_render_direct": (_i, [_vp, _vp, _i, _u64, _u32, _u64, _u64, _u32, _vp, C.POINTER(RlDirectStats)]),
+    "rl_scene_render_features": (_i, [_vp, _i, _u32, _u32, _u64, _u32, _u64, _u64, _u32, _vp, _vp, _vp, _vp, C.POINTER(RlFeatureStats)]),
     "rl_gather_unit_sync": (_i, [_vp]),
     "rl_gather_unit_create": (_i, [_i, _u32, _u32, _pp]),
     "rl_gather_unit_destroy": (_i, [_vp]),
@@ -223,6 +237,7 @@ DEBUG_SIGNATURES = {
     "rl_debug_light_launches": (_i, [_vp]),
     "rl_debug_light_film_launches": (_i, [_vp]),
     "rl_debug_direct_launches": (_i, [_vp]),
+    "rl_debug_feature_launches": (_i, [_vp]),
     "rl_debug_scene_emitters": (_i, [_vp, _u32, _vp, _u32, C.POINTER(_u32)]),
     "rl_debug_light_sample": (_i, [_vp, _u32, _u64, _u32, _vp, _vp, _u32, _vp, _vp]),
     "rl_debug_prism_probe": (_i, [_vp, _u32, _vp, _u32, _vp]),

@@ -51,6 +51,7 @@
 #include "rl_light.hip.h"
 #include "rl_light_film.hip.h"
 #include "rl_direct.hip.h"
+#include "rl_features.hip.h"
 #include "rl_scene.h"
 
 namespace {
@@ -347,7 +348,7 @@ int launch_trace(RlTraceUnit* u, const RlScene* scene, RlMappedPhoton* photons, 
 
 // ---- the persistent ray kernels beside the trace kernel (rl_query.hip.h, rl_occlusion.hip.h, rl_paths.hip.h, rl_step.hip.h, rl_path_list.hip.h) ----
 // A family is one kernel template's six instantiations, index = 2 * stage + cylinders, and the launches of each since the library
-// was loaded (rl_debug_{query,occlusion,path,film,step,path_list,light,light_film,direct}_launches).  P: the kernel's parameters behind the scene blob and its layout.
+// was loaded (rl_debug_{query,occlusion,path,film,step,path_list,light,light_film,direct,feature}_launches).  P: the kernel's parameters behind the scene blob and its layout.
 template <class... P>
 struct KernelFamily {
     void (*variants[6])(const RlF4*, RlSceneLayout, P...);
@@ -363,6 +364,7 @@ KernelFamily<RlPathState*, RlRayHit*, unsigned long long*> g_list_step_kernels =
 KernelFamily<unsigned long long*> g_light_kernels = RL_VARIANTS(rl_light_kernel);
 KernelFamily<unsigned long long*> g_light_film_kernels = RL_VARIANTS(rl_light_film_kernel);
 KernelFamily<unsigned long long*> g_direct_kernels = RL_VARIANTS(rl_direct_paths_kernel);
+KernelFamily<unsigned long long*> g_feature_kernels = RL_VARIANTS(rl_feature_paths_kernel);
 #undef RL_VARIANTS
 template <class... P>
 int family_launches(const KernelFamily<P...>& family, uint64_t* out) {
@@ -436,9 +438,9 @@ void query_ctx_release(int device, QueryCtx* q) {
     std::lock_guard<std::mutex> guard(d->lock);
     d->idle.push_back(q);
 }
-// The context's queue counter (an RlFilmQueue, an RlPathListQueue, an RlLightQueue, an RlLightFilmQueue or an RlDirectQueue: a launch's constants sit behind it), allocated on first use.
+// The context's queue counter (an RlFilmQueue, an RlPathListQueue, an RlLightQueue, an RlLightFilmQueue, an RlDirectQueue or an RlFeatureQueue: a launch's constants sit behind it), allocated on first use.
 int query_ctx_queue(QueryCtx* q) {
-    const size_t bytes = std::max({sizeof(RlFilmQueue), sizeof(RlPathListQueue), sizeof(RlLightQueue), sizeof(RlLightFilmQueue), sizeof(RlDirectQueue)});
+    const size_t bytes = std::max({sizeof(RlFilmQueue), sizeof(RlPathListQueue), sizeof(RlLightQueue), sizeof(RlLightFilmQueue), sizeof(RlDirectQueue), sizeof(RlFeatureQueue)});
     if (!q->queue) RL_HIP(hipMalloc((void**)&q->queue, bytes));
     return RL_OK;
 }
@@ -2306,6 +2308,106 @@ int rl_plot_unit_render_direct(RlPlotUnit* u, const RlScene* scene, int primitiv
     return RL_OK;
 }
 
+// ---- denoising guides (rl_scene_render_features, rl_features.hip.h) ------------------------------------------------------------
+namespace {
+// rl_scene_render_features for paths first_path .. first_path + n_paths - 1 (n_paths > 0) on c's stream, which is the first given
+// unit's: behind what is queued into the other given units (their `ready`), the counters behind the context's queue counter zeroed
+// once, then launches of at most RL_FEATURE_LAUNCH paths back to back -- each behind the copy that zeroes the queue counter and
+// writes the launch's block after it (RlFeatureQueue, up to its counters) -- the copy of the counters into `counters`, which
+// holds them when the stream has drained, and the other given units' streams behind all of it (their `tail`).  `units` are the
+// albedo, normal and aux units; any may be null, and so may `records`.
+#define RL_FEATURE_LAUNCH (1ull << 30)
+int launch_features(const CallCtx& c, const RlScene* scene, int fetch, const PathJob& job, uint32_t width, uint32_t height, uint64_t first_path,
+                    uint64_t n_paths, RlPlotUnit* const units[3], RlFeatureSample* records, unsigned long long* counters) {
+    const int rc = query_ctx_queue(c.q);
+    if (rc != RL_OK) return rc;
+    for (int k = 0; k < 3; ++k) {
+        RlPlotUnit* o = units[k];
+        if (!o || o->stream == c.stream) continue;
+        RL_HIP(hipEventRecord(o->ready, o->stream));
+        RL_HIP(hipStreamWaitEvent(c.stream, o->ready, 0));
+    }
+    RlFeatureQueue* fq = (RlFeatureQueue*)c.q->queue;
+    RL_HIP(hipMemsetAsync(fq->stats, 0, sizeof fq->stats, c.stream));
+    for (uint64_t done = 0; done < n_paths;) {
+        const uint32_t k = (uint32_t)std::min<uint64_t>(n_paths - done, RL_FEATURE_LAUNCH);
+        RlFeatureQueue q;
+        std::memset(&q, 0, sizeof q);
+        q.job.records = records ? records + done : nullptr;
+        q.job.albedo = units[0] ? units[0]->xyz : nullptr;
+        q.job.normal = units[1] ? units[1]->xyz : nullptr;
+        q.job.aux = units[2] ? units[2]->xyz : nullptr;
+        q.job.seed = job.seed;
+        q.job.first_path = first_path + done;
+        q.job.n_paths = k;
+        q.job.stream = job.stream;
+        q.job.max_segments = job.max_segments;
+        q.job.width = width;
+        q.job.height = height;
+        q.job.wm1 = (float)(int)width - 1.0f;
+        q.job.hm1 = (float)(int)height - 1.0f;
+        q.job.aspect_ratio = (float)width / (float)height; // trace_unit.rs:73 and plot_unit.rs:48, as launch_camera and film_of have it
+        q.job.off_cie = scene->lay.off_cie;
+        // (from pageable memory: the copy has left `q` when the call returns)
+        RL_HIP(hipMemcpyAsync(fq, &q, offsetof(RlFeatureQueue, stats), hipMemcpyHostToDevice, c.stream));
+        const int r = launch_persistent(c, g_feature_kernels, scene, fetch, k, c.q->queue);
+        if (r != RL_OK) return r;
+        done += k;
+    }
+    RL_HIP(hipMemcpyAsync(counters, fq->stats, sizeof fq->stats, hipMemcpyDeviceToHost, c.stream));
+    for (int k = 0; k < 3; ++k) {
+        RlPlotUnit* o = units[k];
+        if (!o || o->stream == c.stream) continue;
+        RL_HIP(hipEventRecord(o->tail, c.stream));
+        RL_HIP(hipStreamWaitEvent(o->stream, o->tail, 0));
+    }
+    return RL_OK;
+}
+} // namespace
+
+int rl_scene_render_features(const RlScene* scene, int primitive_fetch, uint32_t width, uint32_t height, uint64_t seed, uint32_t stream,
+                             uint64_t first_path_index, uint64_t n_paths, uint32_t max_segments, RlPlotUnit* albedo, RlPlotUnit* normal,
+                             RlPlotUnit* aux, RlFeatureSample* device_records, RlFeatureStats* stats) {
+    const char* what = "rl_scene_render_features";
+    PathJob job{seed, stream, 0u};
+    if (!scene) return fail(RL_E_INVALID, "null scene");
+    if (fetch_check(primitive_fetch) != RL_OK) return RL_E_INVALID;
+    if (width == 0 || height == 0) return fail(RL_E_INVALID, std::string(what) + ": zero image size");
+    if (check_image_size(what, width, height) != RL_OK) return RL_E_INVALID;
+    if (max_segments_resolve(max_segments, &job.max_segments) != RL_OK) return RL_E_INVALID;
+    if (max_segments == 0u) job.max_segments = RL_FEATURE_MAX_SEGMENTS;
+    if (path_range_check(first_path_index, n_paths) != RL_OK) return RL_E_INVALID;
+    int rc = aligned_check(what, "the record buffer", 16, {device_records});
+    if (rc != RL_OK) return rc;
+    RlPlotUnit* const units[3] = {albedo, normal, aux};
+    if ((albedo && (albedo == normal || albedo == aux)) || (normal && normal == aux))
+        return fail(RL_E_INVALID, std::string(what) + ": the albedo, normal and aux units must be distinct plot units");
+    if (n_paths == 0) {
+        if (stats) std::memset(stats, 0, sizeof *stats);
+        return RL_OK;
+    }
+    RlPlotUnit* first = nullptr;
+    for (RlPlotUnit* u : units) {
+        if (!u) continue;
+        if (u->device != scene->device) return fail(RL_E_STATE, "scene and plot unit live on different devices");
+        if (u->width != width || u->height != height)
+            return fail(RL_E_STATE, std::string(what) + ": a plot unit is not " + std::to_string(width) + " x " + std::to_string(height));
+        if (!first) first = u;
+    }
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    for (RlPlotUnit* u : units) // a fused render begun into a given unit ends first (with_call_ctx: the first one's)
+        if (u && u != first && (rc = plot_settle(u)) != RL_OK) return rc;
+    unsigned long long counters[RL_FEATURE_COUNTERS] = {};
+    rc = with_call_ctx(scene->device, "scene", first, {what, "no such form", {device_records}}, [&](const CallCtx& c) -> int {
+        return launch_features(c, scene, primitive_fetch, job, width, height, first_path_index, n_paths, units, device_records, counters);
+    });
+    if (rc != RL_OK || !stats) return rc;
+    stats->paths = n_paths;
+    stats->segments = counters[RL_FEATURE_SEGMENTS];
+    for (int k = 0; k < 4; ++k) stats->kinds[k] = counters[RL_FEATURE_KINDS + k];
+    return RL_OK;
+}
+
 // ---- GatherUnit ---------------------------------------------------------------------------------
 
 int rl_gather_unit_create(int device, uint32_t width, uint32_t height, RlGatherUnit** out) {
@@ -2828,6 +2930,7 @@ int rl_debug_path_list_launches(uint64_t* out) { return family_launches(g_list_s
 int rl_debug_light_launches(uint64_t* out) { return family_launches(g_light_kernels, out); }
 int rl_debug_light_film_launches(uint64_t* out) { return family_launches(g_light_film_kernels, out); }
 int rl_debug_direct_launches(uint64_t out[6]) { return family_launches(g_direct_kernels, out); }
+int rl_debug_feature_launches(uint64_t out[6]) { return family_launches(g_feature_kernels, out); }
 
 int rl_debug_scene_emitters(const RlObjectDesc* objects, uint32_t n_objects, uint32_t* out, uint32_t cap, uint32_t* n_emitters) {
     if ((!objects && n_objects) || !n_emitters) return fail(RL_E_INVALID, "null argument");
