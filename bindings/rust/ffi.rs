@@ -63,6 +63,12 @@ pub const RL_STEP_NO_ROULETTE: u32 = 1;
 #[repr(C)] #[derive(Copy, Clone, Default)] pub struct RlFeatureStats {     // rl_scene_render_features: what one call did, exact counts
     pub paths: u64, pub segments: u64, pub kinds: [u64; 4],
 } // 48 bytes
+#[repr(C)] #[derive(Copy, Clone, Default)] pub struct RlDenoiseParams {    // rl_denoise_unit_denoise: 0 iterations = 5, a sigma of 0 = that term off
+    pub iterations: u32, pub sigma_colour: f32, pub sigma_normal: f32, pub sigma_depth: f32, pub sigma_albedo: f32,
+    pub reserved: [u32; 3],
+} // 32 bytes
+pub const RL_DENOISE_ITERATIONS: u32 = 5;
+pub const RL_DENOISE_MAX_ITERATIONS: u32 = 6;
 
 pub const RL_MAX_PIXELS: usize = 2147483647;
 pub const RL_TASK_MAX_UNITS: usize = 256;
@@ -83,7 +89,7 @@ pub const RL_COMM_ID_BYTES: usize = 128;
 }
 
 pub enum RlScene {} pub enum RlTraceUnit {} pub enum RlPlotUnit {} pub enum RlGatherUnit {} pub enum RlTonemapUnit {}
-pub enum RlScheduler {} pub enum RlComm {}
+pub enum RlScheduler {} pub enum RlComm {} pub enum RlDenoiseUnit {}
 
 extern "C" {
     pub fn rl_last_error() -> *const c_char;
@@ -189,6 +195,13 @@ extern "C" {
                                     first_path_index: u64, n_paths: u64, max_segments: u32, albedo: *mut RlPlotUnit,
                                     normal: *mut RlPlotUnit, aux: *mut RlPlotUnit, device_records: *mut RlFeatureSample,
                                     stats: *mut RlFeatureStats) -> c_int;
+
+    // The edge-avoiding a-trous filter over the guides of rl_scene_render_features, gather unit to gather unit.
+    pub fn rl_denoise_params_default(out: *mut RlDenoiseParams) -> c_int;
+    pub fn rl_denoise_unit_create(device: c_int, width: u32, height: u32, out: *mut *mut RlDenoiseUnit) -> c_int;
+    pub fn rl_denoise_unit_destroy(unit: *mut RlDenoiseUnit) -> c_int;
+    pub fn rl_denoise_unit_denoise(unit: *mut RlDenoiseUnit, image: *mut RlGatherUnit, albedo: *mut RlGatherUnit, normal: *mut RlGatherUnit,
+                                   aux: *mut RlGatherUnit, params: *const RlDenoiseParams, dst: *mut RlGatherUnit) -> c_int;
 
     pub fn rl_gather_unit_create(device: c_int, w: u32, h: u32, out: *mut *mut RlGatherUnit) -> c_int;
     pub fn rl_gather_unit_destroy(u: *mut RlGatherUnit) -> c_int;

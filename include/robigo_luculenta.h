@@ -115,6 +115,7 @@ typedef struct RlTraceUnit RlTraceUnit;
 typedef struct RlPlotUnit RlPlotUnit;
 typedef struct RlGatherUnit RlGatherUnit;
 typedef struct RlTonemapUnit RlTonemapUnit;
+typedef struct RlDenoiseUnit RlDenoiseUnit;
 typedef struct RlScheduler RlScheduler;
 typedef struct RlComm RlComm;
 
@@ -778,6 +779,64 @@ int rl_scene_render_features(const RlScene* scene, int primitive_fetch, uint32_t
                              uint32_t stream, uint64_t first_path_index, uint64_t n_paths, uint32_t max_segments,
                              RlPlotUnit* albedo, RlPlotUnit* normal, RlPlotUnit* aux, RlFeatureSample* device_records,
                              RlFeatureStats* stats);
+
+/* ---- denoising: the edge-avoiding a-trous filter over the guides (rl_denoise_unit_denoise) ---- */
+
+#define RL_DENOISE_ITERATIONS 5     /* iterations = 0 */
+#define RL_DENOISE_MAX_ITERATIONS 6
+typedef struct RlDenoiseParams {
+    uint32_t iterations;   /* 0 = RL_DENOISE_ITERATIONS (5); otherwise 1 .. RL_DENOISE_MAX_ITERATIONS */
+    float sigma_colour;    /* each sigma: 0 = that term off; otherwise in [1e-3, 1e3] */
+    float sigma_normal;
+    float sigma_depth;
+    float sigma_albedo;
+    uint32_t reserved[3];  /* must be 0 */
+} RlDenoiseParams;         /* 32 bytes */
+
+/* rl_denoise_unit_denoise: the edge-avoiding a-trous wavelet filter of Dammertz et al. 2010 -- `iterations` passes of a 5x5
+ * B3-spline kernel at dilation 1, 2, 4, ..., each tap weighted by an edge-stopping term built from the image's own luminance and
+ * from the guides rl_scene_render_features makes -- from one gather unit into another, on the device.  The chain is: render the
+ * noisy image into a gather unit; render the guides into plot units and accumulate each into a gather unit; one denoise call;
+ * rl_tonemap_unit_tonemap of `dst`.
+ *   The unit owns the call's scratch, sized at creation: a 32-byte guide record per pixel and two width x height XYZ buffers.
+ *   rl_denoise_unit_create refuses a zero size and width * height > RL_MAX_PIXELS as the other units do.
+ *   rl_denoise_params_default writes {5, 0.6, 0.3, 0.1, 0.2} and zero `reserved`.  params == NULL means those.
+ *   Inputs.  `image` and `dst` are required.  albedo, normal and aux -- gather units that accumulated the three films of
+ *   rl_scene_render_features -- may each be NULL: a NULL aux acts as (1, 0, 0) in every pixel, a NULL albedo or normal as zeros.
+ *   The arithmetic.  All f32, in exactly this order, never contracted; rl_sqrtf and rl_expf are csrc/rl_math.h's, division is the
+ *   correctly rounded one.  A, N, X: the tristimulus buffers of albedo, normal, aux.
+ *     Guide record of pixel p, once per call:
+ *       wgt = X.x;  live = wgt > 0;  z = live ? X.y / wgt : 0;  a = live ? (A.x / wgt, A.y / wgt, A.z / wgt) : 0;
+ *       l2 = (N.x*N.x + N.y*N.y) + N.z*N.z;  len = rl_sqrtf(l2);  n = len > 0 ? (N.x / len, N.y / len, N.z / len) : 0.
+ *     Constants, on the host: k(sigma) = sigma == 0 ? 0.0f : 1.0f / (sigma * sigma), giving kc, kn, kz, ka for colour, normal,
+ *       depth, albedo.  Taps h = {1/16, 1/4, 3/8, 1/4, 1/16}.
+ *     Pass i = 0 .. iterations - 1: step s = 1 << i; kc_i = kc * (float)(1u << 2*i) (the colour sigma halves per pass; exact);
+ *       input C_i, C_0 being the image's tristimulus buffer.  Per pixel p: if p is not live, C_{i+1}[p] = C_i[p].  Otherwise
+ *       sum_w = 0, sum_c = (0, 0, 0); for dy = -2 .. 2 (outer), dx = -2 .. 2 (inner), q = p + s * (dx, dy); q outside the image or
+ *       not live is skipped; else
+ *         m = fabsf(C_i[p].y) + fabsf(C_i[q].y);  r = m > 0 ? (C_i[p].y - C_i[q].y) / m : 0;  e_c = r*r;
+ *         d = n_p - n_q;  e_n = (d.x*d.x + d.y*d.y) + d.z*d.z;
+ *         mz = z_p > z_q ? z_p : z_q;  rz = mz > 0 ? (z_p - z_q) / mz : 0;  e_z = rz*rz;
+ *         da = a_p - a_q;  e_a = (da.x*da.x + da.y*da.y) + da.z*da.z;
+ *         x = ((e_c*kc_i + e_n*kn) + e_z*kz) + e_a*ka;  wt = (h[dy+2] * h[dx+2]) * rl_expf(-x);
+ *         sum_w += wt;  sum_c.k += wt * C_i[q].k for k = x, y, z;
+ *       then C_{i+1}[p] = sum_c / sum_w per component.  The centre tap has x = 0 and wt = 9/64, so sum_w > 0 for finite input.
+ *     No special cases for non-finite values: whatever the arithmetic above yields is the answer.
+ *   Result.  dst's tristimulus buffer holds C_iterations and its compensation buffer is all +0, so rl_tonemap_unit_tonemap,
+ *   rl_gather_unit_save, _download and a later _accumulate work on it unchanged.  The inputs are left as they were.
+ *   Determinism.  The result is exact: the same bits on every run, and the bits of the CPU restatement tests/_denoise_oracle.py.
+ *   Arguments, checked in this order, each failure RL_E_INVALID with a message before any device work: a NULL unit, image or dst;
+ *   iterations > RL_DENOISE_MAX_ITERATIONS; a sigma that is negative, NaN, or non-zero and outside [1e-3, 1e3]; non-zero
+ *   `reserved`; two given gather units (dst included) that are the same handle.  Every given gather unit must be width x height and
+ *   on the unit's device, else RL_E_STATE and nothing is written.
+ *   Ordering.  The call waits on the device, through events, for everything queued on the streams of the gather units it reads,
+ *   runs on dst's stream and returns when dst is complete, with a host synchronisation: it is a once-per-image operation.  One
+ *   user per denoise unit at a time. */
+int rl_denoise_params_default(RlDenoiseParams* out);
+int rl_denoise_unit_create(int device, uint32_t width, uint32_t height, RlDenoiseUnit** out);
+int rl_denoise_unit_destroy(RlDenoiseUnit* unit);
+int rl_denoise_unit_denoise(RlDenoiseUnit* unit, RlGatherUnit* image, RlGatherUnit* albedo, RlGatherUnit* normal, RlGatherUnit* aux,
+                            const RlDenoiseParams* params, RlGatherUnit* dst);
 
 /* ---- GatherUnit (gather_unit.rs:24-92) ----------------------------------------------------- */
 

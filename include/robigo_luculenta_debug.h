@@ -65,6 +65,12 @@ int rl_debug_direct_launches(uint64_t out[6]);
 /* out[v], v = 0..5: launches of instantiation v of the feature path kernel (rl_scene_render_features) since the library was
  * loaded, indexed as rl_debug_query_launches is. */
 int rl_debug_feature_launches(uint64_t out[6]);
+/* out[0]: launches of rl_denoise_guides_kernel, out[1]: launches of rl_denoise_pass_kernel (rl_denoise_unit_denoise: one and
+ * `iterations` per call) since the library was loaded. */
+int rl_debug_denoise_launches(uint64_t out[2]);
+/* Device time of the unit's last completed rl_denoise_unit_denoise call, from events on dst's stream, in milliseconds: out[0] the
+ * guide launch, out[1 + i] pass i; 0 for passes the call did not make (all 0 before the first call).  tools/denoise_bench.py. */
+int rl_debug_denoise_pass_ms(RlDenoiseUnit* unit, float out[1 + RL_DENOISE_MAX_ITERATIONS]);
 /* rl_scene_emitters for a description instead of a scene: the sampleable emitters' object indices in scan order, by the function
  * rl_scene_create builds a scene's table with.  Host arithmetic only: callable without a GPU.  The same capacity protocol. */
 int rl_debug_scene_emitters(const RlObjectDesc* objects, uint32_t n_objects, uint32_t* out, uint32_t cap, uint32_t* n_emitters);

@@ -13,7 +13,7 @@ from ._lib import (RlAppConfig, RlAppStats, RlCameraDesc, RlCameraSample, RlErro
                    RL_PATH_END_INVALID, RL_PATH_END_LIMIT, RL_PATH_END_ROULETTE, RL_PATH_END_VOID, RL_PATH_MAX_SEGMENTS,
                    RL_PATH_MAX_SEGMENTS_CAP, RL_TASK_MAX_UNITS, RlLightSample, RlDirectStats, RL_LIGHT_SKIPPED, RL_LIGHT_BACKFACING, RL_LIGHT_OCCLUDED,
                    RL_LIGHT_VISIBLE, RlFeatureSample, RlFeatureStats, RL_FEATURE_VOID, RL_FEATURE_EMITTER, RL_FEATURE_DIFFUSE, RL_FEATURE_LIMIT,
-                   RL_FEATURE_MAX_SEGMENTS)
+                   RL_FEATURE_MAX_SEGMENTS, RlDenoiseParams, RL_DENOISE_ITERATIONS, RL_DENOISE_MAX_ITERATIONS)
 
 PHOTON_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("probability", "<f4"), ("wavelength", "<f4")])
 OBJECT_DTYPE = np.dtype([("surface_kind", "<u4"), ("material_kind", "<u4"), ("v0", "<f4", 3), ("v1", "<f4", 3),
@@ -700,6 +700,46 @@ class TonemapUnit(_Handle):
         return out, mx.value
 
 
+def denoise_params_default():
+    """rl_denoise_params_default as a dict: iterations and the four sigmas (the keywords DenoiseUnit.denoise takes)."""
+    p = RlDenoiseParams()
+    check(lib.rl_denoise_params_default(C.byref(p)))
+    return {"iterations": p.iterations, "sigma_colour": p.sigma_colour, "sigma_normal": p.sigma_normal, "sigma_depth": p.sigma_depth,
+            "sigma_albedo": p.sigma_albedo}
+
+
+class DenoiseUnit(_Handle):
+    """The edge-avoiding a-trous filter over the guides of Scene.render_features (rl_denoise_unit_*)."""
+    _destroy = lib.rl_denoise_unit_destroy
+
+    def __init__(self, width, height, device=0):
+        super().__init__()
+        check(lib.rl_denoise_unit_create(device, width, height, C.byref(self._h)))
+        self.width, self.height, self.device = width, height, device
+
+    def denoise(self, image, albedo=None, normal=None, aux=None, *, dst, **params):
+        """rl_denoise_unit_denoise: gather unit `image` filtered into gather unit `dst`, guided by the gather units that accumulated
+        the films of Scene.render_features (each may be None); complete on return.  params: iterations, sigma_colour, sigma_normal,
+        sigma_depth, sigma_albedo over denoise_params_default(); none given = the library's defaults.  Returns dst."""
+        p = None
+        if params:
+            p = RlDenoiseParams()
+            check(lib.rl_denoise_params_default(C.byref(p)))
+            for name, value in params.items():
+                if name not in ("iterations", "sigma_colour", "sigma_normal", "sigma_depth", "sigma_albedo"):
+                    raise TypeError("denoise() got an unexpected keyword argument %r" % name)
+                setattr(p, name, value)
+        check(lib.rl_denoise_unit_denoise(self._h, image.handle, *[g.handle if g is not None else None for g in (albedo, normal, aux)],
+                                          C.byref(p) if p is not None else None, dst.handle))
+        return dst
+
+    def pass_ms(self):
+        """Device milliseconds of the last denoise(): [the guide launch, pass 0, pass 1, ...] (rl_debug_denoise_pass_ms)."""
+        out = (C.c_float * (1 + RL_DENOISE_MAX_ITERATIONS))()
+        check(lib.rl_debug_denoise_pass_ms(self._h, out))
+        return list(out)
+
+
 class Task:
     """enum Task (task_scheduler.rs:26-41) by unit ids."""
 
@@ -864,6 +904,14 @@ def feature_launches():
     out = (C.c_uint64 * 6)()
     check(lib.rl_debug_feature_launches(out))
     return [int(x) for x in out]
+
+
+def denoise_launches():
+    """(launches of the denoiser's guide kernel, launches of its pass kernel) since the library was loaded
+    (rl_debug_denoise_launches): one and `iterations` per DenoiseUnit.denoise."""
+    out = (C.c_uint64 * 2)()
+    check(lib.rl_debug_denoise_launches(out))
+    return tuple(out)
 
 
 def description_emitters(objects):

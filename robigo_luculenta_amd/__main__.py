@@ -1,9 +1,12 @@
 """`python -m robigo_luculenta_amd` -- the reference's main.rs (main.rs:45-67) on one MI355X: renders the
 built-in scene with the App worker pool and writes output.ppm (+ buffer.raw) when the batch budget is done.
 With --direct the image is rendered with direct light (PlotUnit.render_direct), batch by batch over the unit API.
-With --features PREFIX the denoising guides of the same paths (Scene.render_features) are written beside the image."""
+With --features PREFIX the denoising guides of the same paths (Scene.render_features) are written beside the image.
+With --denoise PATH as well the image is filtered over those guides on the device (DenoiseUnit.denoise) and tonemapped to PATH."""
 import argparse
+import os
 import struct
+import tempfile
 import time
 import zlib
 
@@ -34,7 +37,12 @@ def parse_args(argv=None):
     ap.add_argument("--features", metavar="PREFIX", default=None,
                     help="after the image, write the denoising guides of the same paths: PREFIX.npz (albedo_xyz, normal, aux: raw sums), "
                          "PREFIX-normal.png and PREFIX-depth.png")
+    ap.add_argument("--denoise", metavar="PATH", default=None,
+                    help="with --features: filter the image over the guides (DenoiseUnit.denoise, the library's defaults) and write it, "
+                         "tonemapped, to PATH (*.png or *.ppm)")
     a = ap.parse_args(argv)
+    if a.denoise is not None and a.features is None:
+        ap.error("--denoise needs --features: the filter is guided by the albedo, normal and depth films")
     if a.direct:
         for given, flag in ((a.unfused, "--unfused"), (a.concurrency is not None, "--concurrency"), (a.resume, "--resume")):
             if given:
@@ -87,13 +95,14 @@ def render_direct(a):
     print("direct light: %s" % ", ".join("%s %d" % kv for kv in total.items()))
     print("%d batches, %.1f Mpaths, %.1f Mrays and %.1f M shadow rays in %.2f s; wrote %s"
           % (a.batches, total.get("paths", 0) / 1e6, total.get("segments", 0) / 1e6, total.get("shadow_rays", 0) / 1e6, seconds, a.output))
-    return rgb, total
+    return rgb, total, gather
 
 
 def render_features(a):
     """--features PREFIX: batch b is paths [b * photons_per_batch, (b + 1) * photons_per_batch) of stream 0, one render_features
     call into three plot units and one GatherUnit.accumulate for each; PREFIX.npz holds the raw sums as float32 (h, w, 3) arrays,
-    PREFIX-normal.png the mean normal and PREFIX-depth.png the mean depth over its maximum."""
+    PREFIX-normal.png the mean normal and PREFIX-depth.png the mean depth over its maximum.  Returns the films, the totals and the three
+    gather units (albedo, normal, aux), which --denoise goes on to use."""
     import numpy as np
     from . import GatherUnit, PlotUnit, Scene
     scene = Scene.builtin(SCENE_DEMO if a.scene == "demo" else SCENE_GLASS_STRESS, device=a.device)
@@ -120,26 +129,52 @@ def render_features(a):
     write_image(a.features + "-depth.png", np.repeat(grey.reshape(-1, 1), 3, axis=1), a.width, a.height)
     print("features: paths %d, segments %d, void %d, emitter %d, diffuse %d, limit %d; wrote %s.npz"
           % ((total["paths"], total["segments"]) + tuple(total["kinds"]) + (a.features,)))
-    return films, total
+    return films, total, gathers
+
+
+def denoise(a, image, guides):
+    """--denoise PATH: gather unit `image` filtered over the three guide gather units into a gather unit of its own, tonemapped as
+    the image was, written to PATH."""
+    from . import DenoiseUnit, GatherUnit, TonemapUnit
+    clean = GatherUnit(a.width, a.height, device=a.device)
+    DenoiseUnit(a.width, a.height, device=a.device).denoise(image, albedo=guides[0], normal=guides[1], aux=guides[2], dst=clean)
+    tonemap = TonemapUnit(a.width, a.height, device=a.device)
+    tonemap.tonemap(clean)
+    rgb = tonemap.rgb_buffer
+    write_image(a.denoise, rgb, a.width, a.height)
+    print("denoised: wrote %s" % a.denoise)
+    return rgb
 
 
 def main(argv=None):
     a = parse_args(argv)
     print("rendering %d batches at %dx%d" % (a.batches, a.width, a.height))
     if a.direct:
-        render_direct(a)
+        image = render_direct(a)[2]
         if a.features is not None:
-            render_features(a)
+            guides = render_features(a)[2]
+            if a.denoise is not None:
+                denoise(a, image, guides)
         return
+    # rl_app_run hands out no gather unit: --denoise reads the image back from the checkpoint, a temporary one if none was asked for
+    scratch = tempfile.TemporaryDirectory() if a.denoise is not None and a.checkpoint is None else None
+    checkpoint = os.path.join(scratch.name, "buffer.raw") if scratch else a.checkpoint
     rgb, st = app_run(a.width, a.height, a.batches, concurrency=a.concurrency, device=a.device, seed=a.seed,
                       photons_per_batch=a.photons_per_batch,
                       scene=SCENE_DEMO if a.scene == "demo" else SCENE_GLASS_STRESS, fused=not a.unfused,
-                      output_ppm=a.output, checkpoint=a.checkpoint, resume=a.resume, verbose=not a.quiet)
+                      output_ppm=a.output, checkpoint=checkpoint, resume=a.resume, verbose=not a.quiet)
     print("%d trace tasks, %.1f Mpaths, %.1f Mrays in %.2f s (%.1f Mrays/s, %.1f reference batches/sec); wrote %s"
           % (st["batches"], st["paths"] / 1e6, st["segments"] / 1e6, st["seconds"], st["segments"] / st["seconds"] / 1e6,
              st["paths"] / 524288.0 / st["seconds"], a.output))
     if a.features is not None:
-        render_features(a)
+        guides = render_features(a)[2]
+        if a.denoise is not None:
+            from . import GatherUnit
+            image = GatherUnit(a.width, a.height, device=a.device)
+            image.load(checkpoint)
+            denoise(a, image, guides)
+    if scratch:
+        scratch.cleanup()
 
 
 if __name__ == "__main__":

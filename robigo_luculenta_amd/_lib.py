@@ -108,6 +108,15 @@ class RlFeatureStats(C.Structure):
     _fields_ = [("paths", C.c_uint64), ("segments", C.c_uint64), ("kinds", C.c_uint64 * 4)]
 
 
+RL_DENOISE_ITERATIONS = 5
+RL_DENOISE_MAX_ITERATIONS = 6
+
+
+class RlDenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("sigma_colour", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("sigma_albedo", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
 class RlTask(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("unit", C.c_uint32), ("n_units", C.c_uint32),
                 ("units", C.c_uint32 * RL_TASK_MAX_UNITS)]
@@ -203,6 +212,10 @@ SIGNATURES = {
     "rl_plot_unit_render_samples_direct_device": (_i, [_vp, _vp, _i, _u64, _u32, _u64, _u32, _vp, _u32, _vp]),
     "rl_plot_unit_render_direct": (_i, [_vp, _vp, _i, _u64, _u32, _u64, _u64, _u32, _vp, C.POINTER(RlDirectStats)]),
     "rl_scene_render_features": (_i, [_vp, _i, _u32, _u32, _u64, _u32, _u64, _u64, _u32, _vp, _vp, _vp, _vp, C.POINTER(RlFeatureStats)]),
+    "rl_denoise_params_default": (_i, [C.POINTER(RlDenoiseParams)]),
+    "rl_denoise_unit_create": (_i, [_i, _u32, _u32, _pp]),
+    "rl_denoise_unit_destroy": (_i, [_vp]),
+    "rl_denoise_unit_denoise": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(RlDenoiseParams), _vp]),
     "rl_gather_unit_sync": (_i, [_vp]),
     "rl_gather_unit_create": (_i, [_i, _u32, _u32, _pp]),
     "rl_gather_unit_destroy": (_i, [_vp]),
@@ -238,6 +251,8 @@ DEBUG_SIGNATURES = {
     "rl_debug_light_film_launches": (_i, [_vp]),
     "rl_debug_direct_launches": (_i, [_vp]),
     "rl_debug_feature_launches": (_i, [_vp]),
+    "rl_debug_denoise_launches": (_i, [_vp]),
+    "rl_debug_denoise_pass_ms": (_i, [_vp, _vp]),
     "rl_debug_scene_emitters": (_i, [_vp, _u32, _vp, _u32, C.POINTER(_u32)]),
     "rl_debug_light_sample": (_i, [_vp, _u32, _u64, _u32, _vp, _vp, _u32, _vp, _vp]),
     "rl_debug_prism_probe": (_i, [_vp, _u32, _vp, _u32, _vp]),

@@ -52,6 +52,7 @@
 #include "rl_light_film.hip.h"
 #include "rl_direct.hip.h"
 #include "rl_features.hip.h"
+#include "rl_denoise.hip.h"
 #include "rl_scene.h"
 
 namespace {
@@ -197,6 +198,16 @@ struct RlTonemapUnit {
     float* srgb;
     float* max_intensity;
     hipStream_t last_stream; // the gather stream the last tonemap ran on (downloads wait for it)
+};
+
+struct RlDenoiseUnit {
+    int device;
+    uint32_t width, height;
+    RlF4* guides;        // RL_DENOISE_GUIDE_WORDS words per pixel (rl_denoise_guides_kernel)
+    float* pingpong[2];  // C_1, C_2, ... of a call with more than one pass: width x height x 3 floats each
+    hipEvent_t ready[4]; // recorded on the streams of the gather units a call reads: image, albedo, normal, aux
+    EventPair timed[1 + RL_DENOISE_MAX_ITERATIONS]; // around the guide launch and each pass of the last call (rl_debug_denoise_pass_ms)
+    uint32_t timed_passes; // passes of the last call that completed
 };
 
 // One rank of an RCCL communicator (rl_comm_*).
@@ -2611,6 +2622,142 @@ int rl_tonemap_unit_srgb_float(RlTonemapUnit* u, float* out, float* max_intensit
     return RL_OK;
 }
 
+// ---- DenoiseUnit (rl_denoise.hip.h) -----------------------------------------------------------------
+
+namespace {
+std::atomic<uint64_t> g_denoise_launches[2]; // rl_debug_denoise_launches: guide launches, pass launches
+}
+
+int rl_denoise_params_default(RlDenoiseParams* out) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    std::memset(out, 0, sizeof(*out));
+    out->iterations = RL_DENOISE_ITERATIONS;
+    out->sigma_colour = 0.6f;
+    out->sigma_normal = 0.3f;
+    out->sigma_depth = 0.1f;
+    out->sigma_albedo = 0.2f;
+    return RL_OK;
+}
+
+int rl_denoise_unit_create(int device, uint32_t width, uint32_t height, RlDenoiseUnit** out) {
+    if (!out) return fail(RL_E_INVALID, "null output handle");
+    *out = nullptr;
+    if (width == 0 || height == 0) return fail(RL_E_INVALID, "zero-sized denoise unit");
+    int rc = check_image_size("denoise unit", width, height);
+    if (rc != RL_OK) return rc;
+    rc = use_device(device);
+    if (rc != RL_OK) return rc;
+    RlDenoiseUnit* u = new (std::nothrow) RlDenoiseUnit();
+    if (!u) return fail(RL_E_INVALID, "out of host memory");
+    u->device = device;
+    u->width = width;
+    u->height = height;
+    const size_t n = (size_t)width * height;
+    hipError_t e = hipMalloc((void**)&u->guides, n * RL_DENOISE_GUIDE_WORDS * sizeof(RlF4));
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipMalloc((void**)&u->pingpong[k], n * 3 * sizeof(float));
+    for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&u->ready[k], hipEventDisableTiming);
+    for (int k = 0; k <= RL_DENOISE_MAX_ITERATIONS && e == hipSuccess; ++k) {
+        e = hipEventCreate(&u->timed[k].start);
+        if (e == hipSuccess) e = hipEventCreate(&u->timed[k].stop);
+    }
+    if (e != hipSuccess) {
+        rl_denoise_unit_destroy(u);
+        return fail(RL_E_HIP, std::string("denoise unit allocation: ") + hipGetErrorString(e));
+    }
+    *out = u;
+    return RL_OK;
+}
+
+int rl_denoise_unit_destroy(RlDenoiseUnit* u) {
+    if (!u) return RL_OK;
+    (void)hipSetDevice(u->device); // (every call returns with its work complete: nothing of the unit's is in flight)
+    if (u->guides) (void)hipFree(u->guides);
+    for (float* b : u->pingpong)
+        if (b) (void)hipFree(b);
+    for (hipEvent_t ev : u->ready)
+        if (ev) (void)hipEventDestroy(ev);
+    for (EventPair& ep : u->timed) {
+        if (ep.start) (void)hipEventDestroy(ep.start);
+        if (ep.stop) (void)hipEventDestroy(ep.stop);
+    }
+    delete u;
+    return RL_OK;
+}
+
+int rl_denoise_unit_denoise(RlDenoiseUnit* u, RlGatherUnit* image, RlGatherUnit* albedo, RlGatherUnit* normal, RlGatherUnit* aux,
+                            const RlDenoiseParams* params, RlGatherUnit* dst) {
+    if (!u || !image || !dst) return fail(RL_E_INVALID, "rl_denoise_unit_denoise: null denoise unit, image or dst");
+    RlDenoiseParams p;
+    if (params) p = *params;
+    else (void)rl_denoise_params_default(&p);
+    if (p.iterations > RL_DENOISE_MAX_ITERATIONS)
+        return fail(RL_E_INVALID, "rl_denoise_unit_denoise: iterations " + std::to_string(p.iterations) + " above RL_DENOISE_MAX_ITERATIONS = " +
+                                      std::to_string(RL_DENOISE_MAX_ITERATIONS));
+    const float sigmas[4] = {p.sigma_colour, p.sigma_normal, p.sigma_depth, p.sigma_albedo};
+    const char* const sigma_names[4] = {"sigma_colour", "sigma_normal", "sigma_depth", "sigma_albedo"};
+    for (int k = 0; k < 4; ++k)
+        if (!(sigmas[k] == 0.0f || (sigmas[k] >= 1e-3f && sigmas[k] <= 1e3f))) // (a NaN fails both)
+            return fail(RL_E_INVALID, std::string("rl_denoise_unit_denoise: ") + sigma_names[k] + " must be 0 (the term is off) or in [1e-3, 1e3]");
+    if (p.reserved[0] != 0u || p.reserved[1] != 0u || p.reserved[2] != 0u) return fail(RL_E_INVALID, "rl_denoise_unit_denoise: params.reserved must be 0");
+    RlGatherUnit* const given[5] = {image, albedo, normal, aux, dst};
+    for (int a = 0; a < 5; ++a)
+        for (int b = a + 1; b < 5; ++b)
+            if (given[a] && given[a] == given[b]) return fail(RL_E_INVALID, "rl_denoise_unit_denoise: the gather units must be distinct handles");
+    for (RlGatherUnit* g : given)
+        if (g && (g->device != u->device || g->width != u->width || g->height != u->height))
+            return fail(RL_E_STATE, "gather unit does not match the denoise unit (device or size)");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    int cus = 256;
+    if ((rc = cu_count_of(u->device, &cus)) != RL_OK) return rc;
+    const uint32_t iterations = p.iterations ? p.iterations : RL_DENOISE_ITERATIONS;
+    const uint32_t n_pixels = u->width * u->height;
+    hipStream_t stream = dst->stream;
+    for (int k = 0; k < 4; ++k) { // everything queued on the streams of the units the call reads
+        if (!given[k]) continue;
+        RL_HIP(hipEventRecord(u->ready[k], given[k]->stream));
+        RL_HIP(hipStreamWaitEvent(stream, u->ready[k], 0));
+    }
+    u->timed_passes = 0;
+    RL_HIP(hipEventRecord(u->timed[0].start, stream));
+    hipLaunchKernelGGL(rl_denoise_guides_kernel, dim3(grid_for(n_pixels, cus)), dim3(RL_BLOCK), 0, stream, albedo ? albedo->acc : nullptr,
+                       normal ? normal->acc : nullptr, aux ? aux->acc : nullptr, n_pixels, u->guides);
+    RL_HIP(hipGetLastError());
+    RL_HIP(hipEventRecord(u->timed[0].stop, stream));
+    g_denoise_launches[0].fetch_add(1, std::memory_order_relaxed);
+    // k(sigma), f32 on the host
+    float k[4];
+    for (int t = 0; t < 4; ++t) k[t] = sigmas[t] == 0.0f ? 0.0f : 1.0f / (sigmas[t] * sigmas[t]);
+    const float* in = image->acc;
+    for (uint32_t i = 0; i < iterations; ++i) {
+        float* out = i + 1 == iterations ? dst->acc : u->pingpong[i & 1u];
+        RlDenoisePass job;
+        job.width = u->width;
+        job.height = u->height;
+        job.step = 1u << i;
+        job.classes_x = std::min(job.step, u->width);
+        job.classes_y = std::min(job.step, u->height);
+        job.tiles_x = ((u->width + job.step - 1) / job.step + RL_DENOISE_TILE - 1) / RL_DENOISE_TILE;
+        job.tiles_y = ((u->height + job.step - 1) / job.step + RL_DENOISE_TILE - 1) / RL_DENOISE_TILE;
+        job.kc = k[0] * (float)(1u << 2 * i); // the colour sigma halves per pass; exact
+        job.kn = k[1];
+        job.kz = k[2];
+        job.ka = k[3];
+        RL_HIP(hipEventRecord(u->timed[1 + i].start, stream));
+        // (at most 2^31 / 17 * 32 / 256 workgroups for any image the units accept: one grid dimension holds them)
+        const uint64_t groups = (uint64_t)job.tiles_x * job.classes_x * job.tiles_y * job.classes_y;
+        hipLaunchKernelGGL(rl_denoise_pass_kernel, dim3((uint32_t)groups), dim3(RL_DENOISE_TILE * RL_DENOISE_TILE), 0, stream, in, u->guides, job, out);
+        RL_HIP(hipGetLastError());
+        RL_HIP(hipEventRecord(u->timed[1 + i].stop, stream));
+        g_denoise_launches[1].fetch_add(1, std::memory_order_relaxed);
+        in = out;
+    }
+    RL_HIP(hipMemsetAsync(dst->comp, 0, (size_t)n_pixels * 3 * sizeof(float), stream));
+    RL_HIP(hipStreamSynchronize(stream));
+    u->timed_passes = iterations;
+    return RL_OK;
+}
+
 // ---- GatherUnit-time exchange across GPUs (gather_unit.rs:49-64 with the plot buffers of G GPUs) ----
 
 namespace {
@@ -2931,6 +3078,22 @@ int rl_debug_light_launches(uint64_t* out) { return family_launches(g_light_kern
 int rl_debug_light_film_launches(uint64_t* out) { return family_launches(g_light_film_kernels, out); }
 int rl_debug_direct_launches(uint64_t out[6]) { return family_launches(g_direct_kernels, out); }
 int rl_debug_feature_launches(uint64_t out[6]) { return family_launches(g_feature_kernels, out); }
+
+int rl_debug_denoise_launches(uint64_t out[2]) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    for (int k = 0; k < 2; ++k) out[k] = g_denoise_launches[k].load(std::memory_order_relaxed);
+    return RL_OK;
+}
+int rl_debug_denoise_pass_ms(RlDenoiseUnit* u, float out[1 + RL_DENOISE_MAX_ITERATIONS]) {
+    if (!u || !out) return fail(RL_E_INVALID, "null argument");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    for (uint32_t k = 0; k <= RL_DENOISE_MAX_ITERATIONS; ++k) {
+        out[k] = 0.0f;
+        if (u->timed_passes != 0u && k <= u->timed_passes) RL_HIP(hipEventElapsedTime(&out[k], u->timed[k].start, u->timed[k].stop));
+    }
+    return RL_OK;
+}
 
 int rl_debug_scene_emitters(const RlObjectDesc* objects, uint32_t n_objects, uint32_t* out, uint32_t cap, uint32_t* n_emitters) {
     if ((!objects && n_objects) || !n_emitters) return fail(RL_E_INVALID, "null argument");
