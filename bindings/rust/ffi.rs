@@ -69,6 +69,7 @@ pub const RL_STEP_NO_ROULETTE: u32 = 1;
 } // 32 bytes
 pub const RL_DENOISE_ITERATIONS: u32 = 5;
 pub const RL_DENOISE_MAX_ITERATIONS: u32 = 6;
+pub const RL_SPECTRAL_MAX_NODES: u32 = 401;
 
 pub const RL_MAX_PIXELS: usize = 2147483647;
 pub const RL_TASK_MAX_UNITS: usize = 256;
@@ -89,7 +90,7 @@ pub const RL_COMM_ID_BYTES: usize = 128;
 }
 
 pub enum RlScene {} pub enum RlTraceUnit {} pub enum RlPlotUnit {} pub enum RlGatherUnit {} pub enum RlTonemapUnit {}
-pub enum RlScheduler {} pub enum RlComm {} pub enum RlDenoiseUnit {}
+pub enum RlScheduler {} pub enum RlComm {} pub enum RlDenoiseUnit {} pub enum RlSpectralUnit {}
 
 extern "C" {
     pub fn rl_last_error() -> *const c_char;
@@ -202,6 +203,18 @@ extern "C" {
     pub fn rl_denoise_unit_destroy(unit: *mut RlDenoiseUnit) -> c_int;
     pub fn rl_denoise_unit_denoise(unit: *mut RlDenoiseUnit, image: *mut RlGatherUnit, albedo: *mut RlGatherUnit, normal: *mut RlGatherUnit,
                                    aux: *mut RlGatherUnit, params: *const RlDenoiseParams, dst: *mut RlGatherUnit) -> c_int;
+
+    // The spectral film: photons kept by wavelength in n_nodes planes, projected into a gather unit under an n_nodes x 3 matrix.
+    pub fn rl_spectral_unit_create(device: c_int, width: u32, height: u32, n_nodes: u32, out: *mut *mut RlSpectralUnit) -> c_int;
+    pub fn rl_spectral_unit_destroy(unit: *mut RlSpectralUnit) -> c_int;
+    pub fn rl_spectral_unit_clear(unit: *mut RlSpectralUnit) -> c_int;
+    pub fn rl_spectral_unit_plot(unit: *mut RlSpectralUnit, trace_units: *const *mut RlTraceUnit, n_trace_units: u32) -> c_int;
+    pub fn rl_spectral_unit_plot_photons(unit: *mut RlSpectralUnit, photons: *const RlMappedPhoton, n: u64) -> c_int;
+    pub fn rl_spectral_unit_plot_photons_device(unit: *mut RlSpectralUnit, device_photons: *const RlMappedPhoton, n: u64) -> c_int;
+    pub fn rl_spectral_unit_download(unit: *mut RlSpectralUnit, out: *mut f32) -> c_int;
+    pub fn rl_spectral_unit_upload(unit: *mut RlSpectralUnit, input: *const f32) -> c_int;
+    pub fn rl_spectral_unit_project(unit: *mut RlSpectralUnit, matrix: *const f32, dst: *mut RlGatherUnit) -> c_int;
+    pub fn rl_spectral_observer_cie1931(n_nodes: u32, out: *mut f32) -> c_int;
 
     pub fn rl_gather_unit_create(device: c_int, w: u32, h: u32, out: *mut *mut RlGatherUnit) -> c_int;
     pub fn rl_gather_unit_destroy(u: *mut RlGatherUnit) -> c_int;

@@ -116,6 +116,7 @@ typedef struct RlPlotUnit RlPlotUnit;
 typedef struct RlGatherUnit RlGatherUnit;
 typedef struct RlTonemapUnit RlTonemapUnit;
 typedef struct RlDenoiseUnit RlDenoiseUnit;
+typedef struct RlSpectralUnit RlSpectralUnit;
 typedef struct RlScheduler RlScheduler;
 typedef struct RlComm RlComm;
 
@@ -837,6 +838,70 @@ int rl_denoise_unit_create(int device, uint32_t width, uint32_t height, RlDenois
 int rl_denoise_unit_destroy(RlDenoiseUnit* unit);
 int rl_denoise_unit_denoise(RlDenoiseUnit* unit, RlGatherUnit* image, RlGatherUnit* albedo, RlGatherUnit* normal, RlGatherUnit* aux,
                             const RlDenoiseParams* params, RlGatherUnit* dst);
+
+/* ---- spectral film: photons kept by wavelength, projected under any observer (rl_spectral_unit_*) ---- */
+
+#define RL_SPECTRAL_MAX_NODES 401
+
+/* A spectral unit is a film of `n_nodes` planes of width x height floats.  Every other film of the library multiplies a photon by
+ * rl_tristimulus(wavelength) inside the splat and keeps three floats per pixel; this one splats the photon's intensity by wavelength
+ * and leaves the observer to a projection, rl_spectral_unit_project, under a caller-supplied n_nodes x 3 matrix: CIE 1931
+ * (rl_spectral_observer_cie1931), a camera's measured sensitivities, a single band, another white point -- without a re-trace.  The
+ * projection writes a gather unit, so rl_tonemap_unit_tonemap, rl_gather_unit_save, _download and rl_denoise_unit_denoise work on
+ * the result unchanged.  The chain is: rl_trace_unit_render (un-fused); rl_spectral_unit_plot; rl_spectral_unit_project; tonemap.
+ *   The node model is the CIE table's own (81 nodes at 380 + 5 i nm, interpolated linearly, a linear fall-off beyond each end):
+ *   at n_nodes = 81, projecting with the CIE table reproduces the XYZ film of the same photons up to rounding.
+ *   The arithmetic.  All f32, in exactly this order, never contracted; division is the correctly rounded one.
+ *     Constants, on the host: spacing = 400.0f / (float)(n_nodes - 1); node b sits at 380.0f + (float)b * spacing.
+ *     Splat of one photon {x, y, probability, wavelength}.  Skipped if probability == 0; skipped if x or y is NaN or infinite
+ *       (rl_plot_unit_plot_photons' rule); skipped if wavelength is NaN or infinite -- a DIFFERENCE from the XYZ film, which has no
+ *       such rule and plots what rl_tristimulus makes of that wavelength.  Otherwise
+ *         f = (wavelength - 380.0f) / spacing;  fl = floorf(f);  r = f - fl;
+ *         lo = probability * (1.0f - r)  -> node (int)fl;      hi = probability * r  -> node (int)fl + 1.
+ *       Whether a node is in the film is decided by comparing fl as a float (0 <= fl <= n_nodes - 1 for lo, -1 <= fl <= n_nodes - 2
+ *       for hi) before any conversion to int, so no conversion of an out-of-range float is relied on.  A node outside
+ *       0 .. n_nodes - 1 is dropped: the table's linear fall-off at 375-380 and 780-785 nm, and zero beyond.  Each kept value is
+ *       multiplied by each of the four weights of the plot unit's splat (rl_splat_weights(width, height, aspect, x, y), aspect =
+ *       (float)width / (float)height; the four pixels are clamped into the film) and each product is added with an f32 atomic to
+ *       film[node * width * height + pixel], onto what is there: at most eight atomics per photon.  A negative probability
+ *       subtracts; an infinite one is plotted as the arithmetic gives.
+ *     Project, per pixel p and component k of 3: acc = 0.0f; for b = 0 .. n_nodes - 1 in order
+ *       acc = acc + matrix[b * 3 + k] * film[b * n_pixels + p]; dst's tristimulus buffer gets acc.  No special cases for non-finite
+ *       values.  dst's compensation buffer is all +0, as after rl_denoise_unit_denoise.  The film is left as it was.
+ *   rl_spectral_unit_create.  Checked in this order before any device work, each failure RL_E_INVALID with a message: a NULL
+ *   `out`; a zero width or height; n_nodes < 2 or > RL_SPECTRAL_MAX_NODES; width * height * n_nodes > RL_MAX_PIXELS (computed in
+ *   64 bits).  The film is zeroed.  rl_spectral_unit_clear zeroes it again (queued on the unit; everything below is ordered after it).
+ *   rl_spectral_unit_plot takes the photons of each given trace unit's last un-fused render, as rl_plot_unit_plot does; it is
+ *   ordered after those renders on the device (a render that was begun is ended) and returns when the splats are in the film.  It
+ *   is synchronous on purpose: it takes no part in what makes a trace unit's next render wait for a plot unit, so the same trace
+ *   units may be plotted into a plot unit and a spectral unit, in either order.  A NULL unit, or NULL trace_units with
+ *   n_trace_units > 0, is RL_E_INVALID; a NULL trace unit or one on another device is RL_E_STATE, as for rl_plot_unit_plot.
+ *   rl_spectral_unit_plot_photons / _device.  Every rule of rl_plot_unit_plot_photons / _device holds: any n is accepted, the host
+ *   form stages in chunks of 2^20 records, the _device form refuses pageable host memory (RL_E_INVALID), n = 0 does nothing, a
+ *   NULL unit, or NULL photons with n > 0, is RL_E_INVALID before any device work; the splats are in the film on return.
+ *   rl_spectral_unit_download / _upload move the whole film, n_nodes * width * height floats, planes in node order (node-major:
+ *   part of the ABI), each plane rows of `width`.
+ *   rl_spectral_unit_project.  Checked in this order: a NULL unit, matrix or dst is RL_E_INVALID; a dst of another size or device
+ *   is RL_E_STATE, and nothing is written.  `matrix` is host memory, n_nodes x 3 floats, row b = what one unit of node b adds to the
+ *   three components; it is read as given, non-finite entries included.  Ordering is the denoiser's: the call waits on the device
+ *   for everything queued on dst's stream and on the film, runs on dst's stream and returns when dst is complete.
+ *   rl_spectral_observer_cie1931(n_nodes, out) writes n_nodes x 3 floats, row b = rl_tristimulus of node b's wavelength from the
+ *   library's table: at 81 nodes the table's rows exactly.  Host arithmetic only: callable without a GPU.  A NULL `out` or an
+ *   n_nodes outside 2 .. RL_SPECTRAL_MAX_NODES is RL_E_INVALID.
+ *   Determinism.  The film differs between runs only by the order of its atomics; a (node, pixel) that received at most two
+ *   non-zero terms holds the same bits on every run.  The projection is exact given the film: the same bits on every run, and the
+ *   bits of the CPU restatement tests/_spectral_oracle.py.
+ *   One user per spectral unit at a time. */
+int rl_spectral_unit_create(int device, uint32_t width, uint32_t height, uint32_t n_nodes, RlSpectralUnit** out);
+int rl_spectral_unit_destroy(RlSpectralUnit* unit);
+int rl_spectral_unit_clear(RlSpectralUnit* unit);
+int rl_spectral_unit_plot(RlSpectralUnit* unit, RlTraceUnit* const* trace_units, uint32_t n_trace_units);
+int rl_spectral_unit_plot_photons(RlSpectralUnit* unit, const RlMappedPhoton* photons, uint64_t n);
+int rl_spectral_unit_plot_photons_device(RlSpectralUnit* unit, const RlMappedPhoton* device_photons, uint64_t n);
+int rl_spectral_unit_download(RlSpectralUnit* unit, float* out);
+int rl_spectral_unit_upload(RlSpectralUnit* unit, const float* in);
+int rl_spectral_unit_project(RlSpectralUnit* unit, const float* matrix, RlGatherUnit* dst);
+int rl_spectral_observer_cie1931(uint32_t n_nodes, float* out);
 
 /* ---- GatherUnit (gather_unit.rs:24-92) ----------------------------------------------------- */
 

@@ -71,6 +71,14 @@ int rl_debug_denoise_launches(uint64_t out[2]);
 /* Device time of the unit's last completed rl_denoise_unit_denoise call, from events on dst's stream, in milliseconds: out[0] the
  * guide launch, out[1 + i] pass i; 0 for passes the call did not make (all 0 before the first call).  tools/denoise_bench.py. */
 int rl_debug_denoise_pass_ms(RlDenoiseUnit* unit, float out[1 + RL_DENOISE_MAX_ITERATIONS]);
+/* out[0]: launches of rl_spectral_photons_kernel (one per trace unit of rl_spectral_unit_plot, one per chunk of
+ * rl_spectral_unit_plot_photons, one per rl_spectral_unit_plot_photons_device), out[1]: launches of rl_spectral_project_kernel (one
+ * per rl_spectral_unit_project) since the library was loaded. */
+int rl_debug_spectral_launches(uint64_t out[2]);
+/* Device time in milliseconds, from events around the launch: out[0] the last splat launch of the unit's last completed splat call
+ * (rl_spectral_unit_plot, _plot_photons, _plot_photons_device), out[1] the projection launch of its last completed
+ * rl_spectral_unit_project; 0 before the first.  tools/spectral_bench.py. */
+int rl_debug_spectral_ms(RlSpectralUnit* unit, float out[2]);
 /* rl_scene_emitters for a description instead of a scene: the sampleable emitters' object indices in scan order, by the function
  * rl_scene_create builds a scene's table with.  Host arithmetic only: callable without a GPU.  The same capacity protocol. */
 int rl_debug_scene_emitters(const RlObjectDesc* objects, uint32_t n_objects, uint32_t* out, uint32_t cap, uint32_t* n_emitters);

@@ -13,7 +13,8 @@ from ._lib import (RlAppConfig, RlAppStats, RlCameraDesc, RlCameraSample, RlErro
                    RL_PATH_END_INVALID, RL_PATH_END_LIMIT, RL_PATH_END_ROULETTE, RL_PATH_END_VOID, RL_PATH_MAX_SEGMENTS,
                    RL_PATH_MAX_SEGMENTS_CAP, RL_TASK_MAX_UNITS, RlLightSample, RlDirectStats, RL_LIGHT_SKIPPED, RL_LIGHT_BACKFACING, RL_LIGHT_OCCLUDED,
                    RL_LIGHT_VISIBLE, RlFeatureSample, RlFeatureStats, RL_FEATURE_VOID, RL_FEATURE_EMITTER, RL_FEATURE_DIFFUSE, RL_FEATURE_LIMIT,
-                   RL_FEATURE_MAX_SEGMENTS, RlDenoiseParams, RL_DENOISE_ITERATIONS, RL_DENOISE_MAX_ITERATIONS)
+                   RL_FEATURE_MAX_SEGMENTS, RlDenoiseParams, RL_DENOISE_ITERATIONS, RL_DENOISE_MAX_ITERATIONS,
+                   RL_SPECTRAL_MAX_NODES)
 
 PHOTON_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("probability", "<f4"), ("wavelength", "<f4")])
 OBJECT_DTYPE = np.dtype([("surface_kind", "<u4"), ("material_kind", "<u4"), ("v0", "<f4", 3), ("v1", "<f4", 3),
@@ -740,6 +741,67 @@ class DenoiseUnit(_Handle):
         return list(out)
 
 
+def spectral_observer_cie1931(n_nodes=81):
+    """rl_spectral_observer_cie1931: the (n_nodes, 3) float32 matrix whose row b is the library's CIE 1931 tristimulus of node b's
+    wavelength, 380 + b * 400 / (n_nodes - 1) nm -- at 81 nodes the table itself.  Host arithmetic: needs no device."""
+    out = np.zeros((max(int(n_nodes), 0), 3), dtype=np.float32)
+    check(lib.rl_spectral_observer_cie1931(n_nodes, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+class SpectralUnit(_Handle):
+    """A film that keeps photons by wavelength: n_nodes planes of width x height floats (rl_spectral_unit_*), projected into a
+    gather unit under any (n_nodes, 3) matrix."""
+    _destroy = lib.rl_spectral_unit_destroy
+
+    def __init__(self, width, height, n_nodes=81, device=0):
+        super().__init__()
+        check(lib.rl_spectral_unit_create(device, width, height, n_nodes, C.byref(self._h)))
+        self.width, self.height, self.n_nodes, self.device = width, height, n_nodes, device
+
+    def plot(self, trace_units):
+        """rl_spectral_unit_plot: the photons of each trace unit's last un-fused render, in the film on return."""
+        arr = (C.c_void_p * len(trace_units))(*[t.handle for t in trace_units])
+        check(lib.rl_spectral_unit_plot(self._h, arr, len(trace_units)))
+
+    def plot_photons(self, photons):
+        """An (n,) PHOTON_DTYPE array of the caller's (rl_spectral_unit_plot_photons), or a device buffer on the unit's device with
+        data_ptr() (e.g. a torch tensor; rl_spectral_unit_plot_photons_device: as many records as it holds whole): added onto the
+        film, complete on return.  A photon whose x, y or wavelength is not finite is skipped."""
+        if hasattr(photons, "data_ptr"):
+            n = _n_bytes(photons) // PHOTON_DTYPE.itemsize
+            check(lib.rl_spectral_unit_plot_photons_device(self._h, C.c_void_p(photons.data_ptr()), n))
+            return
+        photons = np.ascontiguousarray(photons, dtype=PHOTON_DTYPE)
+        check(lib.rl_spectral_unit_plot_photons(self._h, photons.ctypes.data_as(C.c_void_p), len(photons)))
+
+    def clear(self):
+        check(lib.rl_spectral_unit_clear(self._h))
+
+    def download(self):
+        """The film: (n_nodes, height, width) float32."""
+        out = np.zeros((self.n_nodes, self.height, self.width), dtype=np.float32)
+        check(lib.rl_spectral_unit_download(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def upload(self, film):
+        film = np.ascontiguousarray(film, dtype=np.float32).reshape(self.n_nodes, self.height, self.width)
+        check(lib.rl_spectral_unit_upload(self._h, film.ctypes.data_as(C.c_void_p)))
+
+    def project(self, matrix, dst):
+        """rl_spectral_unit_project: gather unit `dst` = the film under the (n_nodes, 3) `matrix`, complete on return; its
+        compensation buffer is zeroed, the film is left as it was.  Returns dst."""
+        matrix = np.ascontiguousarray(matrix, dtype=np.float32).reshape(self.n_nodes, 3)
+        check(lib.rl_spectral_unit_project(self._h, matrix.ctypes.data_as(C.c_void_p), dst.handle))
+        return dst
+
+    def launch_ms(self):
+        """Device milliseconds of (the last splat launch, the last projection launch) of this unit (rl_debug_spectral_ms)."""
+        out = (C.c_float * 2)()
+        check(lib.rl_debug_spectral_ms(self._h, out))
+        return tuple(out)
+
+
 class Task:
     """enum Task (task_scheduler.rs:26-41) by unit ids."""
 
@@ -911,6 +973,14 @@ def denoise_launches():
     (rl_debug_denoise_launches): one and `iterations` per DenoiseUnit.denoise."""
     out = (C.c_uint64 * 2)()
     check(lib.rl_debug_denoise_launches(out))
+    return tuple(out)
+
+
+def spectral_launches():
+    """(launches of the spectral film's splat kernel, launches of its projection kernel) since the library was loaded
+    (rl_debug_spectral_launches)."""
+    out = (C.c_uint64 * 2)()
+    check(lib.rl_debug_spectral_launches(out))
     return tuple(out)
 
 

@@ -2,7 +2,8 @@
 built-in scene with the App worker pool and writes output.ppm (+ buffer.raw) when the batch budget is done.
 With --direct the image is rendered with direct light (PlotUnit.render_direct), batch by batch over the unit API.
 With --features PREFIX the denoising guides of the same paths (Scene.render_features) are written beside the image.
-With --denoise PATH as well the image is filtered over those guides on the device (DenoiseUnit.denoise) and tonemapped to PATH."""
+With --denoise PATH as well the image is filtered over those guides on the device (DenoiseUnit.denoise) and tonemapped to PATH.
+With --spectral PATH the same paths are rendered once more into a spectral film (SpectralUnit) and the cube is saved as PATH (.npy)."""
 import argparse
 import os
 import struct
@@ -40,7 +41,14 @@ def parse_args(argv=None):
     ap.add_argument("--denoise", metavar="PATH", default=None,
                     help="with --features: filter the image over the guides (DenoiseUnit.denoise, the library's defaults) and write it, "
                          "tonemapped, to PATH (*.png or *.ppm)")
+    ap.add_argument("--spectral", metavar="PATH", default=None,
+                    help="after the image, render the same paths un-fused into a spectral film (SpectralUnit.plot) and save the cube, "
+                         "float32 (nodes, height, width), to PATH with numpy.save (*.npy)")
+    ap.add_argument("--spectral-nodes", metavar="K", type=int, default=81,
+                    help="with --spectral: nodes from 380 to 780 nm (default 81, the CIE table's own)")
     a = ap.parse_args(argv)
+    if a.spectral is not None and a.direct:
+        ap.error("--spectral cannot be combined with --direct: the direct renderer writes no photons")
     if a.denoise is not None and a.features is None:
         ap.error("--denoise needs --features: the filter is guided by the albedo, normal and depth films")
     if a.direct:
@@ -132,6 +140,29 @@ def render_features(a):
     return films, total, gathers
 
 
+def render_spectral(a):
+    """--spectral PATH: the batches x photons_per_batch paths of stream 0 once more, un-fused -- TraceUnit.render in runs of at most
+    2^22 paths, SpectralUnit.plot of each -- and the cube saved with numpy.save.  Returns the cube, float32 (nodes, height, width)."""
+    import numpy as np
+    from . import Scene, SpectralUnit, TraceUnit
+    scene = Scene.builtin(SCENE_DEMO if a.scene == "demo" else SCENE_GLASS_STRESS, device=a.device)
+    film = SpectralUnit(a.width, a.height, a.spectral_nodes, device=a.device)
+    total = a.batches * a.photons_per_batch
+    run = max(1, min(total, 1 << 22))
+    traces = {}
+    for first in range(0, total, run):
+        n = min(run, total - first)
+        if n not in traces:
+            traces[n] = TraceUnit(0, a.width, a.height, n_photons=n, device=a.device)
+        traces[n].render(scene, seed=a.seed, stream=0, first_path_index=first)
+        film.plot([traces[n]])
+    cube = film.download()
+    with open(a.spectral, "wb") as f:     # (numpy.save would append .npy to a name that lacks it)
+        np.save(f, cube)
+    print("spectral film: %d nodes, %d paths; wrote %s" % (a.spectral_nodes, total, a.spectral))
+    return cube
+
+
 def denoise(a, image, guides):
     """--denoise PATH: gather unit `image` filtered over the three guide gather units into a gather unit of its own, tonemapped as
     the image was, written to PATH."""
@@ -173,6 +204,8 @@ def main(argv=None):
             image = GatherUnit(a.width, a.height, device=a.device)
             image.load(checkpoint)
             denoise(a, image, guides)
+    if a.spectral is not None:
+        render_spectral(a)
     if scratch:
         scratch.cleanup()
 

@@ -117,6 +117,9 @@ class RlDenoiseParams(C.Structure):
                 ("sigma_albedo", C.c_float), ("reserved", C.c_uint32 * 3)]
 
 
+RL_SPECTRAL_MAX_NODES = 401
+
+
 class RlTask(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("unit", C.c_uint32), ("n_units", C.c_uint32),
                 ("units", C.c_uint32 * RL_TASK_MAX_UNITS)]
@@ -216,6 +219,16 @@ SIGNATURES = {
     "rl_denoise_unit_create": (_i, [_i, _u32, _u32, _pp]),
     "rl_denoise_unit_destroy": (_i, [_vp]),
     "rl_denoise_unit_denoise": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(RlDenoiseParams), _vp]),
+    "rl_spectral_unit_create": (_i, [_i, _u32, _u32, _u32, _pp]),
+    "rl_spectral_unit_destroy": (_i, [_vp]),
+    "rl_spectral_unit_clear": (_i, [_vp]),
+    "rl_spectral_unit_plot": (_i, [_vp, _pp, _u32]),
+    "rl_spectral_unit_plot_photons": (_i, [_vp, _vp, _u64]),
+    "rl_spectral_unit_plot_photons_device": (_i, [_vp, _vp, _u64]),
+    "rl_spectral_unit_download": (_i, [_vp, _vp]),
+    "rl_spectral_unit_upload": (_i, [_vp, _vp]),
+    "rl_spectral_unit_project": (_i, [_vp, _vp, _vp]),
+    "rl_spectral_observer_cie1931": (_i, [_u32, _vp]),
     "rl_gather_unit_sync": (_i, [_vp]),
     "rl_gather_unit_create": (_i, [_i, _u32, _u32, _pp]),
     "rl_gather_unit_destroy": (_i, [_vp]),
@@ -253,6 +266,8 @@ DEBUG_SIGNATURES = {
     "rl_debug_feature_launches": (_i, [_vp]),
     "rl_debug_denoise_launches": (_i, [_vp]),
     "rl_debug_denoise_pass_ms": (_i, [_vp, _vp]),
+    "rl_debug_spectral_launches": (_i, [_vp]),
+    "rl_debug_spectral_ms": (_i, [_vp, _vp]),
     "rl_debug_scene_emitters": (_i, [_vp, _u32, _vp, _u32, C.POINTER(_u32)]),
     "rl_debug_light_sample": (_i, [_vp, _u32, _u64, _u32, _vp, _vp, _u32, _vp, _vp]),
     "rl_debug_prism_probe": (_i, [_vp, _u32, _vp, _u32, _vp]),

@@ -53,6 +53,7 @@
 #include "rl_direct.hip.h"
 #include "rl_features.hip.h"
 #include "rl_denoise.hip.h"
+#include "rl_spectral.hip.h"
 #include "rl_scene.h"
 
 namespace {
@@ -208,6 +209,18 @@ struct RlDenoiseUnit {
     hipEvent_t ready[4]; // recorded on the streams of the gather units a call reads: image, albedo, normal, aux
     EventPair timed[1 + RL_DENOISE_MAX_ITERATIONS]; // around the guide launch and each pass of the last call (rl_debug_denoise_pass_ms)
     uint32_t timed_passes; // passes of the last call that completed
+};
+
+struct RlSpectralUnit {
+    int device;
+    uint32_t width, height, n_nodes;
+    float spacing;      // 400.0f / (float)(n_nodes - 1): the nodes sit at 380.0f + (float)b * spacing
+    float* film;        // n_nodes planes of width x height floats, node-major
+    float* matrix;      // the n_nodes x 3 matrix of the projection in flight (RL_SPECTRAL_MAX_NODES x 3 floats)
+    hipStream_t stream; // clears and splats; every splat call returns with it drained
+    hipEvent_t ready;   // recorded on `stream` when a projection takes the film
+    EventPair timed[2]; // around the last splat launch and the last projection launch (rl_debug_spectral_ms)
+    bool timed_done[2]; // ... of a call that completed
 };
 
 // One rank of an RCCL communicator (rl_comm_*).
@@ -2758,6 +2771,207 @@ int rl_denoise_unit_denoise(RlDenoiseUnit* u, RlGatherUnit* image, RlGatherUnit*
     return RL_OK;
 }
 
+// ---- SpectralUnit (rl_spectral.hip.h) ---------------------------------------------------------------
+
+namespace {
+std::atomic<uint64_t> g_spectral_launches[2]; // rl_debug_spectral_launches: splat launches, project launches
+
+int spectral_nodes_check(const char* what, uint32_t n_nodes) {
+    if (n_nodes >= 2u && n_nodes <= RL_SPECTRAL_MAX_NODES) return RL_OK;
+    return fail(RL_E_INVALID, std::string(what) + ": n_nodes " + std::to_string(n_nodes) + " outside 2 .. RL_SPECTRAL_MAX_NODES = " +
+                                  std::to_string(RL_SPECTRAL_MAX_NODES));
+}
+float spectral_spacing(uint32_t n_nodes) { return 400.0f / (float)(n_nodes - 1u); }
+
+// The splat kernel for device array photons [0, n) (n > 0) on `stream`.
+int launch_spectral_photons(RlSpectralUnit* u, hipStream_t stream, int cus, const RlMappedPhoton* photons, uint64_t n) {
+    const float aspect = (float)u->width / (float)u->height; // plot_unit.rs:48
+    u->timed_done[0] = false;
+    RL_HIP(hipEventRecord(u->timed[0].start, stream));
+    hipLaunchKernelGGL(rl_spectral_photons_kernel, dim3(grid_for(n, cus)), dim3(RL_BLOCK), 0, stream, photons, n, u->width, u->height, u->n_nodes,
+                       u->spacing, aspect, u->film);
+    RL_HIP(hipGetLastError());
+    RL_HIP(hipEventRecord(u->timed[0].stop, stream));
+    g_spectral_launches[0].fetch_add(1, std::memory_order_relaxed);
+    return RL_OK;
+}
+
+// A splat call borrows a query context (with_call_ctx: its staging buffers; its own stream stays idle) and queues everything on the
+// spectral unit's stream, which has drained when the call returns, also after a failure: rc is what the call's body returned.
+int spectral_drained(RlSpectralUnit* u, int rc) {
+    const hipError_t e = hipStreamSynchronize(u->stream);
+    if (rc != RL_OK) return rc;
+    RL_HIP(e);
+    u->timed_done[0] = true;
+    return RL_OK;
+}
+} // namespace
+
+int rl_spectral_unit_create(int device, uint32_t width, uint32_t height, uint32_t n_nodes, RlSpectralUnit** out) {
+    if (!out) return fail(RL_E_INVALID, "null output handle");
+    *out = nullptr;
+    if (width == 0 || height == 0) return fail(RL_E_INVALID, "zero-sized spectral unit");
+    int rc = spectral_nodes_check("spectral unit", n_nodes);
+    if (rc != RL_OK) return rc;
+    const uint64_t n_pixels = (uint64_t)width * height; // (below 2^64; times n_nodes only once it is known to be below 2^31)
+    if (n_pixels > RL_MAX_PIXELS || n_pixels * n_nodes > RL_MAX_PIXELS)
+        return fail(RL_E_INVALID, "spectral unit: " + std::to_string(width) + " x " + std::to_string(height) + " pixels x " + std::to_string(n_nodes) +
+                                      " nodes exceed RL_MAX_PIXELS = 2^31 - 1");
+    rc = use_device(device);
+    if (rc != RL_OK) return rc;
+    RlSpectralUnit* u = new (std::nothrow) RlSpectralUnit();
+    if (!u) return fail(RL_E_INVALID, "out of host memory");
+    u->device = device;
+    u->width = width;
+    u->height = height;
+    u->n_nodes = n_nodes;
+    u->spacing = spectral_spacing(n_nodes);
+    const size_t bytes = (size_t)n_pixels * n_nodes * sizeof(float);
+    hipError_t e = hipMalloc((void**)&u->film, bytes);
+    if (e == hipSuccess) e = hipMemset(u->film, 0, bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&u->matrix, (size_t)RL_SPECTRAL_MAX_NODES * 3 * sizeof(float));
+    if (e == hipSuccess) e = create_unit_stream(&u->stream);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&u->ready, hipEventDisableTiming);
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+        e = hipEventCreate(&u->timed[k].start);
+        if (e == hipSuccess) e = hipEventCreate(&u->timed[k].stop);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr); // the synchronous memset above ran on the null stream
+    if (e != hipSuccess) {
+        rl_spectral_unit_destroy(u);
+        return fail(RL_E_HIP, std::string("spectral unit allocation: ") + hipGetErrorString(e));
+    }
+    *out = u;
+    return RL_OK;
+}
+
+int rl_spectral_unit_destroy(RlSpectralUnit* u) {
+    if (!u) return RL_OK;
+    (void)hipSetDevice(u->device);
+    if (u->stream) {
+        (void)hipStreamSynchronize(u->stream);
+        (void)hipStreamDestroy(u->stream);
+    }
+    if (u->ready) (void)hipEventDestroy(u->ready);
+    for (EventPair& ep : u->timed) {
+        if (ep.start) (void)hipEventDestroy(ep.start);
+        if (ep.stop) (void)hipEventDestroy(ep.stop);
+    }
+    if (u->film) (void)hipFree(u->film);
+    if (u->matrix) (void)hipFree(u->matrix);
+    delete u;
+    return RL_OK;
+}
+
+int rl_spectral_unit_clear(RlSpectralUnit* u) {
+    if (!u) return fail(RL_E_INVALID, "null spectral unit");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    RL_HIP(hipMemsetAsync(u->film, 0, (size_t)u->width * u->height * u->n_nodes * sizeof(float), u->stream));
+    return RL_OK;
+}
+
+int rl_spectral_unit_plot(RlSpectralUnit* u, RlTraceUnit* const* trace_units, uint32_t n_trace_units) {
+    if (!u || (!trace_units && n_trace_units)) return fail(RL_E_INVALID, "null argument");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    int cus = 256;
+    if ((rc = cu_count_of(u->device, &cus)) != RL_OK) return rc;
+    for (uint32_t k = 0; k < n_trace_units && rc == RL_OK; ++k) {
+        RlTraceUnit* t = trace_units[k];
+        if (!t || t->device != u->device) {
+            rc = fail(RL_E_STATE, "trace unit missing or on another device");
+            break;
+        }
+        if ((rc = render_end(t)) != RL_OK) break;              // a render that was begun: its photons are complete after this
+        RL_HIP(hipStreamWaitEvent(u->stream, t->rendered, 0)); // mapped_photons complete (a no-op after a synchronous render)
+        rc = launch_spectral_photons(u, u->stream, cus, t->photons, t->n_photons);
+    }
+    // The splats are in the film on return, so the trace units' next renders need no event of this unit's to wait for.
+    return n_trace_units != 0 ? spectral_drained(u, rc) : rc;
+}
+
+int rl_spectral_unit_plot_photons(RlSpectralUnit* u, const RlMappedPhoton* photons, uint64_t n) {
+    if (!u) return fail(RL_E_INVALID, "null spectral unit");
+    if (n > 0 && !photons) return fail(RL_E_INVALID, "null photon buffer");
+    if (n == 0) return RL_OK;
+    return with_call_ctx(u->device, "spectral unit", nullptr, DeviceArrays{}, [&](const CallCtx& q) -> int {
+        const CallCtx c{q.q, u->stream, q.cus};
+        return spectral_drained(u, staged_chunks(c, n, {staged_in(STAGING_RAYS, photons, sizeof(RlMappedPhoton))}, [&](uint64_t, uint64_t k) -> int {
+            return launch_spectral_photons(u, c.stream, c.cus, (const RlMappedPhoton*)c.q->staging[STAGING_RAYS], k);
+        }));
+    });
+}
+
+int rl_spectral_unit_plot_photons_device(RlSpectralUnit* u, const RlMappedPhoton* device_photons, uint64_t n) {
+    if (!u) return fail(RL_E_INVALID, "null spectral unit");
+    if (n > 0 && !device_photons) return fail(RL_E_INVALID, "null photon buffer");
+    if (n == 0) return RL_OK;
+    return with_call_ctx(u->device, "spectral unit", nullptr, {"rl_spectral_unit_plot_photons_device", "rl_spectral_unit_plot_photons", {device_photons}},
+                         [&](const CallCtx& q) -> int { return spectral_drained(u, launch_spectral_photons(u, u->stream, q.cus, device_photons, n)); });
+}
+
+int rl_spectral_unit_download(RlSpectralUnit* u, float* out) {
+    if (!u || !out) return fail(RL_E_INVALID, "null argument");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    RL_HIP(hipStreamSynchronize(u->stream));
+    RL_HIP(hipMemcpy(out, u->film, (size_t)u->width * u->height * u->n_nodes * sizeof(float), hipMemcpyDeviceToHost));
+    return RL_OK;
+}
+
+int rl_spectral_unit_upload(RlSpectralUnit* u, const float* in) {
+    if (!u || !in) return fail(RL_E_INVALID, "null argument");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    RL_HIP(hipStreamSynchronize(u->stream));
+    RL_HIP(hipMemcpy(u->film, in, (size_t)u->width * u->height * u->n_nodes * sizeof(float), hipMemcpyHostToDevice));
+    RL_HIP(hipStreamSynchronize(nullptr)); // (the null stream only: a resident open trace kernel of another unit is not waited for)
+    return RL_OK;
+}
+
+int rl_spectral_unit_project(RlSpectralUnit* u, const float* matrix, RlGatherUnit* dst) {
+    if (!u || !matrix || !dst) return fail(RL_E_INVALID, "rl_spectral_unit_project: null spectral unit, matrix or dst");
+    if (dst->device != u->device || dst->width != u->width || dst->height != u->height)
+        return fail(RL_E_STATE, "gather unit does not match the spectral unit (device or size)");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    int cus = 256;
+    if ((rc = cu_count_of(u->device, &cus)) != RL_OK) return rc;
+    const uint64_t n_pixels = (uint64_t)u->width * u->height;
+    hipStream_t stream = dst->stream;
+    RL_HIP(hipEventRecord(u->ready, u->stream)); // everything queued on the film (a clear; the splats have drained)
+    RL_HIP(hipStreamWaitEvent(stream, u->ready, 0));
+    RL_HIP(hipMemcpyAsync(u->matrix, matrix, (size_t)u->n_nodes * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
+    u->timed_done[1] = false;
+    RL_HIP(hipEventRecord(u->timed[1].start, stream));
+    hipLaunchKernelGGL(rl_spectral_project_kernel, dim3(grid_for(n_pixels, cus)), dim3(RL_BLOCK), 0, stream, (const float*)u->film,
+                       (const float*)u->matrix, n_pixels, u->n_nodes, dst->acc);
+    RL_HIP(hipGetLastError());
+    RL_HIP(hipEventRecord(u->timed[1].stop, stream));
+    g_spectral_launches[1].fetch_add(1, std::memory_order_relaxed);
+    RL_HIP(hipMemsetAsync(dst->comp, 0, (size_t)n_pixels * 3 * sizeof(float), stream));
+    RL_HIP(hipStreamSynchronize(stream));
+    u->timed_done[1] = true;
+    return RL_OK;
+}
+
+int rl_spectral_observer_cie1931(uint32_t n_nodes, float* out) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    const int rc = spectral_nodes_check("rl_spectral_observer_cie1931", n_nodes);
+    if (rc != RL_OK) return rc;
+    RlF4 table[RL_CIE_SAMPLES];
+    std::memcpy(table, RL_CIE1931_XYZ0, sizeof table);
+    const float spacing = spectral_spacing(n_nodes);
+    for (uint32_t b = 0; b < n_nodes; ++b) {
+        const RlF3 c = rl_tristimulus(table, 380.0f + (float)b * spacing);
+        out[3u * b] = c.x;
+        out[3u * b + 1u] = c.y;
+        out[3u * b + 2u] = c.z;
+    }
+    return RL_OK;
+}
+
 // ---- GatherUnit-time exchange across GPUs (gather_unit.rs:49-64 with the plot buffers of G GPUs) ----
 
 namespace {
@@ -3082,6 +3296,21 @@ int rl_debug_feature_launches(uint64_t out[6]) { return family_launches(g_featur
 int rl_debug_denoise_launches(uint64_t out[2]) {
     if (!out) return fail(RL_E_INVALID, "null output");
     for (int k = 0; k < 2; ++k) out[k] = g_denoise_launches[k].load(std::memory_order_relaxed);
+    return RL_OK;
+}
+int rl_debug_spectral_launches(uint64_t out[2]) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    for (int k = 0; k < 2; ++k) out[k] = g_spectral_launches[k].load(std::memory_order_relaxed);
+    return RL_OK;
+}
+int rl_debug_spectral_ms(RlSpectralUnit* u, float out[2]) {
+    if (!u || !out) return fail(RL_E_INVALID, "null argument");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    for (int k = 0; k < 2; ++k) {
+        out[k] = 0.0f;
+        if (u->timed_done[k]) RL_HIP(hipEventElapsedTime(&out[k], u->timed[k].start, u->timed[k].stop));
+    }
     return RL_OK;
 }
 int rl_debug_denoise_pass_ms(RlDenoiseUnit* u, float out[1 + RL_DENOISE_MAX_ITERATIONS]) {
