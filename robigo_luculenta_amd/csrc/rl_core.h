@@ -583,7 +583,12 @@ RL_HD int rl_hex_prism_fast(const RlF4* pr, RlF3 o, RlF3 d, RlCand* out, RlF4 pr
 #if defined(__HIP_DEVICE_COMPILE__)
         // The four running extrema two planes at a time, with v_max3 / v_min3 spelled out (round 6): tk is made by bit operations, so
         // the compiler cannot rule out a signalling NaN and put a canonicalising v_max_f32 x, x in front of every fmaxf / fminf of
-        // it -- fourteen instructions per round.  The instructions themselves treat a (quiet) NaN as fmaxf / fminf do: the other operand.
+        // it -- fourteen instructions per round.  A tk that IS a NaN pattern occurs: from |o| ~ 1e33 the quotient overflows, and an
+        // infinity with plane number k >= 1 in its low bits is a signalling NaN (k = 0 leaves a true infinity); 0 * inf gives quiet ones.
+        // No rule for what the instructions return for those is assumed here; it is measured (tests/test_gpu_scene_shapes.py: the
+        // probe from far origins and the "beyond" family, gfx950): on unit rays from 1e8 units away to FLT_MAX this branch decides
+        // exactly as many pairs as the host branch's fmaxf / fminf, which ignore a NaN -- hits and misses alike, none against the
+        // tree -- and every ray kernel returns the reference's miss for every ray from beyond 1e12.
         const float sel_in = entering ? tk : -INF, sel_out = entering ? INF : tk;
         if (k & 1) {
             asm("v_max3_f32 %0, %0, %1, %2" : "+v"(t_in) : "v"(pair_in), "v"(sel_in));

@@ -150,6 +150,162 @@ def far_rays(objs, n):
     return o[keep], d[keep]
 
 
+ALL_KINDS = (0, 1, 2, 3, 4)      # sphere, plane, circle, paraboloid, hexagonal prism
+FLT_MAX = float(np.finfo(np.float32).max)
+
+
+def _d2(d):
+    """The kernels' own f32 |d|^2: d.x*d.x + d.y*d.y + d.z*d.z, left to right, every step rounded."""
+    return d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]
+
+
+def _targets(objs, kinds, rng, n):
+    """n points in f64, each within about half an object size of an anchor of a randomly chosen object of `kinds`: v0 for a sphere,
+    v1 otherwise -- for a prism, whose v1 is the centre of its base, a point on its axis between base and top.  The size is the
+    radius of a sphere or circle, the focal distance of a paraboloid, half the edge length of a prism (its base triangle's inscribed
+    radius is 0.29 edges) and 10 units for a plane."""
+    sk = objs["surface_kind"]
+    anchor = np.where((sk == 0)[:, None], objs["v0"], objs["v1"]).astype(np.float64)
+    size = np.where(sk == 1, 10.0, np.abs(objs["f"][:, 0].astype(np.float64)) * np.where(sk == 4, 0.5, 1.0))
+    ok = np.isin(sk, kinds) & np.isfinite(anchor).all(axis=1) & (np.abs(anchor).max(axis=1) < 1e4) & np.isfinite(size) & (size > 0)
+    pool = np.flatnonzero(ok)
+    assert len(pool), kinds
+    k = pool[rng.integers(0, len(pool), n)]
+    along = np.where(sk[k] == 4, rng.random(n) * objs["f"][k, 3], 0.0)
+    return anchor[k] + along[:, None] * objs["v0"][k].astype(np.float64) + 0.5 * size[k, None] * rng.uniform(-1.0, 1.0, (n, 3))
+
+
+def _aimed(target, o, instead=None):
+    """(o, d): f32 origins with the direction re-aimed at `target` from the ROUNDED origin, normalised in f64 and rounded (or the
+    row of `instead`, where that is not NaN); without the rays whose f32 |d|^2 is further than 2^-20 from 1 or whose origin has a
+    component that is not finite, so that every ray left takes the culled scan."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        o = np.asarray(o, np.float64).astype(np.float32)
+        finite = np.isfinite(o).all(axis=1)
+        d = target - o.astype(np.float64)
+        d = d / np.abs(d).max(axis=1, keepdims=True)     # (|d|^2 of a difference near FLT_MAX overflows nothing in f64; scaled all the same)
+        d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+        if instead is not None:
+            d = np.where(np.isnan(instead[:, :1]), d, instead).astype(np.float32)
+        keep = finite & (np.abs(_d2(d) - np.float32(1.0)) <= np.float32(2.0 ** -20))
+    return np.ascontiguousarray(o[keep]), np.ascontiguousarray(d[keep])
+
+
+def far_rays_at(objs, n, lo, hi, kinds=ALL_KINDS):
+    """far_rays for every surface kind: (origins, directions) of up to n unit rays from 10^U(lo, hi) units away, aimed within about
+    half an object size of an anchor of a randomly chosen object of the surface kinds asked for (_targets).  The origin is rounded
+    to f32 first and the direction re-aimed from it in f64 and rounded (_aimed): from 10^8 on the f32 direction cannot hold the
+    target any more (one ulp of it is 6 units wide at 10^8), and what such a ray hits is the reference's rounding to decide.
+    Drawn from a generator of its own."""
+    rng = np.random.default_rng([len(objs), n, int(round(lo * 1000)), int(round(hi * 1000)), sum(1 << int(k) for k in kinds)])
+    target = _targets(objs, kinds, rng, n)
+    u = QR.uniform_directions(rng, n).astype(np.float64)
+    return _aimed(target, target - (10.0 ** rng.uniform(lo, hi, n))[:, None] * u)
+
+
+def limit_rays(objs, n):
+    """far_rays_at from 10^11.9 to 10^12.1 units away over all surface kinds: hit distances on both sides of the 1e12 below which
+    alone a hit counts (scene.rs:43)."""
+    return far_rays_at(objs, n, 11.9, 12.1, ALL_KINDS)
+
+
+def beyond_rays(objs, n):
+    """(origins, directions) of up to n unit rays from 10^12.1 units to FLT_MAX away, aimed like far_rays_at's: finite origins, so
+    the culled scan takes them, and beyond the 1e12 of scene.rs:43, so the reference reports a miss for every one.  In eighths of n:
+      0-1  log-uniform distances over the whole range;
+      2    distances 10^19 .. 10^19.6, around the 1.8e19 from which |o|^2 overflows;
+      3-4  distances 10^33 .. 10^38.5, where the prism shortcut's quotients n.(o - off) / n.d overflow;
+      5    the origin's largest component set to +-FLT_MAX itself;
+      6-7  the origin displaced along ONE axis only (distances over the whole range and, every other ray, from 10^33 up), so that
+           n.(o - off) stays small for the planes whose normal is across that axis while the others' overflow; half of them keep
+           the aimed direction (along the axis); half get a uniform one, which no plane of a prism is parallel to -- unless the
+           description has a plane or a paraboloid: those are unbounded, and a ray beside one would reach it.
+    Drawn from a generator of its own."""
+    rng = np.random.default_rng([len(objs), n, 0xbe7])
+    top = np.log10(FLT_MAX) - 0.03
+    target = _targets(objs, ALL_KINDS, rng, n)
+    part = (np.arange(n) * 8) // n
+    e = rng.uniform(12.1, top, n)
+    e = np.where(part == 2, rng.uniform(19.0, 19.6, n), e)
+    e = np.where((part == 3) | (part == 4) | ((part >= 6) & (np.arange(n) % 2 == 1)), rng.uniform(33.0, top, n), e)
+    u = QR.uniform_directions(rng, n).astype(np.float64)
+    axis = rng.integers(0, 3, n)
+    one = np.zeros((n, 3))
+    one[np.arange(n), axis] = rng.choice([-1.0, 1.0], n)
+    u = np.where((part >= 6)[:, None], one, u)
+    o = target - (10.0 ** e)[:, None] * u
+    edge = np.flatnonzero(part == 5)
+    big = np.abs(o[edge]).argmax(axis=1)
+    o[edge, big] = np.sign(o[edge, big]) * FLT_MAX
+    loose = QR.uniform_directions(rng, n)                # (drawn for every ray: the draws do not depend on the parts' sizes)
+    loose[~((part >= 6) & (rng.random(n) < 0.5))] = np.nan
+    if np.isin(objs["surface_kind"], (1, 3)).any():
+        loose[:] = np.nan    # a plane or a paraboloid is unbounded: a ray that runs beside one reaches it whatever the distance along the axis
+    return _aimed(target, o, instead=loose)
+
+
+EDGE_TARGETS = ("below-outside", "below-on", "below-inside", "above-inside", "above-on", "above-outside")
+
+
+def unit_edge_rays(o, d):
+    """{target: (origins, directions)} from given unit rays, ray i made for target i mod 6: the directions' largest component moved
+    by nextafter steps until the kernels' own f32 |d|^2 (_d2) minus one is, in the order of EDGE_TARGETS,
+        -2^-20 - 2^-24, -2^-20, -2^-20 + 2^-24, 2^-20 - 2^-23, 2^-20, 2^-20 + 2^-23
+    -- the two values on the threshold `fabsf(d2 - 1) <= 2^-20` between the culled and the exact scan and their f32 neighbours on
+    either side (one ulp of |d|^2 is 2^-24 below one and 2^-23 above).  A step of the largest component moves |d|^2 by one to two
+    of its ulps, so where it steps over the target the second largest component, whose steps are finer, is moved as well; a ray
+    for which no such pair of moves gives the target exactly is left out.  The directions change by under 1e-6 of their length."""
+    o, d = np.asarray(o, np.float32), np.asarray(d, np.float32)
+    h = 2.0 ** -20
+    wanted = np.array([-h - 2.0 ** -24, -h, -h + 2.0 ** -24, h - 2.0 ** -23, h, h + 2.0 ** -23], np.float32)
+    goal = wanted[np.arange(len(d)) % 6]
+    order = np.argsort(-np.abs(d), axis=1)
+    rows = np.arange(len(d))
+    first, second = order[:, 0], order[:, 1]
+    a = d[rows, first].astype(np.float64)
+    rest = (d.astype(np.float64) ** 2).sum(axis=1) - a * a
+    start = d.copy()
+    start[rows, first] = (np.sign(a) * np.sqrt(np.maximum(1.0 + goal.astype(np.float64) - rest, 0.0))).astype(np.float32)
+    out = start.copy()
+    found = np.zeros(len(d), bool)
+    one = np.float32(1.0)
+    for i in (0, 1, -1, 2, -2, 3, -3):
+        for j in range(-24, 25):
+            trial = start.copy()
+            trial[rows, first] = _stepped_by(start[rows, first], i)
+            trial[rows, second] = _stepped_by(start[rows, second], j)
+            hit = ~found & (_d2(trial) - one == goal)
+            out[hit], found = trial[hit], found | hit
+    return {name: (np.ascontiguousarray(o[found & (rows % 6 == k)]), np.ascontiguousarray(out[found & (rows % 6 == k)]))
+            for k, name in enumerate(EDGE_TARGETS)}
+
+
+def _stepped_by(x, steps):
+    """x moved by `steps` nextafter steps away from zero (towards it for a negative count)."""
+    for _ in range(abs(steps)):
+        x = np.nextafter(x, np.where(steps > 0, np.float32(np.inf), np.float32(0.0)) * np.sign(x)).astype(np.float32)
+    return x
+
+
+def far_families(objs, cam, n, edge=False):
+    """{family: (origins, directions)} of the rays from far outside for one description, n rays a family before the generators drop
+    any: "far-prisms" (far_rays_at 10^3 .. 10^8 at the prisms), "far-others" (the same at planes, circles and paraboloids, where
+    there are any), "deep" (10^8 .. 10^11.9 at every kind), "limit" (limit_rays), "beyond" (beyond_rays) and, with `edge`, the six
+    groups of unit_edge_rays made from camera rays, as "edge-" + the names of EDGE_TARGETS."""
+    kinds = tuple(int(k) for k in np.unique(objs["surface_kind"]))
+    others = tuple(k for k in kinds if k in (1, 2, 3))
+    sets = {"far-prisms": far_rays_at(objs, n, 3.0, 8.0, (4,))}
+    if others:
+        sets["far-others"] = far_rays_at(objs, n, 3.0, 8.0, others)
+    sets["deep"] = far_rays_at(objs, n, 8.0, 11.9, kinds)
+    sets["limit"] = limit_rays(objs, n)
+    sets["beyond"] = beyond_rays(objs, n)
+    if edge:
+        groups = unit_edge_rays(*QR.camera_rays(cam, 1920, 1080, np.random.default_rng([len(objs), n, 0xed9e]), n))
+        sets.update({"edge-" + name: rays for name, rays in groups.items()})
+    return sets
+
+
 def _filter(want, t_max):
     out = want.copy()
     miss = (want["object"] == NONE) | ~(want["distance"] < t_max)

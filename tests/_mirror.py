@@ -26,12 +26,15 @@ def lib():
         L.mirror_render.argtypes = [vp, u32, u32, u64, u32, u64, u64, vp, vp]
         L.mirror_plot.argtypes = [vp, u32, u32, vp, u64]
         L.mirror_prism_fast_check.argtypes = [vp, u64, u64, vp]
+        L.mirror_prism_fast_check_band.argtypes = [vp, u64, u64, C.c_double, C.c_double, vp]
         L.mirror_prism_fast_check_paths.argtypes = [vp, u32, u32, u64, u32, u64, u64, vp]
         L.mirror_prism_cylinders.restype = u32
         L.mirror_prism_cylinders.argtypes = [vp, vp, u32]
         L.mirror_cull_counts.argtypes = [vp, u32, u32, u64, u32, u64, u64, vp]
         L.mirror_prism_pairs.restype = u64
         L.mirror_prism_pairs.argtypes = [vp, u64, u64, vp, vp, vp, u64]
+        L.mirror_prism_pairs_band.restype = u64
+        L.mirror_prism_pairs_band.argtypes = [vp, u64, u64, C.c_double, C.c_double, vp, vp, vp, u64]
         _lib = L
     return _lib
 
@@ -63,11 +66,16 @@ class Scene:
         return photons, segs.value
 
 
-def prism_fast_check(scene, trials, seed):
+def prism_fast_check(scene, trials, seed, band=None):
     """rl_hex_prism_fast against rl_hex_prism on random and adversarial (prism, ray) pairs of `scene`:
-    {pairs, decided hits, decided misses, undecided, decided-but-different (must be 0), tree hits}."""
+    {pairs, decided hits, decided misses, undecided, decided-but-different (must be 0), tree hits}.
+    With band = (lo, hi): on unit rays from 10^lo .. 10^hi units away from the prism instead, a quarter of the origins displaced
+    along one axis only, three quarters of the directions aimed into the prism's bound from the rounded origin."""
     counts = np.zeros(6, dtype=np.uint64)
-    lib().mirror_prism_fast_check(scene.h, trials, seed, O.ptr(counts))
+    if band is not None:
+        lib().mirror_prism_fast_check_band(scene.h, trials, seed, float(band[0]), float(band[1]), O.ptr(counts))
+    else:
+        lib().mirror_prism_fast_check(scene.h, trials, seed, O.ptr(counts))
     return dict(zip(("pairs", "hits", "misses", "undecided", "wrong", "tree_hits"), (int(c) for c in counts)))
 
 
@@ -78,12 +86,16 @@ def prism_fast_check_paths(scene, w, h, seed, stream, first, n):
     return dict(zip(("pairs", "hits", "misses", "undecided", "wrong", "tree_hits"), (int(c) for c in counts)))
 
 
-def prism_pairs(scene, trials, seed):
-    """The adversarial (prism, ray) pairs of prism_fast_check as data: prism numbers, rays (n x 6), the tree's {t bits, half-space}."""
+def prism_pairs(scene, trials, seed, band=None):
+    """The adversarial (prism, ray) pairs of prism_fast_check, or the pairs of its `band`, as data: prism numbers, rays (n x 6), the
+    tree's {t bits, half-space}."""
     prisms = np.zeros(trials, dtype=np.uint32)
     rays = np.zeros((trials, 6), dtype=np.float32)
     tree = np.zeros((trials, 2), dtype=np.uint32)
-    n = lib().mirror_prism_pairs(scene.h, trials, seed, O.ptr(prisms), O.ptr(rays), O.ptr(tree), trials)
+    if band is not None:
+        n = lib().mirror_prism_pairs_band(scene.h, trials, seed, float(band[0]), float(band[1]), O.ptr(prisms), O.ptr(rays), O.ptr(tree), trials)
+    else:
+        n = lib().mirror_prism_pairs(scene.h, trials, seed, O.ptr(prisms), O.ptr(rays), O.ptr(tree), trials)
     return prisms[:n], rays[:n], tree[:n]
 
 

@@ -1,5 +1,5 @@
 """Scene descriptions by name for the tests of the ray calls: the built-in scenes, random scenes at the sizes that reach every kernel
-variant, the degenerate sphere layouts, the same with emitters to sample, and a small closed scene for the estimator's mean.  Every
+variant, the degenerate sphere layouts, parts of the built-in scenes without their walls, the same with emitters to sample, and a small closed scene for the estimator's mean.  Every
 call builds its description anew: tests write into the arrays they get back."""
 import numpy as np
 
@@ -18,6 +18,24 @@ SCENES = ["demo", "demo-2500", "glass", "random-seed-1", "random-seed-2", "rando
 # whose objects coincide across the kernel's tables.
 SHAPE_SCENES = ["room-tilted", "room-plus-disc", "room-reordered", "shuffled-40", "shuffled-300", "shuffled-3000", "shuffled-6000",
                 "coincident-300", "coincident-3000"]
+
+
+# Parts of the built-in descriptions for rays from far outside (tests/_cases.py: far_rays_at and its kin): the walls of the closed
+# room stop nearly every such ray before a prism, so these leave them out.  glass-spheres-prisms keeps the glass-stress scene's
+# 66 prisms -- 40 or more, so it runs the kernels' CYL variants and their cylinder bound.
+# demo-open is the built-in scene without its plane and paraboloids: lights, spheres and prisms that a camera far outside can see.
+FAR_SUBSETS = {"demo-prisms": ("demo", (4,)), "demo-spheres-prisms": ("demo", (0, 4)), "demo-prisms-paraboloids": ("demo", (3, 4)),
+               "glass-spheres-prisms": ("glass", (0, 4)), "demo-open": ("demo", (0, 2, 4))}
+
+
+def camera_moved_back(cam, back, telescope=False):
+    """A copy of the camera record `cam` translated `back` units back along its view axis (it looks at the scene's origin from
+    dist0); with `telescope`, its field of view narrowed to half of what shows the same part of the scene as before."""
+    moved = type(cam).from_buffer_copy(bytes(cam))
+    moved.dist0 = cam.dist0 + back
+    if telescope:
+        moved.fov_over_pi = 0.5 * cam.fov_over_pi * cam.dist0 / (cam.dist0 + back)
+    return moved
 
 
 def _room(change):
@@ -85,6 +103,11 @@ def _scene(name):
         if family == "shuffled":
             return _shuffled(38 if what == "40" else int(what))   # 38 and the light: 39 spheres, the most that get no clusters
         return _coincident(int(what))
+    if name in FAR_SUBSETS:
+        whole, kinds = FAR_SUBSETS[name]
+        objs, cam = _scene(whole)
+        objs = np.ascontiguousarray(objs).view(R.OBJECT_DTYPE)
+        return objs[np.isin(objs["surface_kind"], kinds)].copy(), cam
     if name == "demo":
         return R.builtin_scene_desc(R.SCENE_DEMO)
     if name == "demo-2500":

@@ -401,6 +401,104 @@ extern "C" void mirror_prism_fast_check(void* scene, uint64_t trials, uint64_t s
     }
 }
 
+// The same comparison for origins far from the prism: |o - centre| = 10^U(lo, hi), up to FLT_MAX (an origin with a component that
+// is not finite in f32 is drawn again).  A quarter of the origins are displaced along one axis only -- n.(o - off) then stays small
+// for the planes across that axis while the others' overflow -- and the direction is a unit vector aimed into the prism's bound
+// from the rounded origin (normalised in double), or, for a quarter of the pairs, any unit vector.  From about 1e33 the shortcut's
+// tagged quotients are infinities that carry a plane number in their low bits, i.e. NaN patterns.
+static bool gen_band_pair(const RlFlatScene& fs, uint64_t& s, double lo, double hi, uint32_t* prism_out, RlF3* o_out, RlF3* d_out) {
+    const uint32_t n_prisms = (uint32_t)(fs.prisms.size() / RL_PRISM_STRIDE);
+    const uint32_t prism = (uint32_t)(mix64(s) % n_prisms);
+    const RlF4* pr = &fs.prisms[RL_PRISM_STRIDE * prism];
+    const RlF4 bound = pr[16];
+    if (!(bound.w > 0.0f) || !(bound.w < 1e30f)) return false; // a padding prism
+    const double R = std::sqrt((double)bound.w);
+    double u[3];
+    double m;
+    do {
+        m = 0.0;
+        for (int a = 0; a < 3; ++a) u[a] = (double)sym(s), m += u[a] * u[a];
+    } while (m < 0.01 || m > 1.0);
+    const uint64_t how = mix64(s);
+    if ((how & 3) == 0) { // one axis only
+        const int axis = (int)((how >> 2) % 3);
+        for (int a = 0; a < 3; ++a) u[a] = a == axis ? ((how >> 8) & 1 ? 1.0 : -1.0) : 0.0;
+        m = 1.0;
+    }
+    const double dist = std::pow(10.0, lo + (hi - lo) * (double)unit01(s)) / std::sqrt(m);
+    const double c[3] = {bound.x, bound.y, bound.z};
+    const double of[3] = {c[0] + u[0] * dist, c[1] + u[1] * dist, c[2] + u[2] * dist};
+    if (!(std::fabs(of[0]) <= 3.4028234663852886e38 && std::fabs(of[1]) <= 3.4028234663852886e38 && std::fabs(of[2]) <= 3.4028234663852886e38)) return false;
+    const RlF3 o = rl_f3((float)of[0], (float)of[1], (float)of[2]);
+    double t[3], big = 0.0, len = 0.0;
+    const double spread = (how >> 9) & 1 ? 0.5 : 1.0e-3; // into the bound, or at its middle: from afar the rounded direction scatters by itself
+    for (int a = 0; a < 3; ++a) t[a] = c[a] + (double)sym(s) * R * spread;
+    t[0] -= (double)o.x, t[1] -= (double)o.y, t[2] -= (double)o.z;
+    for (int a = 0; a < 3; ++a) big = std::fmax(big, std::fabs(t[a]));
+    for (int a = 0; a < 3; ++a) t[a] /= big, len += t[a] * t[a];
+    len = std::sqrt(len);
+    RlF3 d = rl_f3((float)(t[0] / len), (float)(t[1] / len), (float)(t[2] / len));
+    if (((how >> 10) & 3) == 0) {
+        for (;;) {
+            const RlF3 v = rl_f3(sym(s), sym(s), sym(s));
+            const float mm = rl_dot(v, v);
+            if (mm > 0.01f && mm <= 1.0f) { d = rl_normalise(v); break; }
+        }
+    }
+    *prism_out = prism;
+    *o_out = o;
+    *d_out = d;
+    return true;
+}
+
+extern "C" void mirror_prism_fast_check_band(void* scene, uint64_t trials, uint64_t seed, double lo, double hi, uint64_t* counts) {
+    const RlFlatScene& fs = ((MirrorScene*)scene)->flat;
+    for (int i = 0; i < 6; ++i) counts[i] = 0;
+    if (fs.prisms.empty()) return;
+    uint64_t s = seed;
+    for (uint64_t it = 0; it < trials; ++it) {
+        uint32_t prism;
+        RlF3 o, d;
+        if (!gen_band_pair(fs, s, lo, hi, &prism, &o, &d)) continue;
+        const RlF4* pr = &fs.prisms[RL_PRISM_STRIDE * prism];
+        const RlCand want = rl_hex_prism(pr, o, d);
+        RlCand got;
+        const int status = rl_hex_prism_fast(pr, o, d, &got);
+        counts[0] += 1;
+        if (want.t >= 0.0f) counts[5] += 1;
+        if (status == RL_PRISM_UNSURE) {
+            counts[3] += 1;
+        } else if (status == RL_PRISM_HIT) {
+            counts[1] += 1;
+            if (!(want.t >= 0.0f) || rl_f2u(want.t) != rl_f2u(got.t) || want.k != got.k) counts[4] += 1;
+        } else {
+            counts[2] += 1;
+            if (want.t >= 0.0f) counts[4] += 1;
+        }
+    }
+}
+
+// The band's pairs as data, as mirror_prism_pairs gives the adversarial ones.
+extern "C" uint64_t mirror_prism_pairs_band(void* scene, uint64_t trials, uint64_t seed, double lo, double hi, uint32_t* prisms, float* rays6,
+                                            uint32_t* tree2, uint64_t cap) {
+    const RlFlatScene& fs = ((MirrorScene*)scene)->flat;
+    if (fs.prisms.empty()) return 0;
+    uint64_t s = seed, n = 0;
+    for (uint64_t it = 0; it < trials && n < cap; ++it) {
+        uint32_t prism;
+        RlF3 o, d;
+        if (!gen_band_pair(fs, s, lo, hi, &prism, &o, &d)) continue;
+        const RlCand want = rl_hex_prism(&fs.prisms[RL_PRISM_STRIDE * prism], o, d);
+        prisms[n] = prism;
+        float* r = rays6 + 6 * n;
+        r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z;
+        tree2[2 * n] = want.t >= 0.0f ? rl_f2u(want.t) : 0xffffffffu;
+        tree2[2 * n + 1] = want.k;
+        n += 1;
+    }
+    return n;
+}
+
 // The same pairs as data, for the device-side comparison (rl_debug_prism_probe): prism numbers, rays {o, d} and the g++
 // tree's answer {t bits or 0xffffffff, half-space}.  Returns the number of pairs written (<= cap).
 extern "C" uint64_t mirror_prism_pairs(void* scene, uint64_t trials, uint64_t seed, uint32_t* prisms, float* rays6, uint32_t* tree2, uint64_t cap) {

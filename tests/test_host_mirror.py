@@ -291,6 +291,18 @@ def test_prism_shortcut_never_contradicts_the_compound_tree(which):
     assert abs(p["hits"] + p["undecided"] - p["tree_hits"]) <= p["undecided"], p
 
 
+@pytest.mark.parametrize("which", [0, 1])
+@pytest.mark.parametrize("band", [(8.0, 12.0), (12.0, float(np.log10(np.finfo(np.float32).max)))], ids=["1e8-1e12", "1e12-FLT_MAX"])
+def test_prism_shortcut_from_far_origins_never_contradicts_the_compound_tree(band, which):
+    """The same on unit rays from 10^8 .. 10^12 and from 10^12 .. FLT_MAX units away, the one-ulp reciprocal noise on.  In the
+    upper band the tagged quotients overflow: infinities that carry a plane number in their low bits -- NaN patterns, which this
+    build's fmaxf / fminf ignore.  The tree still reports hits there (rounding noise), so a wrong miss would show."""
+    objs, cam = M.builtin_desc(which)
+    r = M.prism_fast_check(M.Scene(objs, cam), 2_000_000, 20261020 + which, band=band)
+    assert r["pairs"] > 1_500_000 and r["wrong"] == 0, r
+    assert r["hits"] + r["misses"] > 0.15 * r["pairs"] and r["tree_hits"] > 0.02 * r["pairs"], r   # it decides, and there are hits to contradict
+
+
 def test_prism_shortcut_on_random_prisms():
     """Randomly oriented, sized and placed prisms (tests/_random_scene.py), incl. far from the origin."""
     import _random_scene as RS

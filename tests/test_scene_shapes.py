@@ -18,7 +18,25 @@ circles together, read from the host mirror: M.small_counts):
 
 The two tie conditions, from the oracle's per-object intersection alone: on each coincident-* scene at least 10 % of the camera
 rays' hits have a second object at exactly the same distance; on the built-in scene at least 5 % of the far family's hits
-(tests/_cases.py: far_rays) tie exactly with a different sphere."""
+(tests/_cases.py: far_rays) tie exactly with a different sphere.
+
+The rays from far outside at anything but spheres (tests/_cases.py: far_families) on the scenes of FAR_ON, held to what makes them
+worth running, by the oracle alone; the shares are the oracle's at 4,096 rays a family, hits by surface kind in the order sphere,
+plane, circle, paraboloid, prism:
+
+    scene                    far-prisms 10^3..10^8    deep 10^8..10^11.9      limit 10^11.9..10^12.1   beyond (to FLT_MAX)
+    demo-prisms              86 % (all prisms)        2 % (prisms)            none                     none
+    demo-spheres-prisms      3076 / 0 / 0 / 0 / 1007  1892 / 0 / 0 / 0 / 6    593 spheres              none
+    demo-prisms-paraboloids  0 / 0 / 0 / 3678 / 337   0 / 0 / 0 / 2731 / 13   1269 paraboloids, 1      none
+    glass-spheres-prisms     786 / 0 / 0 / 0 / 2992   1319 / 0 / 0 / 0 / 90   672 spheres, 1 prism     none
+    demo                     1612 / 598 / 0 / 1886 / 0  1000 / 1268 / 3 / 1825 / 0  249 / 776 / 0 / 1024 / 0, largest 9.998e11  none
+    random-6000              2509 / 1004 / 0 / 583 / 0  1289 / 1552 / 0 / 1254 / 1  256 / 1077 / 0 / 733 / 0  none
+                             (its 12 prisms stand among 6,000 spheres and inside two planes: the rays aimed at them meet those)
+far-others (10^3..10^8 at planes, circles and paraboloids): demo-prisms-paraboloids 0 / 0 / 0 / 3790 / 22, demo 1571 / 528 / 0 / 1997 / 0,
+random-6000 2613 / 719 / 5 / 759 / 0.  The six unit-edge groups on demo: 671 to 683 rays each, every one a hit (about 290 spheres,
+330 paraboloids and 50 prisms a group).
+
+(In the closed room the walls take every ray before a prism: that is why the subsets are there.)"""
 import numpy as np
 import pytest
 
@@ -26,8 +44,8 @@ import _mirror as M
 import _oracle as O
 import _query_rays as QR
 from _boundary import _ocam
-from _cases import far_rays, oracle_hits, tied_hits
-from _scenes import SCENES, SHAPE_SCENES, _scene
+from _cases import EDGE_TARGETS, FLT_MAX, _d2, far_families, far_rays, oracle_hits, tied_hits
+from _scenes import FAR_SUBSETS, SCENES, SHAPE_SCENES, _scene, camera_moved_back
 
 NONE = 0xffffffff
 #            name: (small_ordered, small_axis_z, paraboloids, planes and circles, table)
@@ -131,3 +149,101 @@ def test_a_twentieth_of_the_far_rays_hits_on_the_built_in_scene_tie_with_another
     share = float(tied[hit].mean())
     print("demo far: %d of %d rays hit, %.1f %% of the hits tied with another sphere" % (hit.sum(), len(o), 100 * share))
     assert hit.mean() > 0.3 and share >= 0.05, share
+
+
+# ---- rays from far outside, at anything but spheres -------------------------------------------------------------------------------
+
+FAR_ON = ["demo-prisms", "demo-spheres-prisms", "demo-prisms-paraboloids", "glass-spheres-prisms", "demo", "random-6000"]
+_FAR = {}
+
+
+def _far(name):
+    """(objects, {family: (o, d)}, {family: the oracle's hits}) of scene `name`; made once, no test writes into them."""
+    if name not in _FAR:
+        objs, cam = _described(name)
+        sets = far_families(objs, cam, 4096, edge=name == "demo")
+        so = O.Scene(objs, cam)
+        _FAR[name] = (objs, sets, {family: oracle_hits(so, o, d) for family, (o, d) in sets.items()})
+    return _FAR[name]
+
+
+def _by_kind(objs, want):
+    """Hits of `want` by the surface kind of the object hit: five counts."""
+    return np.bincount(objs["surface_kind"][want["object"][want["object"] != NONE]], minlength=5)
+
+
+@pytest.mark.parametrize("name", FAR_ON)
+def test_every_far_ray_takes_the_culled_scan_and_the_shares_are_printed(name):
+    objs, sets, want = _far(name)
+    assert name == "demo" or name == "random-6000" or name in FAR_SUBSETS
+    for family, (o, d) in sets.items():
+        print("%s %s: %d rays, hits by kind %s" % (name, family, len(o), _by_kind(objs, want[family])))
+        assert len(o) >= (64 if family.startswith("edge-") else 3900), (name, family, len(o))   # (the |d|^2 test drops next to nothing)
+        assert np.isfinite(o).all() and o.dtype == d.dtype == np.float32, (name, family)
+        if not family.endswith("-outside"):
+            assert (np.abs(_d2(d) - np.float32(1)) <= np.float32(2.0 ** -20)).all(), (name, family)
+
+
+@pytest.mark.parametrize("name,least", [("demo-prisms", 0.5), ("demo-spheres-prisms", 0.1), ("glass-spheres-prisms", 0.5)])
+def test_far_rays_at_the_prisms_hit_prisms(name, least):
+    """Over half on the prisms alone; at least a tenth beside the built-in scene's spheres, which take the rest; over half again
+    among the glass-stress scene's 66, which stand closer together."""
+    objs, sets, want = _far(name)
+    o = sets["far-prisms"][0]
+    dist = np.linalg.norm(o.astype(np.float64), axis=1)
+    assert dist.min() < 3e3 and dist.max() > 3e7
+    assert _by_kind(objs, want["far-prisms"])[4] > least * len(o), (name, _by_kind(objs, want["far-prisms"]))
+
+
+def test_deep_rays_hit_the_paraboloids_and_the_limit_family_straddles_1e12():
+    objs, sets, want = _far("demo-prisms-paraboloids")
+    assert (want["deep"]["object"] != NONE).mean() >= 0.25
+    objs, sets, want = _far("demo")
+    hit = want["limit"]["object"] != NONE
+    assert 0.25 <= hit.mean() <= 0.75, hit.mean()
+    assert (_by_kind(objs, want["limit"]) >= 64).sum() >= 2, _by_kind(objs, want["limit"])
+    assert 9.9e11 < want["limit"]["distance"][hit].max() < 1e12
+    for family in ("far-prisms", "far-others", "deep"):      # the walls and paraboloids of the whole room, each by the hundreds
+        assert (_by_kind(objs, want[family])[[1, 3]] >= 400).all(), (family, _by_kind(objs, want[family]))
+
+
+@pytest.mark.parametrize("name", FAR_ON)
+def test_the_oracle_reports_no_hit_from_beyond_1e12(name):
+    """scene.rs:43: a hit counts below 1e12 only.  The family covers what it says: the whole range, the band where |o|^2 overflows,
+    the band where the prism shortcut's quotients do, components equal to FLT_MAX, and origins displaced along one axis."""
+    objs, sets, want = _far(name)
+    o, d = sets["beyond"]
+    assert (want["beyond"]["object"] == NONE).all() and not want["beyond"]["distance"].any(), name
+    size = np.linalg.norm(o.astype(np.float64), axis=1)
+    assert size.min() > 1e12 and (size < 1e13).any()
+    assert ((size > 1e19) & (size < 4e19)).sum() >= 400 and (size > 1e33).sum() >= 1400
+    assert 100 <= (np.abs(o).max(axis=1) == np.float32(FLT_MAX)).sum() <= 600
+    one_axis = (np.abs(o) < 1e4).sum(axis=1) == 2
+    along = (np.abs(d) == 1).any(axis=1)
+    assert one_axis.sum() >= 900 and (one_axis & along).sum() >= 400
+    if not np.isin(objs["surface_kind"], (1, 3)).any():
+        assert (one_axis & ~along).sum() >= 400                # uniform directions from beside the scene, where nothing unbounded is there to reach
+
+
+def test_unit_edge_rays_sit_on_the_threshold_and_its_neighbours():
+    objs, sets, want = _far("demo")
+    h = 2.0 ** -20
+    exact = dict(zip(EDGE_TARGETS, (-h - 2.0 ** -24, -h, -h + 2.0 ** -24, h - 2.0 ** -23, h, h + 2.0 ** -23)))
+    hits = rays = 0
+    for target, value in exact.items():
+        o, d = sets["edge-" + target]
+        assert len(o) >= 64 and (_d2(d) - np.float32(1) == np.float32(value)).all(), target
+        assert (np.abs(_d2(d) - np.float32(1)) <= np.float32(h)).all() == (not target.endswith("outside")), target
+        hits, rays = hits + int((want["edge-" + target]["object"] != NONE).sum()), rays + len(o)
+    assert hits > rays / 3
+
+
+@pytest.mark.parametrize("name,back,telescope", [("demo", 10.0, False), ("demo-open", 1e4, True), ("demo-open", 1e7, True)])
+def test_mirror_renders_the_oracles_photons_from_a_camera_moved_back(name, back, telescope):
+    """The cameras of test_gpu_scene_shapes.py's far renders, on the host: not black, and the mirror's photons are the oracle's."""
+    objs, cam = _described(name)
+    cam = camera_moved_back(cam, back, telescope)
+    want, segs = O.Scene(objs, cam).render(320, 180, 5, 2, 777, 1 << 13, threads=16)
+    got, segs2 = M.Scene(objs, cam).render(320, 180, 5, 2, 777, 1 << 13)
+    assert (want["probability"] != 0).mean() >= 0.05, name
+    assert segs == segs2 and got.tobytes() == want.tobytes(), name
