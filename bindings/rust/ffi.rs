@@ -70,6 +70,7 @@ pub const RL_STEP_NO_ROULETTE: u32 = 1;
 pub const RL_DENOISE_ITERATIONS: u32 = 5;
 pub const RL_DENOISE_MAX_ITERATIONS: u32 = 6;
 pub const RL_SPECTRAL_MAX_NODES: u32 = 401;
+pub const RL_ERROR_TILE: u32 = 16;
 
 pub const RL_MAX_PIXELS: usize = 2147483647;
 pub const RL_TASK_MAX_UNITS: usize = 256;
@@ -89,8 +90,19 @@ pub const RL_COMM_ID_BYTES: usize = 128;
     pub batches_per_sec_mean: c_float, pub batches_per_sec_stddev: c_float, pub tonemaps: u32, pub next_batch: u64,
 }
 
+#[repr(C)] #[derive(Copy, Clone, Default)] pub struct RlErrorStats {
+    pub observations: u64, pub paths: u64, pub tiles_x: u32, pub tiles_y: u32, pub worst_tile_x: u32, pub worst_tile_y: u32,
+    pub sum_y: f64, pub sum_se: f64, pub relative_error: f64, pub worst_tile_error: f64,
+}
+#[repr(C)] #[derive(Copy, Clone, Default)] pub struct RlErrorTarget {
+    pub relative_error: f64, pub worst_tile_error: f64, pub min_observations: u32, pub reserved: u32,
+}
+#[repr(C)] #[derive(Copy, Clone, Default)] pub struct RlAppErrorStats {
+    pub at_stop: RlErrorStats, pub at_end: RlErrorStats, pub reached: u32, pub estimates: u32,
+}
+
 pub enum RlScene {} pub enum RlTraceUnit {} pub enum RlPlotUnit {} pub enum RlGatherUnit {} pub enum RlTonemapUnit {}
-pub enum RlScheduler {} pub enum RlComm {} pub enum RlDenoiseUnit {} pub enum RlSpectralUnit {}
+pub enum RlScheduler {} pub enum RlComm {} pub enum RlDenoiseUnit {} pub enum RlSpectralUnit {} pub enum RlErrorUnit {}
 
 extern "C" {
     pub fn rl_last_error() -> *const c_char;
@@ -216,6 +228,15 @@ extern "C" {
     pub fn rl_spectral_unit_project(unit: *mut RlSpectralUnit, matrix: *const f32, dst: *mut RlGatherUnit) -> c_int;
     pub fn rl_spectral_observer_cie1931(n_nodes: u32, out: *mut f32) -> c_int;
 
+    // The noise estimate: f64 sums of Y and Y^2 / n over the plot buffers shown to the unit; the standard error per pixel and tile.
+    pub fn rl_error_unit_create(device: c_int, width: u32, height: u32, out: *mut *mut RlErrorUnit) -> c_int;
+    pub fn rl_error_unit_destroy(unit: *mut RlErrorUnit) -> c_int;
+    pub fn rl_error_unit_clear(unit: *mut RlErrorUnit) -> c_int;
+    pub fn rl_error_unit_observe(unit: *mut RlErrorUnit, plot: *mut RlPlotUnit, n_paths: u64) -> c_int;
+    pub fn rl_error_unit_estimate(unit: *mut RlErrorUnit, stats: *mut RlErrorStats, se: *mut f32, tiles: *mut f64) -> c_int;
+    pub fn rl_error_unit_download(unit: *mut RlErrorUnit, sum_y: *mut f64, sum_q: *mut f64, observations: *mut u64, paths: *mut u64) -> c_int;
+    pub fn rl_error_unit_upload(unit: *mut RlErrorUnit, sum_y: *const f64, sum_q: *const f64, observations: u64, paths: u64) -> c_int;
+
     pub fn rl_gather_unit_create(device: c_int, w: u32, h: u32, out: *mut *mut RlGatherUnit) -> c_int;
     pub fn rl_gather_unit_destroy(u: *mut RlGatherUnit) -> c_int;
     pub fn rl_gather_unit_accumulate(u: *mut RlGatherUnit, plot: *mut RlPlotUnit) -> c_int;
@@ -251,6 +272,10 @@ extern "C" {
     pub fn rl_scheduler_get_new_task(s: *mut RlScheduler, completed: *const RlTask, now_ms: i64, next: *mut RlTask) -> c_int;
     pub fn rl_scheduler_performance(s: *mut RlScheduler, mean: *mut f32, stddev: *mut f32) -> c_int;
     pub fn rl_app_run(config: *const RlAppConfig, stats: *mut RlAppStats, rgb_out: *mut u8) -> c_int;
+    // rl_app_run with a stopping rule: render until the estimated relative error is below a target (NULL target: rl_app_run).
+    pub fn rl_app_run_to_error(config: *const RlAppConfig, target: *const RlErrorTarget, stats: *mut RlAppStats,
+                               error_stats: *mut RlAppErrorStats, rgb_out: *mut u8) -> c_int;
+    pub fn rl_app_error_tiles(tiles: *mut f64, capacity: u32, n_tiles: *mut u32) -> c_int;
 
 }
 

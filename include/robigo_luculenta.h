@@ -117,6 +117,7 @@ typedef struct RlGatherUnit RlGatherUnit;
 typedef struct RlTonemapUnit RlTonemapUnit;
 typedef struct RlDenoiseUnit RlDenoiseUnit;
 typedef struct RlSpectralUnit RlSpectralUnit;
+typedef struct RlErrorUnit RlErrorUnit;
 typedef struct RlScheduler RlScheduler;
 typedef struct RlComm RlComm;
 
@@ -903,6 +904,65 @@ int rl_spectral_unit_upload(RlSpectralUnit* unit, const float* in);
 int rl_spectral_unit_project(RlSpectralUnit* unit, const float* matrix, RlGatherUnit* dst);
 int rl_spectral_observer_cie1931(uint32_t n_nodes, float* out);
 
+/* ---- noise estimate: the standard error of the accumulated luminance (rl_error_unit_*) ---- */
+
+#define RL_ERROR_TILE 16
+
+/* An error unit says how noisy an accumulated image is.  It is shown every plot buffer just before the buffer is gathered
+ * (rl_error_unit_observe; the caller gathers afterwards) and keeps, per pixel, two f64 sums over these observations: observation j
+ * is a plot buffer that holds the sum of what n_j independent paths splatted; y_j is the Y component of a pixel in it.
+ *     S = sum_j y_j,   Q = sum_j y_j^2 / n_j,   N = sum_j n_j,   k = the number of observations.
+ * d = Q - S^2 / N is the weighted sum of squared deviations of the batch means, on k - 1 degrees of freedom, and
+ * sqrt(d N / (k - 1)) estimates the standard deviation of S itself, in the gather unit's own units; batches of unequal size are
+ * handled exactly.  Luminance only.  The sums are f64 because d cancels: f32 sums lose 6e-4 of d at 7,000 paths per pixel per
+ * observation and 6e-2 at 116,000.  The unit keeps its own S: a gather unit may hold samples the error unit never saw (a resumed
+ * checkpoint, rl_gather_unit_load).
+ *   The arithmetic.  f64 and f32 as stated, in exactly this order, never contracted; division and square root correctly rounded.
+ *   rl_error_unit_observe(unit, plot, n_paths).  Reads the plot unit's Y plane and leaves the plot buffer exactly as it was.  Per
+ *     pixel: yd = (double)y;  S = S + yd;  Q = Q + (yd * yd) / (double)n_paths.  On the host: k += 1; N += n_paths.  No special
+ *     cases for a negative or non-finite y.  Checked in this order: a NULL unit or plot, or n_paths == 0, is RL_E_INVALID; N
+ *     overflowing 64 bits is RL_E_INVALID; a plot unit of another size or device is RL_E_STATE, and nothing is written.
+ *     Ordering is rl_gather_unit_accumulate's: a fused render begun into the plot unit is ended first; the kernel waits through an
+ *     event for everything queued on the plot unit's stream and runs on the error unit's own stream; the plot unit's stream then
+ *     waits for the kernel, so a later clear or gather cannot overtake the read.  The call does not synchronise the host.
+ *   rl_error_unit_estimate(unit, stats, se, tiles).  Needs k >= 2, else RL_E_STATE (after: a NULL unit or stats is RL_E_INVALID).
+ *     Per pixel: d = Q - (S * S) / (double)N;  d = d < 0 ? 0 : d (a NaN stays a NaN);  v = d * ((double)N / (double)(k - 1));
+ *       se = rl_sqrtf((float)v);  ay = fabs(S).
+ *     Per RL_ERROR_TILE x RL_ERROR_TILE tile (each tile starts at a multiple of 16): the 256 values of (double)se in tile raster
+ *       order, +0.0 for positions outside the image; for stride = 128, 64, ..., 1: v[i] = v[i] + v[i + stride] for i < stride; v[0]
+ *       is the tile's t_se.  The same tree over ay gives t_y.  The bits of that tree are the contract.
+ *     On the host, from the tile pairs, sequentially in f64 in tile raster order: sum_se = sum t_se, sum_y = sum t_y (each from
+ *       +0.0), relative_error = sum_se / sum_y as the arithmetic gives (a black image: NaN); m = sum_y / (double)n_tiles;
+ *       rel = t_se / (t_y > m ? t_y : m); worst_tile_error starts as tile 0's rel and is replaced where a later rel > it (so
+ *       worst_tile_x, _y name the first tile that holds it).  A tile at least as bright as the average reports its own relative
+ *       error; a darker one is measured against the average brightness, which is what its noise costs after tonemapping.
+ *     `se` may be NULL; otherwise width x height floats of host memory, in rows.  `tiles` may be NULL; otherwise
+ *     tiles_y * tiles_x * 2 doubles of host memory, {t_se, t_y} per tile, tiles in raster order.  The call waits for the
+ *     observations queued on the unit and returns with a host synchronisation: a once-per-tonemap operation.  The result is exact:
+ *     the same bits on every run, and the bits of the CPU restatement tests/_error_oracle.py.
+ *   rl_error_unit_download / _upload move S and Q as planar width x height doubles in rows (the host layout is part of the ABI),
+ *     and k and N; any of download's outputs may be NULL; upload needs both planes (a NULL unit or plane is RL_E_INVALID).  They
+ *     wait for what is queued on the unit.  State can be kept across runs by hand with them.
+ *   rl_error_unit_create refuses a NULL `out`, a zero size and width * height > RL_MAX_PIXELS (RL_E_INVALID, in this order, before
+ *     any device work).  The planes start as +0 and k = N = 0; rl_error_unit_clear restores that (queued on the unit).
+ *   One user per error unit at a time. */
+typedef struct RlErrorStats {
+    uint64_t observations, paths;        /* k, N */
+    uint32_t tiles_x, tiles_y;           /* ceil(width / 16), ceil(height / 16) */
+    uint32_t worst_tile_x, worst_tile_y;
+    double sum_y, sum_se;                /* over the image */
+    double relative_error;               /* sum_se / sum_y */
+    double worst_tile_error;
+} RlErrorStats;
+
+int rl_error_unit_create(int device, uint32_t width, uint32_t height, RlErrorUnit** out);
+int rl_error_unit_destroy(RlErrorUnit* unit);
+int rl_error_unit_clear(RlErrorUnit* unit);
+int rl_error_unit_observe(RlErrorUnit* unit, RlPlotUnit* plot, uint64_t n_paths);
+int rl_error_unit_estimate(RlErrorUnit* unit, RlErrorStats* stats, float* se, double* tiles);
+int rl_error_unit_download(RlErrorUnit* unit, double* sum_y, double* sum_q, uint64_t* observations, uint64_t* paths);
+int rl_error_unit_upload(RlErrorUnit* unit, const double* sum_y, const double* sum_q, uint64_t observations, uint64_t paths);
+
 /* ---- GatherUnit (gather_unit.rs:24-92) ----------------------------------------------------- */
 
 /* GatherUnit::new(width, height) WITHOUT the implicit read() of ./buffer.raw
@@ -1065,6 +1125,42 @@ typedef struct RlAppStats {
  * batches of its trace units as one launch over the next contiguous range), so the final image does not
  * depend on which worker or unit ran which task.  rgb_out (may be NULL) receives the last RGB8 image. */
 int rl_app_run(const RlAppConfig* config, RlAppStats* stats, uint8_t* rgb_out);
+
+/* ---- render until a target error (rl_app_run_to_error) ---- */
+
+typedef struct RlErrorTarget {
+    double relative_error;     /* stop when the estimate is <= this; 0 never stops a noisy render */
+    double worst_tile_error;   /* 0 = not part of the rule; otherwise the worst tile must be <= this too */
+    uint32_t min_observations; /* 0 = 16 */
+    uint32_t reserved;         /* must be 0 */
+} RlErrorTarget;
+
+typedef struct RlAppErrorStats {
+    RlErrorStats at_stop;      /* the estimate that met the target; zeros if none did */
+    RlErrorStats at_end;       /* after the last gather (zeros if the run made fewer than two observations) */
+    uint32_t reached, estimates;
+} RlAppErrorStats;
+
+/* rl_app_run with a stopping rule.  With a NULL target it is rl_app_run (error_stats, if given, is zeroed).  With a target the App
+ * owns an error unit on rank 0's device.  It counts, per plot unit, the paths plotted or fused into it since its last gather, over
+ * all ranks; the Gather task calls rl_error_unit_observe with that count just before its rl_gather_unit_accumulate, after the
+ * ranks' buffers have been summed onto rank 0, and skips a buffer whose count is zero.  Every Tonemap task runs the estimate before
+ * tonemapping (once k >= 2); when k >= min_observations and relative_error <= target->relative_error (and, with a non-zero
+ * target->worst_tile_error, worst_tile_error <= it: a NaN meets neither) the hand-out of trace tasks ends exactly as at an exhausted
+ * max_batches, which stays the upper limit.  The run then gathers what is in flight, estimates once more (at_end) and tonemaps.
+ * `estimates` counts the estimates made, at_end's included.  Tonemap tasks come every tonemap_interval_ms, so that is how often
+ * the rule is looked at.  16 observations by default: the relative standard deviation of a variance estimate on k - 1 degrees of
+ * freedom is sqrt(2 / (k - 1)), 0.37 at 16, so about 0.18 on one pixel's se, and the sums average that over hundreds of pixels.
+ *   Checked before any device work, after rl_app_run's own checks: a negative or NaN relative_error or worst_tile_error, or a
+ * non-zero reserved, is RL_E_INVALID.
+ *   With `resume` the estimate covers this run's samples only, so it overstates the error of the resumed image: conservative.  The
+ * error state is not kept beside the checkpoint.
+ *   rl_app_error_tiles: the {t_se, t_y} pairs of at_end of the calling thread's last rl_app_run_to_error, tiles in raster order.
+ * *n_tiles (may be NULL) is always set to their number (0 if that run made no final estimate); `tiles` receives 2 * n doubles when
+ * capacity >= n, else RL_E_INVALID -- the capacity protocol of rl_scene_emitters. */
+int rl_app_run_to_error(const RlAppConfig* config, const RlErrorTarget* target, RlAppStats* stats, RlAppErrorStats* error_stats,
+                        uint8_t* rgb_out);
+int rl_app_error_tiles(double* tiles, uint32_t capacity, uint32_t* n_tiles);
 
 #ifdef __cplusplus
 }

@@ -79,6 +79,16 @@ int rl_debug_spectral_launches(uint64_t out[2]);
  * (rl_spectral_unit_plot, _plot_photons, _plot_photons_device), out[1] the projection launch of its last completed
  * rl_spectral_unit_project; 0 before the first.  tools/spectral_bench.py. */
 int rl_debug_spectral_ms(RlSpectralUnit* unit, float out[2]);
+/* out[0]: launches of rl_error_observe_kernel (one per rl_error_unit_observe), out[1]: launches of rl_error_estimate_kernel (one per
+ * rl_error_unit_estimate) since the library was loaded. */
+int rl_debug_error_launches(uint64_t out[2]);
+/* Device time in milliseconds, from events around the launch: out[0] the unit's last observe launch, out[1] its last estimate
+ * launch; 0 before the first.  Waits for the launch.  tools/error_bench.py. */
+int rl_debug_error_ms(RlErrorUnit* unit, float out[2]);
+/* rl_gather_unit_accumulate(unit, plot) between two events on the gather unit's stream, with both units' streams drained before
+ * and the gather unit's after: *ms is the device time of that call's rl_gather_kernel launch, the yardstick tools/error_bench.py
+ * holds the observe kernel to.  The accumulation happens as usual. */
+int rl_debug_gather_accumulate_ms(RlGatherUnit* unit, RlPlotUnit* plot, float* ms);
 /* rl_scene_emitters for a description instead of a scene: the sampleable emitters' object indices in scan order, by the function
  * rl_scene_create builds a scene's table with.  Host arithmetic only: callable without a GPU.  The same capacity protocol. */
 int rl_debug_scene_emitters(const RlObjectDesc* objects, uint32_t n_objects, uint32_t* out, uint32_t cap, uint32_t* n_emitters);

@@ -14,7 +14,7 @@ from ._lib import (RlAppConfig, RlAppStats, RlCameraDesc, RlCameraSample, RlErro
                    RL_PATH_MAX_SEGMENTS_CAP, RL_TASK_MAX_UNITS, RlLightSample, RlDirectStats, RL_LIGHT_SKIPPED, RL_LIGHT_BACKFACING, RL_LIGHT_OCCLUDED,
                    RL_LIGHT_VISIBLE, RlFeatureSample, RlFeatureStats, RL_FEATURE_VOID, RL_FEATURE_EMITTER, RL_FEATURE_DIFFUSE, RL_FEATURE_LIMIT,
                    RL_FEATURE_MAX_SEGMENTS, RlDenoiseParams, RL_DENOISE_ITERATIONS, RL_DENOISE_MAX_ITERATIONS,
-                   RL_SPECTRAL_MAX_NODES)
+                   RL_SPECTRAL_MAX_NODES, RlErrorStats, RlErrorTarget, RlAppErrorStats, RL_ERROR_TILE)
 
 PHOTON_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("probability", "<f4"), ("wavelength", "<f4")])
 OBJECT_DTYPE = np.dtype([("surface_kind", "<u4"), ("material_kind", "<u4"), ("v0", "<f4", 3), ("v1", "<f4", 3),
@@ -802,6 +802,70 @@ class SpectralUnit(_Handle):
         return tuple(out)
 
 
+def _error_stats(stats):
+    return {name: getattr(stats, name) for name, _ in RlErrorStats._fields_}
+
+
+class ErrorUnit(_Handle):
+    """The noise estimate (rl_error_unit_*): f64 sums S of y and Q of y^2 / n over the plot buffers shown to the unit just before
+    they are gathered, and from them the standard error of the accumulated luminance per pixel and per 16 x 16 tile."""
+    _destroy = lib.rl_error_unit_destroy
+
+    def __init__(self, width, height, device=0):
+        super().__init__()
+        check(lib.rl_error_unit_create(device, width, height, C.byref(self._h)))
+        self.width, self.height, self.device = width, height, device
+        self.tiles_x, self.tiles_y = -(-width // RL_ERROR_TILE), -(-height // RL_ERROR_TILE)
+
+    def clear(self):
+        check(lib.rl_error_unit_clear(self._h))
+
+    def observe(self, plot_unit, n_paths):
+        """rl_error_unit_observe: the plot unit's buffer, the sum over n_paths independent paths, is one observation.  The buffer is
+        left as it was: gather it afterwards.  Does not wait on the host."""
+        check(lib.rl_error_unit_observe(self._h, plot_unit.handle, n_paths))
+
+    def estimate(self, se=True, tiles=True):
+        """rl_error_unit_estimate: (stats dict, se as (height, width) float32 or None, tiles as (tiles_y, tiles_x, 2) float64
+        {t_se, t_y} or None).  Needs two observations."""
+        stats = RlErrorStats()
+        se_out = np.zeros((self.height, self.width), dtype=np.float32) if se else None
+        tiles_out = np.zeros((self.tiles_y, self.tiles_x, 2), dtype=np.float64) if tiles else None
+        check(lib.rl_error_unit_estimate(self._h, C.byref(stats), se_out.ctypes.data_as(C.c_void_p) if se else None,
+                                         tiles_out.ctypes.data_as(C.c_void_p) if tiles else None))
+        return _error_stats(stats), se_out, tiles_out
+
+    def download(self):
+        """(S, Q) as (height, width) float64 arrays, k, N."""
+        s, q = np.zeros((self.height, self.width), dtype=np.float64), np.zeros((self.height, self.width), dtype=np.float64)
+        k, n = C.c_uint64(0), C.c_uint64(0)
+        check(lib.rl_error_unit_download(self._h, s.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p), C.byref(k), C.byref(n)))
+        return s, q, k.value, n.value
+
+    def upload(self, sum_y, sum_q, observations, paths):
+        s = np.ascontiguousarray(sum_y, dtype=np.float64).reshape(self.height, self.width)
+        q = np.ascontiguousarray(sum_q, dtype=np.float64).reshape(self.height, self.width)
+        check(lib.rl_error_unit_upload(self._h, s.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p), observations, paths))
+
+    def launch_ms(self):
+        """Device milliseconds of (the last observe launch, the last estimate launch) of this unit (rl_debug_error_ms)."""
+        out = (C.c_float * 2)()
+        check(lib.rl_debug_error_ms(self._h, out))
+        return tuple(out)
+
+
+def error_tile_rel(tiles):
+    """The per-tile relative error of rl_error_unit_estimate's host statistics, from (tiles_y, tiles_x, 2) {t_se, t_y} pairs:
+    t_se / max(t_y, mean t_y), the sums sequential in f64 in tile raster order."""
+    pairs = np.asarray(tiles, dtype=np.float64).reshape(-1, 2)
+    sum_y = np.float64(0)
+    for t_y in pairs[:, 1]:
+        sum_y = sum_y + t_y
+    m = sum_y / np.float64(len(pairs))
+    with np.errstate(all="ignore"):
+        return (pairs[:, 0] / np.where(pairs[:, 1] > m, pairs[:, 1], m)).reshape(np.asarray(tiles).shape[:-1])
+
+
 class Task:
     """enum Task (task_scheduler.rs:26-41) by unit ids."""
 
@@ -867,9 +931,41 @@ def app_run(width, height, max_batches, concurrency=1, device=0, photons_per_bat
     stats = RlAppStats()
     rgb = np.zeros((height, width, 3), dtype=np.uint8)
     check(lib.rl_app_run(C.byref(cfg), C.byref(stats), rgb.ctypes.data_as(C.c_void_p)))
+    return rgb, _app_stats(stats)
+
+
+def _app_stats(stats):
     out = {name: getattr(stats, name) for name, _ in RlAppStats._fields_ if name != "tasks"}
     out["tasks"] = dict(zip(["sleep", "trace", "plot", "gather", "tonemap"], list(stats.tasks)))
-    return rgb, out
+    return out
+
+
+def app_run_to_error(width, height, max_batches, target_error=None, worst_tile_error=0.0, min_observations=0, concurrency=1, device=0,
+                     photons_per_batch=NUMBER_OF_PHOTONS, seed=1, stream=0, scene=SCENE_DEMO, scene_param=0, tonemap_interval_ms=30000,
+                     fused=False, output_ppm=None, checkpoint=None, resume=False, verbose=False, sleep_us=0, first_batch=0, devices=None,
+                     blocking_trace=False, threads=0, reserved=0):
+    """rl_app_run_to_error: app_run that ends the hand-out of batches once an estimate made at a tonemap (every tonemap_interval_ms)
+    has at least min_observations (0 = 16) observations and a relative error <= target_error (and, with a non-zero worst_tile_error,
+    a worst tile <= it); max_batches stays the cap.  target_error=None passes no target: app_run.  Returns (rgb, stats dict, error
+    dict {at_stop, at_end: rl_error_unit_estimate's stats, reached, estimates, tiles: at_end's (tiles_y, tiles_x, 2) pairs or None})."""
+    dev_arr = (C.c_int * len(devices))(*devices) if devices else None
+    cfg = RlAppConfig(width, height, device, concurrency, photons_per_batch, seed, stream, scene, scene_param, max_batches,
+                      tonemap_interval_ms, int(fused), output_ppm.encode() if output_ppm else None,
+                      checkpoint.encode() if checkpoint else None, int(resume), int(verbose), sleep_us, first_batch,
+                      len(devices) if devices else 0, int(blocking_trace), dev_arr, int(threads))
+    target = None if target_error is None else C.byref(RlErrorTarget(target_error, worst_tile_error, min_observations, reserved))
+    stats, es = RlAppStats(), RlAppErrorStats()
+    rgb = np.zeros((height, width, 3), dtype=np.uint8)
+    check(lib.rl_app_run_to_error(C.byref(cfg), target, C.byref(stats), C.byref(es), rgb.ctypes.data_as(C.c_void_p)))
+    n = C.c_uint32(0)
+    lib.rl_app_error_tiles(None, 0, C.byref(n))     # (RL_E_INVALID when there are tiles: the count is what is asked for)
+    tiles = None
+    if n.value:
+        tiles = np.zeros((-(-height // RL_ERROR_TILE), -(-width // RL_ERROR_TILE), 2), dtype=np.float64)
+        check(lib.rl_app_error_tiles(tiles.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+    error = {"at_stop": _error_stats(es.at_stop), "at_end": _error_stats(es.at_end), "reached": es.reached, "estimates": es.estimates,
+             "tiles": tiles}
+    return rgb, _app_stats(stats), error
 
 
 def batch_histogram(device=0):
@@ -981,6 +1077,21 @@ def spectral_launches():
     (rl_debug_spectral_launches)."""
     out = (C.c_uint64 * 2)()
     check(lib.rl_debug_spectral_launches(out))
+    return tuple(out)
+
+
+def gather_accumulate_ms(gather, plot_unit):
+    """rl_debug_gather_accumulate_ms: gather.accumulate(plot_unit), returning the device milliseconds of its kernel launch."""
+    ms = C.c_float(0)
+    check(lib.rl_debug_gather_accumulate_ms(gather.handle, plot_unit.handle, C.byref(ms)))
+    return ms.value
+
+
+def error_launches():
+    """(launches of the error unit's observe kernel, launches of its estimate kernel) since the library was loaded
+    (rl_debug_error_launches)."""
+    out = (C.c_uint64 * 2)()
+    check(lib.rl_debug_error_launches(out))
     return tuple(out)
 
 

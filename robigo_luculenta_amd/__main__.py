@@ -3,7 +3,9 @@ built-in scene with the App worker pool and writes output.ppm (+ buffer.raw) whe
 With --direct the image is rendered with direct light (PlotUnit.render_direct), batch by batch over the unit API.
 With --features PREFIX the denoising guides of the same paths (Scene.render_features) are written beside the image.
 With --denoise PATH as well the image is filtered over those guides on the device (DenoiseUnit.denoise) and tonemapped to PATH.
-With --spectral PATH the same paths are rendered once more into a spectral film (SpectralUnit) and the cube is saved as PATH (.npy)."""
+With --spectral PATH the same paths are rendered once more into a spectral film (SpectralUnit) and the cube is saved as PATH (.npy).
+With --target-error E the run ends once the estimated relative error of the image (rl_app_run_to_error) is at most E; --batches stays
+the cap.  With --error-map PATH the per-tile relative error of the last estimate is written as a grey image."""
 import argparse
 import os
 import struct
@@ -11,7 +13,9 @@ import tempfile
 import time
 import zlib
 
-from . import SCENE_DEMO, SCENE_GLASS_STRESS, app_run
+from . import SCENE_DEMO, SCENE_GLASS_STRESS, app_run, app_run_to_error
+
+TARGET_TONEMAP_INTERVAL_MS = 250   # with --target-error the stopping rule is looked at at every tonemap: four times a second
 
 
 def parse_args(argv=None):
@@ -46,7 +50,24 @@ def parse_args(argv=None):
                          "float32 (nodes, height, width), to PATH with numpy.save (*.npy)")
     ap.add_argument("--spectral-nodes", metavar="K", type=int, default=81,
                     help="with --spectral: nodes from 380 to 780 nm (default 81, the CIE table's own)")
+    ap.add_argument("--target-error", metavar="E", type=float, default=None,
+                    help="end the run once the estimated relative error of the image, sum of the pixels' standard errors over the sum "
+                         "of their luminance, is at most E (looked at every %d ms); --batches stays the cap" % TARGET_TONEMAP_INTERVAL_MS)
+    ap.add_argument("--min-observations", metavar="K", type=int, default=None,
+                    help="with --target-error: gathered plot buffers the estimate must rest on before it may end the run (default 16)")
+    ap.add_argument("--error-map", metavar="PATH", default=None,
+                    help="write the per-tile relative error of the last estimate as a grey image, the worst 16 x 16 tile white, to "
+                         "PATH (*.png or *.ppm); without --target-error the run estimates once at the end")
     a = ap.parse_args(argv)
+    if a.target_error is not None and not a.target_error >= 0:
+        ap.error("--target-error must be a number >= 0")
+    if a.min_observations is not None and a.target_error is None:
+        ap.error("--min-observations needs --target-error")
+    if a.min_observations is not None and a.min_observations < 2:
+        ap.error("--min-observations must be at least 2: the estimate needs two observations")
+    for flag, given in (("--target-error", a.target_error is not None), ("--error-map", a.error_map is not None)):
+        if given and a.direct:
+            ap.error("%s cannot be combined with --direct: the estimate is made by the App worker pool" % flag)
     if a.spectral is not None and a.direct:
         ap.error("--spectral cannot be combined with --direct: the direct renderer writes no photons")
     if a.denoise is not None and a.features is None:
@@ -163,6 +184,32 @@ def render_spectral(a):
     return cube
 
 
+def report_error(a, st, err):
+    """The estimate's line, and --error-map: per tile rel = t_se / max(t_y, mean t_y) (error_tile_rel), grey = rel over the worst
+    tile's, every pixel of a tile alike."""
+    import numpy as np
+    from . import RL_ERROR_TILE, error_tile_rel
+    last = err["at_stop"] if err["reached"] else err["at_end"]
+    if not err["estimates"]:
+        print("no estimate: fewer than two plot buffers were gathered (%d batches)" % st["batches"])
+        return None
+    print("relative_error %.6g, worst tile (%d, %d) %.6g, from %d observations of %d paths; reached %d, %d of %d batches used"
+          % (last["relative_error"], last["worst_tile_x"], last["worst_tile_y"], last["worst_tile_error"], last["observations"],
+             last["paths"], err["reached"], st["batches"], a.batches))
+    if err["reached"]:
+        print("after the last gather: relative_error %.6g from %d observations" % (err["at_end"]["relative_error"], err["at_end"]["observations"]))
+    if a.error_map is None:
+        return None
+    rel = error_tile_rel(err["tiles"])
+    finite = rel[np.isfinite(rel)]
+    worst = float(finite.max()) if finite.size and finite.max() > 0 else 1.0
+    grey = np.clip(np.where(np.isfinite(rel), rel, worst) / worst * 255.0 + 0.5, 0, 255).astype(np.uint8)
+    grey = np.repeat(np.repeat(grey, RL_ERROR_TILE, axis=0), RL_ERROR_TILE, axis=1)[:a.height, :a.width]
+    write_image(a.error_map, np.repeat(grey.reshape(-1, 1), 3, axis=1), a.width, a.height)
+    print("error map: wrote %s" % a.error_map)
+    return grey
+
+
 def denoise(a, image, guides):
     """--denoise PATH: gather unit `image` filtered over the three guide gather units into a gather unit of its own, tonemapped as
     the image was, written to PATH."""
@@ -190,10 +237,17 @@ def main(argv=None):
     # rl_app_run hands out no gather unit: --denoise reads the image back from the checkpoint, a temporary one if none was asked for
     scratch = tempfile.TemporaryDirectory() if a.denoise is not None and a.checkpoint is None else None
     checkpoint = os.path.join(scratch.name, "buffer.raw") if scratch else a.checkpoint
-    rgb, st = app_run(a.width, a.height, a.batches, concurrency=a.concurrency, device=a.device, seed=a.seed,
-                      photons_per_batch=a.photons_per_batch,
-                      scene=SCENE_DEMO if a.scene == "demo" else SCENE_GLASS_STRESS, fused=not a.unfused,
-                      output_ppm=a.output, checkpoint=checkpoint, resume=a.resume, verbose=not a.quiet)
+    common = dict(concurrency=a.concurrency, device=a.device, seed=a.seed, photons_per_batch=a.photons_per_batch,
+                  scene=SCENE_DEMO if a.scene == "demo" else SCENE_GLASS_STRESS, fused=not a.unfused,
+                  output_ppm=a.output, checkpoint=checkpoint, resume=a.resume, verbose=not a.quiet)
+    if a.target_error is not None or a.error_map is not None:
+        # without a target the rule is 0, which no noisy render meets: the run goes to the cap and estimates at its end
+        rgb, st, err = app_run_to_error(a.width, a.height, a.batches, target_error=a.target_error or 0.0,
+                                        min_observations=a.min_observations or 0,
+                                        tonemap_interval_ms=TARGET_TONEMAP_INTERVAL_MS if a.target_error is not None else 30000, **common)
+        report_error(a, st, err)
+    else:
+        rgb, st = app_run(a.width, a.height, a.batches, **common)
     print("%d trace tasks, %.1f Mpaths, %.1f Mrays in %.2f s (%.1f Mrays/s, %.1f reference batches/sec); wrote %s"
           % (st["batches"], st["paths"] / 1e6, st["segments"] / 1e6, st["seconds"], st["segments"] / st["seconds"] / 1e6,
              st["paths"] / 524288.0 / st["seconds"], a.output))

@@ -118,6 +118,22 @@ class RlDenoiseParams(C.Structure):
 
 
 RL_SPECTRAL_MAX_NODES = 401
+RL_ERROR_TILE = 16
+
+
+class RlErrorStats(C.Structure):
+    _fields_ = [("observations", C.c_uint64), ("paths", C.c_uint64), ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32),
+                ("worst_tile_x", C.c_uint32), ("worst_tile_y", C.c_uint32), ("sum_y", C.c_double), ("sum_se", C.c_double),
+                ("relative_error", C.c_double), ("worst_tile_error", C.c_double)]
+
+
+class RlErrorTarget(C.Structure):
+    _fields_ = [("relative_error", C.c_double), ("worst_tile_error", C.c_double), ("min_observations", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class RlAppErrorStats(C.Structure):
+    _fields_ = [("at_stop", RlErrorStats), ("at_end", RlErrorStats), ("reached", C.c_uint32), ("estimates", C.c_uint32)]
 
 
 class RlTask(C.Structure):
@@ -229,6 +245,13 @@ SIGNATURES = {
     "rl_spectral_unit_upload": (_i, [_vp, _vp]),
     "rl_spectral_unit_project": (_i, [_vp, _vp, _vp]),
     "rl_spectral_observer_cie1931": (_i, [_u32, _vp]),
+    "rl_error_unit_create": (_i, [_i, _u32, _u32, _pp]),
+    "rl_error_unit_destroy": (_i, [_vp]),
+    "rl_error_unit_clear": (_i, [_vp]),
+    "rl_error_unit_observe": (_i, [_vp, _vp, _u64]),
+    "rl_error_unit_estimate": (_i, [_vp, C.POINTER(RlErrorStats), _vp, _vp]),
+    "rl_error_unit_download": (_i, [_vp, _vp, _vp, C.POINTER(_u64), C.POINTER(_u64)]),
+    "rl_error_unit_upload": (_i, [_vp, _vp, _vp, _u64, _u64]),
     "rl_gather_unit_sync": (_i, [_vp]),
     "rl_gather_unit_create": (_i, [_i, _u32, _u32, _pp]),
     "rl_gather_unit_destroy": (_i, [_vp]),
@@ -246,6 +269,8 @@ SIGNATURES = {
     "rl_scheduler_get_new_task": (_i, [_vp, C.POINTER(RlTask), _i64, C.POINTER(RlTask)]),
     "rl_scheduler_performance": (_i, [_vp, C.POINTER(_f), C.POINTER(_f)]),
     "rl_app_run": (_i, [C.POINTER(RlAppConfig), C.POINTER(RlAppStats), _vp]),
+    "rl_app_run_to_error": (_i, [C.POINTER(RlAppConfig), C.POINTER(RlErrorTarget), C.POINTER(RlAppStats), C.POINTER(RlAppErrorStats), _vp]),
+    "rl_app_error_tiles": (_i, [_vp, _u32, C.POINTER(_u32)]),
 }
 # include/robigo_luculenta_debug.h: diagnostics, not part of the drop-in boundary
 DEBUG_SIGNATURES = {
@@ -268,6 +293,9 @@ DEBUG_SIGNATURES = {
     "rl_debug_denoise_pass_ms": (_i, [_vp, _vp]),
     "rl_debug_spectral_launches": (_i, [_vp]),
     "rl_debug_spectral_ms": (_i, [_vp, _vp]),
+    "rl_debug_error_launches": (_i, [_vp]),
+    "rl_debug_error_ms": (_i, [_vp, _vp]),
+    "rl_debug_gather_accumulate_ms": (_i, [_vp, _vp, C.POINTER(C.c_float)]),
     "rl_debug_scene_emitters": (_i, [_vp, _u32, _vp, _u32, C.POINTER(_u32)]),
     "rl_debug_light_sample": (_i, [_vp, _u32, _u64, _u32, _vp, _vp, _u32, _vp, _vp]),
     "rl_debug_prism_probe": (_i, [_vp, _u32, _vp, _u32, _vp]),

@@ -54,6 +54,7 @@
 #include "rl_features.hip.h"
 #include "rl_denoise.hip.h"
 #include "rl_spectral.hip.h"
+#include "rl_error.hip.h"
 #include "rl_scene.h"
 
 namespace {
@@ -221,6 +222,21 @@ struct RlSpectralUnit {
     hipEvent_t ready;   // recorded on `stream` when a projection takes the film
     EventPair timed[2]; // around the last splat launch and the last projection launch (rl_debug_spectral_ms)
     bool timed_done[2]; // ... of a call that completed
+};
+
+struct RlErrorUnit {
+    int device;
+    uint32_t width, height, tiles_x, tiles_y;
+    double* sum_y;         // S: width x height doubles in rows
+    double* sum_q;         // Q: the same
+    float* se;             // the estimate's per-pixel result, width x height floats
+    double* tiles;         // the estimate's {t_se, t_y} per tile, tiles in raster order
+    uint64_t observations; // k
+    uint64_t paths;        // N
+    hipStream_t stream;    // clears, observes and estimates
+    hipEvent_t observed;   // recorded on `stream` after an observe kernel: the plot unit's stream waits for it
+    EventPair timed[2];    // around the last observe launch and the last estimate launch (rl_debug_error_ms)
+    bool timed_done[2];    // ... recorded at least once
 };
 
 // One rank of an RCCL communicator (rl_comm_*).
@@ -2972,6 +2988,181 @@ int rl_spectral_observer_cie1931(uint32_t n_nodes, float* out) {
     return RL_OK;
 }
 
+// ---- ErrorUnit (rl_error.hip.h) ------------------------------------------------------------------
+
+namespace {
+std::atomic<uint64_t> g_error_launches[2]; // rl_debug_error_launches: observe launches, estimate launches
+}
+
+int rl_error_unit_create(int device, uint32_t width, uint32_t height, RlErrorUnit** out) {
+    if (!out) return fail(RL_E_INVALID, "null output handle");
+    *out = nullptr;
+    if (width == 0 || height == 0) return fail(RL_E_INVALID, "zero-sized error unit");
+    int rc = check_image_size("error unit", width, height);
+    if (rc != RL_OK) return rc;
+    rc = use_device(device);
+    if (rc != RL_OK) return rc;
+    RlErrorUnit* u = new (std::nothrow) RlErrorUnit();
+    if (!u) return fail(RL_E_INVALID, "out of host memory");
+    u->device = device;
+    u->width = width;
+    u->height = height;
+    u->tiles_x = (width + RL_ERROR_TILE - 1u) / RL_ERROR_TILE;
+    u->tiles_y = (height + RL_ERROR_TILE - 1u) / RL_ERROR_TILE;
+    const size_t n_pixels = (size_t)width * height, n_tiles = (size_t)u->tiles_x * u->tiles_y;
+    hipError_t e = hipMalloc((void**)&u->sum_y, n_pixels * sizeof(double));
+    if (e == hipSuccess) e = hipMemset(u->sum_y, 0, n_pixels * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&u->sum_q, n_pixels * sizeof(double));
+    if (e == hipSuccess) e = hipMemset(u->sum_q, 0, n_pixels * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&u->se, n_pixels * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&u->tiles, n_tiles * 2 * sizeof(double));
+    if (e == hipSuccess) e = create_unit_stream(&u->stream);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&u->observed, hipEventDisableTiming);
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+        e = hipEventCreate(&u->timed[k].start);
+        if (e == hipSuccess) e = hipEventCreate(&u->timed[k].stop);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr); // the synchronous memsets above ran on the null stream
+    if (e != hipSuccess) {
+        rl_error_unit_destroy(u);
+        return fail(RL_E_HIP, std::string("error unit allocation: ") + hipGetErrorString(e));
+    }
+    *out = u;
+    return RL_OK;
+}
+
+int rl_error_unit_destroy(RlErrorUnit* u) {
+    if (!u) return RL_OK;
+    (void)hipSetDevice(u->device);
+    if (u->stream) {
+        (void)hipStreamSynchronize(u->stream);
+        (void)hipStreamDestroy(u->stream);
+    }
+    if (u->observed) (void)hipEventDestroy(u->observed);
+    for (EventPair& ep : u->timed) {
+        if (ep.start) (void)hipEventDestroy(ep.start);
+        if (ep.stop) (void)hipEventDestroy(ep.stop);
+    }
+    if (u->sum_y) (void)hipFree(u->sum_y);
+    if (u->sum_q) (void)hipFree(u->sum_q);
+    if (u->se) (void)hipFree(u->se);
+    if (u->tiles) (void)hipFree(u->tiles);
+    delete u;
+    return RL_OK;
+}
+
+int rl_error_unit_clear(RlErrorUnit* u) {
+    if (!u) return fail(RL_E_INVALID, "null error unit");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    const size_t bytes = (size_t)u->width * u->height * sizeof(double);
+    RL_HIP(hipMemsetAsync(u->sum_y, 0, bytes, u->stream));
+    RL_HIP(hipMemsetAsync(u->sum_q, 0, bytes, u->stream));
+    u->observations = u->paths = 0;
+    return RL_OK;
+}
+
+int rl_error_unit_observe(RlErrorUnit* u, RlPlotUnit* plot, uint64_t n_paths) {
+    if (!u || !plot) return fail(RL_E_INVALID, "rl_error_unit_observe: null error unit or plot unit");
+    if (n_paths == 0) return fail(RL_E_INVALID, "rl_error_unit_observe: n_paths is 0: an observation is the sum over at least one path");
+    if (u->paths + n_paths < u->paths) return fail(RL_E_INVALID, "rl_error_unit_observe: the number of paths N overflows 64 bits");
+    if (plot->device != u->device || plot->width != u->width || plot->height != u->height)
+        return fail(RL_E_STATE, "plot unit does not match the error unit (device or size)");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    if ((rc = plot_settle(plot)) != RL_OK) return rc; // a fused render begun into this buffer ends first
+    int cus = 256;
+    if ((rc = cu_count_of(u->device, &cus)) != RL_OK) return rc;
+    const uint64_t n_pixels = (uint64_t)u->width * u->height;
+    RL_HIP(hipEventRecord(plot->ready, plot->stream)); // everything plotted / splatted / reduced into the buffer so far
+    RL_HIP(hipStreamWaitEvent(u->stream, plot->ready, 0));
+    RL_HIP(hipEventRecord(u->timed[0].start, u->stream));
+    hipLaunchKernelGGL(rl_error_observe_kernel, dim3(grid_for(n_pixels / 2 + 1, cus)), dim3(RL_BLOCK), 0, u->stream, u->sum_y, u->sum_q,
+                       (const float*)plot->xyz, n_pixels, (double)n_paths);
+    RL_HIP(hipGetLastError());
+    RL_HIP(hipEventRecord(u->timed[0].stop, u->stream));
+    u->timed_done[0] = true;
+    g_error_launches[0].fetch_add(1, std::memory_order_relaxed);
+    RL_HIP(hipEventRecord(u->observed, u->stream)); // a later clear or gather of the buffer must not overtake the read
+    RL_HIP(hipStreamWaitEvent(plot->stream, u->observed, 0));
+    u->observations += 1;
+    u->paths += n_paths;
+    return RL_OK;
+}
+
+int rl_error_unit_estimate(RlErrorUnit* u, RlErrorStats* stats, float* se, double* tiles) {
+    if (!u || !stats) return fail(RL_E_INVALID, "rl_error_unit_estimate: null error unit or stats");
+    if (u->observations < 2)
+        return fail(RL_E_STATE, "rl_error_unit_estimate: " + std::to_string(u->observations) + " observations: the estimate needs at least 2");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    const size_t n_pixels = (size_t)u->width * u->height, n_tiles = (size_t)u->tiles_x * u->tiles_y;
+    std::vector<double> pairs(2 * n_tiles);
+    const double n_total = (double)u->paths, ratio = n_total / (double)(u->observations - 1);
+    RL_HIP(hipEventRecord(u->timed[1].start, u->stream));
+    hipLaunchKernelGGL(rl_error_estimate_kernel, dim3((unsigned)n_tiles), dim3(RL_ERROR_TILE_PIXELS), 0, u->stream, (const double*)u->sum_y,
+                       (const double*)u->sum_q, u->width, u->height, u->tiles_x, n_total, ratio, u->se, u->tiles);
+    RL_HIP(hipGetLastError());
+    RL_HIP(hipEventRecord(u->timed[1].stop, u->stream));
+    u->timed_done[1] = true;
+    g_error_launches[1].fetch_add(1, std::memory_order_relaxed);
+    RL_HIP(hipMemcpyAsync(pairs.data(), u->tiles, pairs.size() * sizeof(double), hipMemcpyDeviceToHost, u->stream));
+    if (se) RL_HIP(hipMemcpyAsync(se, u->se, n_pixels * sizeof(float), hipMemcpyDeviceToHost, u->stream));
+    RL_HIP(hipStreamSynchronize(u->stream));
+    std::memset(stats, 0, sizeof *stats);
+    stats->observations = u->observations;
+    stats->paths = u->paths;
+    stats->tiles_x = u->tiles_x;
+    stats->tiles_y = u->tiles_y;
+    double sum_se = 0.0, sum_y = 0.0;
+    for (size_t i = 0; i < n_tiles; ++i) {
+        sum_se = sum_se + pairs[2 * i];
+        sum_y = sum_y + pairs[2 * i + 1];
+    }
+    stats->sum_se = sum_se;
+    stats->sum_y = sum_y;
+    stats->relative_error = sum_se / sum_y;
+    const double m = sum_y / (double)n_tiles;
+    for (size_t i = 0; i < n_tiles; ++i) {
+        const double t_se = pairs[2 * i], t_y = pairs[2 * i + 1];
+        const double rel = t_se / (t_y > m ? t_y : m);
+        if (i == 0 || rel > stats->worst_tile_error) {
+            stats->worst_tile_error = rel;
+            stats->worst_tile_x = (uint32_t)(i % u->tiles_x);
+            stats->worst_tile_y = (uint32_t)(i / u->tiles_x);
+        }
+    }
+    if (tiles) std::memcpy(tiles, pairs.data(), pairs.size() * sizeof(double));
+    return RL_OK;
+}
+
+int rl_error_unit_download(RlErrorUnit* u, double* sum_y, double* sum_q, uint64_t* observations, uint64_t* paths) {
+    if (!u) return fail(RL_E_INVALID, "null error unit");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    const size_t bytes = (size_t)u->width * u->height * sizeof(double);
+    RL_HIP(hipStreamSynchronize(u->stream));
+    if (sum_y) RL_HIP(hipMemcpy(sum_y, u->sum_y, bytes, hipMemcpyDeviceToHost));
+    if (sum_q) RL_HIP(hipMemcpy(sum_q, u->sum_q, bytes, hipMemcpyDeviceToHost));
+    if (observations) *observations = u->observations;
+    if (paths) *paths = u->paths;
+    return RL_OK;
+}
+
+int rl_error_unit_upload(RlErrorUnit* u, const double* sum_y, const double* sum_q, uint64_t observations, uint64_t paths) {
+    if (!u || !sum_y || !sum_q) return fail(RL_E_INVALID, "rl_error_unit_upload: null error unit or plane");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    const size_t bytes = (size_t)u->width * u->height * sizeof(double);
+    RL_HIP(hipStreamSynchronize(u->stream));
+    RL_HIP(hipMemcpy(u->sum_y, sum_y, bytes, hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(u->sum_q, sum_q, bytes, hipMemcpyHostToDevice));
+    RL_HIP(hipStreamSynchronize(nullptr)); // (the null stream only: a resident open trace kernel of another unit is not waited for)
+    u->observations = observations;
+    u->paths = paths;
+    return RL_OK;
+}
+
 // ---- GatherUnit-time exchange across GPUs (gather_unit.rs:49-64 with the plot buffers of G GPUs) ----
 
 namespace {
@@ -3311,6 +3502,44 @@ int rl_debug_spectral_ms(RlSpectralUnit* u, float out[2]) {
         out[k] = 0.0f;
         if (u->timed_done[k]) RL_HIP(hipEventElapsedTime(&out[k], u->timed[k].start, u->timed[k].stop));
     }
+    return RL_OK;
+}
+int rl_debug_error_launches(uint64_t out[2]) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    for (int k = 0; k < 2; ++k) out[k] = g_error_launches[k].load(std::memory_order_relaxed);
+    return RL_OK;
+}
+int rl_debug_error_ms(RlErrorUnit* u, float out[2]) {
+    if (!u || !out) return fail(RL_E_INVALID, "null argument");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    for (int k = 0; k < 2; ++k) {
+        out[k] = 0.0f;
+        if (!u->timed_done[k]) continue;
+        RL_HIP(hipEventSynchronize(u->timed[k].stop));
+        RL_HIP(hipEventElapsedTime(&out[k], u->timed[k].start, u->timed[k].stop));
+    }
+    return RL_OK;
+}
+int rl_debug_gather_accumulate_ms(RlGatherUnit* u, RlPlotUnit* plot, float* ms) {
+    if (!u || !plot || !ms) return fail(RL_E_INVALID, "null argument");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    if ((rc = plot_settle(plot)) != RL_OK) return rc;
+    if (plot->device == u->device) RL_HIP(hipStreamSynchronize(plot->stream));
+    RL_HIP(hipStreamSynchronize(u->stream));
+    EventPair ep{};
+    RL_HIP(hipEventCreate(&ep.start));
+    hipError_t e = hipEventCreate(&ep.stop);
+    if (e == hipSuccess) e = hipEventRecord(ep.start, u->stream);
+    if (e == hipSuccess) rc = rl_gather_unit_accumulate(u, plot);
+    if (e == hipSuccess && rc == RL_OK) e = hipEventRecord(ep.stop, u->stream);
+    if (e == hipSuccess && rc == RL_OK) e = hipEventSynchronize(ep.stop);
+    if (e == hipSuccess && rc == RL_OK) e = hipEventElapsedTime(ms, ep.start, ep.stop);
+    (void)hipEventDestroy(ep.start);
+    if (ep.stop) (void)hipEventDestroy(ep.stop);
+    if (rc != RL_OK) return rc;
+    RL_HIP(e);
     return RL_OK;
 }
 int rl_debug_denoise_pass_ms(RlDenoiseUnit* u, float out[1 + RL_DENOISE_MAX_ITERATIONS]) {

@@ -78,7 +78,38 @@ struct AppState {
     std::string error_message;
     std::vector<uint8_t> rgb;
     uint32_t photons;
+    // rl_app_run_to_error with a target; all of it is used by the Plot task that holds a plot unit or under the scheduler's gather
+    // token (Gather and Tonemap tasks never overlap), so none of it needs a lock of its own.
+    const RlErrorTarget* target = nullptr;
+    RlErrorUnit* error_unit = nullptr;   // on rank 0's device
+    std::vector<uint64_t> plot_paths;    // per plot unit: paths plotted or fused into it since its last gather, over all ranks
+    uint64_t error_observations = 0;     // k of the error unit
+    uint32_t min_observations = 16;
+    std::atomic<bool> target_met{false}; // ends the hand-out of trace tasks as an exhausted max_batches does
+    RlAppErrorStats error_stats;
+    std::vector<double> error_tiles;     // the {t_se, t_y} pairs of the last estimate
 };
+
+thread_local std::vector<double> g_last_error_tiles; // rl_app_error_tiles: of this thread's last rl_app_run_to_error
+
+// The estimate of a Tonemap task, and the stopping rule.  A NaN estimate meets no target.
+int estimate_error(AppState& a) {
+    if (!a.error_unit || a.error_observations < 2) return RL_OK;
+    RlErrorStats s;
+    const int rc = rl_error_unit_estimate(a.error_unit, &s, nullptr, a.error_tiles.data());
+    if (rc != RL_OK) return rc;
+    a.error_stats.at_end = s; // the last one stands: the final Tonemap task's, after the last gather
+    a.error_stats.estimates += 1;
+    const RlErrorTarget& t = *a.target;
+    const bool met = s.observations >= a.min_observations && s.relative_error <= t.relative_error &&
+                     (t.worst_tile_error == 0.0 || s.worst_tile_error <= t.worst_tile_error);
+    if (met && !a.error_stats.reached) {
+        a.error_stats.reached = 1;
+        a.error_stats.at_stop = s;
+        a.target_met.store(true);
+    }
+    return RL_OK;
+}
 
 int64_t now_ms(const AppState& a) {
     return std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - a.t0).count();
@@ -313,6 +344,7 @@ void execute_task(AppState& a, const RlTask& task) {
                 for (uint32_t i = 0; i < task.n_units; ++i) units.push_back(a.ranks[r].trace_units[task.units[i]]);
                 rc = rl_plot_unit_plot(a.ranks[r].plot_units[task.unit], units.data(), (uint32_t)units.size());
             }
+            if (a.error_unit) a.plot_paths[task.unit] += (uint64_t)task.n_units * a.photons * a.ranks.size();
         } else {
             // The batches of all the trace units of this task go out as ONE launch over one contiguous
             // range of path indices: a 524,288-path launch of its own would keep an MI355X busy for 0.15 ms
@@ -322,6 +354,7 @@ void execute_task(AppState& a, const RlTask& task) {
             if (task.n_units != 0) {
                 const uint64_t n = (uint64_t)task.n_units * (uint64_t)a.photons;
                 const uint64_t first = a.fused_next_path.fetch_add(n);
+                if (a.error_unit) a.plot_paths[task.unit] += n * a.ranks.size();
                 for (size_t r = 0; r < a.ranks.size() && rc == RL_OK; ++r) {
                     RlTraceUnit* u = a.ranks[r].trace_units[task.units[0]];
                     if (a.distinct_devices) { // begun here, ended by the Gather task that takes the plot unit (as above)
@@ -359,11 +392,17 @@ void execute_task(AppState& a, const RlTask& task) {
                 for (size_t r = 1; r < a.ranks.size() && rc == RL_OK; ++r)
                     if (a.ranks[r].comm) rc = rl_plot_unit_clear(a.ranks[r].plot_units[j]);
             }
+            if (rc == RL_OK && a.error_unit && a.plot_paths[j] != 0) { // the buffer is one batch sum over that many paths
+                rc = rl_error_unit_observe(a.error_unit, a.ranks[0].plot_units[j], a.plot_paths[j]);
+                a.plot_paths[j] = 0;
+                a.error_observations += 1;
+            }
             if (rc == RL_OK) rc = rl_gather_unit_accumulate(a.gather, a.ranks[0].plot_units[j]); // Kahan + clear
         }
         break;
     case RL_TASK_TONEMAP: // app.rs:154-164
-        rc = rl_tonemap_unit_tonemap(a.tonemap, a.gather);
+        rc = estimate_error(a);
+        if (rc == RL_OK) rc = rl_tonemap_unit_tonemap(a.tonemap, a.gather);
         if (rc == RL_OK) rc = rl_tonemap_unit_rgb(a.tonemap, a.rgb.data());
         if (rc == RL_OK && c.output_ppm) rc = write_image(c.output_ppm, a.rgb.data(), c.width, c.height);
         if (rc == RL_OK && c.checkpoint) rc = save_checkpoint(a);
@@ -427,7 +466,7 @@ void worker(AppState* ap) {
         {
             std::lock_guard<std::mutex> guard(a.lock);
             if (a.cfg->verbose) log_completed(a, task);
-            const bool budget_left = a.traces_issued < a.cfg->max_batches;
+            const bool budget_left = a.traces_issued < a.cfg->max_batches && !a.target_met.load();
             if (rl_scheduler_get_new_task(a.scheduler, &task, now_ms(a), &next) != RL_OK) {
                 fail(a, RL_E_INVALID);
                 return;
@@ -459,6 +498,25 @@ void worker(AppState* ap) {
 } // namespace
 
 extern "C" int rl_app_run(const RlAppConfig* config, RlAppStats* stats, uint8_t* rgb_out) {
+    return rl_app_run_to_error(config, nullptr, stats, nullptr, rgb_out);
+}
+
+extern "C" int rl_app_error_tiles(double* tiles, uint32_t capacity, uint32_t* n_tiles) {
+    const size_t n = g_last_error_tiles.size() / 2;
+    if (n_tiles) *n_tiles = (uint32_t)n;
+    if (n == 0) return RL_OK;
+    if (!tiles || capacity < n) {
+        rl_internal_set_last_error("rl_app_error_tiles: the buffer is too small for " + std::to_string(n) + " tile pairs");
+        return RL_E_INVALID;
+    }
+    std::memcpy(tiles, g_last_error_tiles.data(), 2 * n * sizeof(double));
+    return RL_OK;
+}
+
+extern "C" int rl_app_run_to_error(const RlAppConfig* config, const RlErrorTarget* target, RlAppStats* stats, RlAppErrorStats* error_stats,
+                                   uint8_t* rgb_out) {
+    g_last_error_tiles.clear();
+    if (error_stats) std::memset(error_stats, 0, sizeof *error_stats);
     if (!config || config->width == 0 || config->height == 0 || config->concurrency == 0) {
         rl_internal_set_last_error("rl_app_run: null config, zero-sized image or zero workers");
         return RL_E_INVALID;
@@ -474,8 +532,15 @@ extern "C" int rl_app_run(const RlAppConfig* config, RlAppStats* stats, uint8_t*
                                    std::to_string(RL_TASK_MAX_UNITS) + " (at most " + std::to_string(RL_TASK_MAX_UNITS / 3) + " workers)");
         return RL_E_INVALID;
     }
+    if (target && (!(target->relative_error >= 0.0) || !(target->worst_tile_error >= 0.0) || target->reserved != 0)) {
+        rl_internal_set_last_error("rl_app_run_to_error: the target's relative_error and worst_tile_error must be >= 0 (not NaN) and its reserved field 0");
+        return RL_E_INVALID;
+    }
     AppState a;
     a.cfg = config;
+    a.target = target;
+    std::memset(&a.error_stats, 0, sizeof a.error_stats);
+    if (target && target->min_observations) a.min_observations = target->min_observations;
     a.t0 = std::chrono::steady_clock::now(); // also the origin of `seconds` when set-up fails
     a.photons = config->photons_per_batch ? config->photons_per_batch : 1024u * 512u;
     a.rgb.assign((size_t)config->width * config->height * 3, 0);
@@ -528,6 +593,11 @@ extern "C" int rl_app_run(const RlAppConfig* config, RlAppStats* stats, uint8_t*
     const int root_device = a.ranks[0].device;
     if (rc == RL_OK) rc = rl_gather_unit_create(root_device, config->width, config->height, &a.gather);
     if (rc == RL_OK) rc = rl_tonemap_unit_create(root_device, config->width, config->height, &a.tonemap);
+    if (rc == RL_OK && target) {
+        rc = rl_error_unit_create(root_device, config->width, config->height, &a.error_unit);
+        a.plot_paths.assign(n_plot, 0);
+        a.error_tiles.assign((size_t)((config->width + RL_ERROR_TILE - 1) / RL_ERROR_TILE) * ((config->height + RL_ERROR_TILE - 1) / RL_ERROR_TILE) * 2, 0.0);
+    }
     a.first_batch = config->first_batch;
     if (rc == RL_OK && config->resume && config->checkpoint) {
         FILE* f = std::fopen(config->checkpoint, "rb"); // a missing file is not an error (gather_unit.rs:82)
@@ -607,6 +677,8 @@ extern "C" int rl_app_run(const RlAppConfig* config, RlAppStats* stats, uint8_t*
             }
         if (a.scheduler) rl_scheduler_performance(a.scheduler, &stats->batches_per_sec_mean, &stats->batches_per_sec_stddev);
     }
+    if (error_stats && rc == RL_OK) *error_stats = a.error_stats;
+    if (rc == RL_OK && a.error_stats.estimates != 0) g_last_error_tiles = a.error_tiles;
     if (rgb_out && rc == RL_OK) std::memcpy(rgb_out, a.rgb.data(), a.rgb.size());
     std::string message = a.error_message;
     if (rc != RL_OK && message.empty()) message = rl_last_error(); // a set-up call on this thread failed
@@ -617,6 +689,7 @@ extern "C" int rl_app_run(const RlAppConfig* config, RlAppStats* stats, uint8_t*
     }
     rl_gather_unit_destroy(a.gather);
     rl_tonemap_unit_destroy(a.tonemap);
+    rl_error_unit_destroy(a.error_unit);
     for (Rank& k : a.ranks) rl_comm_destroy(k.comm);
     rl_scheduler_destroy(a.scheduler);
     if (rc != RL_OK && !message.empty()) rl_internal_set_last_error(message); // the failing call may have run on a worker thread
