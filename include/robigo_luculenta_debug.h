@@ -89,6 +89,12 @@ int rl_debug_error_ms(RlErrorUnit* unit, float out[2]);
  * and the gather unit's after: *ms is the device time of that call's rl_gather_kernel launch, the yardstick tools/error_bench.py
  * holds the observe kernel to.  The accumulation happens as usual. */
 int rl_debug_gather_accumulate_ms(RlGatherUnit* unit, RlPlotUnit* plot, float* ms);
+/* What the live handles of this process hold on their devices, all devices together: out[0] device allocations, out[1] streams,
+ * out[2] plain (untimed) events, out[3] timed event pairs, spare and unread ones included.  Counted where a handle acquires and
+ * releases them, so a *_destroy that frees exactly what its *_create took -- and whatever the handle's calls added -- returns all
+ * four to their earlier values.  Scenes and the trace, plot, gather, tonemap, denoise, spectral and error units are counted; the
+ * per-device open-launch slots and query contexts, which live as long as the process, and communicators are not. */
+int rl_debug_live_resources(uint64_t out[4]);
 /* rl_scene_emitters for a description instead of a scene: the sampleable emitters' object indices in scan order, by the function
  * rl_scene_create builds a scene's table with.  Host arithmetic only: callable without a GPU.  The same capacity protocol. */
 int rl_debug_scene_emitters(const RlObjectDesc* objects, uint32_t n_objects, uint32_t* out, uint32_t cap, uint32_t* n_emitters);

@@ -975,109 +975,90 @@ def batch_histogram(device=0):
     return {k: int(out[k]) for k in range(1, 257) if out[k]}
 
 
+def _launch_counters(symbol, n, kind):
+    """The n launch counters that `symbol` fills, as a list (a kernel family's instantiations) or a tuple (a unit's two kernels)."""
+    out = (C.c_uint64 * n)()
+    check(symbol(out))
+    return kind(int(x) for x in out)
+
+
 def variant_launches():
     """rl_debug_variant_launches: launches per instantiation of the trace kernel since the library was loaded;
     index = 8 * whole scene staged in LDS + 4 * fused + 2 * open launch + 1 * prisms with a second bound; 16 + the low three
     bits for the variants that stage the scene's tables only."""
-    out = (C.c_uint64 * 24)()
-    check(lib.rl_debug_variant_launches(out))
-    return list(out)
+    return _launch_counters(lib.rl_debug_variant_launches, 24, list)
 
 
 def query_launches():
     """rl_debug_query_launches: launches per instantiation of the query kernel (Scene.intersect*) since the library was loaded;
     index = 2 * stage + 1 * prisms with a second bound, stage 0: nothing staged in LDS, 1: the scene's tables, 2: the whole scene."""
-    out = (C.c_uint64 * 6)()
-    check(lib.rl_debug_query_launches(out))
-    return list(out)
+    return _launch_counters(lib.rl_debug_query_launches, 6, list)
 
 
 def occlusion_launches():
     """rl_debug_occlusion_launches: launches per instantiation of the occlusion kernel (Scene.occluded*) since the library was
     loaded, indexed as query_launches()."""
-    out = (C.c_uint64 * 6)()
-    check(lib.rl_debug_occlusion_launches(out))
-    return list(out)
+    return _launch_counters(lib.rl_debug_occlusion_launches, 6, list)
 
 
 def path_launches():
     """rl_debug_path_launches: launches per instantiation of the path kernel (Scene.render_rays*) since the library was loaded,
     indexed as query_launches()."""
-    out = (C.c_uint64 * 6)()
-    check(lib.rl_debug_path_launches(out))
-    return list(out)
+    return _launch_counters(lib.rl_debug_path_launches, 6, list)
 
 
 def film_launches():
     """rl_debug_film_launches: launches per instantiation of the film path kernel (PlotUnit.render_samples*) since the library was
     loaded, indexed as query_launches()."""
-    out = (C.c_uint64 * 6)()
-    check(lib.rl_debug_film_launches(out))
-    return list(out)
+    return _launch_counters(lib.rl_debug_film_launches, 6, list)
 
 
 def step_launches():
     """rl_debug_step_launches: launches per instantiation of the step kernel (Scene.step_paths*) since the library was loaded,
     indexed as query_launches()."""
-    out = (C.c_uint64 * 6)()
-    check(lib.rl_debug_step_launches(out))
-    return list(out)
+    return _launch_counters(lib.rl_debug_step_launches, 6, list)
 
 
 def path_list_launches():
     """rl_debug_path_list_launches: launches per instantiation of the list-step kernel (Scene.step_path_list*) since the library
     was loaded, indexed as query_launches()."""
-    out = (C.c_uint64 * 6)()
-    check(lib.rl_debug_path_list_launches(out))
-    return list(out)
+    return _launch_counters(lib.rl_debug_path_list_launches, 6, list)
 
 
 def light_launches():
     """Launches per light-kernel instantiation since the library was loaded (rl_debug_light_launches); index = 2 * stage +
     (prisms carry a second bound), as query_launches()."""
-    out = (C.c_uint64 * 6)()
-    check(lib.rl_debug_light_launches(out))
-    return list(out)
+    return _launch_counters(lib.rl_debug_light_launches, 6, list)
 
 
 def light_film_launches():
     """Launches per instantiation of the light kernel with a film (PlotUnit.light_paths*, PlotUnit.render_samples_direct*) since the
     library was loaded (rl_debug_light_film_launches); index = 2 * stage + cylinders, as light_launches()."""
-    out = (C.c_uint64 * 6)()
-    check(lib.rl_debug_light_film_launches(out))
-    return [int(x) for x in out]
+    return _launch_counters(lib.rl_debug_light_film_launches, 6, list)
 
 
 def direct_launches():
     """Launches per instantiation of the direct path kernel (PlotUnit.render_direct) since the library was loaded
     (rl_debug_direct_launches); index = 2 * stage + cylinders, as light_launches()."""
-    out = (C.c_uint64 * 6)()
-    check(lib.rl_debug_direct_launches(out))
-    return [int(x) for x in out]
+    return _launch_counters(lib.rl_debug_direct_launches, 6, list)
 
 
 def feature_launches():
     """Launches per instantiation of the feature path kernel (Scene.render_features) since the library was loaded
     (rl_debug_feature_launches); index = 2 * stage + cylinders, as light_launches()."""
-    out = (C.c_uint64 * 6)()
-    check(lib.rl_debug_feature_launches(out))
-    return [int(x) for x in out]
+    return _launch_counters(lib.rl_debug_feature_launches, 6, list)
 
 
 def denoise_launches():
     """(launches of the denoiser's guide kernel, launches of its pass kernel) since the library was loaded
     (rl_debug_denoise_launches): one and `iterations` per DenoiseUnit.denoise."""
-    out = (C.c_uint64 * 2)()
-    check(lib.rl_debug_denoise_launches(out))
-    return tuple(out)
+    return _launch_counters(lib.rl_debug_denoise_launches, 2, tuple)
 
 
 def spectral_launches():
     """(launches of the spectral film's splat kernel, launches of its projection kernel) since the library was loaded
     (rl_debug_spectral_launches)."""
-    out = (C.c_uint64 * 2)()
-    check(lib.rl_debug_spectral_launches(out))
-    return tuple(out)
+    return _launch_counters(lib.rl_debug_spectral_launches, 2, tuple)
 
 
 def gather_accumulate_ms(gather, plot_unit):
@@ -1090,9 +1071,15 @@ def gather_accumulate_ms(gather, plot_unit):
 def error_launches():
     """(launches of the error unit's observe kernel, launches of its estimate kernel) since the library was loaded
     (rl_debug_error_launches)."""
-    out = (C.c_uint64 * 2)()
-    check(lib.rl_debug_error_launches(out))
-    return tuple(out)
+    return _launch_counters(lib.rl_debug_error_launches, 2, tuple)
+
+
+def live_resources():
+    """rl_debug_live_resources: (device allocations, streams, plain events, timed event pairs) that the live handles of this
+    process hold, all devices together."""
+    out = (C.c_uint64 * 4)()
+    check(lib.rl_debug_live_resources(out))
+    return tuple(int(x) for x in out)
 
 
 def description_emitters(objects):

@@ -296,6 +296,7 @@ DEBUG_SIGNATURES = {
     "rl_debug_error_launches": (_i, [_vp]),
     "rl_debug_error_ms": (_i, [_vp, _vp]),
     "rl_debug_gather_accumulate_ms": (_i, [_vp, _vp, C.POINTER(C.c_float)]),
+    "rl_debug_live_resources": (_i, [_vp]),
     "rl_debug_scene_emitters": (_i, [_vp, _u32, _vp, _u32, C.POINTER(_u32)]),
     "rl_debug_light_sample": (_i, [_vp, _u32, _u64, _u32, _vp, _vp, _u32, _vp, _vp]),
     "rl_debug_prism_probe": (_i, [_vp, _u32, _vp, _u32, _vp]),

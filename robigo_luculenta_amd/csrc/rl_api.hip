@@ -2,7 +2,8 @@
 //
 // Ordering model: every trace, plot and gather unit owns a NON-blocking HIP stream and nothing relies on the
 // null stream's implicit ordering (RCCL and a host framework's side streams are non-blocking too).  Every
-// hand-over between units is an event:
+// hand-over between units is an event, recorded on the stream that gives and waited for on the stream that takes
+// (`hand_over` below; each call site says why it is there):
 //   * a fused render writes the plot unit's buffer from the trace unit's stream: the plot stream waits for it
 //     (so "everything written into this plot unit so far" is always the tail of the plot unit's own stream),
 //     and the render itself waits for the plot unit's last clear;
@@ -14,8 +15,10 @@
 //   * the blocking render calls (open launches, see `Session` below) are ordered on the HOST instead: before a call
 //     is appended to a kernel that is already running, the host waits for whatever still reads or clears its target,
 //     and the call (or whoever ends a begun one) returns only when the kernel has reported its last path.
-// Downloads synchronise the stream that produced the data.  Trace and plot work of different units overlap on
-// the device.  Entry points never throw.
+// Downloads synchronise the stream that produced the data (`download`, `upload`).  Trace and plot work of different
+// units overlap on the device.  The streams, events and device memory of a handle are held by its `Ledger`, whose
+// release drains the handle's streams before anything they may still use is destroyed or freed: a *_destroy ends what
+// only the unit knows of (a begun render), then releases.  Entry points never throw.
 #include <hip/hip_runtime.h>
 #include <sys/prctl.h>
 
@@ -102,14 +105,225 @@ hipError_t create_unit_stream(hipStream_t* stream) {
     return hipStreamCreateWithFlags(stream, getenv("RL_BLOCKING_STREAMS") ? hipStreamDefault : hipStreamNonBlocking);
 }
 
+int cu_count_of(int device, int* out);
+// What a call on a unit starts with once its arguments are checked: the unit's device current, and its CU count.
+int enter_device(int device, int* cus) {
+    const int rc = use_device(device);
+    return rc != RL_OK ? rc : cu_count_of(device, cus);
+}
+
+// A unit handed to a call on another unit must live on the same device and have the same image size.
+const char* unit_name(const RlTraceUnit*) { return "trace unit"; }
+const char* unit_name(const RlPlotUnit*) { return "plot unit"; }
+const char* unit_name(const RlGatherUnit*) { return "gather unit"; }
+const char* unit_name(const RlTonemapUnit*) { return "tonemap unit"; }
+const char* unit_name(const RlDenoiseUnit*) { return "denoise unit"; }
+const char* unit_name(const RlSpectralUnit*) { return "spectral unit"; }
+const char* unit_name(const RlErrorUnit*) { return "error unit"; }
+template <class Given, class Owner>
+int match_check(const Given* given, const Owner* owner) {
+    if (given->device == owner->device && given->width == owner->width && given->height == owner->height) return RL_OK;
+    return fail(RL_E_STATE, std::string(unit_name(given)) + " does not match the " + unit_name(owner) + " (device or size)");
+}
+
+// The hand-over of the ordering model (top of the file): what is queued on `to` from here on runs behind everything queued on
+// `from` so far.  `event` is recorded on `from` and waited for on `to`.
+int hand_over(hipEvent_t event, hipStream_t from, hipStream_t to) {
+    RL_HIP(hipEventRecord(event, from));
+    RL_HIP(hipStreamWaitEvent(to, event, 0));
+    return RL_OK;
+}
+
+// Returns when `stream` has drained, also after a failure: rc if it failed, else what the drain returned.  A call that queued
+// work which reads or writes host memory, or buffers that may be freed next, leaves through this.
+int drained(hipStream_t stream, int rc) {
+    const hipError_t e = hipStreamSynchronize(stream);
+    if (rc != RL_OK) return rc;
+    RL_HIP(e);
+    return RL_OK;
+}
+
+// Host copies of a unit's buffers, plane by plane (a null host pointer: that plane is skipped).  `stream` is the one that
+// produced the data or still reads it, and drains first (null: nothing was ever queued).
+struct Plane {
+    void* dev;
+    const void* host;
+    size_t bytes;
+};
+int download(hipStream_t stream, std::initializer_list<Plane> planes) {
+    if (stream) RL_HIP(hipStreamSynchronize(stream));
+    for (const Plane& p : planes)
+        if (p.host) RL_HIP(hipMemcpy(const_cast<void*>(p.host), p.dev, p.bytes, hipMemcpyDeviceToHost));
+    return RL_OK;
+}
+int upload(hipStream_t stream, std::initializer_list<Plane> planes) {
+    if (stream) RL_HIP(hipStreamSynchronize(stream));
+    for (const Plane& p : planes)
+        if (p.host) RL_HIP(hipMemcpy(p.dev, p.host, p.bytes, hipMemcpyHostToDevice));
+    RL_HIP(hipStreamSynchronize(nullptr)); // (the null stream only: a resident open trace kernel of another unit is not waited for)
+    return RL_OK;
+}
+
 struct EventPair {
     hipEvent_t start, stop;
 };
+
+// One launch on `stream` between the events of `pair`; *launches counts the launches that were accepted.  Whether and when the
+// pair may be read is the caller's: the units differ in it (include/robigo_luculenta_debug.h).
+void count_launch(std::atomic<uint64_t>* launches) { launches->fetch_add(1, std::memory_order_relaxed); }
+void count_launch(uint64_t* launches) { *launches += 1; }
+template <class Counter, class Launch>
+int timed_launch(const EventPair& pair, hipStream_t stream, Counter* launches, Launch launch) {
+    RL_HIP(hipEventRecord(pair.start, stream));
+    launch();
+    RL_HIP(hipGetLastError());
+    RL_HIP(hipEventRecord(pair.stop, stream));
+    count_launch(launches);
+    return RL_OK;
+}
+
+// rl_debug_live_resources: what the ledgers of all live handles hold.  Fed by Ledger's acquire and release and by nothing else.
+enum { LIVE_ALLOCATIONS, LIVE_STREAMS, LIVE_EVENTS, LIVE_PAIRS, LIVE_KINDS };
+std::atomic<uint64_t> g_live[LIVE_KINDS];
+
+// The device resources of one handle.  Every acquisition writes the raw pointer or handle into the field the caller names and
+// records it here; after the first failure the later ones do nothing, so a *_create is a flat list and one check of finish().
+// release() is the only code that destroys or frees what a handle holds, for a complete handle and a half-built one alike.
+struct Ledger {
+    std::vector<void*> memory;
+    std::vector<hipStream_t> streams;
+    std::vector<hipEvent_t> events;
+    std::vector<EventPair> pairs;
+    hipError_t error = hipSuccess; // the first failed acquisition
+    bool filled = false;           // a synchronous memset or copy ran on the null stream
+
+    // Device memory as it comes (fill = nullptr), or holding the `bytes` bytes at `fill`.
+    template <class T>
+    void alloc(T** field, size_t bytes, const void* fill = nullptr) {
+        *field = nullptr;
+        if (error != hipSuccess || (error = hipMalloc((void**)field, bytes)) != hipSuccess) return;
+        memory.push_back((void*)*field);
+        g_live[LIVE_ALLOCATIONS].fetch_add(1, std::memory_order_relaxed);
+        if (fill) error = hipMemcpy((void*)*field, fill, bytes, hipMemcpyHostToDevice), filled = true;
+    }
+    template <class T>
+    void alloc_zeroed(T** field, size_t bytes) {
+        alloc(field, bytes);
+        if (error == hipSuccess) error = hipMemset((void*)*field, 0, bytes), filled = true;
+    }
+    void stream(hipStream_t* field) {
+        *field = nullptr;
+        if (error != hipSuccess || (error = create_unit_stream(field)) != hipSuccess) return;
+        streams.push_back(*field);
+        g_live[LIVE_STREAMS].fetch_add(1, std::memory_order_relaxed);
+    }
+    // A plain event: it orders streams and is never timed.
+    void event(hipEvent_t* field) {
+        *field = nullptr;
+        if (error != hipSuccess || (error = hipEventCreateWithFlags(field, hipEventDisableTiming)) != hipSuccess) return;
+        events.push_back(*field);
+        g_live[LIVE_EVENTS].fetch_add(1, std::memory_order_relaxed);
+    }
+    // A timed pair.  make_pair is the form for a live handle (PairPool): its failure is the call's, not the handle's.
+    hipError_t make_pair(EventPair* field) {
+        *field = EventPair{nullptr, nullptr};
+        hipError_t e = hipEventCreate(&field->start);
+        if (e == hipSuccess && (e = hipEventCreate(&field->stop)) != hipSuccess) (void)hipEventDestroy(field->start);
+        if (e != hipSuccess) return e;
+        pairs.push_back(*field);
+        g_live[LIVE_PAIRS].fetch_add(1, std::memory_order_relaxed);
+        return hipSuccess;
+    }
+    void pair(EventPair* field) {
+        if (error == hipSuccess) error = make_pair(field);
+    }
+    // The end of a *_create: the first failure, if any.
+    hipError_t finish() {
+        if (error == hipSuccess && filled) error = hipStreamSynchronize(nullptr); // the synchronous memsets and copies ran on the null stream (that stream only: a resident open trace kernel of another unit is not waited for)
+        return error;
+    }
+    // Device current.  The streams drain before anything they may still use goes.
+    void release() {
+        for (hipStream_t s : streams) (void)hipStreamSynchronize(s);
+        for (hipStream_t s : streams) (void)hipStreamDestroy(s);
+        for (hipEvent_t e : events) (void)hipEventDestroy(e);
+        for (const EventPair& p : pairs) (void)hipEventDestroy(p.start), (void)hipEventDestroy(p.stop);
+        for (void* p : memory) (void)hipFree(p);
+        g_live[LIVE_ALLOCATIONS].fetch_sub(memory.size(), std::memory_order_relaxed);
+        g_live[LIVE_STREAMS].fetch_sub(streams.size(), std::memory_order_relaxed);
+        g_live[LIVE_EVENTS].fetch_sub(events.size(), std::memory_order_relaxed);
+        g_live[LIVE_PAIRS].fetch_sub(pairs.size(), std::memory_order_relaxed);
+        memory.clear(), streams.clear(), events.clear(), pairs.clear();
+    }
+};
+
+// Timed pairs around work on a stream whose milliseconds are read later, if ever.  The pairs are the ledger's; the pool only
+// says where each one is: spare, taken by a call, or pending (recorded around work, not read yet; oldest first).
+struct PairPool {
+    std::vector<EventPair> pending, spare;
+    int take(Ledger* ledger, EventPair* pair) {
+        if (spare.empty()) {
+            RL_HIP(ledger->make_pair(pair));
+        } else {
+            *pair = spare.back();
+            spare.pop_back();
+        }
+        return RL_OK;
+    }
+    void give_back(const EventPair& pair) { spare.push_back(pair); }
+    // Waits for the `n` oldest pending pairs, adds their milliseconds to *ms and their number to *count, and spares them.
+    int harvest(size_t n, double* ms, uint64_t* count) {
+        size_t done = 0;
+        hipError_t e = hipSuccess;
+        for (n = std::min(n, pending.size()); done < n; ++done) {
+            float t = 0.0f;
+            if ((e = hipEventSynchronize(pending[done].stop)) != hipSuccess) break;
+            if ((e = hipEventElapsedTime(&t, pending[done].start, pending[done].stop)) != hipSuccess) break;
+            *ms += (double)t;
+            *count += 1;
+            spare.push_back(pending[done]);
+        }
+        pending.erase(pending.begin(), pending.begin() + (long)done);
+        if (e != hipSuccess) return fail(RL_E_HIP, std::string("event pair harvest: ") + hipGetErrorString(e));
+        return RL_OK;
+    }
+};
+
+// What the *_unit_create calls share.  unit_new: the argument checks in the header's order -- null output, zero size (`count`:
+// whatever else must not be 0), RL_MAX_PIXELS, then the device -- and the handle with its device and size set.  unit_created:
+// the one check behind the flat list of acquisitions; `destroy` is the unit's own, for a half-built handle as for a whole one.
+template <class Unit>
+int unit_new(const char* name, int device, uint32_t width, uint32_t height, uint32_t count, Unit** out, Unit** unit) {
+    if (!out) return fail(RL_E_INVALID, "null output handle");
+    *out = nullptr;
+    if (width == 0 || height == 0 || count == 0) return fail(RL_E_INVALID, std::string("zero-sized ") + name);
+    int rc = check_image_size(name, width, height);
+    if (rc == RL_OK) rc = use_device(device);
+    if (rc != RL_OK) return rc;
+    Unit* u = new (std::nothrow) Unit();
+    if (!u) return fail(RL_E_INVALID, "out of host memory");
+    u->device = device;
+    u->width = width;
+    u->height = height;
+    *unit = u;
+    return RL_OK;
+}
+template <class Unit>
+int unit_created(const char* what, Unit* u, int (*destroy)(Unit*), Unit** out) {
+    const hipError_t e = u->ledger.finish();
+    if (e != hipSuccess) {
+        destroy(u);
+        return fail(RL_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    }
+    *out = u;
+    return RL_OK;
+}
 
 } // namespace
 
 struct RlScene {
     int device;
+    Ledger ledger; // blob, emitters, emitter_flags
     RlF4* blob;
     RlSceneLayout lay;
     size_t staged_bytes; // the whole blob
@@ -158,7 +372,8 @@ struct RlTraceUnit {
     hipEvent_t rendered; // recorded on `stream` after everything that fills this unit's photons
     int fetch;
     int cu_count;
-    std::vector<EventPair> pending, pool;
+    Ledger ledger;  // photons, queue, stream, rendered, and the pairs of `timed`
+    PairPool timed; // around every launch_trace on `stream`; harvested into kernel_ms
     double kernel_ms;
     uint64_t launches;
     size_t tuned_dyn;  // launch configuration last set up for this unit: dynamic LDS bytes,
@@ -171,15 +386,15 @@ struct RlTraceUnit {
 struct RlPlotUnit {
     int device;
     uint32_t id, width, height;
-    float* xyz;
-    bool owns;
+    float* xyz; // the unit's own, or the caller's (rl_plot_unit_create: external_xyz, which the ledger does not hold)
     RlF4* cie;
     hipStream_t stream; // rl_plot_kernel launches, clears, the RCCL exchange; its tail = every write into xyz so far
     hipEvent_t plotted; // recorded after the last plot kernel of a PlotUnit::plot call
     hipEvent_t ready;   // recorded on `stream` when a gather (or a reader on another stream) takes the buffer
     hipEvent_t cleared; // recorded on the gather stream after accumulate + clear
     hipEvent_t tail;    // scratch: recorded on `stream` by a fused launch that has to start behind everything queued there
-    std::vector<EventPair> exchanges, exchange_pool; // around every rl_plot_unit_reduce on `stream`, not yet read (rl_plot_unit_exchange_stats); spare pairs
+    Ledger ledger;
+    PairPool exchanges; // around every rl_plot_unit_reduce on `stream`; pending until read (rl_plot_unit_exchange_stats)
     uint64_t exchange_count = 0;
     double exchange_ms = 0.0;
     Ticket ticket;      // rl_trace_unit_render_fused_begin: ended by whatever uses the buffer next (plot_settle)
@@ -191,6 +406,8 @@ struct RlGatherUnit {
     float* acc;
     float* comp;
     hipStream_t stream; // accumulate and tonemap kernels
+    Ledger ledger;
+    PairPool timed;     // rl_debug_gather_accumulate_ms
 };
 
 struct RlTonemapUnit {
@@ -200,6 +417,7 @@ struct RlTonemapUnit {
     float* srgb;
     float* max_intensity;
     hipStream_t last_stream; // the gather stream the last tonemap ran on (downloads wait for it)
+    Ledger ledger;
 };
 
 struct RlDenoiseUnit {
@@ -210,6 +428,7 @@ struct RlDenoiseUnit {
     hipEvent_t ready[4]; // recorded on the streams of the gather units a call reads: image, albedo, normal, aux
     EventPair timed[1 + RL_DENOISE_MAX_ITERATIONS]; // around the guide launch and each pass of the last call (rl_debug_denoise_pass_ms)
     uint32_t timed_passes; // passes of the last call that completed
+    Ledger ledger;
 };
 
 struct RlSpectralUnit {
@@ -222,6 +441,7 @@ struct RlSpectralUnit {
     hipEvent_t ready;   // recorded on `stream` when a projection takes the film
     EventPair timed[2]; // around the last splat launch and the last projection launch (rl_debug_spectral_ms)
     bool timed_done[2]; // ... of a call that completed
+    Ledger ledger;
 };
 
 struct RlErrorUnit {
@@ -237,6 +457,7 @@ struct RlErrorUnit {
     hipEvent_t observed;   // recorded on `stream` after an observe kernel: the plot unit's stream waits for it
     EventPair timed[2];    // around the last observe launch and the last estimate launch (rl_debug_error_ms)
     bool timed_done[2];    // ... recorded at least once
+    Ledger ledger;
 };
 
 // One rank of an RCCL communicator (rl_comm_*).
@@ -248,15 +469,8 @@ struct RlComm {
 namespace {
 
 int drain_events(RlTraceUnit* u) {
-    for (EventPair& ep : u->pending) {
-        RL_HIP(hipEventSynchronize(ep.stop));
-        float ms = 0.0f;
-        RL_HIP(hipEventElapsedTime(&ms, ep.start, ep.stop));
-        u->kernel_ms += (double)ms;
-        u->pool.push_back(ep);
-    }
-    u->pending.clear();
-    return RL_OK;
+    uint64_t read = 0;
+    return u->timed.harvest(u->timed.pending.size(), &u->kernel_ms, &read);
 }
 
 // The instantiation of rl_trace_kernel for a launch: primitives staged in LDS or fetched from global memory, fused with
@@ -359,30 +573,31 @@ int launch_trace(RlTraceUnit* u, const RlScene* scene, RlMappedPhoton* photons, 
     if (blocks > needed) blocks = needed;
 
     EventPair ep;
-    if (!u->pool.empty()) {
-        ep = u->pool.back();
-        u->pool.pop_back();
-    } else {
-        RL_HIP(hipEventCreate(&ep.start));
-        RL_HIP(hipEventCreate(&ep.stop));
+    int rc = u->timed.take(&u->ledger, &ep);
+    if (rc != RL_OK) return rc;
+    rc = [&]() -> int {
+        if (plot_unit) {
+            RL_HIP(hipStreamWaitEvent(u->stream, plot_unit->cleared, 0)); // the splat must not race the last gather's clear
+            // nor anything queued on the plot unit's own stream since (rl_plot_unit_add, the RCCL reduce, an upload)
+            const int r = hand_over(plot_unit->tail, plot_unit->stream, u->stream);
+            if (r != RL_OK) return r;
+        }
+        RL_HIP(hipMemsetAsync(u->queue, 0, sizeof(unsigned long long), u->stream));
+        return timed_launch(ep, u->stream, &u->launches, [&] {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(RL_TRACE_BLOCK), dyn, u->stream, scene->blob, scene->lay, job, photons,
+                               plot, u->queue, (const RlJobEntry*)nullptr, (RlOpenDev*)nullptr, (RlOpenCtl*)nullptr);
+        });
+    }();
+    if (rc != RL_OK) {
+        u->timed.give_back(ep); // (whatever of it was recorded is recorded again by the launch that takes it next)
+        return rc;
     }
-    if (plot_unit) {
-        RL_HIP(hipStreamWaitEvent(u->stream, plot_unit->cleared, 0)); // the splat must not race the last gather's clear
-        // nor anything queued on the plot unit's own stream since (rl_plot_unit_add, the RCCL reduce, an upload)
-        RL_HIP(hipEventRecord(plot_unit->tail, plot_unit->stream));
-        RL_HIP(hipStreamWaitEvent(u->stream, plot_unit->tail, 0));
-    }
-    RL_HIP(hipMemsetAsync(u->queue, 0, sizeof(unsigned long long), u->stream));
-    RL_HIP(hipEventRecord(ep.start, u->stream));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(RL_TRACE_BLOCK), dyn, u->stream, scene->blob, scene->lay, job, photons,
-                       plot, u->queue, (const RlJobEntry*)nullptr, (RlOpenDev*)nullptr, (RlOpenCtl*)nullptr);
-    RL_HIP(hipGetLastError());
-    RL_HIP(hipEventRecord(ep.stop, u->stream));
-    RL_HIP(hipEventRecord(u->rendered, u->stream));
-    if (plot_unit) RL_HIP(hipStreamWaitEvent(plot_unit->stream, u->rendered, 0)); // the plot stream's tail covers this splat
-    u->pending.push_back(ep);
-    u->launches += 1;
-    if (u->pending.size() > 512) return drain_events(u);
+    u->timed.pending.push_back(ep);
+    // `rendered`: everything that fills this unit's photons so far.  A fused launch: the plot stream's tail covers this splat.
+    if (plot_unit) rc = hand_over(u->rendered, u->stream, plot_unit->stream);
+    else RL_HIP(hipEventRecord(u->rendered, u->stream));
+    if (rc != RL_OK) return rc;
+    if (u->timed.pending.size() > 512) return drain_events(u);
     return RL_OK;
 }
 
@@ -738,21 +953,17 @@ int plot_settle(RlPlotUnit* plot);
 // arrays are checked once the device is current.
 template <class Body>
 int with_call_ctx(int device, const char* owner, RlPlotUnit* film, const DeviceArrays& arrays, Body body) {
-    int rc = use_device(device);
+    int cus = 256;
+    int rc = enter_device(device, &cus);
     if (rc != RL_OK) return rc;
     if ((rc = device_buffers_check(device, owner, arrays)) != RL_OK) return rc;
     if (film && (rc = plot_settle(film)) != RL_OK) return rc;
-    int cus = 256;
-    if ((rc = cu_count_of(device, &cus)) != RL_OK) return rc;
     QueryCtx* q = nullptr;
     if ((rc = query_ctx_acquire(device, &q)) != RL_OK) return rc;
     const CallCtx c{q, film ? film->stream : q->stream, cus};
-    rc = body(c);
-    const hipError_t e = hipStreamSynchronize(c.stream);
+    rc = drained(c.stream, body(c));
     query_ctx_release(device, q);
-    if (rc != RL_OK) return rc;
-    RL_HIP(e);
-    return RL_OK;
+    return rc;
 }
 // A scene call: on a stream of the call's own.  A host form has no arrays to check.
 template <class Body>
@@ -1077,28 +1288,16 @@ int rl_scene_create(const RlSceneDesc* desc, int device, RlScene** out) {
     s->lay = lay;
     s->staged_bytes = blob.size() * sizeof(RlF4);
     s->tables_bytes = (size_t)(lay.off_objects - lay.off_planes) * sizeof(RlF4);
-    s->blob = nullptr;
-    s->emitters = nullptr;
-    s->emitter_flags = nullptr;
     std::vector<RlF4> emitters;
     emitter_table(desc->objects, desc->n_objects, &emitters, &s->emitter_objects);
     std::vector<uint8_t> flags(desc->n_objects, (uint8_t)0);
     for (uint32_t object : s->emitter_objects) flags[object] = 1;
-    hipError_t e = hipMalloc((void**)&s->blob, s->staged_bytes);
-    if (e == hipSuccess) e = hipMemcpy(s->blob, blob.data(), s->staged_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !emitters.empty()) e = hipMalloc((void**)&s->emitters, emitters.size() * sizeof(RlF4));
-    if (e == hipSuccess && !emitters.empty()) e = hipMemcpy(s->emitters, emitters.data(), emitters.size() * sizeof(RlF4), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !emitters.empty()) e = hipMalloc((void**)&s->emitter_flags, flags.size());
-    if (e == hipSuccess && !emitters.empty()) e = hipMemcpy(s->emitter_flags, flags.data(), flags.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (s->emitter_flags) (void)hipFree(s->emitter_flags);
-        if (s->emitters) (void)hipFree(s->emitters);
-        if (s->blob) (void)hipFree(s->blob);
-        delete s;
-        return fail(RL_E_HIP, std::string("scene upload: ") + hipGetErrorString(e));
+    s->ledger.alloc(&s->blob, s->staged_bytes, blob.data());
+    if (!emitters.empty()) {
+        s->ledger.alloc(&s->emitters, emitters.size() * sizeof(RlF4), emitters.data());
+        s->ledger.alloc(&s->emitter_flags, flags.size(), flags.data());
     }
-    *out = s;
-    return RL_OK;
+    return unit_created("scene upload", s, rl_scene_destroy, out);
 }
 
 namespace {
@@ -1110,9 +1309,7 @@ int rl_scene_destroy(RlScene* scene) {
     if (!scene) return RL_OK;
     (void)hipSetDevice(scene->device);
     (void)sessions_quiesce(scene->device); // an open launch may still be reading the blob
-    (void)hipFree(scene->blob);
-    if (scene->emitters) (void)hipFree(scene->emitters);
-    if (scene->emitter_flags) (void)hipFree(scene->emitter_flags);
+    scene->ledger.release();
     delete scene;
     return RL_OK;
 }
@@ -1343,67 +1540,30 @@ int rl_scene_light_paths(const RlScene* scene, int primitive_fetch, uint64_t see
 
 int rl_trace_unit_create(int device, uint32_t id, uint32_t width, uint32_t height, uint32_t n_photons,
                          RlTraceUnit** out) {
-    if (!out) return fail(RL_E_INVALID, "null output handle");
-    *out = nullptr;
-    if (width == 0 || height == 0 || n_photons == 0) return fail(RL_E_INVALID, "zero-sized trace unit");
-    int rc = check_image_size("trace unit", width, height);
+    RlTraceUnit* u = nullptr; // (value-initialised: no launch yet, nothing tuned, no time)
+    int rc = unit_new("trace unit", device, width, height, n_photons, out, &u);
     if (rc != RL_OK) return rc;
-    rc = use_device(device);
-    if (rc != RL_OK) return rc;
-    RlTraceUnit* u = new (std::nothrow) RlTraceUnit();
-    if (!u) return fail(RL_E_INVALID, "out of host memory");
-    u->device = device;
     u->id = id;
-    u->width = width;
-    u->height = height;
     u->n_photons = n_photons;
-    u->photons = nullptr;
-    u->queue = nullptr;
-    u->stream = nullptr;
-    u->rendered = nullptr;
     u->fetch = RL_FETCH_LDS;
-    u->kernel_ms = 0.0;
-    u->launches = 0;
-    u->tuned_dyn = 0;
-    u->tuned_kernel = nullptr;
-    u->tuned_per_cu = 0;
     u->cu_count = 256;
-    hipError_t e = hipMalloc((void**)&u->photons, (size_t)n_photons * sizeof(RlMappedPhoton));
-    if (e == hipSuccess) e = hipMemset(u->photons, 0, (size_t)n_photons * sizeof(RlMappedPhoton)); // MappedPhoton::new
-    if (e == hipSuccess) e = hipMalloc((void**)&u->queue, 3 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(u->queue, 0, 3 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = create_unit_stream(&u->stream);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&u->rendered, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr); // the memsets above ran on the null stream
-    if (e != hipSuccess) {
-        rl_trace_unit_destroy(u);
-        return fail(RL_E_HIP, std::string("trace unit allocation: ") + hipGetErrorString(e));
-    }
+    u->ledger.alloc_zeroed(&u->photons, (size_t)n_photons * sizeof(RlMappedPhoton)); // MappedPhoton::new
+    u->ledger.alloc_zeroed(&u->queue, 3 * sizeof(unsigned long long));
+    u->ledger.stream(&u->stream);
+    u->ledger.event(&u->rendered);
+    if ((rc = unit_created("trace unit allocation", u, rl_trace_unit_destroy, out)) != RL_OK) return rc;
     if ((rc = cu_count_of(device, &u->cu_count)) != RL_OK) {
+        *out = nullptr;
         rl_trace_unit_destroy(u);
-        return rc;
     }
-    *out = u;
-    return RL_OK;
+    return rc;
 }
 
 int rl_trace_unit_destroy(RlTraceUnit* u) {
     if (!u) return RL_OK;
     (void)hipSetDevice(u->device);
     (void)render_end(u); // a render that was begun writes to this unit's photons until it is complete
-    if (u->stream) (void)hipStreamSynchronize(u->stream);
-    for (EventPair& ep : u->pending) {
-        (void)hipEventDestroy(ep.start);
-        (void)hipEventDestroy(ep.stop);
-    }
-    for (EventPair& ep : u->pool) {
-        (void)hipEventDestroy(ep.start);
-        (void)hipEventDestroy(ep.stop);
-    }
-    if (u->stream) (void)hipStreamDestroy(u->stream);
-    if (u->rendered) (void)hipEventDestroy(u->rendered);
-    if (u->photons) (void)hipFree(u->photons);
-    if (u->queue) (void)hipFree(u->queue);
+    u->ledger.release();
     delete u;
     return RL_OK;
 }
@@ -1836,9 +1996,7 @@ int rl_trace_unit_render_end(RlTraceUnit* u) {
 namespace {
 int check_fused(const RlTraceUnit* u, const RlScene* scene, const RlPlotUnit* plot) {
     if (!u || !scene || !plot) return fail(RL_E_INVALID, "null handle");
-    if (plot->device != u->device || plot->width != u->width || plot->height != u->height)
-        return fail(RL_E_STATE, "plot unit does not match the trace unit (device or size)");
-    return RL_OK;
+    return match_check(plot, u);
 }
 } // namespace
 
@@ -1857,10 +2015,8 @@ int rl_trace_unit_render_fused_begin(RlTraceUnit* u, const RlScene* scene, RlPlo
 
 int rl_trace_unit_render_fused(RlTraceUnit* u, const RlScene* scene, RlPlotUnit* plot, uint64_t seed, uint32_t stream,
                                uint64_t first_path_index, uint64_t n_paths) {
-    if (!u || !scene || !plot) return fail(RL_E_INVALID, "null handle");
-    if (plot->device != u->device || plot->width != u->width || plot->height != u->height)
-        return fail(RL_E_STATE, "plot unit does not match the trace unit (device or size)");
-    int rc = use_device(u->device);
+    int rc = check_fused(u, scene, plot);
+    if (rc == RL_OK) rc = use_device(u->device);
     if (rc != RL_OK) return rc;
     return launch_trace(u, scene, nullptr, plot, seed, stream, first_path_index, n_paths);
 }
@@ -1878,9 +2034,7 @@ int rl_trace_unit_photons(RlTraceUnit* u, RlMappedPhoton* out) {
     int rc = use_device(u->device);
     if (rc != RL_OK) return rc;
     if ((rc = render_end(u)) != RL_OK) return rc; // a render that was begun: its photons are complete after this
-    RL_HIP(hipStreamSynchronize(u->stream));
-    RL_HIP(hipMemcpy(out, u->photons, (size_t)u->n_photons * sizeof(RlMappedPhoton), hipMemcpyDeviceToHost));
-    return RL_OK;
+    return download(u->stream, {{u->photons, out, (size_t)u->n_photons * sizeof(RlMappedPhoton)}});
 }
 
 int rl_trace_unit_stats(RlTraceUnit* u, uint64_t* paths, uint64_t* segments, double* kernel_ms) {
@@ -1903,73 +2057,36 @@ int rl_trace_unit_stats(RlTraceUnit* u, uint64_t* paths, uint64_t* segments, dou
 // ---- PlotUnit -----------------------------------------------------------------------------------
 
 int rl_plot_unit_create(int device, uint32_t id, uint32_t width, uint32_t height, float* external_xyz, RlPlotUnit** out) {
-    if (!out) return fail(RL_E_INVALID, "null output handle");
-    *out = nullptr;
-    if (width == 0 || height == 0) return fail(RL_E_INVALID, "zero-sized plot unit");
-    int rc = check_image_size("plot unit", width, height);
+    RlPlotUnit* u = nullptr;
+    const int rc = unit_new("plot unit", device, width, height, 1u, out, &u);
     if (rc != RL_OK) return rc;
-    rc = use_device(device);
-    if (rc != RL_OK) return rc;
-    RlPlotUnit* u = new (std::nothrow) RlPlotUnit();
-    if (!u) return fail(RL_E_INVALID, "out of host memory");
-    u->device = device;
     u->id = id;
-    u->width = width;
-    u->height = height;
-    u->xyz = external_xyz;
-    u->owns = external_xyz == nullptr;
-    u->cie = nullptr;
-    u->stream = nullptr;
-    u->plotted = u->ready = u->cleared = u->tail = nullptr;
-    const size_t bytes = (size_t)width * height * 3 * sizeof(float);
-    hipError_t e = hipSuccess;
-    if (u->owns) {
-        e = hipMalloc((void**)&u->xyz, bytes);
-        if (e == hipSuccess) e = hipMemset(u->xyz, 0, bytes);
-    }
-    if (e == hipSuccess) e = hipMalloc((void**)&u->cie, sizeof RL_CIE1931_XYZ0);
-    if (e == hipSuccess) e = hipMemcpy(u->cie, RL_CIE1931_XYZ0, sizeof RL_CIE1931_XYZ0, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = create_unit_stream(&u->stream);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&u->plotted, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&u->ready, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&u->cleared, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&u->tail, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr); // the synchronous memsets / copies above ran on the null stream
-    if (e != hipSuccess) {
-        rl_plot_unit_destroy(u);
-        return fail(RL_E_HIP, std::string("plot unit allocation: ") + hipGetErrorString(e));
-    }
-    *out = u;
-    return RL_OK;
+    u->xyz = external_xyz; // (the caller's: not entered in the ledger)
+    if (!external_xyz) u->ledger.alloc_zeroed(&u->xyz, (size_t)width * height * 3 * sizeof(float));
+    u->ledger.alloc(&u->cie, sizeof RL_CIE1931_XYZ0, RL_CIE1931_XYZ0);
+    u->ledger.stream(&u->stream);
+    u->ledger.event(&u->plotted);
+    u->ledger.event(&u->ready);
+    u->ledger.event(&u->cleared);
+    u->ledger.event(&u->tail);
+    return unit_created("plot unit allocation", u, rl_plot_unit_destroy, out);
 }
 
 int rl_plot_unit_destroy(RlPlotUnit* u) {
     if (!u) return RL_OK;
     (void)hipSetDevice(u->device);
     (void)plot_settle(u); // a fused render that was begun splats into this buffer until it is complete
-    if (u->stream) {
-        (void)hipStreamSynchronize(u->stream);
-        (void)hipStreamDestroy(u->stream);
-    }
-    if (u->plotted) (void)hipEventDestroy(u->plotted);
-    if (u->ready) (void)hipEventDestroy(u->ready);
-    if (u->cleared) (void)hipEventDestroy(u->cleared);
-    if (u->tail) (void)hipEventDestroy(u->tail);
-    for (EventPair& ep : u->exchanges) (void)hipEventDestroy(ep.start), (void)hipEventDestroy(ep.stop);
-    for (EventPair& ep : u->exchange_pool) (void)hipEventDestroy(ep.start), (void)hipEventDestroy(ep.stop);
-    if (u->owns && u->xyz) (void)hipFree(u->xyz);
-    if (u->cie) (void)hipFree(u->cie);
+    u->ledger.release();
     delete u;
     return RL_OK;
 }
 
 int rl_plot_unit_plot(RlPlotUnit* u, RlTraceUnit* const* trace_units, uint32_t n_trace_units) {
     if (!u || (!trace_units && n_trace_units)) return fail(RL_E_INVALID, "null argument");
-    int rc = use_device(u->device);
+    int cus = 256;
+    int rc = enter_device(u->device, &cus);
     if (rc != RL_OK) return rc;
     if ((rc = plot_settle(u)) != RL_OK) return rc; // a fused render begun into this buffer ends first
-    int cus = 256;
-    if ((rc = cu_count_of(u->device, &cus)) != RL_OK) return rc;
     const float aspect = (float)u->width / (float)u->height; // plot_unit.rs:48
     for (uint32_t k = 0; k < n_trace_units; ++k) {           // app.rs:138-140
         RlTraceUnit* t = trace_units[k];
@@ -2021,10 +2138,7 @@ int rl_plot_unit_upload(RlPlotUnit* u, const RlVector3* in) {
     int rc = use_device(u->device);
     if (rc != RL_OK) return rc;
     if ((rc = plot_settle(u)) != RL_OK) return rc; // a fused render begun into this buffer ends first
-    RL_HIP(hipStreamSynchronize(u->stream));
-    RL_HIP(hipMemcpy(u->xyz, in, (size_t)u->width * u->height * sizeof(RlVector3), hipMemcpyHostToDevice));
-    RL_HIP(hipStreamSynchronize(nullptr)); // (the null stream only: a resident open trace kernel of another unit is not waited for)
-    return RL_OK;
+    return upload(u->stream, {{u->xyz, in, (size_t)u->width * u->height * sizeof(RlVector3)}});
 }
 
 int rl_plot_unit_download(RlPlotUnit* u, RlVector3* out) {
@@ -2032,9 +2146,7 @@ int rl_plot_unit_download(RlPlotUnit* u, RlVector3* out) {
     int rc = use_device(u->device);
     if (rc != RL_OK) return rc;
     if ((rc = plot_settle(u)) != RL_OK) return rc; // a fused render begun into this buffer ends first
-    RL_HIP(hipStreamSynchronize(u->stream));
-    RL_HIP(hipMemcpy(out, u->xyz, (size_t)u->width * u->height * sizeof(RlVector3), hipMemcpyDeviceToHost));
-    return RL_OK;
+    return download(u->stream, {{u->xyz, out, (size_t)u->width * u->height * sizeof(RlVector3)}});
 }
 
 // ---- film for caller-supplied photons and samples (rl_plot_unit_plot_photons*, rl_plot_unit_render_samples*, rl_film.hip.h) ----
@@ -2359,13 +2471,12 @@ namespace {
 #define RL_FEATURE_LAUNCH (1ull << 30)
 int launch_features(const CallCtx& c, const RlScene* scene, int fetch, const PathJob& job, uint32_t width, uint32_t height, uint64_t first_path,
                     uint64_t n_paths, RlPlotUnit* const units[3], RlFeatureSample* records, unsigned long long* counters) {
-    const int rc = query_ctx_queue(c.q);
+    int rc = query_ctx_queue(c.q);
     if (rc != RL_OK) return rc;
     for (int k = 0; k < 3; ++k) {
         RlPlotUnit* o = units[k];
         if (!o || o->stream == c.stream) continue;
-        RL_HIP(hipEventRecord(o->ready, o->stream));
-        RL_HIP(hipStreamWaitEvent(c.stream, o->ready, 0));
+        if ((rc = hand_over(o->ready, o->stream, c.stream)) != RL_OK) return rc; // the launches write behind what is queued into o
     }
     RlFeatureQueue* fq = (RlFeatureQueue*)c.q->queue;
     RL_HIP(hipMemsetAsync(fq->stats, 0, sizeof fq->stats, c.stream));
@@ -2398,8 +2509,7 @@ int launch_features(const CallCtx& c, const RlScene* scene, int fetch, const Pat
     for (int k = 0; k < 3; ++k) {
         RlPlotUnit* o = units[k];
         if (!o || o->stream == c.stream) continue;
-        RL_HIP(hipEventRecord(o->tail, c.stream));
-        RL_HIP(hipStreamWaitEvent(o->stream, o->tail, 0));
+        if ((rc = hand_over(o->tail, c.stream, o->stream)) != RL_OK) return rc; // o's tail covers what was written into it here
     }
     return RL_OK;
 }
@@ -2451,66 +2561,37 @@ int rl_scene_render_features(const RlScene* scene, int primitive_fetch, uint32_t
 // ---- GatherUnit ---------------------------------------------------------------------------------
 
 int rl_gather_unit_create(int device, uint32_t width, uint32_t height, RlGatherUnit** out) {
-    if (!out) return fail(RL_E_INVALID, "null output handle");
-    *out = nullptr;
-    if (width == 0 || height == 0) return fail(RL_E_INVALID, "zero-sized gather unit");
-    int rc = check_image_size("gather unit", width, height);
+    RlGatherUnit* u = nullptr;
+    const int rc = unit_new("gather unit", device, width, height, 1u, out, &u);
     if (rc != RL_OK) return rc;
-    rc = use_device(device);
-    if (rc != RL_OK) return rc;
-    RlGatherUnit* u = new (std::nothrow) RlGatherUnit();
-    if (!u) return fail(RL_E_INVALID, "out of host memory");
-    u->device = device;
-    u->width = width;
-    u->height = height;
-    u->acc = u->comp = nullptr;
-    u->stream = nullptr;
     const size_t bytes = (size_t)width * height * 3 * sizeof(float);
-    hipError_t e = hipMalloc((void**)&u->acc, bytes);
-    if (e == hipSuccess) e = hipMemset(u->acc, 0, bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&u->comp, bytes);
-    if (e == hipSuccess) e = hipMemset(u->comp, 0, bytes);
-    if (e == hipSuccess) e = create_unit_stream(&u->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr); // (the null stream only: a resident open trace kernel of another unit is not waited for)
-    if (e != hipSuccess) {
-        rl_gather_unit_destroy(u);
-        return fail(RL_E_HIP, std::string("gather unit allocation: ") + hipGetErrorString(e));
-    }
-    *out = u;
-    return RL_OK;
+    u->ledger.alloc_zeroed(&u->acc, bytes);
+    u->ledger.alloc_zeroed(&u->comp, bytes);
+    u->ledger.stream(&u->stream);
+    return unit_created("gather unit allocation", u, rl_gather_unit_destroy, out);
 }
 
 int rl_gather_unit_destroy(RlGatherUnit* u) {
     if (!u) return RL_OK;
     (void)hipSetDevice(u->device);
-    if (u->stream) {
-        (void)hipStreamSynchronize(u->stream);
-        (void)hipStreamDestroy(u->stream);
-    }
-    if (u->acc) (void)hipFree(u->acc);
-    if (u->comp) (void)hipFree(u->comp);
+    u->ledger.release();
     delete u;
     return RL_OK;
 }
 
 int rl_gather_unit_accumulate(RlGatherUnit* u, RlPlotUnit* plot) {
     if (!u || !plot) return fail(RL_E_INVALID, "null handle");
-    if (plot->device != u->device || plot->width != u->width || plot->height != u->height)
-        return fail(RL_E_STATE, "plot unit does not match the gather unit (device or size)");
-    int rc = use_device(u->device);
+    int cus = 256;
+    int rc = match_check(plot, u);
+    if (rc == RL_OK) rc = enter_device(u->device, &cus);
     if (rc != RL_OK) return rc;
     if ((rc = plot_settle(plot)) != RL_OK) return rc; // a fused render begun into this buffer ends first
-    int cus = 256;
-    if ((rc = cu_count_of(u->device, &cus)) != RL_OK) return rc;
     const uint64_t n_floats = (uint64_t)u->width * u->height * 3;
-    RL_HIP(hipEventRecord(plot->ready, plot->stream));        // everything plotted / splatted / reduced into the buffer so far
-    RL_HIP(hipStreamWaitEvent(u->stream, plot->ready, 0));
+    if ((rc = hand_over(plot->ready, plot->stream, u->stream)) != RL_OK) return rc; // everything plotted / splatted / reduced into the buffer so far
     hipLaunchKernelGGL(rl_gather_kernel, dim3(grid_for(n_floats / 4 + 1, cus)), dim3(RL_BLOCK), 0, u->stream, u->acc, u->comp,
                        plot->xyz, n_floats);
     RL_HIP(hipGetLastError());
-    RL_HIP(hipEventRecord(plot->cleared, u->stream));         // the kernel also cleared the plot buffer (app.rs:147)
-    RL_HIP(hipStreamWaitEvent(plot->stream, plot->cleared, 0));
-    return RL_OK;
+    return hand_over(plot->cleared, u->stream, plot->stream); // the kernel also cleared the plot buffer (app.rs:147)
 }
 
 int rl_gather_unit_sync(RlGatherUnit* u) {
@@ -2526,10 +2607,7 @@ int rl_gather_unit_download(RlGatherUnit* u, RlVector3* tristimulus, RlVector3* 
     int rc = use_device(u->device);
     if (rc != RL_OK) return rc;
     const size_t bytes = (size_t)u->width * u->height * sizeof(RlVector3);
-    RL_HIP(hipStreamSynchronize(u->stream));
-    if (tristimulus) RL_HIP(hipMemcpy(tristimulus, u->acc, bytes, hipMemcpyDeviceToHost));
-    if (compensation) RL_HIP(hipMemcpy(compensation, u->comp, bytes, hipMemcpyDeviceToHost));
-    return RL_OK;
+    return download(u->stream, {{u->acc, tristimulus, bytes}, {u->comp, compensation, bytes}});
 }
 
 int rl_gather_unit_save(RlGatherUnit* u, const char* path) {
@@ -2562,65 +2640,36 @@ int rl_gather_unit_load(RlGatherUnit* u, const char* path) {
     }
     (void)std::fread(host.data(), 1, 2 * n * sizeof(RlVector3), f);
     std::fclose(f);
-    RL_HIP(hipMemcpy(u->acc, host.data(), n * sizeof(RlVector3), hipMemcpyHostToDevice)); // the download above drained u->stream
-    RL_HIP(hipMemcpy(u->comp, host.data() + n, n * sizeof(RlVector3), hipMemcpyHostToDevice));
-    RL_HIP(hipStreamSynchronize(nullptr)); // (the null stream only: a resident open trace kernel of another unit is not waited for)
-    return RL_OK;
+    return upload(u->stream, {{u->acc, host.data(), n * sizeof(RlVector3)}, {u->comp, host.data() + n, n * sizeof(RlVector3)}});
 }
 
 // ---- TonemapUnit --------------------------------------------------------------------------------
 
 int rl_tonemap_unit_create(int device, uint32_t width, uint32_t height, RlTonemapUnit** out) {
-    if (!out) return fail(RL_E_INVALID, "null output handle");
-    *out = nullptr;
-    if (width == 0 || height == 0) return fail(RL_E_INVALID, "zero-sized tonemap unit");
-    int rc = check_image_size("tonemap unit", width, height);
+    RlTonemapUnit* u = nullptr; // (no stream of its own: last_stream is a gather unit's)
+    const int rc = unit_new("tonemap unit", device, width, height, 1u, out, &u);
     if (rc != RL_OK) return rc;
-    rc = use_device(device);
-    if (rc != RL_OK) return rc;
-    RlTonemapUnit* u = new (std::nothrow) RlTonemapUnit();
-    if (!u) return fail(RL_E_INVALID, "out of host memory");
-    u->device = device;
-    u->width = width;
-    u->height = height;
-    u->rgb = nullptr;
-    u->srgb = nullptr;
-    u->max_intensity = nullptr;
-    u->last_stream = nullptr;
     const size_t n = (size_t)width * height * 3;
-    hipError_t e = hipMalloc((void**)&u->rgb, n);
-    if (e == hipSuccess) e = hipMemset(u->rgb, 0, n);
-    if (e == hipSuccess) e = hipMalloc((void**)&u->srgb, n * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(u->srgb, 0, n * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&u->max_intensity, sizeof(float));
-    if (e == hipSuccess) e = hipMemset(u->max_intensity, 0, sizeof(float));
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr); // (the null stream only: a resident open trace kernel of another unit is not waited for)
-    if (e != hipSuccess) {
-        rl_tonemap_unit_destroy(u);
-        return fail(RL_E_HIP, std::string("tonemap unit allocation: ") + hipGetErrorString(e));
-    }
-    *out = u;
-    return RL_OK;
+    u->ledger.alloc_zeroed(&u->rgb, n);
+    u->ledger.alloc_zeroed(&u->srgb, n * sizeof(float));
+    u->ledger.alloc_zeroed(&u->max_intensity, sizeof(float));
+    return unit_created("tonemap unit allocation", u, rl_tonemap_unit_destroy, out);
 }
 
 int rl_tonemap_unit_destroy(RlTonemapUnit* u) {
     if (!u) return RL_OK;
     (void)hipSetDevice(u->device);
-    if (u->rgb) (void)hipFree(u->rgb);
-    if (u->srgb) (void)hipFree(u->srgb);
-    if (u->max_intensity) (void)hipFree(u->max_intensity);
+    u->ledger.release();
     delete u;
     return RL_OK;
 }
 
 int rl_tonemap_unit_tonemap(RlTonemapUnit* u, RlGatherUnit* gather) {
     if (!u || !gather) return fail(RL_E_INVALID, "null handle");
-    if (gather->device != u->device || gather->width != u->width || gather->height != u->height)
-        return fail(RL_E_STATE, "gather unit does not match the tonemap unit (device or size)");
-    int rc = use_device(u->device);
-    if (rc != RL_OK) return rc;
     int cus = 256;
-    if ((rc = cu_count_of(u->device, &cus)) != RL_OK) return rc;
+    int rc = match_check(gather, u);
+    if (rc == RL_OK) rc = enter_device(u->device, &cus);
+    if (rc != RL_OK) return rc;
     const uint32_t n_pixels = u->width * u->height;
     hipLaunchKernelGGL(rl_exposure_kernel, dim3(1), dim3(RL_EXPOSURE_BLOCK), 0, gather->stream, gather->acc, n_pixels, (float)n_pixels,
                        u->max_intensity);
@@ -2636,19 +2685,14 @@ int rl_tonemap_unit_rgb(RlTonemapUnit* u, uint8_t* out) {
     if (!u || !out) return fail(RL_E_INVALID, "null argument");
     int rc = use_device(u->device);
     if (rc != RL_OK) return rc;
-    if (u->last_stream) RL_HIP(hipStreamSynchronize(u->last_stream));
-    RL_HIP(hipMemcpy(out, u->rgb, (size_t)u->width * u->height * 3, hipMemcpyDeviceToHost));
-    return RL_OK;
+    return download(u->last_stream, {{u->rgb, out, (size_t)u->width * u->height * 3}});
 }
 
 int rl_tonemap_unit_srgb_float(RlTonemapUnit* u, float* out, float* max_intensity) {
     if (!u) return fail(RL_E_INVALID, "null tonemap unit");
     int rc = use_device(u->device);
     if (rc != RL_OK) return rc;
-    if (u->last_stream) RL_HIP(hipStreamSynchronize(u->last_stream));
-    if (out) RL_HIP(hipMemcpy(out, u->srgb, (size_t)u->width * u->height * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (max_intensity) RL_HIP(hipMemcpy(max_intensity, u->max_intensity, sizeof(float), hipMemcpyDeviceToHost));
-    return RL_OK;
+    return download(u->last_stream, {{u->srgb, out, (size_t)u->width * u->height * 3 * sizeof(float)}, {u->max_intensity, max_intensity, sizeof(float)}});
 }
 
 // ---- DenoiseUnit (rl_denoise.hip.h) -----------------------------------------------------------------
@@ -2669,46 +2713,23 @@ int rl_denoise_params_default(RlDenoiseParams* out) {
 }
 
 int rl_denoise_unit_create(int device, uint32_t width, uint32_t height, RlDenoiseUnit** out) {
-    if (!out) return fail(RL_E_INVALID, "null output handle");
-    *out = nullptr;
-    if (width == 0 || height == 0) return fail(RL_E_INVALID, "zero-sized denoise unit");
-    int rc = check_image_size("denoise unit", width, height);
+    RlDenoiseUnit* u = nullptr;
+    const int rc = unit_new("denoise unit", device, width, height, 1u, out, &u);
     if (rc != RL_OK) return rc;
-    rc = use_device(device);
-    if (rc != RL_OK) return rc;
-    RlDenoiseUnit* u = new (std::nothrow) RlDenoiseUnit();
-    if (!u) return fail(RL_E_INVALID, "out of host memory");
-    u->device = device;
-    u->width = width;
-    u->height = height;
     const size_t n = (size_t)width * height;
-    hipError_t e = hipMalloc((void**)&u->guides, n * RL_DENOISE_GUIDE_WORDS * sizeof(RlF4));
-    for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipMalloc((void**)&u->pingpong[k], n * 3 * sizeof(float));
-    for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&u->ready[k], hipEventDisableTiming);
-    for (int k = 0; k <= RL_DENOISE_MAX_ITERATIONS && e == hipSuccess; ++k) {
-        e = hipEventCreate(&u->timed[k].start);
-        if (e == hipSuccess) e = hipEventCreate(&u->timed[k].stop);
-    }
-    if (e != hipSuccess) {
-        rl_denoise_unit_destroy(u);
-        return fail(RL_E_HIP, std::string("denoise unit allocation: ") + hipGetErrorString(e));
-    }
-    *out = u;
-    return RL_OK;
+    u->ledger.alloc(&u->guides, n * RL_DENOISE_GUIDE_WORDS * sizeof(RlF4));
+    for (float*& b : u->pingpong) u->ledger.alloc(&b, n * 3 * sizeof(float));
+    for (hipEvent_t& ev : u->ready) u->ledger.event(&ev);
+    for (EventPair& ep : u->timed) u->ledger.pair(&ep);
+    return unit_created("denoise unit allocation", u, rl_denoise_unit_destroy, out);
 }
 
+// The unit has no stream of its own: its work runs on dst's, and rl_denoise_unit_denoise returns with that stream drained, also
+// after a failure (drained), so nothing reads or writes the unit's buffers here.
 int rl_denoise_unit_destroy(RlDenoiseUnit* u) {
     if (!u) return RL_OK;
-    (void)hipSetDevice(u->device); // (every call returns with its work complete: nothing of the unit's is in flight)
-    if (u->guides) (void)hipFree(u->guides);
-    for (float* b : u->pingpong)
-        if (b) (void)hipFree(b);
-    for (hipEvent_t ev : u->ready)
-        if (ev) (void)hipEventDestroy(ev);
-    for (EventPair& ep : u->timed) {
-        if (ep.start) (void)hipEventDestroy(ep.start);
-        if (ep.stop) (void)hipEventDestroy(ep.stop);
-    }
+    (void)hipSetDevice(u->device);
+    u->ledger.release();
     delete u;
     return RL_OK;
 }
@@ -2732,59 +2753,55 @@ int rl_denoise_unit_denoise(RlDenoiseUnit* u, RlGatherUnit* image, RlGatherUnit*
     for (int a = 0; a < 5; ++a)
         for (int b = a + 1; b < 5; ++b)
             if (given[a] && given[a] == given[b]) return fail(RL_E_INVALID, "rl_denoise_unit_denoise: the gather units must be distinct handles");
+    int rc = RL_OK, cus = 256;
     for (RlGatherUnit* g : given)
-        if (g && (g->device != u->device || g->width != u->width || g->height != u->height))
-            return fail(RL_E_STATE, "gather unit does not match the denoise unit (device or size)");
-    int rc = use_device(u->device);
-    if (rc != RL_OK) return rc;
-    int cus = 256;
-    if ((rc = cu_count_of(u->device, &cus)) != RL_OK) return rc;
+        if (g && (rc = match_check(g, u)) != RL_OK) return rc;
+    if ((rc = enter_device(u->device, &cus)) != RL_OK) return rc;
     const uint32_t iterations = p.iterations ? p.iterations : RL_DENOISE_ITERATIONS;
     const uint32_t n_pixels = u->width * u->height;
     hipStream_t stream = dst->stream;
-    for (int k = 0; k < 4; ++k) { // everything queued on the streams of the units the call reads
-        if (!given[k]) continue;
-        RL_HIP(hipEventRecord(u->ready[k], given[k]->stream));
-        RL_HIP(hipStreamWaitEvent(stream, u->ready[k], 0));
-    }
-    u->timed_passes = 0;
-    RL_HIP(hipEventRecord(u->timed[0].start, stream));
-    hipLaunchKernelGGL(rl_denoise_guides_kernel, dim3(grid_for(n_pixels, cus)), dim3(RL_BLOCK), 0, stream, albedo ? albedo->acc : nullptr,
-                       normal ? normal->acc : nullptr, aux ? aux->acc : nullptr, n_pixels, u->guides);
-    RL_HIP(hipGetLastError());
-    RL_HIP(hipEventRecord(u->timed[0].stop, stream));
-    g_denoise_launches[0].fetch_add(1, std::memory_order_relaxed);
-    // k(sigma), f32 on the host
-    float k[4];
-    for (int t = 0; t < 4; ++t) k[t] = sigmas[t] == 0.0f ? 0.0f : 1.0f / (sigmas[t] * sigmas[t]);
-    const float* in = image->acc;
-    for (uint32_t i = 0; i < iterations; ++i) {
-        float* out = i + 1 == iterations ? dst->acc : u->pingpong[i & 1u];
-        RlDenoisePass job;
-        job.width = u->width;
-        job.height = u->height;
-        job.step = 1u << i;
-        job.classes_x = std::min(job.step, u->width);
-        job.classes_y = std::min(job.step, u->height);
-        job.tiles_x = ((u->width + job.step - 1) / job.step + RL_DENOISE_TILE - 1) / RL_DENOISE_TILE;
-        job.tiles_y = ((u->height + job.step - 1) / job.step + RL_DENOISE_TILE - 1) / RL_DENOISE_TILE;
-        job.kc = k[0] * (float)(1u << 2 * i); // the colour sigma halves per pass; exact
-        job.kn = k[1];
-        job.kz = k[2];
-        job.ka = k[3];
-        RL_HIP(hipEventRecord(u->timed[1 + i].start, stream));
-        // (at most 2^31 / 17 * 32 / 256 workgroups for any image the units accept: one grid dimension holds them)
-        const uint64_t groups = (uint64_t)job.tiles_x * job.classes_x * job.tiles_y * job.classes_y;
-        hipLaunchKernelGGL(rl_denoise_pass_kernel, dim3((uint32_t)groups), dim3(RL_DENOISE_TILE * RL_DENOISE_TILE), 0, stream, in, u->guides, job, out);
-        RL_HIP(hipGetLastError());
-        RL_HIP(hipEventRecord(u->timed[1 + i].stop, stream));
-        g_denoise_launches[1].fetch_add(1, std::memory_order_relaxed);
-        in = out;
-    }
-    RL_HIP(hipMemsetAsync(dst->comp, 0, (size_t)n_pixels * 3 * sizeof(float), stream));
-    RL_HIP(hipStreamSynchronize(stream));
-    u->timed_passes = iterations;
-    return RL_OK;
+    u->timed_passes = 0; // the pairs are re-recorded from here on: readable again once the call has completed
+    rc = drained(stream, [&]() -> int {
+        for (int k = 0; k < 4; ++k) { // everything queued on the streams of the units the call reads
+            const int r = given[k] ? hand_over(u->ready[k], given[k]->stream, stream) : RL_OK;
+            if (r != RL_OK) return r;
+        }
+        int r = timed_launch(u->timed[0], stream, &g_denoise_launches[0], [&] {
+            hipLaunchKernelGGL(rl_denoise_guides_kernel, dim3(grid_for(n_pixels, cus)), dim3(RL_BLOCK), 0, stream, albedo ? albedo->acc : nullptr,
+                               normal ? normal->acc : nullptr, aux ? aux->acc : nullptr, n_pixels, u->guides);
+        });
+        if (r != RL_OK) return r;
+        // k(sigma), f32 on the host
+        float k[4];
+        for (int t = 0; t < 4; ++t) k[t] = sigmas[t] == 0.0f ? 0.0f : 1.0f / (sigmas[t] * sigmas[t]);
+        const float* in = image->acc;
+        for (uint32_t i = 0; i < iterations; ++i) {
+            float* out = i + 1 == iterations ? dst->acc : u->pingpong[i & 1u];
+            RlDenoisePass job;
+            job.width = u->width;
+            job.height = u->height;
+            job.step = 1u << i;
+            job.classes_x = std::min(job.step, u->width);
+            job.classes_y = std::min(job.step, u->height);
+            job.tiles_x = ((u->width + job.step - 1) / job.step + RL_DENOISE_TILE - 1) / RL_DENOISE_TILE;
+            job.tiles_y = ((u->height + job.step - 1) / job.step + RL_DENOISE_TILE - 1) / RL_DENOISE_TILE;
+            job.kc = k[0] * (float)(1u << 2 * i); // the colour sigma halves per pass; exact
+            job.kn = k[1];
+            job.kz = k[2];
+            job.ka = k[3];
+            // (at most 2^31 / 17 * 32 / 256 workgroups for any image the units accept: one grid dimension holds them)
+            const uint64_t groups = (uint64_t)job.tiles_x * job.classes_x * job.tiles_y * job.classes_y;
+            r = timed_launch(u->timed[1 + i], stream, &g_denoise_launches[1], [&] {
+                hipLaunchKernelGGL(rl_denoise_pass_kernel, dim3((uint32_t)groups), dim3(RL_DENOISE_TILE * RL_DENOISE_TILE), 0, stream, in, u->guides, job, out);
+            });
+            if (r != RL_OK) return r;
+            in = out;
+        }
+        RL_HIP(hipMemsetAsync(dst->comp, 0, (size_t)n_pixels * 3 * sizeof(float), stream));
+        return RL_OK;
+    }());
+    if (rc == RL_OK) u->timed_passes = iterations;
+    return rc;
 }
 
 // ---- SpectralUnit (rl_spectral.hip.h) ---------------------------------------------------------------
@@ -2802,24 +2819,18 @@ float spectral_spacing(uint32_t n_nodes) { return 400.0f / (float)(n_nodes - 1u)
 // The splat kernel for device array photons [0, n) (n > 0) on `stream`.
 int launch_spectral_photons(RlSpectralUnit* u, hipStream_t stream, int cus, const RlMappedPhoton* photons, uint64_t n) {
     const float aspect = (float)u->width / (float)u->height; // plot_unit.rs:48
-    u->timed_done[0] = false;
-    RL_HIP(hipEventRecord(u->timed[0].start, stream));
-    hipLaunchKernelGGL(rl_spectral_photons_kernel, dim3(grid_for(n, cus)), dim3(RL_BLOCK), 0, stream, photons, n, u->width, u->height, u->n_nodes,
-                       u->spacing, aspect, u->film);
-    RL_HIP(hipGetLastError());
-    RL_HIP(hipEventRecord(u->timed[0].stop, stream));
-    g_spectral_launches[0].fetch_add(1, std::memory_order_relaxed);
-    return RL_OK;
+    u->timed_done[0] = false; // readable again once the call has completed (spectral_drained)
+    return timed_launch(u->timed[0], stream, &g_spectral_launches[0], [&] {
+        hipLaunchKernelGGL(rl_spectral_photons_kernel, dim3(grid_for(n, cus)), dim3(RL_BLOCK), 0, stream, photons, n, u->width, u->height, u->n_nodes,
+                           u->spacing, aspect, u->film);
+    });
 }
 
 // A splat call borrows a query context (with_call_ctx: its staging buffers; its own stream stays idle) and queues everything on the
 // spectral unit's stream, which has drained when the call returns, also after a failure: rc is what the call's body returned.
 int spectral_drained(RlSpectralUnit* u, int rc) {
-    const hipError_t e = hipStreamSynchronize(u->stream);
-    if (rc != RL_OK) return rc;
-    RL_HIP(e);
-    u->timed_done[0] = true;
-    return RL_OK;
+    if ((rc = drained(u->stream, rc)) == RL_OK) u->timed_done[0] = true;
+    return rc;
 }
 } // namespace
 
@@ -2842,39 +2853,18 @@ int rl_spectral_unit_create(int device, uint32_t width, uint32_t height, uint32_
     u->height = height;
     u->n_nodes = n_nodes;
     u->spacing = spectral_spacing(n_nodes);
-    const size_t bytes = (size_t)n_pixels * n_nodes * sizeof(float);
-    hipError_t e = hipMalloc((void**)&u->film, bytes);
-    if (e == hipSuccess) e = hipMemset(u->film, 0, bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&u->matrix, (size_t)RL_SPECTRAL_MAX_NODES * 3 * sizeof(float));
-    if (e == hipSuccess) e = create_unit_stream(&u->stream);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&u->ready, hipEventDisableTiming);
-    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-        e = hipEventCreate(&u->timed[k].start);
-        if (e == hipSuccess) e = hipEventCreate(&u->timed[k].stop);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr); // the synchronous memset above ran on the null stream
-    if (e != hipSuccess) {
-        rl_spectral_unit_destroy(u);
-        return fail(RL_E_HIP, std::string("spectral unit allocation: ") + hipGetErrorString(e));
-    }
-    *out = u;
-    return RL_OK;
+    u->ledger.alloc_zeroed(&u->film, (size_t)n_pixels * n_nodes * sizeof(float));
+    u->ledger.alloc(&u->matrix, (size_t)RL_SPECTRAL_MAX_NODES * 3 * sizeof(float));
+    u->ledger.stream(&u->stream);
+    u->ledger.event(&u->ready);
+    for (EventPair& ep : u->timed) u->ledger.pair(&ep);
+    return unit_created("spectral unit allocation", u, rl_spectral_unit_destroy, out);
 }
 
 int rl_spectral_unit_destroy(RlSpectralUnit* u) {
     if (!u) return RL_OK;
     (void)hipSetDevice(u->device);
-    if (u->stream) {
-        (void)hipStreamSynchronize(u->stream);
-        (void)hipStreamDestroy(u->stream);
-    }
-    if (u->ready) (void)hipEventDestroy(u->ready);
-    for (EventPair& ep : u->timed) {
-        if (ep.start) (void)hipEventDestroy(ep.start);
-        if (ep.stop) (void)hipEventDestroy(ep.stop);
-    }
-    if (u->film) (void)hipFree(u->film);
-    if (u->matrix) (void)hipFree(u->matrix);
+    u->ledger.release();
     delete u;
     return RL_OK;
 }
@@ -2889,22 +2879,21 @@ int rl_spectral_unit_clear(RlSpectralUnit* u) {
 
 int rl_spectral_unit_plot(RlSpectralUnit* u, RlTraceUnit* const* trace_units, uint32_t n_trace_units) {
     if (!u || (!trace_units && n_trace_units)) return fail(RL_E_INVALID, "null argument");
-    int rc = use_device(u->device);
-    if (rc != RL_OK) return rc;
     int cus = 256;
-    if ((rc = cu_count_of(u->device, &cus)) != RL_OK) return rc;
-    for (uint32_t k = 0; k < n_trace_units && rc == RL_OK; ++k) {
-        RlTraceUnit* t = trace_units[k];
-        if (!t || t->device != u->device) {
-            rc = fail(RL_E_STATE, "trace unit missing or on another device");
-            break;
-        }
-        if ((rc = render_end(t)) != RL_OK) break;              // a render that was begun: its photons are complete after this
-        RL_HIP(hipStreamWaitEvent(u->stream, t->rendered, 0)); // mapped_photons complete (a no-op after a synchronous render)
-        rc = launch_spectral_photons(u, u->stream, cus, t->photons, t->n_photons);
-    }
+    const int rc = enter_device(u->device, &cus);
+    if (rc != RL_OK || n_trace_units == 0) return rc;
     // The splats are in the film on return, so the trace units' next renders need no event of this unit's to wait for.
-    return n_trace_units != 0 ? spectral_drained(u, rc) : rc;
+    return spectral_drained(u, [&]() -> int {
+        for (uint32_t k = 0; k < n_trace_units; ++k) {
+            RlTraceUnit* t = trace_units[k];
+            if (!t || t->device != u->device) return fail(RL_E_STATE, "trace unit missing or on another device");
+            int r = render_end(t); // a render that was begun: its photons are complete after this
+            if (r != RL_OK) return r;
+            RL_HIP(hipStreamWaitEvent(u->stream, t->rendered, 0)); // mapped_photons complete (a no-op after a synchronous render)
+            if ((r = launch_spectral_photons(u, u->stream, cus, t->photons, t->n_photons)) != RL_OK) return r;
+        }
+        return RL_OK;
+    }());
 }
 
 int rl_spectral_unit_plot_photons(RlSpectralUnit* u, const RlMappedPhoton* photons, uint64_t n) {
@@ -2931,45 +2920,40 @@ int rl_spectral_unit_download(RlSpectralUnit* u, float* out) {
     if (!u || !out) return fail(RL_E_INVALID, "null argument");
     int rc = use_device(u->device);
     if (rc != RL_OK) return rc;
-    RL_HIP(hipStreamSynchronize(u->stream));
-    RL_HIP(hipMemcpy(out, u->film, (size_t)u->width * u->height * u->n_nodes * sizeof(float), hipMemcpyDeviceToHost));
-    return RL_OK;
+    return download(u->stream, {{u->film, out, (size_t)u->width * u->height * u->n_nodes * sizeof(float)}});
 }
 
 int rl_spectral_unit_upload(RlSpectralUnit* u, const float* in) {
     if (!u || !in) return fail(RL_E_INVALID, "null argument");
     int rc = use_device(u->device);
     if (rc != RL_OK) return rc;
-    RL_HIP(hipStreamSynchronize(u->stream));
-    RL_HIP(hipMemcpy(u->film, in, (size_t)u->width * u->height * u->n_nodes * sizeof(float), hipMemcpyHostToDevice));
-    RL_HIP(hipStreamSynchronize(nullptr)); // (the null stream only: a resident open trace kernel of another unit is not waited for)
-    return RL_OK;
+    return upload(u->stream, {{u->film, in, (size_t)u->width * u->height * u->n_nodes * sizeof(float)}});
 }
 
 int rl_spectral_unit_project(RlSpectralUnit* u, const float* matrix, RlGatherUnit* dst) {
     if (!u || !matrix || !dst) return fail(RL_E_INVALID, "rl_spectral_unit_project: null spectral unit, matrix or dst");
-    if (dst->device != u->device || dst->width != u->width || dst->height != u->height)
-        return fail(RL_E_STATE, "gather unit does not match the spectral unit (device or size)");
-    int rc = use_device(u->device);
-    if (rc != RL_OK) return rc;
     int cus = 256;
-    if ((rc = cu_count_of(u->device, &cus)) != RL_OK) return rc;
+    int rc = match_check(dst, u);
+    if (rc == RL_OK) rc = enter_device(u->device, &cus);
+    if (rc != RL_OK) return rc;
     const uint64_t n_pixels = (uint64_t)u->width * u->height;
     hipStream_t stream = dst->stream;
-    RL_HIP(hipEventRecord(u->ready, u->stream)); // everything queued on the film (a clear; the splats have drained)
-    RL_HIP(hipStreamWaitEvent(stream, u->ready, 0));
-    RL_HIP(hipMemcpyAsync(u->matrix, matrix, (size_t)u->n_nodes * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
-    u->timed_done[1] = false;
-    RL_HIP(hipEventRecord(u->timed[1].start, stream));
-    hipLaunchKernelGGL(rl_spectral_project_kernel, dim3(grid_for(n_pixels, cus)), dim3(RL_BLOCK), 0, stream, (const float*)u->film,
-                       (const float*)u->matrix, n_pixels, u->n_nodes, dst->acc);
-    RL_HIP(hipGetLastError());
-    RL_HIP(hipEventRecord(u->timed[1].stop, stream));
-    g_spectral_launches[1].fetch_add(1, std::memory_order_relaxed);
-    RL_HIP(hipMemsetAsync(dst->comp, 0, (size_t)n_pixels * 3 * sizeof(float), stream));
-    RL_HIP(hipStreamSynchronize(stream));
-    u->timed_done[1] = true;
-    return RL_OK;
+    // (the copy reads the caller's matrix and the kernel the unit's buffers: neither outlives the call, also after a failure)
+    rc = drained(stream, [&]() -> int {
+        int r = hand_over(u->ready, u->stream, stream); // everything queued on the film (a clear; the splats have drained)
+        if (r != RL_OK) return r;
+        RL_HIP(hipMemcpyAsync(u->matrix, matrix, (size_t)u->n_nodes * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
+        u->timed_done[1] = false; // readable again once the call has completed
+        r = timed_launch(u->timed[1], stream, &g_spectral_launches[1], [&] {
+            hipLaunchKernelGGL(rl_spectral_project_kernel, dim3(grid_for(n_pixels, cus)), dim3(RL_BLOCK), 0, stream, (const float*)u->film,
+                               (const float*)u->matrix, n_pixels, u->n_nodes, dst->acc);
+        });
+        if (r != RL_OK) return r;
+        RL_HIP(hipMemsetAsync(dst->comp, 0, (size_t)n_pixels * 3 * sizeof(float), stream));
+        return RL_OK;
+    }());
+    if (rc == RL_OK) u->timed_done[1] = true;
+    return rc;
 }
 
 int rl_spectral_observer_cie1931(uint32_t n_nodes, float* out) {
@@ -2995,58 +2979,26 @@ std::atomic<uint64_t> g_error_launches[2]; // rl_debug_error_launches: observe l
 }
 
 int rl_error_unit_create(int device, uint32_t width, uint32_t height, RlErrorUnit** out) {
-    if (!out) return fail(RL_E_INVALID, "null output handle");
-    *out = nullptr;
-    if (width == 0 || height == 0) return fail(RL_E_INVALID, "zero-sized error unit");
-    int rc = check_image_size("error unit", width, height);
+    RlErrorUnit* u = nullptr;
+    const int rc = unit_new("error unit", device, width, height, 1u, out, &u);
     if (rc != RL_OK) return rc;
-    rc = use_device(device);
-    if (rc != RL_OK) return rc;
-    RlErrorUnit* u = new (std::nothrow) RlErrorUnit();
-    if (!u) return fail(RL_E_INVALID, "out of host memory");
-    u->device = device;
-    u->width = width;
-    u->height = height;
     u->tiles_x = (width + RL_ERROR_TILE - 1u) / RL_ERROR_TILE;
     u->tiles_y = (height + RL_ERROR_TILE - 1u) / RL_ERROR_TILE;
     const size_t n_pixels = (size_t)width * height, n_tiles = (size_t)u->tiles_x * u->tiles_y;
-    hipError_t e = hipMalloc((void**)&u->sum_y, n_pixels * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(u->sum_y, 0, n_pixels * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&u->sum_q, n_pixels * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(u->sum_q, 0, n_pixels * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&u->se, n_pixels * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&u->tiles, n_tiles * 2 * sizeof(double));
-    if (e == hipSuccess) e = create_unit_stream(&u->stream);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&u->observed, hipEventDisableTiming);
-    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-        e = hipEventCreate(&u->timed[k].start);
-        if (e == hipSuccess) e = hipEventCreate(&u->timed[k].stop);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr); // the synchronous memsets above ran on the null stream
-    if (e != hipSuccess) {
-        rl_error_unit_destroy(u);
-        return fail(RL_E_HIP, std::string("error unit allocation: ") + hipGetErrorString(e));
-    }
-    *out = u;
-    return RL_OK;
+    u->ledger.alloc_zeroed(&u->sum_y, n_pixels * sizeof(double));
+    u->ledger.alloc_zeroed(&u->sum_q, n_pixels * sizeof(double));
+    u->ledger.alloc(&u->se, n_pixels * sizeof(float));
+    u->ledger.alloc(&u->tiles, n_tiles * 2 * sizeof(double));
+    u->ledger.stream(&u->stream);
+    u->ledger.event(&u->observed);
+    for (EventPair& ep : u->timed) u->ledger.pair(&ep);
+    return unit_created("error unit allocation", u, rl_error_unit_destroy, out);
 }
 
 int rl_error_unit_destroy(RlErrorUnit* u) {
     if (!u) return RL_OK;
     (void)hipSetDevice(u->device);
-    if (u->stream) {
-        (void)hipStreamSynchronize(u->stream);
-        (void)hipStreamDestroy(u->stream);
-    }
-    if (u->observed) (void)hipEventDestroy(u->observed);
-    for (EventPair& ep : u->timed) {
-        if (ep.start) (void)hipEventDestroy(ep.start);
-        if (ep.stop) (void)hipEventDestroy(ep.stop);
-    }
-    if (u->sum_y) (void)hipFree(u->sum_y);
-    if (u->sum_q) (void)hipFree(u->sum_q);
-    if (u->se) (void)hipFree(u->se);
-    if (u->tiles) (void)hipFree(u->tiles);
+    u->ledger.release();
     delete u;
     return RL_OK;
 }
@@ -3066,25 +3018,20 @@ int rl_error_unit_observe(RlErrorUnit* u, RlPlotUnit* plot, uint64_t n_paths) {
     if (!u || !plot) return fail(RL_E_INVALID, "rl_error_unit_observe: null error unit or plot unit");
     if (n_paths == 0) return fail(RL_E_INVALID, "rl_error_unit_observe: n_paths is 0: an observation is the sum over at least one path");
     if (u->paths + n_paths < u->paths) return fail(RL_E_INVALID, "rl_error_unit_observe: the number of paths N overflows 64 bits");
-    if (plot->device != u->device || plot->width != u->width || plot->height != u->height)
-        return fail(RL_E_STATE, "plot unit does not match the error unit (device or size)");
-    int rc = use_device(u->device);
+    int cus = 256;
+    int rc = match_check(plot, u);
+    if (rc == RL_OK) rc = enter_device(u->device, &cus);
     if (rc != RL_OK) return rc;
     if ((rc = plot_settle(plot)) != RL_OK) return rc; // a fused render begun into this buffer ends first
-    int cus = 256;
-    if ((rc = cu_count_of(u->device, &cus)) != RL_OK) return rc;
     const uint64_t n_pixels = (uint64_t)u->width * u->height;
-    RL_HIP(hipEventRecord(plot->ready, plot->stream)); // everything plotted / splatted / reduced into the buffer so far
-    RL_HIP(hipStreamWaitEvent(u->stream, plot->ready, 0));
-    RL_HIP(hipEventRecord(u->timed[0].start, u->stream));
-    hipLaunchKernelGGL(rl_error_observe_kernel, dim3(grid_for(n_pixels / 2 + 1, cus)), dim3(RL_BLOCK), 0, u->stream, u->sum_y, u->sum_q,
-                       (const float*)plot->xyz, n_pixels, (double)n_paths);
-    RL_HIP(hipGetLastError());
-    RL_HIP(hipEventRecord(u->timed[0].stop, u->stream));
-    u->timed_done[0] = true;
-    g_error_launches[0].fetch_add(1, std::memory_order_relaxed);
-    RL_HIP(hipEventRecord(u->observed, u->stream)); // a later clear or gather of the buffer must not overtake the read
-    RL_HIP(hipStreamWaitEvent(plot->stream, u->observed, 0));
+    if ((rc = hand_over(plot->ready, plot->stream, u->stream)) != RL_OK) return rc; // everything plotted / splatted / reduced into the buffer so far
+    rc = timed_launch(u->timed[0], u->stream, &g_error_launches[0], [&] {
+        hipLaunchKernelGGL(rl_error_observe_kernel, dim3(grid_for(n_pixels / 2 + 1, cus)), dim3(RL_BLOCK), 0, u->stream, u->sum_y, u->sum_q,
+                           (const float*)plot->xyz, n_pixels, (double)n_paths);
+    });
+    if (rc != RL_OK) return rc;
+    u->timed_done[0] = true; // recorded: rl_debug_error_ms waits for the launch itself
+    if ((rc = hand_over(u->observed, u->stream, plot->stream)) != RL_OK) return rc; // a later clear or gather of the buffer must not overtake the read
     u->observations += 1;
     u->paths += n_paths;
     return RL_OK;
@@ -3099,16 +3046,19 @@ int rl_error_unit_estimate(RlErrorUnit* u, RlErrorStats* stats, float* se, doubl
     const size_t n_pixels = (size_t)u->width * u->height, n_tiles = (size_t)u->tiles_x * u->tiles_y;
     std::vector<double> pairs(2 * n_tiles);
     const double n_total = (double)u->paths, ratio = n_total / (double)(u->observations - 1);
-    RL_HIP(hipEventRecord(u->timed[1].start, u->stream));
-    hipLaunchKernelGGL(rl_error_estimate_kernel, dim3((unsigned)n_tiles), dim3(RL_ERROR_TILE_PIXELS), 0, u->stream, (const double*)u->sum_y,
-                       (const double*)u->sum_q, u->width, u->height, u->tiles_x, n_total, ratio, u->se, u->tiles);
-    RL_HIP(hipGetLastError());
-    RL_HIP(hipEventRecord(u->timed[1].stop, u->stream));
-    u->timed_done[1] = true;
-    g_error_launches[1].fetch_add(1, std::memory_order_relaxed);
-    RL_HIP(hipMemcpyAsync(pairs.data(), u->tiles, pairs.size() * sizeof(double), hipMemcpyDeviceToHost, u->stream));
-    if (se) RL_HIP(hipMemcpyAsync(se, u->se, n_pixels * sizeof(float), hipMemcpyDeviceToHost, u->stream));
-    RL_HIP(hipStreamSynchronize(u->stream));
+    // (the copies write `pairs` and the caller's `se`: neither may be written after the call, also after a failure)
+    rc = drained(u->stream, [&]() -> int {
+        const int r = timed_launch(u->timed[1], u->stream, &g_error_launches[1], [&] {
+            hipLaunchKernelGGL(rl_error_estimate_kernel, dim3((unsigned)n_tiles), dim3(RL_ERROR_TILE_PIXELS), 0, u->stream, (const double*)u->sum_y,
+                               (const double*)u->sum_q, u->width, u->height, u->tiles_x, n_total, ratio, u->se, u->tiles);
+        });
+        if (r != RL_OK) return r;
+        u->timed_done[1] = true; // recorded: rl_debug_error_ms waits for the launch itself
+        RL_HIP(hipMemcpyAsync(pairs.data(), u->tiles, pairs.size() * sizeof(double), hipMemcpyDeviceToHost, u->stream));
+        if (se) RL_HIP(hipMemcpyAsync(se, u->se, n_pixels * sizeof(float), hipMemcpyDeviceToHost, u->stream));
+        return RL_OK;
+    }());
+    if (rc != RL_OK) return rc;
     std::memset(stats, 0, sizeof *stats);
     stats->observations = u->observations;
     stats->paths = u->paths;
@@ -3141,9 +3091,7 @@ int rl_error_unit_download(RlErrorUnit* u, double* sum_y, double* sum_q, uint64_
     int rc = use_device(u->device);
     if (rc != RL_OK) return rc;
     const size_t bytes = (size_t)u->width * u->height * sizeof(double);
-    RL_HIP(hipStreamSynchronize(u->stream));
-    if (sum_y) RL_HIP(hipMemcpy(sum_y, u->sum_y, bytes, hipMemcpyDeviceToHost));
-    if (sum_q) RL_HIP(hipMemcpy(sum_q, u->sum_q, bytes, hipMemcpyDeviceToHost));
+    if ((rc = download(u->stream, {{u->sum_y, sum_y, bytes}, {u->sum_q, sum_q, bytes}})) != RL_OK) return rc;
     if (observations) *observations = u->observations;
     if (paths) *paths = u->paths;
     return RL_OK;
@@ -3154,10 +3102,7 @@ int rl_error_unit_upload(RlErrorUnit* u, const double* sum_y, const double* sum_
     int rc = use_device(u->device);
     if (rc != RL_OK) return rc;
     const size_t bytes = (size_t)u->width * u->height * sizeof(double);
-    RL_HIP(hipStreamSynchronize(u->stream));
-    RL_HIP(hipMemcpy(u->sum_y, sum_y, bytes, hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(u->sum_q, sum_q, bytes, hipMemcpyHostToDevice));
-    RL_HIP(hipStreamSynchronize(nullptr)); // (the null stream only: a resident open trace kernel of another unit is not waited for)
+    if ((rc = upload(u->stream, {{u->sum_y, sum_y, bytes}, {u->sum_q, sum_q, bytes}})) != RL_OK) return rc;
     u->observations = observations;
     u->paths = paths;
     return RL_OK;
@@ -3331,20 +3276,7 @@ int rl_comm_group_end(void) {
 
 namespace {
 // Reads the `n` oldest exchange timings of `u` into its totals (waits for them) and returns their events to the pool.
-int exchanges_harvest(RlPlotUnit* u, size_t n) {
-    if (n > u->exchanges.size()) n = u->exchanges.size();
-    for (size_t i = 0; i < n; ++i) {
-        EventPair& ep = u->exchanges[i];
-        RL_HIP(hipEventSynchronize(ep.stop));
-        float ms = 0.0f;
-        RL_HIP(hipEventElapsedTime(&ms, ep.start, ep.stop));
-        u->exchange_ms += (double)ms;
-        u->exchange_count += 1;
-        u->exchange_pool.push_back(ep);
-    }
-    u->exchanges.erase(u->exchanges.begin(), u->exchanges.begin() + (long)n);
-    return RL_OK;
-}
+int exchanges_harvest(RlPlotUnit* u, size_t n) { return u->exchanges.harvest(n, &u->exchange_ms, &u->exchange_count); }
 } // namespace
 
 int rl_plot_unit_reduce(RlPlotUnit* u, RlComm* comm, int root) {
@@ -3360,15 +3292,9 @@ int rl_plot_unit_reduce(RlPlotUnit* u, RlComm* comm, int root) {
     // In place on the root; on the plot unit's stream, i.e. after every plot / fused splat into this buffer.
     // bracketed by events for rl_plot_unit_exchange_stats; a long run never asks, so the pairs are recycled and at most
     // 32 stay unread (the oldest is complete long before: it is on this unit's stream, 32 exchanges back)
-    if (u->exchanges.size() >= 32 && (rc = exchanges_harvest(u, 16)) != RL_OK) return rc;
+    if (u->exchanges.pending.size() >= 32 && (rc = exchanges_harvest(u, 16)) != RL_OK) return rc;
     EventPair ep;
-    if (!u->exchange_pool.empty()) {
-        ep = u->exchange_pool.back();
-        u->exchange_pool.pop_back();
-    } else {
-        RL_HIP(hipEventCreate(&ep.start));
-        RL_HIP(hipEventCreate(&ep.stop));
-    }
+    if ((rc = u->exchanges.take(&u->ledger, &ep)) != RL_OK) return rc;
     // (Inside rl_comm_group_start / _end -- one thread driving several ranks -- RCCL enqueues the collective at GroupEnd, so both
     // events land in front of it and the exchange reads as ~0 ms: rl_plot_unit_exchange_stats is meaningful for ungrouped
     // reduces only, which is what bench.py's one-rank-per-process runs issue.)
@@ -3377,11 +3303,11 @@ int rl_plot_unit_reduce(RlPlotUnit* u, RlComm* comm, int root) {
     if (he == hipSuccess) ne = api->Reduce(u->xyz, u->xyz, count, ncclFloat32, ncclSum, root, (ncclComm_t)comm->nccl, u->stream);
     if (he == hipSuccess && ne == ncclSuccess) he = hipEventRecord(ep.stop, u->stream);
     if (he != hipSuccess || ne != ncclSuccess) {
-        u->exchange_pool.push_back(ep); // not leaked
+        u->exchanges.give_back(ep); // not leaked
         if (ne != ncclSuccess) return fail(RL_E_HIP, std::string("ncclReduce: ") + api->GetErrorString(ne));
         return fail(RL_E_HIP, std::string("hipEventRecord: ") + hipGetErrorString(he));
     }
-    u->exchanges.push_back(ep);
+    u->exchanges.pending.push_back(ep);
     return RL_OK;
 }
 
@@ -3389,7 +3315,7 @@ int rl_plot_unit_exchange_stats(RlPlotUnit* u, uint64_t* exchanges, double* devi
     if (!u) return fail(RL_E_INVALID, "null plot unit");
     int rc = use_device(u->device);
     if (rc != RL_OK) return rc;
-    if ((rc = exchanges_harvest(u, u->exchanges.size())) != RL_OK) return rc;
+    if ((rc = exchanges_harvest(u, u->exchanges.pending.size())) != RL_OK) return rc;
     if (exchanges) *exchanges = u->exchange_count;
     if (device_ms) *device_ms = u->exchange_ms;
     return RL_OK;
@@ -3421,19 +3347,15 @@ int rl_plot_unit_add(RlPlotUnit* dst, RlPlotUnit* src) {
     if (dst == src) return fail(RL_E_INVALID, "a plot unit cannot be added to itself");
     if (dst->device != src->device || dst->width != src->width || dst->height != src->height)
         return fail(RL_E_STATE, "plot units do not match (device or size)");
-    int rc = use_device(dst->device);
+    int cus = 256;
+    int rc = enter_device(dst->device, &cus);
     if (rc != RL_OK) return rc;
     if ((rc = plot_settle(dst)) != RL_OK || (rc = plot_settle(src)) != RL_OK) return rc; // begun fused renders end first
-    int cus = 256;
-    if ((rc = cu_count_of(dst->device, &cus)) != RL_OK) return rc;
     const uint64_t n = (uint64_t)dst->width * dst->height * 3;
-    RL_HIP(hipEventRecord(src->ready, src->stream));
-    RL_HIP(hipStreamWaitEvent(dst->stream, src->ready, 0));
+    if ((rc = hand_over(src->ready, src->stream, dst->stream)) != RL_OK) return rc; // everything written into src so far is added
     hipLaunchKernelGGL(rl_add_kernel, dim3(grid_for(n, cus)), dim3(RL_BLOCK), 0, dst->stream, dst->xyz, src->xyz, n);
     RL_HIP(hipGetLastError());
-    RL_HIP(hipEventRecord(dst->plotted, dst->stream));
-    RL_HIP(hipStreamWaitEvent(src->stream, dst->plotted, 0)); // src may be cleared or splatted into only after it was read
-    return RL_OK;
+    return hand_over(dst->plotted, dst->stream, src->stream); // src may be cleared or splatted into only after it was read
 }
 
 int rl_gather_unit_allreduce(RlGatherUnit* gather, RlPlotUnit* plot, RlComm* comm) {
@@ -3528,18 +3450,27 @@ int rl_debug_gather_accumulate_ms(RlGatherUnit* u, RlPlotUnit* plot, float* ms) 
     if ((rc = plot_settle(plot)) != RL_OK) return rc;
     if (plot->device == u->device) RL_HIP(hipStreamSynchronize(plot->stream));
     RL_HIP(hipStreamSynchronize(u->stream));
-    EventPair ep{};
-    RL_HIP(hipEventCreate(&ep.start));
-    hipError_t e = hipEventCreate(&ep.stop);
-    if (e == hipSuccess) e = hipEventRecord(ep.start, u->stream);
+    EventPair ep;
+    if ((rc = u->timed.take(&u->ledger, &ep)) != RL_OK) return rc;
+    hipError_t e = hipEventRecord(ep.start, u->stream);
     if (e == hipSuccess) rc = rl_gather_unit_accumulate(u, plot);
     if (e == hipSuccess && rc == RL_OK) e = hipEventRecord(ep.stop, u->stream);
-    if (e == hipSuccess && rc == RL_OK) e = hipEventSynchronize(ep.stop);
-    if (e == hipSuccess && rc == RL_OK) e = hipEventElapsedTime(ms, ep.start, ep.stop);
-    (void)hipEventDestroy(ep.start);
-    if (ep.stop) (void)hipEventDestroy(ep.stop);
-    if (rc != RL_OK) return rc;
-    RL_HIP(e);
+    if (e != hipSuccess || rc != RL_OK) {
+        u->timed.give_back(ep);
+        if (rc != RL_OK) return rc;
+        RL_HIP(e);
+    }
+    u->timed.pending.push_back(ep);
+    double total = 0.0;
+    uint64_t read = 0;
+    rc = u->timed.harvest(1, &total, &read); // waits for the launch
+    *ms = (float)total;
+    return rc;
+}
+
+int rl_debug_live_resources(uint64_t out[4]) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    for (int k = 0; k < LIVE_KINDS; ++k) out[k] = g_live[k].load(std::memory_order_relaxed);
     return RL_OK;
 }
 int rl_debug_denoise_pass_ms(RlDenoiseUnit* u, float out[1 + RL_DENOISE_MAX_ITERATIONS]) {

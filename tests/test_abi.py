@@ -275,6 +275,51 @@ def test_images_beyond_32_bit_pixel_indices_are_refused_before_any_device_work()
             assert "RL_MAX_PIXELS" in str(e.value), (name, w, h, str(e.value))
 
 
+def test_every_unit_create_checks_its_arguments_before_the_device():
+    """The argument checks of all seven *_unit_create calls, in the header's order and each with its message: null output, zero
+    size, RL_MAX_PIXELS (the spectral unit: its node count, then pixels x nodes), and only then the device -- so each is
+    RL_E_INVALID here, where asking for the device is RL_E_NO_DEVICE -- and the handle is left null."""
+    lib, last = _lib.lib, lambda: _lib.lib.rl_last_error().decode()
+    RL_E_INVALID, RL_E_NO_DEVICE = -1, -2
+    # name -> (symbol, arguments between the size and the handle)
+    units = {"trace unit": (lambda w, h, out: lib.rl_trace_unit_create(0, 0, w, h, 64, out)),
+             "plot unit": (lambda w, h, out: lib.rl_plot_unit_create(0, 0, w, h, None, out)),
+             "gather unit": (lambda w, h, out: lib.rl_gather_unit_create(0, w, h, out)),
+             "tonemap unit": (lambda w, h, out: lib.rl_tonemap_unit_create(0, w, h, out)),
+             "denoise unit": (lambda w, h, out: lib.rl_denoise_unit_create(0, w, h, out)),
+             "spectral unit": (lambda w, h, out: lib.rl_spectral_unit_create(0, w, h, 81, out)),
+             "error unit": (lambda w, h, out: lib.rl_error_unit_create(0, w, h, out))}
+    poison = 0xDEAD0
+
+    def refused(create, w, h, message):
+        handle = C.c_void_p(poison)
+        assert create(w, h, C.byref(handle)) == RL_E_INVALID, (message, w, h, last())
+        assert message in last() and handle.value is None, (message, w, h, last(), handle.value)
+
+    for name, create in units.items():
+        assert create(4, 4, None) == RL_E_INVALID and last() == "null output handle", name
+        assert create(0, 0, None) == RL_E_INVALID and last() == "null output handle", name  # the null output comes first
+        for w, h in [(0, 4), (4, 0), (0, 0), (0, 0xFFFFFFFF)]:  # ... then the zero size, before RL_MAX_PIXELS
+            refused(create, w, h, "zero-sized " + name)
+        for w, h in [(46341, 46341), (65536, 32768), (32768, 65536), (0xFFFFFFFF, 0xFFFFFFFF), (0x80000000, 1)]:
+            refused(create, w, h, "%s: %d x %d pixels" % (name, w, h))
+            assert "exceed RL_MAX_PIXELS = 2^31 - 1" in last(), (name, w, h, last())
+        if R.device_count() == 0:  # what comes next is the device
+            handle = C.c_void_p(poison)
+            assert create(4, 4, C.byref(handle)) == RL_E_NO_DEVICE and handle.value is None, (name, last())
+    handle = C.c_void_p(poison)
+    assert lib.rl_trace_unit_create(0, 0, 4, 4, 0, C.byref(handle)) == RL_E_INVALID and last() == "zero-sized trace unit"
+    assert handle.value is None
+    # the spectral unit: the node count between the zero size and the size limit, then pixels x nodes
+    spectral = lambda nodes: (lambda w, h, out: lib.rl_spectral_unit_create(0, w, h, nodes, out))
+    for nodes in (0, 1, 402, 0xFFFFFFFF):
+        refused(spectral(nodes), 4, 4, "spectral unit: n_nodes %d outside 2 .. RL_SPECTRAL_MAX_NODES = 401" % nodes)
+        refused(spectral(nodes), 46341, 46341, "n_nodes %d outside" % nodes)
+        refused(spectral(nodes), 0, 4, "zero-sized spectral unit")
+    for w, h, nodes in [(32768, 32768, 2), (4096, 4096, 128), (65536, 128, 256), (1 << 23, 1, 256), (0xFFFFFFFF, 0xFFFFFFFF, 256)]:
+        refused(spectral(nodes), w, h, "spectral unit: %d x %d pixels x %d nodes exceed RL_MAX_PIXELS = 2^31 - 1" % (w, h, nodes))
+
+
 def _app_run_without_an_image(w, h):
     """rl_app_run with no output image (R.app_run would allocate the w x h one first)."""
     cfg = _lib.RlAppConfig()
