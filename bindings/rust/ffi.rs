@@ -215,6 +215,12 @@ extern "C" {
     pub fn rl_denoise_unit_destroy(unit: *mut RlDenoiseUnit) -> c_int;
     pub fn rl_denoise_unit_denoise(unit: *mut RlDenoiseUnit, image: *mut RlGatherUnit, albedo: *mut RlGatherUnit, normal: *mut RlGatherUnit,
                                    aux: *mut RlGatherUnit, params: *const RlDenoiseParams, dst: *mut RlGatherUnit) -> c_int;
+    // The same filter with the error unit's variance as its colour term; sigma_colour in standard deviations, default 3.0.
+    // variance_out: host, width x height floats, may be null.
+    pub fn rl_denoise_variance_params_default(out: *mut RlDenoiseParams) -> c_int;
+    pub fn rl_denoise_unit_denoise_variance(unit: *mut RlDenoiseUnit, image: *mut RlGatherUnit, albedo: *mut RlGatherUnit, normal: *mut RlGatherUnit,
+                                            aux: *mut RlGatherUnit, error: *mut RlErrorUnit, params: *const RlDenoiseParams, dst: *mut RlGatherUnit,
+                                            variance_out: *mut f32) -> c_int;
 
     // The spectral film: photons kept by wavelength in n_nodes planes, projected into a gather unit under an n_nodes x 3 matrix.
     pub fn rl_spectral_unit_create(device: c_int, width: u32, height: u32, n_nodes: u32, out: *mut *mut RlSpectralUnit) -> c_int;
@@ -276,6 +282,8 @@ extern "C" {
     pub fn rl_app_run_to_error(config: *const RlAppConfig, target: *const RlErrorTarget, stats: *mut RlAppStats,
                                error_stats: *mut RlAppErrorStats, rgb_out: *mut u8) -> c_int;
     pub fn rl_app_error_tiles(tiles: *mut f64, capacity: u32, n_tiles: *mut u32) -> c_int;
+    pub fn rl_app_error_state(sum_y: *mut f64, sum_q: *mut f64, capacity_pixels: u64, n_pixels: *mut u64, observations: *mut u64,
+                              paths: *mut u64) -> c_int;
 
 }
 

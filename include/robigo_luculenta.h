@@ -840,6 +840,50 @@ int rl_denoise_unit_destroy(RlDenoiseUnit* unit);
 int rl_denoise_unit_denoise(RlDenoiseUnit* unit, RlGatherUnit* image, RlGatherUnit* albedo, RlGatherUnit* normal, RlGatherUnit* aux,
                             const RlDenoiseParams* params, RlGatherUnit* dst);
 
+/* ---- variance-guided denoising: the same filter with the error unit's variance as its colour term ---- */
+
+/* rl_denoise_unit_denoise_variance: the a-trous filter above with the relative colour term replaced by the squared luminance
+ * difference over the sum of the two pixels' variances, the variance being the error unit's (rl_error_unit_*) and filtered along
+ * with the image.  The plain filter does not know how noisy a pixel is and blurs a converged image as hard as a noisy one; this
+ * one backs off as the image converges, which is what an image rendered to a target error (rl_app_run_to_error) needs.
+ *   rl_denoise_variance_params_default writes {5, 3.0, 0.3, 0.1, 0.2} and zero `reserved`.  params == NULL means those.  The struct
+ *   is RlDenoiseParams; here sigma_colour is in standard deviations of the luminance difference.
+ *   Inputs.  As rl_denoise_unit_denoise, and `error`: an error unit with at least two observations.  `image` must be in the units
+ *   of the error unit's S, which holds when the error unit observed every plot buffer the image gathered.  THE CALL DOES NOT CHECK
+ *   THIS: an image in other units is filtered with a variance that does not belong to it.
+ *   The unit's scratch grows by two width x height float planes at its first variance call; a unit that never makes one owns what
+ *   rl_denoise_unit_denoise states.
+ *   The arithmetic.  All f32 unless stated, in exactly this order, never contracted; division is correctly rounded; rl_expf is
+ *   csrc/rl_math.h's.  The guide record, the constants kn, kz, ka, the taps h, the step s = 1 << i, the tap order (dy outer, dx
+ *   inner) and the liveness rules are those of rl_denoise_unit_denoise.
+ *     V_0 of pixel p, once per call, from the error unit's S, Q (f64), N, k:
+ *       d = Q - (S * S) / (double)N;  d = d < 0 ? 0 : d (a NaN stays a NaN);  v = d * ((double)N / (double)(k - 1));  V_0 = (float)v.
+ *       This is rl_error_unit_estimate's v: rl_sqrtf(V_0) has the bits of that call's `se`.
+ *     Pass i = 0 .. iterations - 1: kv = k(sigma_colour), the same for every pass (the filtered variance shrinks instead of the
+ *       sigma).  For a live p: sum_w = 0, sum_c = (0, 0, 0), sum_v = 0; for each tap q inside the image and live
+ *         dl = C_i[p].y - C_i[q].y;  m = V_i[p] + V_i[q];  e_c = m > 0 ? (dl * dl) / m : 0
+ *           (a pair without variance information has the term off; a NaN m too);
+ *         e_n, e_z, e_a as in the plain filter;
+ *         x = ((e_c*kv + e_n*kn) + e_z*kz) + e_a*ka;  wt = (h[dy+2] * h[dx+2]) * rl_expf(-x);
+ *         sum_w += wt;  sum_c.k += wt * C_i[q].k;  sum_v += (wt * wt) * V_i[q];
+ *       then C_{i+1}[p] = sum_c / sum_w per component and V_{i+1}[p] = sum_v / (sum_w * sum_w).
+ *       For a p that is not live: C_{i+1}[p] = C_i[p] and V_{i+1}[p] = V_i[p].
+ *     No special cases for non-finite values.
+ *   Result.  dst holds C_iterations with a +0 compensation buffer, as after the plain call.  variance_out (host, width x height
+ *   floats, may be NULL) receives V_iterations: under the model of independent pixels, the variance of the denoised luminance.  The
+ *   inputs, the error unit included, are left as they were.
+ *   Determinism.  The result is exact: the same bits on every run, and the bits of tests/_denoise_variance_oracle.py.
+ *   Arguments, checked in this order before any device work: a NULL unit, image, dst or error (RL_E_INVALID); the plain call's
+ *   checks of params and its rule that the given gather units are distinct, in its order (RL_E_INVALID); an error unit with fewer
+ *   than two observations (RL_E_STATE); any given unit, the error unit included, of another size or device (RL_E_STATE).  In the
+ *   refused cases nothing is written.
+ *   Ordering.  As the plain call; the call also waits, through an event, for what is queued on the error unit's stream.  The copy
+ *   to variance_out happens after the last pass and before the return. */
+int rl_denoise_variance_params_default(RlDenoiseParams* out);
+int rl_denoise_unit_denoise_variance(RlDenoiseUnit* unit, RlGatherUnit* image, RlGatherUnit* albedo, RlGatherUnit* normal, RlGatherUnit* aux,
+                                     RlErrorUnit* error, const RlDenoiseParams* params, RlGatherUnit* dst,
+                                     float* variance_out /* host, width x height, may be NULL */);
+
 /* ---- spectral film: photons kept by wavelength, projected under any observer (rl_spectral_unit_*) ---- */
 
 #define RL_SPECTRAL_MAX_NODES 401
@@ -1157,10 +1201,18 @@ typedef struct RlAppErrorStats {
  * error state is not kept beside the checkpoint.
  *   rl_app_error_tiles: the {t_se, t_y} pairs of at_end of the calling thread's last rl_app_run_to_error, tiles in raster order.
  * *n_tiles (may be NULL) is always set to their number (0 if that run made no final estimate); `tiles` receives 2 * n doubles when
- * capacity >= n, else RL_E_INVALID -- the capacity protocol of rl_scene_emitters. */
+ * capacity >= n, else RL_E_INVALID -- the capacity protocol of rl_scene_emitters.
+ *   rl_app_error_state: the error unit's state at the end of the calling thread's last rl_app_run_to_error -- the planes S and Q,
+ * width x height doubles in rows, the observations k and the paths N -- which otherwise dies with the run.  The same protocol:
+ * *n_pixels, *observations and *paths (each may be NULL) are always set, to zeros after a run without a target or one that made no
+ * observation; sum_y and sum_q each receive n doubles when capacity_pixels >= n, else RL_E_INVALID.  The planes are downloaded
+ * once per run, after the final estimate and after stats->seconds is taken.  Uploaded into an error unit of the caller's
+ * (rl_error_unit_upload) they give at_end's estimate again, and rl_denoise_unit_denoise_variance the variance of the run's image. */
 int rl_app_run_to_error(const RlAppConfig* config, const RlErrorTarget* target, RlAppStats* stats, RlAppErrorStats* error_stats,
                         uint8_t* rgb_out);
 int rl_app_error_tiles(double* tiles, uint32_t capacity, uint32_t* n_tiles);
+int rl_app_error_state(double* sum_y, double* sum_q, uint64_t capacity_pixels, uint64_t* n_pixels, uint64_t* observations,
+                       uint64_t* paths);
 
 #ifdef __cplusplus
 }

@@ -71,6 +71,13 @@ int rl_debug_denoise_launches(uint64_t out[2]);
 /* Device time of the unit's last completed rl_denoise_unit_denoise call, from events on dst's stream, in milliseconds: out[0] the
  * guide launch, out[1 + i] pass i; 0 for passes the call did not make (all 0 before the first call).  tools/denoise_bench.py. */
 int rl_debug_denoise_pass_ms(RlDenoiseUnit* unit, float out[1 + RL_DENOISE_MAX_ITERATIONS]);
+/* out[0]: launches of the V_0 kernel (rl_variance_denoise_kernel), out[1]: launches of the variance form of the pass kernel
+ * (rl_variance_denoise_pass_kernel) since the library was loaded: rl_denoise_unit_denoise_variance adds (1, iterations).  Its guide
+ * launch counts in rl_debug_denoise_launches' out[0]; its passes do not count in out[1] there. */
+int rl_debug_denoise_variance_launches(uint64_t out[2]);
+/* Device time of the V_0 launch of the unit's last completed rl_denoise_unit_denoise_variance call, in milliseconds (0 before the
+ * first); that call's guide launch and passes are read with rl_debug_denoise_pass_ms.  tools/denoise_variance_bench.py. */
+int rl_debug_denoise_variance_ms(RlDenoiseUnit* unit, float* ms);
 /* out[0]: launches of rl_spectral_photons_kernel (one per trace unit of rl_spectral_unit_plot, one per chunk of
  * rl_spectral_unit_plot_photons, one per rl_spectral_unit_plot_photons_device), out[1]: launches of rl_spectral_project_kernel (one
  * per rl_spectral_unit_project) since the library was loaded. */

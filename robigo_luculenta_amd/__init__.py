@@ -709,6 +709,14 @@ def denoise_params_default():
             "sigma_albedo": p.sigma_albedo}
 
 
+def denoise_variance_params_default():
+    """rl_denoise_variance_params_default as a dict (the keywords DenoiseUnit.denoise_variance takes)."""
+    p = RlDenoiseParams()
+    check(lib.rl_denoise_variance_params_default(C.byref(p)))
+    return {"iterations": p.iterations, "sigma_colour": p.sigma_colour, "sigma_normal": p.sigma_normal, "sigma_depth": p.sigma_depth,
+            "sigma_albedo": p.sigma_albedo}
+
+
 class DenoiseUnit(_Handle):
     """The edge-avoiding a-trous filter over the guides of Scene.render_features (rl_denoise_unit_*)."""
     _destroy = lib.rl_denoise_unit_destroy
@@ -734,11 +742,39 @@ class DenoiseUnit(_Handle):
                                           C.byref(p) if p is not None else None, dst.handle))
         return dst
 
+    def denoise_variance(self, image, error, albedo=None, normal=None, aux=None, dst=None, variance=False, **params):
+        """rl_denoise_unit_denoise_variance: denoise() with the variance of ErrorUnit `error` (at least two observations, of the
+        plot buffers `image` gathered) as the colour term; sigma_colour is in standard deviations.  params are over
+        denoise_variance_params_default().  Returns dst, or (dst, V as (height, width) float32: the variance of the denoised
+        luminance) when `variance` is set."""
+        if dst is None:
+            raise TypeError("denoise_variance() needs dst, a gather unit")
+        p = None
+        if params:
+            p = RlDenoiseParams()
+            check(lib.rl_denoise_variance_params_default(C.byref(p)))
+            for name, value in params.items():
+                if name not in ("iterations", "sigma_colour", "sigma_normal", "sigma_depth", "sigma_albedo"):
+                    raise TypeError("denoise_variance() got an unexpected keyword argument %r" % name)
+                setattr(p, name, value)
+        v = np.zeros((self.height, self.width), dtype=np.float32) if variance else None
+        check(lib.rl_denoise_unit_denoise_variance(self._h, image.handle, *[g.handle if g is not None else None for g in (albedo, normal, aux)],
+                                                   error.handle, C.byref(p) if p is not None else None, dst.handle,
+                                                   v.ctypes.data_as(C.c_void_p) if variance else None))
+        return (dst, v) if variance else dst
+
     def pass_ms(self):
-        """Device milliseconds of the last denoise(): [the guide launch, pass 0, pass 1, ...] (rl_debug_denoise_pass_ms)."""
+        """Device milliseconds of the last denoise() or denoise_variance(): [the guide launch, pass 0, pass 1, ...]
+        (rl_debug_denoise_pass_ms)."""
         out = (C.c_float * (1 + RL_DENOISE_MAX_ITERATIONS))()
         check(lib.rl_debug_denoise_pass_ms(self._h, out))
         return list(out)
+
+    def variance_ms(self):
+        """Device milliseconds of the V_0 launch of the last denoise_variance() (rl_debug_denoise_variance_ms)."""
+        ms = C.c_float(0)
+        check(lib.rl_debug_denoise_variance_ms(self._h, C.byref(ms)))
+        return ms.value
 
 
 def spectral_observer_cie1931(n_nodes=81):
@@ -968,6 +1004,18 @@ def app_run_to_error(width, height, max_batches, target_error=None, worst_tile_e
     return rgb, _app_stats(stats), error
 
 
+def app_error_state():
+    """rl_app_error_state: (S, Q as flat float64 arrays of width * height, k, N) of the error unit at the end of this thread's last
+    app_run_to_error; empty arrays and zeros after a run without a target or without an observation.  Reshape to (height, width)
+    and ErrorUnit.upload them to estimate again or to DenoiseUnit.denoise_variance the run's image."""
+    n, k, paths = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    lib.rl_app_error_state(None, None, 0, C.byref(n), C.byref(k), C.byref(paths))   # (RL_E_INVALID when there is a state: the size is what is asked for)
+    s, q = np.zeros(n.value, dtype=np.float64), np.zeros(n.value, dtype=np.float64)
+    if n.value:
+        check(lib.rl_app_error_state(s.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p), n.value, C.byref(n), C.byref(k), C.byref(paths)))
+    return s, q, k.value, paths.value
+
+
 def batch_histogram(device=0):
     """{k: open launches that carried k blocking render calls} since the library was loaded (waits for running ones)."""
     out = (C.c_uint64 * 257)()
@@ -1053,6 +1101,13 @@ def denoise_launches():
     """(launches of the denoiser's guide kernel, launches of its pass kernel) since the library was loaded
     (rl_debug_denoise_launches): one and `iterations` per DenoiseUnit.denoise."""
     return _launch_counters(lib.rl_debug_denoise_launches, 2, tuple)
+
+
+def denoise_variance_launches():
+    """(launches of the V_0 kernel, launches of the variance form of the pass kernel) since the library was loaded
+    (rl_debug_denoise_variance_launches): one and `iterations` per DenoiseUnit.denoise_variance, whose guide launch counts in
+    denoise_launches()."""
+    return _launch_counters(lib.rl_debug_denoise_variance_launches, 2, tuple)
 
 
 def spectral_launches():

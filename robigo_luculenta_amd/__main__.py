@@ -3,6 +3,8 @@ built-in scene with the App worker pool and writes output.ppm (+ buffer.raw) whe
 With --direct the image is rendered with direct light (PlotUnit.render_direct), batch by batch over the unit API.
 With --features PREFIX the denoising guides of the same paths (Scene.render_features) are written beside the image.
 With --denoise PATH as well the image is filtered over those guides on the device (DenoiseUnit.denoise) and tonemapped to PATH.
+With --denoise-variance as well the filter's colour term is the noise estimate's variance (DenoiseUnit.denoise_variance): it backs off
+as the image converges, which the plain filter does not.
 With --spectral PATH the same paths are rendered once more into a spectral film (SpectralUnit) and the cube is saved as PATH (.npy).
 With --target-error E the run ends once the estimated relative error of the image (rl_app_run_to_error) is at most E; --batches stays
 the cap.  With --error-map PATH the per-tile relative error of the last estimate is written as a grey image."""
@@ -45,6 +47,10 @@ def parse_args(argv=None):
     ap.add_argument("--denoise", metavar="PATH", default=None,
                     help="with --features: filter the image over the guides (DenoiseUnit.denoise, the library's defaults) and write it, "
                          "tonemapped, to PATH (*.png or *.ppm)")
+    ap.add_argument("--denoise-variance", action="store_true",
+                    help="with --denoise: the variance-guided filter (DenoiseUnit.denoise_variance, the library's defaults).  With --direct "
+                         "every batch is observed by an error unit; otherwise the run must estimate (--target-error or --error-map). "
+                         "Needs two batches at least")
     ap.add_argument("--spectral", metavar="PATH", default=None,
                     help="after the image, render the same paths un-fused into a spectral film (SpectralUnit.plot) and save the cube, "
                          "float32 (nodes, height, width), to PATH with numpy.save (*.npy)")
@@ -72,6 +78,15 @@ def parse_args(argv=None):
         ap.error("--spectral cannot be combined with --direct: the direct renderer writes no photons")
     if a.denoise is not None and a.features is None:
         ap.error("--denoise needs --features: the filter is guided by the albedo, normal and depth films")
+    if a.denoise_variance:
+        if a.denoise is None:
+            ap.error("--denoise-variance needs --denoise PATH: it chooses the filter that writes PATH")
+        if not a.direct and a.target_error is None and a.error_map is None:
+            ap.error("--denoise-variance needs --direct, --target-error or --error-map: the variance comes from a run that estimates its error")
+        if a.resume:
+            ap.error("--denoise-variance cannot be combined with --resume: the estimate covers this run's samples only, the image all of them")
+        if a.batches < 2:
+            ap.error("--denoise-variance needs at least two batches: the variance rests on two observations")
     if a.direct:
         for given, flag in ((a.unfused, "--unfused"), (a.concurrency is not None, "--concurrency"), (a.resume, "--resume")):
             if given:
@@ -100,15 +115,19 @@ def write_image(path, rgb, width, height):
 
 def render_direct(a):
     """--direct: batch b is paths [b * photons_per_batch, (b + 1) * photons_per_batch) of stream 0, one render_direct call into a
-    plot unit and one GatherUnit.accumulate each; one tonemap at the end."""
-    from . import GatherUnit, PlotUnit, Scene, TonemapUnit
+    plot unit and one GatherUnit.accumulate each; one tonemap at the end.  With --denoise-variance an ErrorUnit observes each batch's
+    plot buffer before it is gathered.  Returns (rgb, totals, the gather unit, the error unit or None)."""
+    from . import ErrorUnit, GatherUnit, PlotUnit, Scene, TonemapUnit
     scene = Scene.builtin(SCENE_DEMO if a.scene == "demo" else SCENE_GLASS_STRESS, device=a.device)
     plot = PlotUnit(0, a.width, a.height, device=a.device)
     gather = GatherUnit(a.width, a.height, device=a.device)
+    error = ErrorUnit(a.width, a.height, device=a.device) if a.denoise_variance else None
     total = {}
     t0 = time.perf_counter()
     for b in range(a.batches):
         stats = plot.render_direct(scene, a.seed, 0, b * a.photons_per_batch, a.photons_per_batch, max_segments=a.max_segments or 0)
+        if error is not None:
+            error.observe(plot, a.photons_per_batch)
         gather.accumulate(plot)
         for k, v in stats.items():
             total[k] = total.get(k, 0) + v
@@ -124,7 +143,7 @@ def render_direct(a):
     print("direct light: %s" % ", ".join("%s %d" % kv for kv in total.items()))
     print("%d batches, %.1f Mpaths, %.1f Mrays and %.1f M shadow rays in %.2f s; wrote %s"
           % (a.batches, total.get("paths", 0) / 1e6, total.get("segments", 0) / 1e6, total.get("shadow_rays", 0) / 1e6, seconds, a.output))
-    return rgb, total, gather
+    return rgb, total, gather, error
 
 
 def render_features(a):
@@ -210,17 +229,21 @@ def report_error(a, st, err):
     return grey
 
 
-def denoise(a, image, guides):
+def denoise(a, image, guides, error=None):
     """--denoise PATH: gather unit `image` filtered over the three guide gather units into a gather unit of its own, tonemapped as
-    the image was, written to PATH."""
+    the image was, written to PATH.  With --denoise-variance `error` is the ErrorUnit that observed what `image` gathered."""
     from . import DenoiseUnit, GatherUnit, TonemapUnit
     clean = GatherUnit(a.width, a.height, device=a.device)
-    DenoiseUnit(a.width, a.height, device=a.device).denoise(image, albedo=guides[0], normal=guides[1], aux=guides[2], dst=clean)
+    unit = DenoiseUnit(a.width, a.height, device=a.device)
+    if a.denoise_variance:
+        unit.denoise_variance(image, error, albedo=guides[0], normal=guides[1], aux=guides[2], dst=clean)
+    else:
+        unit.denoise(image, albedo=guides[0], normal=guides[1], aux=guides[2], dst=clean)
     tonemap = TonemapUnit(a.width, a.height, device=a.device)
     tonemap.tonemap(clean)
     rgb = tonemap.rgb_buffer
     write_image(a.denoise, rgb, a.width, a.height)
-    print("denoised: wrote %s" % a.denoise)
+    print("denoised%s: wrote %s" % (" with the variance term" if a.denoise_variance else "", a.denoise))
     return rgb
 
 
@@ -228,11 +251,11 @@ def main(argv=None):
     a = parse_args(argv)
     print("rendering %d batches at %dx%d" % (a.batches, a.width, a.height))
     if a.direct:
-        image = render_direct(a)[2]
+        image, error = render_direct(a)[2:]
         if a.features is not None:
             guides = render_features(a)[2]
             if a.denoise is not None:
-                denoise(a, image, guides)
+                denoise(a, image, guides, error)
         return
     # rl_app_run hands out no gather unit: --denoise reads the image back from the checkpoint, a temporary one if none was asked for
     scratch = tempfile.TemporaryDirectory() if a.denoise is not None and a.checkpoint is None else None
@@ -257,7 +280,17 @@ def main(argv=None):
             from . import GatherUnit
             image = GatherUnit(a.width, a.height, device=a.device)
             image.load(checkpoint)
-            denoise(a, image, guides)
+            error = None
+            if a.denoise_variance:
+                # the App's error unit dies with the run: its state goes into one of our own
+                from . import ErrorUnit, app_error_state
+                s, q, k, n = app_error_state()
+                if k < 2:
+                    raise SystemExit("--denoise-variance: the run gathered %d plot buffers and the variance needs two observations; "
+                                     "%s was not written (more --batches, or a lower --concurrency)" % (k, a.denoise))
+                error = ErrorUnit(a.width, a.height, device=a.device)
+                error.upload(s, q, k, n)
+            denoise(a, image, guides, error)
     if a.spectral is not None:
         render_spectral(a)
     if scratch:

@@ -235,6 +235,8 @@ SIGNATURES = {
     "rl_denoise_unit_create": (_i, [_i, _u32, _u32, _pp]),
     "rl_denoise_unit_destroy": (_i, [_vp]),
     "rl_denoise_unit_denoise": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(RlDenoiseParams), _vp]),
+    "rl_denoise_variance_params_default": (_i, [C.POINTER(RlDenoiseParams)]),
+    "rl_denoise_unit_denoise_variance": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(RlDenoiseParams), _vp, _vp]),
     "rl_spectral_unit_create": (_i, [_i, _u32, _u32, _u32, _pp]),
     "rl_spectral_unit_destroy": (_i, [_vp]),
     "rl_spectral_unit_clear": (_i, [_vp]),
@@ -271,6 +273,7 @@ SIGNATURES = {
     "rl_app_run": (_i, [C.POINTER(RlAppConfig), C.POINTER(RlAppStats), _vp]),
     "rl_app_run_to_error": (_i, [C.POINTER(RlAppConfig), C.POINTER(RlErrorTarget), C.POINTER(RlAppStats), C.POINTER(RlAppErrorStats), _vp]),
     "rl_app_error_tiles": (_i, [_vp, _u32, C.POINTER(_u32)]),
+    "rl_app_error_state": (_i, [_vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
 }
 # include/robigo_luculenta_debug.h: diagnostics, not part of the drop-in boundary
 DEBUG_SIGNATURES = {
@@ -291,6 +294,8 @@ DEBUG_SIGNATURES = {
     "rl_debug_feature_launches": (_i, [_vp]),
     "rl_debug_denoise_launches": (_i, [_vp]),
     "rl_debug_denoise_pass_ms": (_i, [_vp, _vp]),
+    "rl_debug_denoise_variance_launches": (_i, [_vp]),
+    "rl_debug_denoise_variance_ms": (_i, [_vp, C.POINTER(C.c_float)]),
     "rl_debug_spectral_launches": (_i, [_vp]),
     "rl_debug_spectral_ms": (_i, [_vp, _vp]),
     "rl_debug_error_launches": (_i, [_vp]),

@@ -224,6 +224,25 @@ struct Ledger {
         events.push_back(*field);
         g_live[LIVE_EVENTS].fetch_add(1, std::memory_order_relaxed);
     }
+    // Device memory and a plain event for a live handle, taken at the first call that needs them: as make_pair, the failure is
+    // the call's, not the handle's.
+    template <class T>
+    hipError_t make_alloc(T** field, size_t bytes) {
+        *field = nullptr;
+        const hipError_t e = hipMalloc((void**)field, bytes);
+        if (e != hipSuccess) return e;
+        memory.push_back((void*)*field);
+        g_live[LIVE_ALLOCATIONS].fetch_add(1, std::memory_order_relaxed);
+        return hipSuccess;
+    }
+    hipError_t make_event(hipEvent_t* field) {
+        *field = nullptr;
+        const hipError_t e = hipEventCreateWithFlags(field, hipEventDisableTiming);
+        if (e != hipSuccess) return e;
+        events.push_back(*field);
+        g_live[LIVE_EVENTS].fetch_add(1, std::memory_order_relaxed);
+        return hipSuccess;
+    }
     // A timed pair.  make_pair is the form for a live handle (PairPool): its failure is the call's, not the handle's.
     hipError_t make_pair(EventPair* field) {
         *field = EventPair{nullptr, nullptr};
@@ -428,6 +447,11 @@ struct RlDenoiseUnit {
     hipEvent_t ready[4]; // recorded on the streams of the gather units a call reads: image, albedo, normal, aux
     EventPair timed[1 + RL_DENOISE_MAX_ITERATIONS]; // around the guide launch and each pass of the last call (rl_debug_denoise_pass_ms)
     uint32_t timed_passes; // passes of the last call that completed
+    // rl_denoise_unit_denoise_variance, taken at the first such call (null before it):
+    float* variance[2];       // V_0, V_1, ... ping-pong: width x height floats each
+    hipEvent_t error_ready;   // recorded on the error unit's stream
+    EventPair timed_variance; // around the V_0 launch of the last variance call (rl_debug_denoise_variance_ms)
+    bool timed_variance_done; // ... of a call that completed
     Ledger ledger;
 };
 
@@ -2699,6 +2723,7 @@ int rl_tonemap_unit_srgb_float(RlTonemapUnit* u, float* out, float* max_intensit
 
 namespace {
 std::atomic<uint64_t> g_denoise_launches[2]; // rl_debug_denoise_launches: guide launches, pass launches
+std::atomic<uint64_t> g_denoise_variance_launches[2]; // rl_debug_denoise_variance_launches: V_0 launches, variance pass launches
 }
 
 int rl_denoise_params_default(RlDenoiseParams* out) {
@@ -2734,43 +2759,74 @@ int rl_denoise_unit_destroy(RlDenoiseUnit* u) {
     return RL_OK;
 }
 
-int rl_denoise_unit_denoise(RlDenoiseUnit* u, RlGatherUnit* image, RlGatherUnit* albedo, RlGatherUnit* normal, RlGatherUnit* aux,
-                            const RlDenoiseParams* params, RlGatherUnit* dst) {
-    if (!u || !image || !dst) return fail(RL_E_INVALID, "rl_denoise_unit_denoise: null denoise unit, image or dst");
+int rl_denoise_variance_params_default(RlDenoiseParams* out) {
+    const int rc = rl_denoise_params_default(out);
+    if (rc == RL_OK) out->sigma_colour = 3.0f; // standard deviations of the luminance difference
+    return rc;
+}
+
+namespace {
+
+// Both denoise calls: `what` is the call's name; `error` non-null makes it the variance form (rl_denoise_unit_denoise_variance),
+// whose null check of `error` is its caller's.  The checks and their order are the header's.
+int denoise_call(const char* what, RlDenoiseUnit* u, RlGatherUnit* image, RlGatherUnit* albedo, RlGatherUnit* normal, RlGatherUnit* aux,
+                 RlErrorUnit* error, const RlDenoiseParams* params, RlGatherUnit* dst, float* variance_out) {
+    const std::string name = std::string(what) + ": ";
     RlDenoiseParams p;
     if (params) p = *params;
+    else if (error) (void)rl_denoise_variance_params_default(&p);
     else (void)rl_denoise_params_default(&p);
     if (p.iterations > RL_DENOISE_MAX_ITERATIONS)
-        return fail(RL_E_INVALID, "rl_denoise_unit_denoise: iterations " + std::to_string(p.iterations) + " above RL_DENOISE_MAX_ITERATIONS = " +
+        return fail(RL_E_INVALID, name + "iterations " + std::to_string(p.iterations) + " above RL_DENOISE_MAX_ITERATIONS = " +
                                       std::to_string(RL_DENOISE_MAX_ITERATIONS));
     const float sigmas[4] = {p.sigma_colour, p.sigma_normal, p.sigma_depth, p.sigma_albedo};
     const char* const sigma_names[4] = {"sigma_colour", "sigma_normal", "sigma_depth", "sigma_albedo"};
     for (int k = 0; k < 4; ++k)
         if (!(sigmas[k] == 0.0f || (sigmas[k] >= 1e-3f && sigmas[k] <= 1e3f))) // (a NaN fails both)
-            return fail(RL_E_INVALID, std::string("rl_denoise_unit_denoise: ") + sigma_names[k] + " must be 0 (the term is off) or in [1e-3, 1e3]");
-    if (p.reserved[0] != 0u || p.reserved[1] != 0u || p.reserved[2] != 0u) return fail(RL_E_INVALID, "rl_denoise_unit_denoise: params.reserved must be 0");
+            return fail(RL_E_INVALID, name + sigma_names[k] + " must be 0 (the term is off) or in [1e-3, 1e3]");
+    if (p.reserved[0] != 0u || p.reserved[1] != 0u || p.reserved[2] != 0u) return fail(RL_E_INVALID, name + "params.reserved must be 0");
     RlGatherUnit* const given[5] = {image, albedo, normal, aux, dst};
     for (int a = 0; a < 5; ++a)
         for (int b = a + 1; b < 5; ++b)
-            if (given[a] && given[a] == given[b]) return fail(RL_E_INVALID, "rl_denoise_unit_denoise: the gather units must be distinct handles");
+            if (given[a] && given[a] == given[b]) return fail(RL_E_INVALID, name + "the gather units must be distinct handles");
+    if (error && error->observations < 2)
+        return fail(RL_E_STATE, name + std::to_string(error->observations) + " observations in the error unit: a variance needs at least 2");
     int rc = RL_OK, cus = 256;
     for (RlGatherUnit* g : given)
         if (g && (rc = match_check(g, u)) != RL_OK) return rc;
+    if (error && (rc = match_check(error, u)) != RL_OK) return rc;
     if ((rc = enter_device(u->device, &cus)) != RL_OK) return rc;
     const uint32_t iterations = p.iterations ? p.iterations : RL_DENOISE_ITERATIONS;
     const uint32_t n_pixels = u->width * u->height;
+    if (error && !u->variance[1]) { // the first variance call on this unit: its two planes, its event and its timed pair
+        if (!u->variance[0]) RL_HIP(u->ledger.make_alloc(&u->variance[0], (size_t)n_pixels * sizeof(float)));
+        if (!u->error_ready) RL_HIP(u->ledger.make_event(&u->error_ready));
+        if (!u->timed_variance.start) RL_HIP(u->ledger.make_pair(&u->timed_variance));
+        RL_HIP(u->ledger.make_alloc(&u->variance[1], (size_t)n_pixels * sizeof(float)));
+    }
     hipStream_t stream = dst->stream;
     u->timed_passes = 0; // the pairs are re-recorded from here on: readable again once the call has completed
+    if (error) u->timed_variance_done = false;
     rc = drained(stream, [&]() -> int {
         for (int k = 0; k < 4; ++k) { // everything queued on the streams of the units the call reads
             const int r = given[k] ? hand_over(u->ready[k], given[k]->stream, stream) : RL_OK;
             if (r != RL_OK) return r;
         }
-        int r = timed_launch(u->timed[0], stream, &g_denoise_launches[0], [&] {
+        int r = error ? hand_over(u->error_ready, error->stream, stream) : RL_OK;
+        if (r != RL_OK) return r;
+        r = timed_launch(u->timed[0], stream, &g_denoise_launches[0], [&] {
             hipLaunchKernelGGL(rl_denoise_guides_kernel, dim3(grid_for(n_pixels, cus)), dim3(RL_BLOCK), 0, stream, albedo ? albedo->acc : nullptr,
                                normal ? normal->acc : nullptr, aux ? aux->acc : nullptr, n_pixels, u->guides);
         });
         if (r != RL_OK) return r;
+        if (error) { // V_0, from the planes as everything queued on the error unit's stream leaves them
+            const double n_total = (double)error->paths, ratio = n_total / (double)(error->observations - 1);
+            r = timed_launch(u->timed_variance, stream, &g_denoise_variance_launches[0], [&] {
+                hipLaunchKernelGGL(rl_variance_denoise_kernel, dim3(grid_for((uint64_t)n_pixels / 2 + 1, cus)), dim3(RL_BLOCK), 0, stream,
+                                   (const double*)error->sum_y, (const double*)error->sum_q, (uint64_t)n_pixels, n_total, ratio, u->variance[0]);
+            });
+            if (r != RL_OK) return r;
+        }
         // k(sigma), f32 on the host
         float k[4];
         for (int t = 0; t < 4; ++t) k[t] = sigmas[t] == 0.0f ? 0.0f : 1.0f / (sigmas[t] * sigmas[t]);
@@ -2785,23 +2841,47 @@ int rl_denoise_unit_denoise(RlDenoiseUnit* u, RlGatherUnit* image, RlGatherUnit*
             job.classes_y = std::min(job.step, u->height);
             job.tiles_x = ((u->width + job.step - 1) / job.step + RL_DENOISE_TILE - 1) / RL_DENOISE_TILE;
             job.tiles_y = ((u->height + job.step - 1) / job.step + RL_DENOISE_TILE - 1) / RL_DENOISE_TILE;
-            job.kc = k[0] * (float)(1u << 2 * i); // the colour sigma halves per pass; exact
+            // the colour sigma halves per pass (exact); in the variance form it stays and the filtered variance shrinks instead
+            job.kc = error ? k[0] : k[0] * (float)(1u << 2 * i);
             job.kn = k[1];
             job.kz = k[2];
             job.ka = k[3];
             // (at most 2^31 / 17 * 32 / 256 workgroups for any image the units accept: one grid dimension holds them)
             const uint64_t groups = (uint64_t)job.tiles_x * job.classes_x * job.tiles_y * job.classes_y;
-            r = timed_launch(u->timed[1 + i], stream, &g_denoise_launches[1], [&] {
-                hipLaunchKernelGGL(rl_denoise_pass_kernel, dim3((uint32_t)groups), dim3(RL_DENOISE_TILE * RL_DENOISE_TILE), 0, stream, in, u->guides, job, out);
-            });
+            if (error)
+                r = timed_launch(u->timed[1 + i], stream, &g_denoise_variance_launches[1], [&] {
+                    hipLaunchKernelGGL(rl_variance_denoise_pass_kernel, dim3((uint32_t)groups), dim3(RL_DENOISE_TILE * RL_DENOISE_TILE), 0, stream, in,
+                                       (const float*)u->variance[i & 1u], (const RlF4*)u->guides, job, out, u->variance[(i + 1u) & 1u]);
+                });
+            else
+                r = timed_launch(u->timed[1 + i], stream, &g_denoise_launches[1], [&] {
+                    hipLaunchKernelGGL(rl_denoise_pass_kernel, dim3((uint32_t)groups), dim3(RL_DENOISE_TILE * RL_DENOISE_TILE), 0, stream, in, u->guides, job, out);
+                });
             if (r != RL_OK) return r;
             in = out;
         }
         RL_HIP(hipMemsetAsync(dst->comp, 0, (size_t)n_pixels * 3 * sizeof(float), stream));
+        if (error && variance_out) // V_iterations, after the last pass and before the drain
+            RL_HIP(hipMemcpyAsync(variance_out, u->variance[iterations & 1u], (size_t)n_pixels * sizeof(float), hipMemcpyDeviceToHost, stream));
         return RL_OK;
     }());
     if (rc == RL_OK) u->timed_passes = iterations;
+    if (rc == RL_OK && error) u->timed_variance_done = true;
     return rc;
+}
+
+} // namespace
+
+int rl_denoise_unit_denoise(RlDenoiseUnit* u, RlGatherUnit* image, RlGatherUnit* albedo, RlGatherUnit* normal, RlGatherUnit* aux,
+                            const RlDenoiseParams* params, RlGatherUnit* dst) {
+    if (!u || !image || !dst) return fail(RL_E_INVALID, "rl_denoise_unit_denoise: null denoise unit, image or dst");
+    return denoise_call("rl_denoise_unit_denoise", u, image, albedo, normal, aux, nullptr, params, dst, nullptr);
+}
+
+int rl_denoise_unit_denoise_variance(RlDenoiseUnit* u, RlGatherUnit* image, RlGatherUnit* albedo, RlGatherUnit* normal, RlGatherUnit* aux,
+                                     RlErrorUnit* error, const RlDenoiseParams* params, RlGatherUnit* dst, float* variance_out) {
+    if (!u || !image || !dst || !error) return fail(RL_E_INVALID, "rl_denoise_unit_denoise_variance: null denoise unit, image, dst or error unit");
+    return denoise_call("rl_denoise_unit_denoise_variance", u, image, albedo, normal, aux, error, params, dst, variance_out);
 }
 
 // ---- SpectralUnit (rl_spectral.hip.h) ---------------------------------------------------------------
@@ -3409,6 +3489,19 @@ int rl_debug_feature_launches(uint64_t out[6]) { return family_launches(g_featur
 int rl_debug_denoise_launches(uint64_t out[2]) {
     if (!out) return fail(RL_E_INVALID, "null output");
     for (int k = 0; k < 2; ++k) out[k] = g_denoise_launches[k].load(std::memory_order_relaxed);
+    return RL_OK;
+}
+int rl_debug_denoise_variance_launches(uint64_t out[2]) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    for (int k = 0; k < 2; ++k) out[k] = g_denoise_variance_launches[k].load(std::memory_order_relaxed);
+    return RL_OK;
+}
+int rl_debug_denoise_variance_ms(RlDenoiseUnit* u, float* ms) {
+    if (!u || !ms) return fail(RL_E_INVALID, "null argument");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    *ms = 0.0f;
+    if (u->timed_variance_done) RL_HIP(hipEventElapsedTime(ms, u->timed_variance.start, u->timed_variance.stop));
     return RL_OK;
 }
 int rl_debug_spectral_launches(uint64_t out[2]) {

@@ -91,6 +91,9 @@ struct AppState {
 };
 
 thread_local std::vector<double> g_last_error_tiles; // rl_app_error_tiles: of this thread's last rl_app_run_to_error
+// rl_app_error_state: the error unit's planes S then Q, k and N at the end of this thread's last rl_app_run_to_error
+thread_local std::vector<double> g_last_error_planes;
+thread_local uint64_t g_last_error_observations = 0, g_last_error_paths = 0;
 
 // The estimate of a Tonemap task, and the stopping rule.  A NaN estimate meets no target.
 int estimate_error(AppState& a) {
@@ -513,9 +516,27 @@ extern "C" int rl_app_error_tiles(double* tiles, uint32_t capacity, uint32_t* n_
     return RL_OK;
 }
 
+extern "C" int rl_app_error_state(double* sum_y, double* sum_q, uint64_t capacity_pixels, uint64_t* n_pixels, uint64_t* observations,
+                                  uint64_t* paths) {
+    const size_t n = g_last_error_planes.size() / 2;
+    if (n_pixels) *n_pixels = (uint64_t)n;
+    if (observations) *observations = g_last_error_observations;
+    if (paths) *paths = g_last_error_paths;
+    if (n == 0) return RL_OK;
+    if (!sum_y || !sum_q || capacity_pixels < n) {
+        rl_internal_set_last_error("rl_app_error_state: the buffers are too small for " + std::to_string(n) + " pixels");
+        return RL_E_INVALID;
+    }
+    std::memcpy(sum_y, g_last_error_planes.data(), n * sizeof(double));
+    std::memcpy(sum_q, g_last_error_planes.data() + n, n * sizeof(double));
+    return RL_OK;
+}
+
 extern "C" int rl_app_run_to_error(const RlAppConfig* config, const RlErrorTarget* target, RlAppStats* stats, RlAppErrorStats* error_stats,
                                    uint8_t* rgb_out) {
     g_last_error_tiles.clear();
+    g_last_error_planes.clear();
+    g_last_error_observations = g_last_error_paths = 0;
     if (error_stats) std::memset(error_stats, 0, sizeof *error_stats);
     if (!config || config->width == 0 || config->height == 0 || config->concurrency == 0) {
         rl_internal_set_last_error("rl_app_run: null config, zero-sized image or zero workers");
@@ -679,6 +700,16 @@ extern "C" int rl_app_run_to_error(const RlAppConfig* config, const RlErrorTarge
     }
     if (error_stats && rc == RL_OK) *error_stats = a.error_stats;
     if (rc == RL_OK && a.error_stats.estimates != 0) g_last_error_tiles = a.error_tiles;
+    if (rc == RL_OK && a.error_unit && a.error_observations != 0) { // rl_app_error_state: the one download of the planes
+        const size_t n = (size_t)config->width * config->height;
+        g_last_error_planes.assign(2 * n, 0.0);
+        rc = rl_error_unit_download(a.error_unit, g_last_error_planes.data(), g_last_error_planes.data() + n, &g_last_error_observations,
+                                    &g_last_error_paths);
+        if (rc != RL_OK) {
+            g_last_error_planes.clear();
+            g_last_error_observations = g_last_error_paths = 0;
+        }
+    }
     if (rgb_out && rc == RL_OK) std::memcpy(rgb_out, a.rgb.data(), a.rgb.size());
     std::string message = a.error_message;
     if (rc != RL_OK && message.empty()) message = rl_last_error(); // a set-up call on this thread failed

@@ -2,7 +2,8 @@
 // over a gather unit's tristimulus buffer, guided by the films of rl_scene_render_features.  The arithmetic is the contract stated
 // in include/robigo_luculenta.h: f32, in the stated order, no contraction; add, multiply, the correctly rounded divide, rl_sqrtf and
 // rl_expf only, so the CPU restatement (tests/_denoise_oracle.py) is held bit for bit.  Included by rl_api.hip; needs rl_math.h and
-// rl_core.h (RlF4) only: no scene, no ray kernel.
+// rl_core.h (RlF4) only: no scene, no ray kernel.  At the end, the two kernels of rl_denoise_unit_denoise_variance: the same pass with
+// the error unit's variance as the colour term, held to tests/_denoise_variance_oracle.py in the same way.
 #pragma once
 
 static_assert(sizeof(RlF4) == 16 && alignof(RlF4) == 16, "the guide record and the LDS tile are read in 16-byte words");
@@ -44,13 +45,24 @@ struct RlDenoisePass {
     float kc, kn, kz, ka;
 };
 
-// The weight of tap q for centre p and its three products, added to the sums: the per-tap table of the contract, in its order.
-// cp, cq: C_i of p and q; np, nq: {n.xyz, z}; ap, aq: {a.xyz, live}; hh: h[dy + 2] * h[dx + 2].
-__device__ __forceinline__ void rl_denoise_tap(const RlDenoisePass& job, RlF3 cp, RlF4 np, RlF4 ap, RlF3 cq, RlF4 nq, RlF4 aq, float hh,
-                                               float* sum_w, RlF3* sum_c) {
-    const float m = fabsf(cp.y) + fabsf(cq.y);
-    const float r = m > 0.0f ? (cp.y - cq.y) / m : 0.0f;
-    const float e_c = r * r;
+// The weight of tap q for centre p and its products, added to the sums: the per-tap table of the contract, in its order.
+// cp, cq: C_i of p and q; np, nq: {n.xyz, z}; ap, aq: {a.xyz, live}; hh: h[dy + 2] * h[dx + 2].  The colour term is all that
+// differs between the two forms: the relative difference of luminance (rl_denoise_unit_denoise), or, with VARIANCE, the squared
+// difference over the sum vp + vq of the two pixels' variances V_i (rl_denoise_unit_denoise_variance), whose filtered sum the tap
+// then adds to *sum_v.
+template <bool VARIANCE>
+__device__ __forceinline__ void rl_denoise_tap(const RlDenoisePass& job, RlF3 cp, float vp, RlF4 np, RlF4 ap, RlF3 cq, float vq, RlF4 nq, RlF4 aq,
+                                               float hh, float* sum_w, RlF3* sum_c, float* sum_v) {
+    float e_c;
+    if (VARIANCE) {
+        const float dl = cp.y - cq.y;
+        const float m = vp + vq;
+        e_c = m > 0.0f ? (dl * dl) / m : 0.0f;
+    } else {
+        const float m = fabsf(cp.y) + fabsf(cq.y);
+        const float r = m > 0.0f ? (cp.y - cq.y) / m : 0.0f;
+        e_c = r * r;
+    }
     const float dx = np.x - nq.x, dy = np.y - nq.y, dz = np.z - nq.z;
     const float e_n = (dx * dx + dy * dy) + dz * dz;
     const float mz = np.w > nq.w ? np.w : nq.w;
@@ -64,6 +76,7 @@ __device__ __forceinline__ void rl_denoise_tap(const RlDenoisePass& job, RlF3 cp
     sum_c->x += wt * cq.x;
     sum_c->y += wt * cq.y;
     sum_c->z += wt * cq.z;
+    if (VARIANCE) *sum_v += (wt * wt) * vq;
 }
 
 // The taps of a pixel lie on the lattice of stride s through it, so a workgroup takes a 16 x 16 LATTICE tile -- the pixels
@@ -77,6 +90,7 @@ __device__ __forceinline__ void rl_denoise_tap(const RlDenoisePass& job, RlF3 cp
 //   lane lx of either row on word (lx + const) mod 16: conflict-free.  32 is the smallest such pitch that holds 20.
 //   Measured against the same loop reading every tap from global memory (profiles/denoise_bench.txt): the
 //   tile wins at s = 1, 2, 4 and draws at s = 8, 16, where its staging loads are strided; it is kept for every step.
+//   The body of the kernel is rl_denoise_pass.inc.h, shared as text with the variance form below.
 #define RL_DENOISE_TILE 16
 #define RL_DENOISE_HALO 2
 #define RL_DENOISE_SPAN (RL_DENOISE_TILE + 2 * RL_DENOISE_HALO)
@@ -85,59 +99,49 @@ __device__ __forceinline__ void rl_denoise_tap(const RlDenoisePass& job, RlF3 cp
 
 __global__ __launch_bounds__(RL_DENOISE_TILE * RL_DENOISE_TILE) void rl_denoise_pass_kernel(const float* __restrict__ in, const RlF4* __restrict__ guides,
                                                                                           RlDenoisePass job, float* __restrict__ out) {
-    __shared__ RlF4 s_c[RL_DENOISE_LDS_WORDS], s_n[RL_DENOISE_LDS_WORDS], s_a[RL_DENOISE_LDS_WORDS];
-    // the workgroup's residue class and tile: blockIdx.x = ((ry * tiles_y + ty) * classes_x + rx) * tiles_x + tx
-    uint32_t b = blockIdx.x;
-    const uint32_t tx = b % job.tiles_x;
-    b /= job.tiles_x;
-    const uint32_t rx = b % job.classes_x;
-    b /= job.classes_x;
-    const uint32_t ty = b % job.tiles_y;
-    const uint32_t ry = b / job.tiles_y;
-    const int s = (int)job.step;
-    // lattice coordinates of the neighbourhood's corner; pixel = residue + s * lattice
-    const long long lx0 = (long long)tx * RL_DENOISE_TILE - RL_DENOISE_HALO, ly0 = (long long)ty * RL_DENOISE_TILE - RL_DENOISE_HALO;
-    for (uint32_t e = threadIdx.x; e < RL_DENOISE_SPAN * RL_DENOISE_SPAN; e += RL_DENOISE_TILE * RL_DENOISE_TILE) {
-        const uint32_t u = e % RL_DENOISE_SPAN, v = e / RL_DENOISE_SPAN;
-        // (64-bit: s * lattice stays far below 2^63 for any image the units accept, and a pixel past the edge must not wrap)
-        const long long px = (long long)rx + s * (lx0 + u), py = (long long)ry + s * (ly0 + v);
-        RlF4 c = RlF4{0.0f, 0.0f, 0.0f, 0.0f}, gn = c, ga = c;
-        if (px >= 0 && px < (long long)job.width && py >= 0 && py < (long long)job.height) {
-            const size_t p = (size_t)py * job.width + (size_t)px;
-            gn = guides[p * RL_DENOISE_GUIDE_WORDS];
-            ga = guides[p * RL_DENOISE_GUIDE_WORDS + 1];
-            c = RlF4{in[p * 3], in[p * 3 + 1], in[p * 3 + 2], ga.w};
-        }
-        s_c[v * RL_DENOISE_PITCH + u] = c;
-        s_n[v * RL_DENOISE_PITCH + u] = gn;
-        s_a[v * RL_DENOISE_PITCH + u] = ga;
+#define RL_DENOISE_VARIANCE 0
+#include "rl_denoise_pass.inc.h"
+#undef RL_DENOISE_VARIANCE
+}
+
+// ---- the variance form (rl_denoise_unit_denoise_variance) ----
+// (The two kernels are named apart from the rl_denoise_ pair: tests/test_denoise.py holds that prefix to exactly the two above.)
+
+// The same pass with the variance colour term: reads C_i and V_i, writes C_{i+1} and V_{i+1}.  job.kc is kv, the same every pass.
+__global__ __launch_bounds__(RL_DENOISE_TILE * RL_DENOISE_TILE) void rl_variance_denoise_pass_kernel(const float* __restrict__ in,
+                                                                                                   const float* __restrict__ v_in,
+                                                                                                   const RlF4* __restrict__ guides, RlDenoisePass job,
+                                                                                                   float* __restrict__ out, float* __restrict__ v_out) {
+#define RL_DENOISE_VARIANCE 1
+#include "rl_denoise_pass.inc.h"
+#undef RL_DENOISE_VARIANCE
+}
+
+// V_0 from the error unit's planes: d = Q - (S * S) / N, d < 0 ? 0 : d, v = d * ratio, (float)v -- rl_error_estimate_kernel's v, so
+// rl_sqrtf(V_0) is that kernel's se.  `ratio` is (double)N / (double)(k - 1), divided on the host.  Pointwise, 16 B read and 4 B
+// written per pixel; two pixels a lane as rl_error_observe_kernel takes them, for the same reason held to 32 VGPRs: it may run
+// beside a resident open trace kernel.
+__device__ __forceinline__ float rl_denoise_variance_one(double s, double q, double n_total, double ratio) {
+    double d = q - (s * s) / n_total;
+    d = d < 0.0 ? 0.0 : d;
+    const double v = d * ratio;
+    return (float)v;
+}
+
+__global__ __launch_bounds__(RL_BLOCK) __attribute__((amdgpu_num_vgpr(32))) void rl_variance_denoise_kernel(const double* __restrict__ sum_y,
+                                                                                                           const double* __restrict__ sum_q,
+                                                                                                           uint64_t n_pixels, double n_total, double ratio,
+                                                                                                           float* __restrict__ variance) {
+    const uint64_t n2 = n_pixels / 2;
+    const double2* s2 = (const double2*)sum_y;
+    const double2* q2 = (const double2*)sum_q;
+    float2* v2 = (float2*)variance;
+    for (uint64_t i = (uint64_t)blockIdx.x * RL_BLOCK + threadIdx.x; i < n2; i += (uint64_t)gridDim.x * RL_BLOCK) {
+        const double2 s = s2[i], q = q2[i];
+        v2[i] = float2{rl_denoise_variance_one(s.x, q.x, n_total, ratio), rl_denoise_variance_one(s.y, q.y, n_total, ratio)};
     }
-    __syncthreads();
-    const uint32_t i = threadIdx.x % RL_DENOISE_TILE, j = threadIdx.x / RL_DENOISE_TILE;
-    const long long px = (long long)rx + s * (lx0 + RL_DENOISE_HALO + i), py = (long long)ry + s * (ly0 + RL_DENOISE_HALO + j);
-    if (px >= (long long)job.width || py >= (long long)job.height) return;
-    const uint32_t centre = (j + RL_DENOISE_HALO) * RL_DENOISE_PITCH + (i + RL_DENOISE_HALO);
-    const RlF4 c4 = s_c[centre];
-    const RlF3 cp = rl_f3(c4.x, c4.y, c4.z);
-    RlF3 result = cp;
-    if (c4.w != 0.0f) {
-        const RlF4 np = s_n[centre], ap = s_a[centre];
-        const float h[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
-        float sum_w = 0.0f;
-        RlF3 sum_c = rl_f3(0.0f, 0.0f, 0.0f);
-#pragma unroll
-        for (int dy = -2; dy <= 2; ++dy) {
-#pragma unroll
-            for (int dx = -2; dx <= 2; ++dx) {
-                const uint32_t q = (uint32_t)((int)centre + dy * RL_DENOISE_PITCH + dx);
-                const RlF4 q4 = s_c[q];
-                if (q4.w != 0.0f) rl_denoise_tap(job, cp, np, ap, rl_f3(q4.x, q4.y, q4.z), s_n[q], s_a[q], h[dy + 2] * h[dx + 2], &sum_w, &sum_c);
-            }
-        }
-        result = rl_f3(sum_c.x / sum_w, sum_c.y / sum_w, sum_c.z / sum_w);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && (n_pixels & 1)) {
+        const uint64_t p = n_pixels - 1;
+        variance[p] = rl_denoise_variance_one(sum_y[p], sum_q[p], n_total, ratio);
     }
-    const size_t p = (size_t)py * job.width + (size_t)px;
-    out[p * 3] = result.x;
-    out[p * 3 + 1] = result.y;
-    out[p * 3 + 2] = result.z;
 }
