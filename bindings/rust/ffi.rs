@@ -97,12 +97,17 @@ pub const RL_COMM_ID_BYTES: usize = 128;
 #[repr(C)] #[derive(Copy, Clone, Default)] pub struct RlErrorTarget {
     pub relative_error: f64, pub worst_tile_error: f64, pub min_observations: u32, pub reserved: u32,
 }
+#[repr(C)] #[derive(Copy, Clone, Default)] pub struct RlAdaptiveStats {
+    pub n_paths: u64, pub tiles_x: u32, pub tiles_y: u32, pub min_count: u32, pub max_count: u32,
+    pub min_weight: f32, pub max_weight: f32, pub importance_sum: f64,
+}
 #[repr(C)] #[derive(Copy, Clone, Default)] pub struct RlAppErrorStats {
     pub at_stop: RlErrorStats, pub at_end: RlErrorStats, pub reached: u32, pub estimates: u32,
 }
 
 pub enum RlScene {} pub enum RlTraceUnit {} pub enum RlPlotUnit {} pub enum RlGatherUnit {} pub enum RlTonemapUnit {}
 pub enum RlScheduler {} pub enum RlComm {} pub enum RlDenoiseUnit {} pub enum RlSpectralUnit {} pub enum RlErrorUnit {}
+pub enum RlAdaptiveUnit {}
 
 extern "C" {
     pub fn rl_last_error() -> *const c_char;
@@ -242,6 +247,17 @@ extern "C" {
     pub fn rl_error_unit_estimate(unit: *mut RlErrorUnit, stats: *mut RlErrorStats, se: *mut f32, tiles: *mut f64) -> c_int;
     pub fn rl_error_unit_download(unit: *mut RlErrorUnit, sum_y: *mut f64, sum_q: *mut f64, observations: *mut u64, paths: *mut u64) -> c_int;
     pub fn rl_error_unit_upload(unit: *mut RlErrorUnit, sum_y: *const f64, sum_q: *const f64, observations: u64, paths: u64) -> c_int;
+    pub fn rl_adaptive_unit_create(device: c_int, width: u32, height: u32, out: *mut *mut RlAdaptiveUnit) -> c_int;
+    pub fn rl_adaptive_unit_destroy(unit: *mut RlAdaptiveUnit) -> c_int;
+    pub fn rl_adaptive_unit_plan(unit: *mut RlAdaptiveUnit, importance: *const f64, uniform_share: f64, n_paths: u64,
+                                 stats: *mut RlAdaptiveStats) -> c_int;
+    pub fn rl_adaptive_unit_download_plan(unit: *mut RlAdaptiveUnit, counts: *mut u32, weights: *mut f32) -> c_int;
+    pub fn rl_adaptive_unit_samples(unit: *mut RlAdaptiveUnit, scene: *const RlScene, seed: u64, stream: u32, first_path_index: u64,
+                                    first_sample: u64, n: u32, out: *mut RlCameraSample) -> c_int;
+    pub fn rl_adaptive_unit_samples_device(unit: *mut RlAdaptiveUnit, scene: *const RlScene, seed: u64, stream: u32, first_path_index: u64,
+                                           first_sample: u64, n: u32, device_out: *mut RlCameraSample) -> c_int;
+    pub fn rl_plot_unit_render_adaptive(plot: *mut RlPlotUnit, unit: *mut RlAdaptiveUnit, scene: *const RlScene, primitive_fetch: c_int,
+                                        seed: u64, stream: u32, first_path_index: u64, max_segments: u32) -> c_int;
 
     pub fn rl_gather_unit_create(device: c_int, w: u32, h: u32, out: *mut *mut RlGatherUnit) -> c_int;
     pub fn rl_gather_unit_destroy(u: *mut RlGatherUnit) -> c_int;

@@ -118,6 +118,7 @@ typedef struct RlTonemapUnit RlTonemapUnit;
 typedef struct RlDenoiseUnit RlDenoiseUnit;
 typedef struct RlSpectralUnit RlSpectralUnit;
 typedef struct RlErrorUnit RlErrorUnit;
+typedef struct RlAdaptiveUnit RlAdaptiveUnit;
 typedef struct RlScheduler RlScheduler;
 typedef struct RlComm RlComm;
 
@@ -1006,6 +1007,87 @@ int rl_error_unit_observe(RlErrorUnit* unit, RlPlotUnit* plot, uint64_t n_paths)
 int rl_error_unit_estimate(RlErrorUnit* unit, RlErrorStats* stats, float* se, double* tiles);
 int rl_error_unit_download(RlErrorUnit* unit, double* sum_y, double* sum_q, uint64_t* observations, uint64_t* paths);
 int rl_error_unit_upload(RlErrorUnit* unit, const double* sum_y, const double* sum_q, uint64_t observations, uint64_t paths);
+
+/* ---- adaptive sampling: camera samples drawn tile by tile from an importance map (rl_adaptive_unit_*) ---- */
+
+/* An adaptive unit holds a plan for one batch of n_paths camera paths over a width x height film: how many of them start in each
+ * RL_ERROR_TILE x RL_ERROR_TILE tile (the error unit's tiles, raster order, tiles_x = ceil(width / 16)), and the weight their
+ * splats carry so that the film's expectation is the uniform sampler's.  The importance is the caller's: a tile's t_se of
+ * rl_error_unit_estimate is the intended one.
+ *   Cells.  In continuous pixel coordinates a photon sits at px = (x * 0.5 + 0.5) * (width - 1) (plot_unit.rs:60-61).  The cell of
+ *     tile column i is [max(0, 16 i - 0.5), min(width - 1, 16 i + 15.5)], rows the same way with the height: the cells tile
+ *     [0, width - 1] x [0, height - 1] exactly, a partial last tile is a cell like any other (for width = 16 i + 1 the last cell
+ *     is 0.5 wide).  The area a_t of a cell is exact in f64; the areas sum to A = (width - 1)(height - 1).
+ *   rl_adaptive_unit_plan(unit, importance, uniform_share, n_paths, stats).  importance: tiles_y * tiles_x doubles of host memory
+ *     in raster order, or NULL for the uniform plan.  The rule, in f64 in exactly this order, never contracted, the divide correctly
+ *     rounded:
+ *       g_t = importance[t] if it is finite and > 0, else 0;  G = the sequential sum of g_t in raster order from +0.0.
+ *       A G that is infinite is RL_E_INVALID.  NULL, or G == 0: q_t = a_t / A.  Otherwise, with u = uniform_share:
+ *         q_t = u * (a_t / A) + (1 - u) * (g_t / G).
+ *       e_t = (double)n_paths * q_t;  c_t = floor(e_t);  r_t = e_t - floor(e_t).
+ *       The n_paths - sum c_t paths left over go one each to the tiles with the largest r_t, ties to the lower tile index.
+ *       w_t = (float)(((double)n_paths * a_t) / (A * (double)c_t)).
+ *     So sum c_t == n_paths exactly and |c_t - n_paths q_t| < 1.  Every tile must have c_t >= 1 -- a tile nobody samples is a
+ *     biased image: if one would get 0 the call is RL_E_INVALID and the unit keeps its previous plan.  w_t is the unbiasedness
+ *     condition: c_t w_t / a_t = n_paths / A for every tile, so any weighted splat has the uniform sampler's expectation, whichever
+ *     pixels its four taps land on, a neighbouring tile's included.  The bits of c_t and w_t are the contract
+ *     (tests/_adaptive_oracle.py restates the rule in numpy).
+ *     Checked in this order, each RL_E_INVALID before any device work: a NULL unit; uniform_share not in (0, 1] (a NaN too);
+ *     n_paths == 0 or > 2^32 - 1; then the rule's own refusals.  `stats` may be NULL.  The call uploads the exclusive prefix sums
+ *     off[t] of the counts (32 bits), the cells and the weights, and returns when they are on the device.
+ *   rl_adaptive_unit_download_plan(unit, counts, weights) reads the plan back from the device: tiles_y * tiles_x uint32_t and
+ *     floats of host memory, either may be NULL.  A unit starts with no plan; calls that need one return RL_E_STATE.
+ *   rl_adaptive_unit_samples(unit, scene, seed, stream, first_path_index, first_sample, n, out).  out[i] is sample
+ *     j = first_sample + i of the plan, which is path first_path_index + j of RNG stream `stream` under `seed`; its tile is the t
+ *     with off[t] <= j < off[t + 1].  It draws what rl_scene_camera_rays draws for that path from blocks 0 and 1, word for word: the
+ *     wavelength from w[0], the camera time from w[3], the lens from block 1.  Only the screen position differs, f32 in exactly
+ *     this order, never contracted, the divide correctly rounded:
+ *       u = get_unit(w[1]);  px = x_lo + (x_hi - x_lo) * u;  x = (px / ((float)width - 1) - 0.5f) * 2.0f;
+ *       v = get_unit(w[2]);  py = y_lo + (y_hi - y_lo) * v;  y = ((py / ((float)height - 1) - 0.5f) * 2.0f) / aspect_ratio;
+ *     with the cell's bounds rounded to f32 and aspect_ratio = (float)width / (float)height.  From there the ray is
+ *     rl_scene_camera_rays' arithmetic.  out[i] holds the ray, x, y, reserved0 = t and reserved1 = the bits of w_t; the film calls
+ *     that take camera samples ignore both reserved fields.
+ *     Checked in this order: a NULL unit, a NULL scene, NULL `out` with n > 0 (RL_E_INVALID); no plan (RL_E_STATE);
+ *     first_sample + n > n_paths, path indices that reach 2^64 - 1 (RL_E_INVALID); unit and scene on different devices
+ *     (RL_E_STATE).  n = 0 does nothing.  Host and _device forms as rl_scene_camera_rays*; the _device form wants device_out
+ *     16-byte aligned (RL_E_INVALID).
+ *   rl_plot_unit_render_adaptive(plot, unit, scene, primitive_fetch, seed, stream, first_path_index, max_segments) renders the
+ *     whole plan into `plot`, in chunks of at most 2^20 samples in scratch the adaptive unit owns (taken at the first such call):
+ *     the samples; their rays traced as rl_scene_render_rays_device traces them (the same launch of the same kernel, so the
+ *     results are that call's bit for bit); and for every path with value != 0 and a finite position
+ *     get_tristimulus(wavelength) * (value * w_t) -- one f32 multiply of value and weight -- added to the four pixels of
+ *     plot_pixel(x, y) by rl_plot_unit_plot_photons' arithmetic.  The buffer then holds an unbiased estimate of what n_paths
+ *     uniform paths would sum to, so rl_error_unit_observe(error, plot, n_paths) and rl_gather_unit_accumulate take it as they take
+ *     any batch.  Batches under different plans are independent but not identically distributed: the batch-deviation estimate of
+ *     the error unit stays valid on the conservative side (the spread between plans adds to the spread it measures).
+ *     Checked in this order, each RL_E_INVALID before any device work: NULL plot unit, NULL adaptive unit, NULL scene, unknown
+ *     fetch mode, max_segments > RL_PATH_MAX_SEGMENTS_CAP; then no plan (RL_E_STATE); path indices that reach 2^64 - 1
+ *     (RL_E_INVALID); a film of another size than the plot unit's, or the three handles not on one device (RL_E_STATE).
+ *     Ordering is rl_plot_unit_render_samples_device's: a fused render begun into `plot` ends first, the call runs after everything
+ *     queued into the plot unit, orders against open launches as rl_scene_render_rays does, and returns when the splats are in the
+ *     buffer.
+ *   rl_adaptive_unit_create refuses a NULL `out`, a width or height below 2 (plot_pixel maps x onto [0, width - 1]: a 1-wide film
+ *     has no area) and width * height > RL_MAX_PIXELS (RL_E_INVALID, in this order, before any device work).
+ *   One user per adaptive unit at a time. */
+typedef struct RlAdaptiveStats {
+    uint64_t n_paths;
+    uint32_t tiles_x, tiles_y;        /* ceil(width / 16), ceil(height / 16) */
+    uint32_t min_count, max_count;    /* over the tiles */
+    float min_weight, max_weight;
+    double importance_sum;            /* G; 0 for the uniform plan */
+} RlAdaptiveStats;
+
+int rl_adaptive_unit_create(int device, uint32_t width, uint32_t height, RlAdaptiveUnit** out);
+int rl_adaptive_unit_destroy(RlAdaptiveUnit* unit);
+int rl_adaptive_unit_plan(RlAdaptiveUnit* unit, const double* importance, double uniform_share, uint64_t n_paths,
+                          RlAdaptiveStats* stats);
+int rl_adaptive_unit_download_plan(RlAdaptiveUnit* unit, uint32_t* counts, float* weights);
+int rl_adaptive_unit_samples(RlAdaptiveUnit* unit, const RlScene* scene, uint64_t seed, uint32_t stream, uint64_t first_path_index,
+                             uint64_t first_sample, uint32_t n, RlCameraSample* out);
+int rl_adaptive_unit_samples_device(RlAdaptiveUnit* unit, const RlScene* scene, uint64_t seed, uint32_t stream,
+                                    uint64_t first_path_index, uint64_t first_sample, uint32_t n, RlCameraSample* device_out);
+int rl_plot_unit_render_adaptive(RlPlotUnit* plot, RlAdaptiveUnit* unit, const RlScene* scene, int primitive_fetch, uint64_t seed,
+                                 uint32_t stream, uint64_t first_path_index, uint32_t max_segments);
 
 /* ---- GatherUnit (gather_unit.rs:24-92) ----------------------------------------------------- */
 

@@ -92,6 +92,13 @@ int rl_debug_error_launches(uint64_t out[2]);
 /* Device time in milliseconds, from events around the launch: out[0] the unit's last observe launch, out[1] its last estimate
  * launch; 0 before the first.  Waits for the launch.  tools/error_bench.py. */
 int rl_debug_error_ms(RlErrorUnit* unit, float out[2]);
+/* out[0]: launches of rl_adaptive_samples_kernel (one per chunk of rl_adaptive_unit_samples* and of rl_plot_unit_render_adaptive),
+ * out[1]: path kernel launches made by rl_plot_unit_render_adaptive (counted in rl_debug_path_launches too), out[2]: launches of
+ * rl_adaptive_splat_kernel, since the library was loaded. */
+int rl_debug_adaptive_launches(uint64_t out[3]);
+/* Device time in milliseconds, from events around the launches of the last chunk of the unit's last completed
+ * rl_plot_unit_render_adaptive: out[0] the sample kernel, out[1] the path kernel, out[2] the splat kernel; 0 before the first. */
+int rl_debug_adaptive_ms(RlAdaptiveUnit* unit, float out[3]);
 /* rl_gather_unit_accumulate(unit, plot) between two events on the gather unit's stream, with both units' streams drained before
  * and the gather unit's after: *ms is the device time of that call's rl_gather_kernel launch, the yardstick tools/error_bench.py
  * holds the observe kernel to.  The accumulation happens as usual. */

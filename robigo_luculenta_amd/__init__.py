@@ -14,7 +14,7 @@ from ._lib import (RlAppConfig, RlAppStats, RlCameraDesc, RlCameraSample, RlErro
                    RL_PATH_MAX_SEGMENTS_CAP, RL_TASK_MAX_UNITS, RlLightSample, RlDirectStats, RL_LIGHT_SKIPPED, RL_LIGHT_BACKFACING, RL_LIGHT_OCCLUDED,
                    RL_LIGHT_VISIBLE, RlFeatureSample, RlFeatureStats, RL_FEATURE_VOID, RL_FEATURE_EMITTER, RL_FEATURE_DIFFUSE, RL_FEATURE_LIMIT,
                    RL_FEATURE_MAX_SEGMENTS, RlDenoiseParams, RL_DENOISE_ITERATIONS, RL_DENOISE_MAX_ITERATIONS,
-                   RL_SPECTRAL_MAX_NODES, RlErrorStats, RlErrorTarget, RlAppErrorStats, RL_ERROR_TILE)
+                   RL_SPECTRAL_MAX_NODES, RlErrorStats, RlErrorTarget, RlAppErrorStats, RL_ERROR_TILE, RlAdaptiveStats)
 
 PHOTON_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("probability", "<f4"), ("wavelength", "<f4")])
 OBJECT_DTYPE = np.dtype([("surface_kind", "<u4"), ("material_kind", "<u4"), ("v0", "<f4", 3), ("v1", "<f4", 3),
@@ -523,6 +523,11 @@ class PlotUnit(_Handle):
         check(lib.rl_plot_unit_render_samples_device(self._h, scene.handle, fetch, seed, stream, first, max_segments, _device_ptr(samples), n,
                                                      _device_ptr(results)))
 
+    def render_adaptive(self, adaptive, scene, seed, stream, first_path_index=0, fetch=FETCH_LDS, max_segments=0):
+        """rl_plot_unit_render_adaptive: renders the whole plan of AdaptiveUnit `adaptive` as paths first_path_index .. of (seed,
+        stream): its samples traced as Scene.render_rays_device traces them and splatted with their tiles' weights, complete on
+        return.  The buffer then holds an unbiased estimate of what as many uniform paths would sum to."""
+        check(lib.rl_plot_unit_render_adaptive(self._h, adaptive.handle, scene.handle, fetch, seed, stream, first_path_index, max_segments))
 
     def light_paths(self, scene, states, hits, camera, seed, stream, list=None, n_list=None, fetch=FETCH_LDS, sampled=None, samples=None):
         """Scene.light_paths with a film (rl_plot_unit_light_paths): the states of an (n,) PATH_STATE_DTYPE array that `list`
@@ -902,6 +907,89 @@ def error_tile_rel(tiles):
         return (pairs[:, 0] / np.where(pairs[:, 1] > m, pairs[:, 1], m)).reshape(np.asarray(tiles).shape[:-1])
 
 
+class AdaptiveUnit(_Handle):
+    """Adaptive sampling (rl_adaptive_unit_*): a plan of how many of a batch's camera paths start in each 16 x 16 tile of the film
+    and the weight their splats carry, so that the film's expectation is the uniform sampler's."""
+    _destroy = lib.rl_adaptive_unit_destroy
+
+    def __init__(self, width, height, device=0):
+        super().__init__()
+        check(lib.rl_adaptive_unit_create(device, width, height, C.byref(self._h)))
+        self.width, self.height, self.device = width, height, device
+        self.tiles_x, self.tiles_y = -(-width // RL_ERROR_TILE), -(-height // RL_ERROR_TILE)
+
+    def plan(self, importance, uniform_share, n_paths):
+        """rl_adaptive_unit_plan: importance is None (the uniform plan) or tiles_y * tiles_x values in raster order.  Returns the
+        plan's stats as a dict.  A plan that would leave a tile without a sample raises RlError and the previous plan stays."""
+        g = None
+        if importance is not None:
+            g = np.ascontiguousarray(importance, dtype=np.float64).reshape(-1)
+            if len(g) != self.tiles_x * self.tiles_y:
+                raise ValueError("importance must hold tiles_y * tiles_x values")
+        stats = RlAdaptiveStats()
+        check(lib.rl_adaptive_unit_plan(self._h, _host_ptr(g), uniform_share, n_paths, C.byref(stats)))
+        return {name: getattr(stats, name) for name, _ in RlAdaptiveStats._fields_}
+
+    def plan_from_error_tiles(self, tiles, uniform_share, n_paths):
+        """plan() with a tile's t_se as its importance: `tiles` is rl_error_unit_estimate's (tiles_y, tiles_x, 2) {t_se, t_y} array."""
+        return self.plan(np.asarray(tiles, dtype=np.float64).reshape(self.tiles_y, self.tiles_x, 2)[:, :, 0], uniform_share, n_paths)
+
+    def download_plan(self):
+        """(counts uint32, weights float32), each (tiles_y, tiles_x), read back from the device."""
+        counts = np.zeros((self.tiles_y, self.tiles_x), dtype=np.uint32)
+        weights = np.zeros((self.tiles_y, self.tiles_x), dtype=np.float32)
+        check(lib.rl_adaptive_unit_download_plan(self._h, _host_ptr(counts), _host_ptr(weights)))
+        return counts, weights
+
+    def samples(self, scene, seed, stream, first_path_index, first_sample, n):
+        """rl_adaptive_unit_samples: samples first_sample .. first_sample + n - 1 of the plan as an (n,) CAMERA_SAMPLE_DTYPE array;
+        reserved0 is the sample's tile, reserved1 the bits of its weight."""
+        out = np.empty(n, dtype=CAMERA_SAMPLE_DTYPE)
+        check(lib.rl_adaptive_unit_samples(self._h, scene.handle, seed, stream, first_path_index, first_sample, n, _host_ptr(out)))
+        return out
+
+    def samples_device(self, scene, seed, stream, first_path_index, first_sample, samples, n=None):
+        """rl_adaptive_unit_samples_device: fills a device buffer with data_ptr() (e.g. a torch tensor) with n records, by default
+        as many as it holds whole."""
+        room = _n_bytes(samples) // CAMERA_SAMPLE_DTYPE.itemsize
+        n = room if n is None else n
+        if n > room:
+            raise ValueError("samples must have room for n 48-byte records")
+        check(lib.rl_adaptive_unit_samples_device(self._h, scene.handle, seed, stream, first_path_index, first_sample, n, _device_ptr(samples)))
+
+    def launch_ms(self):
+        """Device milliseconds of the (sample, path, splat) launches of the last chunk of this unit's last render (rl_debug_adaptive_ms)."""
+        out = (C.c_float * 3)()
+        check(lib.rl_debug_adaptive_ms(self._h, out))
+        return tuple(out)
+
+
+def render_adaptive_to_error(scene, plot, gather, error, adaptive, n_paths_per_batch, max_batches, target_error, uniform_share=0.25,
+                             min_observations=4, seed=1, stream=0, first_path_index=0, fetch=FETCH_LDS, max_segments=0, adaptive_sampling=True):
+    """Renders batches of n_paths_per_batch paths into `plot`, shows each to `error` and accumulates it into `gather` (the plot unit is
+    cleared by the accumulation), until rl_error_unit_estimate's relative_error is at most target_error or max_batches are made.  The plans
+    are uniform until the error unit has min_observations (at least 2); from then on every batch is planned from the running tile
+    map (a tile's t_se), with uniform_share of the paths spread by area.  adaptive_sampling=False keeps the uniform plan throughout:
+    the same driver as the yardstick.  `error` must be empty (ErrorUnit.clear): the driver counts its own batches as the unit's
+    observations.  Returns (batches made, the last estimate's stats or None, its tiles or None)."""
+    if max(2, min_observations) > max_batches:
+        raise ValueError("max_batches leaves no room for min_observations")
+    stats = tiles = None
+    adaptive.plan(None, uniform_share, n_paths_per_batch)
+    for batch in range(max_batches):
+        plot.render_adaptive(adaptive, scene, seed, stream, first_path_index + batch * n_paths_per_batch, fetch=fetch, max_segments=max_segments)
+        error.observe(plot, n_paths_per_batch)
+        gather.accumulate(plot)       # (and clears the plot unit)
+        if batch + 1 < max(2, min_observations):
+            continue
+        stats, _, tiles = error.estimate(se=False)
+        if stats["relative_error"] <= target_error:
+            return batch + 1, stats, tiles
+        if adaptive_sampling and batch + 1 < max_batches:
+            adaptive.plan_from_error_tiles(tiles, uniform_share, n_paths_per_batch)
+    return max_batches, stats, tiles
+
+
 class Task:
     """enum Task (task_scheduler.rs:26-41) by unit ids."""
 
@@ -1127,6 +1215,12 @@ def error_launches():
     """(launches of the error unit's observe kernel, launches of its estimate kernel) since the library was loaded
     (rl_debug_error_launches)."""
     return _launch_counters(lib.rl_debug_error_launches, 2, tuple)
+
+
+def adaptive_launches():
+    """(sample kernel launches, path kernel launches made by render_adaptive, splat kernel launches) since the library was loaded
+    (rl_debug_adaptive_launches)."""
+    return _launch_counters(lib.rl_debug_adaptive_launches, 3, tuple)
 
 
 def live_resources():

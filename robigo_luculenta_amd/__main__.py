@@ -7,7 +7,9 @@ With --denoise-variance as well the filter's colour term is the noise estimate's
 as the image converges, which the plain filter does not.
 With --spectral PATH the same paths are rendered once more into a spectral film (SpectralUnit) and the cube is saved as PATH (.npy).
 With --target-error E the run ends once the estimated relative error of the image (rl_app_run_to_error) is at most E; --batches stays
-the cap.  With --error-map PATH the per-tile relative error of the last estimate is written as a grey image."""
+the cap.  With --error-map PATH the per-tile relative error of the last estimate is written as a grey image.
+With --adaptive as well the batches are rendered over the unit API by render_adaptive_to_error: from --min-observations on, every batch's
+camera samples are drawn tile by tile from the running error map (AdaptiveUnit), --uniform-share of them spread by area."""
 import argparse
 import os
 import struct
@@ -64,7 +66,28 @@ def parse_args(argv=None):
     ap.add_argument("--error-map", metavar="PATH", default=None,
                     help="write the per-tile relative error of the last estimate as a grey image, the worst 16 x 16 tile white, to "
                          "PATH (*.png or *.ppm); without --target-error the run estimates once at the end")
+    ap.add_argument("--adaptive", action="store_true",
+                    help="with --target-error: draw each batch's camera samples tile by tile from the running error map "
+                         "(render_adaptive_to_error over the unit API, not the App worker pool)")
+    ap.add_argument("--uniform-share", metavar="F", type=float, default=None,
+                    help="with --adaptive: the share of a batch's paths spread by area, 0 < F <= 1 (default 0.25)")
     a = ap.parse_args(argv)
+    if a.adaptive and a.target_error is None:
+        ap.error("--adaptive needs --target-error: the samples follow the estimate the target is held to")
+    if a.uniform_share is not None and not a.adaptive:
+        ap.error("--uniform-share needs --adaptive")
+    if a.uniform_share is not None and not 0 < a.uniform_share <= 1:
+        ap.error("--uniform-share must be a number in (0, 1]")
+    if a.adaptive:
+        for given, flag in ((a.resume, "--resume"), (a.unfused, "--unfused"), (a.denoise_variance, "--denoise-variance"),
+                            (a.concurrency is not None, "--concurrency"), (a.spectral is not None, "--spectral")):
+            if given:
+                ap.error("%s cannot be combined with --adaptive: the adaptive mode renders batch by batch over the unit API" % flag)
+        if (a.min_observations or 16) > a.batches:
+            ap.error("--adaptive needs --batches of at least --min-observations (default 16): the plans follow an estimate that rests on "
+                     "that many batches")
+        if not 0 < a.photons_per_batch < 1 << 32:
+            ap.error("--adaptive needs --photons-per-batch in 1 .. 2^32 - 1: a plan's size")
     if a.target_error is not None and not a.target_error >= 0:
         ap.error("--target-error must be a number >= 0")
     if a.min_observations is not None and a.target_error is None:
@@ -229,6 +252,34 @@ def report_error(a, st, err):
     return grey
 
 
+def render_adaptive(a):
+    """--adaptive: render_adaptive_to_error over units of its own; batch b is paths [b * photons_per_batch, (b + 1) * photons_per_batch)
+    of stream 0.  One tonemap at the end.  Returns (rgb, batches made, the last estimate's stats, the gather unit)."""
+    from . import AdaptiveUnit, ErrorUnit, GatherUnit, PlotUnit, Scene, TonemapUnit, render_adaptive_to_error
+    scene = Scene.builtin(SCENE_DEMO if a.scene == "demo" else SCENE_GLASS_STRESS, device=a.device)
+    plot = PlotUnit(0, a.width, a.height, device=a.device)
+    gather = GatherUnit(a.width, a.height, device=a.device)
+    error = ErrorUnit(a.width, a.height, device=a.device)
+    adaptive = AdaptiveUnit(a.width, a.height, device=a.device)
+    t0 = time.perf_counter()
+    batches, stats, tiles = render_adaptive_to_error(scene, plot, gather, error, adaptive, a.photons_per_batch, a.batches, a.target_error,
+                                                     uniform_share=a.uniform_share or 0.25, min_observations=a.min_observations or 16,
+                                                     seed=a.seed)
+    tonemap = TonemapUnit(a.width, a.height, device=a.device)
+    tonemap.tonemap(gather)
+    rgb = tonemap.rgb_buffer
+    seconds = time.perf_counter() - t0
+    write_image(a.output, rgb, a.width, a.height)
+    if a.checkpoint:
+        gather.save(a.checkpoint)
+    reached = stats is not None and stats["relative_error"] <= a.target_error
+    err = {"at_stop": stats, "at_end": stats, "reached": int(reached), "estimates": int(stats is not None), "tiles": tiles}
+    report_error(a, {"batches": batches}, err)
+    print("adaptive: %d of %d batches, %.1f Mpaths in %.2f s, target %s; wrote %s"
+          % (batches, a.batches, batches * a.photons_per_batch / 1e6, seconds, "reached" if reached else "not reached", a.output))
+    return rgb, batches, stats, gather
+
+
 def denoise(a, image, guides, error=None):
     """--denoise PATH: gather unit `image` filtered over the three guide gather units into a gather unit of its own, tonemapped as
     the image was, written to PATH.  With --denoise-variance `error` is the ErrorUnit that observed what `image` gathered."""
@@ -256,6 +307,13 @@ def main(argv=None):
             guides = render_features(a)[2]
             if a.denoise is not None:
                 denoise(a, image, guides, error)
+        return
+    if a.adaptive:
+        image = render_adaptive(a)[3]
+        if a.features is not None:
+            guides = render_features(a)[2]
+            if a.denoise is not None:
+                denoise(a, image, guides)
         return
     # rl_app_run hands out no gather unit: --denoise reads the image back from the checkpoint, a temporary one if none was asked for
     scratch = tempfile.TemporaryDirectory() if a.denoise is not None and a.checkpoint is None else None

@@ -127,6 +127,11 @@ class RlErrorStats(C.Structure):
                 ("relative_error", C.c_double), ("worst_tile_error", C.c_double)]
 
 
+class RlAdaptiveStats(C.Structure):
+    _fields_ = [("n_paths", C.c_uint64), ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32), ("min_count", C.c_uint32),
+                ("max_count", C.c_uint32), ("min_weight", C.c_float), ("max_weight", C.c_float), ("importance_sum", C.c_double)]
+
+
 class RlErrorTarget(C.Structure):
     _fields_ = [("relative_error", C.c_double), ("worst_tile_error", C.c_double), ("min_observations", C.c_uint32),
                 ("reserved", C.c_uint32)]
@@ -254,6 +259,13 @@ SIGNATURES = {
     "rl_error_unit_estimate": (_i, [_vp, C.POINTER(RlErrorStats), _vp, _vp]),
     "rl_error_unit_download": (_i, [_vp, _vp, _vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "rl_error_unit_upload": (_i, [_vp, _vp, _vp, _u64, _u64]),
+    "rl_adaptive_unit_create": (_i, [_i, _u32, _u32, _pp]),
+    "rl_adaptive_unit_destroy": (_i, [_vp]),
+    "rl_adaptive_unit_plan": (_i, [_vp, _vp, C.c_double, _u64, C.POINTER(RlAdaptiveStats)]),
+    "rl_adaptive_unit_download_plan": (_i, [_vp, _vp, _vp]),
+    "rl_adaptive_unit_samples": (_i, [_vp, _vp, _u64, _u32, _u64, _u64, _u32, _vp]),
+    "rl_adaptive_unit_samples_device": (_i, [_vp, _vp, _u64, _u32, _u64, _u64, _u32, _vp]),
+    "rl_plot_unit_render_adaptive": (_i, [_vp, _vp, _vp, _i, _u64, _u32, _u64, _u32]),
     "rl_gather_unit_sync": (_i, [_vp]),
     "rl_gather_unit_create": (_i, [_i, _u32, _u32, _pp]),
     "rl_gather_unit_destroy": (_i, [_vp]),
@@ -300,6 +312,8 @@ DEBUG_SIGNATURES = {
     "rl_debug_spectral_ms": (_i, [_vp, _vp]),
     "rl_debug_error_launches": (_i, [_vp]),
     "rl_debug_error_ms": (_i, [_vp, _vp]),
+    "rl_debug_adaptive_launches": (_i, [_vp]),
+    "rl_debug_adaptive_ms": (_i, [_vp, _vp]),
     "rl_debug_gather_accumulate_ms": (_i, [_vp, _vp, C.POINTER(C.c_float)]),
     "rl_debug_live_resources": (_i, [_vp]),
     "rl_debug_scene_emitters": (_i, [_vp, _u32, _vp, _u32, C.POINTER(_u32)]),

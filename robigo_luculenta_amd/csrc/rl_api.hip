@@ -58,6 +58,7 @@
 #include "rl_denoise.hip.h"
 #include "rl_spectral.hip.h"
 #include "rl_error.hip.h"
+#include "rl_adaptive.hip.h"
 #include "rl_scene.h"
 
 namespace {
@@ -120,6 +121,7 @@ const char* unit_name(const RlTonemapUnit*) { return "tonemap unit"; }
 const char* unit_name(const RlDenoiseUnit*) { return "denoise unit"; }
 const char* unit_name(const RlSpectralUnit*) { return "spectral unit"; }
 const char* unit_name(const RlErrorUnit*) { return "error unit"; }
+const char* unit_name(const RlAdaptiveUnit*) { return "adaptive unit"; }
 template <class Given, class Owner>
 int match_check(const Given* given, const Owner* owner) {
     if (given->device == owner->device && given->width == owner->width && given->height == owner->height) return RL_OK;
@@ -483,6 +485,29 @@ struct RlErrorUnit {
     bool timed_done[2];    // ... recorded at least once
     Ledger ledger;
 };
+
+struct RlAdaptiveUnit {
+    int device;
+    uint32_t width, height, tiles_x, tiles_y;
+    bool planned;              // a plan is on the device
+    uint64_t n_paths;          // the plan's
+    uint32_t* off;             // tiles + 1 exclusive prefix sums of the counts
+    RlAdaptiveCell* cells;     // the tiles' cells
+    uint32_t* weight_bits;     // the bits of w_t
+    // rl_plot_unit_render_adaptive's scratch, taken at the first such call (null before it): RL_QUERY_CHUNK records each
+    RlCameraSample* samples;
+    RlSpectralRay* rays;
+    RlPathResult* results;
+    EventPair timed[3];        // around the three launches of the last chunk of the last render (rl_debug_adaptive_ms)
+    bool timed_done;           // ... of a call that completed
+    Ledger ledger;
+};
+
+// tests/test_adaptive_abi.py writes a stand-in handle's first fields at these offsets (the checks that read a handle before any
+// device work): a field that moves must move there too.
+static_assert(offsetof(RlAdaptiveUnit, width) == 4 && offsetof(RlAdaptiveUnit, height) == 8 && offsetof(RlAdaptiveUnit, planned) == 20 &&
+                  offsetof(RlAdaptiveUnit, n_paths) == 24,
+              "tests/test_adaptive_abi.py: test_a_stand_in_with_a_plan_is_checked_for_its_range_size_and_device");
 
 // One rank of an RCCL communicator (rl_comm_*).
 struct RlComm {
@@ -3188,6 +3213,201 @@ int rl_error_unit_upload(RlErrorUnit* u, const double* sum_y, const double* sum_
     return RL_OK;
 }
 
+// ---- AdaptiveUnit (rl_adaptive_plan.h, rl_adaptive.hip.h) ----------------------------------------
+
+namespace {
+std::atomic<uint64_t> g_adaptive_launches[3]; // rl_debug_adaptive_launches: sample, path and splat launches
+
+RlAdaptivePlan adaptive_plan_of(const RlAdaptiveUnit* u) {
+    RlAdaptivePlan plan;
+    plan.off = u->off;
+    plan.cells = u->cells;
+    plan.weight_bits = u->weight_bits;
+    plan.n_tiles = u->tiles_x * u->tiles_y;
+    plan.wm1 = (float)(int)u->width - 1.0f; // as film_of has them
+    plan.hm1 = (float)(int)u->height - 1.0f;
+    plan.aspect_ratio = (float)u->width / (float)u->height; // trace_unit.rs:73, as launch_camera has it
+    return plan;
+}
+
+// The sample kernel for samples first_sample .. first_sample + n - 1 of u's plan (n > 0, inside the plan) into device array
+// `samples`, and their rays into `rays` if given, on c's stream.
+void launch_adaptive_samples(const CallCtx& c, const RlAdaptiveUnit* u, const RlScene* scene, uint64_t seed, uint32_t stream, uint64_t first_path,
+                             uint32_t first_sample, RlCameraSample* samples, RlSpectralRay* rays, uint32_t n) {
+    hipLaunchKernelGGL(rl_adaptive_samples_kernel, dim3(grid_for(n, c.cus)), dim3(RL_BLOCK), 0, c.stream, scene->blob, scene->lay,
+                       adaptive_plan_of(u), seed, stream, first_path, first_sample, samples, rays, n);
+    g_adaptive_launches[0].fetch_add(1, std::memory_order_relaxed);
+}
+
+int adaptive_samples_check(const RlAdaptiveUnit* u, const RlScene* scene, uint64_t first_path, uint64_t first_sample, uint32_t n, const void* out) {
+    if (!u) return fail(RL_E_INVALID, "null adaptive unit");
+    if (!scene) return fail(RL_E_INVALID, "null scene");
+    if (n > 0 && !out) return fail(RL_E_INVALID, "null sample buffer");
+    if (!u->planned) return fail(RL_E_STATE, "the adaptive unit has no plan: call rl_adaptive_unit_plan first");
+    if (first_sample > u->n_paths || (uint64_t)n > u->n_paths - first_sample)
+        return fail(RL_E_INVALID, "samples past the end of the plan: first_sample + n exceeds its " + std::to_string(u->n_paths) + " paths");
+    if (path_range_check(first_path, first_sample + n) != RL_OK) return RL_E_INVALID;
+    if (scene->device != u->device) return fail(RL_E_STATE, "scene and adaptive unit live on different devices");
+    return RL_OK;
+}
+} // namespace
+
+int rl_adaptive_unit_create(int device, uint32_t width, uint32_t height, RlAdaptiveUnit** out) {
+    if (out && (width < 2 || height < 2)) {
+        *out = nullptr;
+        return fail(RL_E_INVALID, "adaptive unit: width and height must be at least 2 (a 1-wide film has no area)");
+    }
+    RlAdaptiveUnit* u = nullptr;
+    const int rc = unit_new("adaptive unit", device, width, height, 1u, out, &u);
+    if (rc != RL_OK) return rc;
+    u->tiles_x = (width + RL_ERROR_TILE - 1u) / RL_ERROR_TILE;
+    u->tiles_y = (height + RL_ERROR_TILE - 1u) / RL_ERROR_TILE;
+    const size_t n_tiles = (size_t)u->tiles_x * u->tiles_y;
+    u->ledger.alloc(&u->off, (n_tiles + 1) * sizeof(uint32_t));
+    u->ledger.alloc(&u->cells, n_tiles * sizeof(RlAdaptiveCell));
+    u->ledger.alloc(&u->weight_bits, n_tiles * sizeof(uint32_t));
+    for (EventPair& ep : u->timed) u->ledger.pair(&ep);
+    return unit_created("adaptive unit allocation", u, rl_adaptive_unit_destroy, out);
+}
+
+int rl_adaptive_unit_destroy(RlAdaptiveUnit* u) {
+    if (!u) return RL_OK;
+    (void)hipSetDevice(u->device);
+    u->ledger.release();
+    delete u;
+    return RL_OK;
+}
+
+int rl_adaptive_unit_plan(RlAdaptiveUnit* u, const double* importance, double uniform_share, uint64_t n_paths, RlAdaptiveStats* stats) {
+    if (!u) return fail(RL_E_INVALID, "null adaptive unit");
+    if (!(uniform_share > 0.0 && uniform_share <= 1.0)) return fail(RL_E_INVALID, "rl_adaptive_unit_plan: uniform_share must be in (0, 1]");
+    if (n_paths == 0 || n_paths > 0xffffffffull) return fail(RL_E_INVALID, "rl_adaptive_unit_plan: n_paths must be 1 .. 2^32 - 1");
+    const size_t n_tiles = (size_t)u->tiles_x * u->tiles_y;
+    std::vector<uint32_t> counts(n_tiles), off(n_tiles + 1);
+    std::vector<float> weights(n_tiles);
+    std::vector<RlAdaptiveCell> cells(n_tiles);
+    double g_sum = 0.0;
+    switch (rl_adaptive_plan_rule(u->width, u->height, importance, uniform_share, n_paths, counts.data(), weights.data(), cells.data(), &g_sum)) {
+    case RL_PLAN_OK: break;
+    case RL_PLAN_OVERFLOW: return fail(RL_E_INVALID, "rl_adaptive_unit_plan: the sum of the importance overflows");
+    case RL_PLAN_EMPTY_TILE:
+        return fail(RL_E_INVALID, "rl_adaptive_unit_plan: a tile would get no sample (a biased image): more paths or a larger uniform_share");
+    default: return fail(RL_E_INVALID, "rl_adaptive_unit_plan: the shares do not sum to 1");
+    }
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    uint64_t sum = 0; // (every prefix is below n_paths <= 2^32 - 1)
+    for (size_t t = 0; t < n_tiles; ++t) off[t] = (uint32_t)sum, sum += counts[t];
+    off[n_tiles] = (uint32_t)sum;
+    u->planned = false; // (a failed upload leaves no plan)
+    static_assert(sizeof(float) == sizeof(uint32_t), "the weights travel as their bits");
+    if ((rc = upload(nullptr, {{u->off, off.data(), off.size() * sizeof(uint32_t)},
+                               {u->cells, cells.data(), cells.size() * sizeof(RlAdaptiveCell)},
+                               {u->weight_bits, weights.data(), weights.size() * sizeof(float)}})) != RL_OK)
+        return rc;
+    u->planned = true;
+    u->n_paths = n_paths;
+    if (stats) {
+        std::memset(stats, 0, sizeof *stats);
+        stats->n_paths = n_paths;
+        stats->tiles_x = u->tiles_x;
+        stats->tiles_y = u->tiles_y;
+        stats->min_count = *std::min_element(counts.begin(), counts.end());
+        stats->max_count = *std::max_element(counts.begin(), counts.end());
+        stats->min_weight = *std::min_element(weights.begin(), weights.end());
+        stats->max_weight = *std::max_element(weights.begin(), weights.end());
+        stats->importance_sum = g_sum;
+    }
+    return RL_OK;
+}
+
+int rl_adaptive_unit_download_plan(RlAdaptiveUnit* u, uint32_t* counts, float* weights) {
+    if (!u) return fail(RL_E_INVALID, "null adaptive unit");
+    if (!u->planned) return fail(RL_E_STATE, "the adaptive unit has no plan: call rl_adaptive_unit_plan first");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    const size_t n_tiles = (size_t)u->tiles_x * u->tiles_y;
+    std::vector<uint32_t> off(counts ? n_tiles + 1 : 0);
+    if ((rc = download(nullptr, {{u->off, counts ? off.data() : nullptr, off.size() * sizeof(uint32_t)},
+                                 {u->weight_bits, weights, n_tiles * sizeof(float)}})) != RL_OK)
+        return rc;
+    if (counts) {
+        for (size_t t = 0; t + 1 < n_tiles; ++t) counts[t] = off[t + 1] - off[t];
+        counts[n_tiles - 1] = (uint32_t)(u->n_paths - off[n_tiles - 1]);
+    }
+    return RL_OK;
+}
+
+int rl_adaptive_unit_samples(RlAdaptiveUnit* u, const RlScene* scene, uint64_t seed, uint32_t stream, uint64_t first_path_index,
+                             uint64_t first_sample, uint32_t n, RlCameraSample* out) {
+    const int rc = adaptive_samples_check(u, scene, first_path_index, first_sample, n, out);
+    if (rc != RL_OK || n == 0) return rc;
+    return with_query_ctx(scene, [&](const CallCtx& c) -> int {
+        return staged_chunks(c, n, {staged_out(STAGING_HITS, out, sizeof(RlCameraSample))}, [&](uint32_t first, uint32_t k) -> int {
+            launch_adaptive_samples(c, u, scene, seed, stream, first_path_index, (uint32_t)(first_sample + first),
+                                    (RlCameraSample*)c.q->staging[STAGING_HITS], nullptr, k);
+            RL_HIP(hipGetLastError());
+            return RL_OK;
+        });
+    });
+}
+
+int rl_adaptive_unit_samples_device(RlAdaptiveUnit* u, const RlScene* scene, uint64_t seed, uint32_t stream, uint64_t first_path_index,
+                                    uint64_t first_sample, uint32_t n, RlCameraSample* device_out) {
+    const int rc = adaptive_samples_check(u, scene, first_path_index, first_sample, n, device_out);
+    if (rc != RL_OK || n == 0) return rc;
+    if (aligned_check("rl_adaptive_unit_samples_device", "the sample buffer", 16, {device_out}) != RL_OK) return RL_E_INVALID;
+    return with_query_ctx(scene, {"rl_adaptive_unit_samples_device", "rl_adaptive_unit_samples", {device_out}}, [&](const CallCtx& c) -> int {
+        launch_adaptive_samples(c, u, scene, seed, stream, first_path_index, (uint32_t)first_sample, device_out, nullptr, n);
+        RL_HIP(hipGetLastError());
+        return RL_OK;
+    });
+}
+
+int rl_plot_unit_render_adaptive(RlPlotUnit* plot, RlAdaptiveUnit* u, const RlScene* scene, int primitive_fetch, uint64_t seed,
+                                 uint32_t stream, uint64_t first_path_index, uint32_t max_segments) {
+    PathJob job{seed, stream, 0u};
+    if (!plot) return fail(RL_E_INVALID, "null plot unit");
+    if (!u) return fail(RL_E_INVALID, "null adaptive unit");
+    if (!scene) return fail(RL_E_INVALID, "null scene");
+    if (fetch_check(primitive_fetch) != RL_OK || max_segments_resolve(max_segments, &job.max_segments) != RL_OK) return RL_E_INVALID;
+    if (!u->planned) return fail(RL_E_STATE, "the adaptive unit has no plan: call rl_adaptive_unit_plan first");
+    if (path_range_check(first_path_index, u->n_paths) != RL_OK) return RL_E_INVALID;
+    int rc = match_check(u, plot);
+    if (rc != RL_OK) return rc;
+    if (scene->device != plot->device) return fail(RL_E_STATE, "scene and plot unit live on different devices");
+    if ((rc = use_device(u->device)) != RL_OK) return rc;
+    if (!u->samples) RL_HIP(u->ledger.make_alloc(&u->samples, (size_t)RL_QUERY_CHUNK * sizeof(RlCameraSample)));
+    if (!u->rays) RL_HIP(u->ledger.make_alloc(&u->rays, (size_t)RL_QUERY_CHUNK * sizeof(RlSpectralRay)));
+    if (!u->results) RL_HIP(u->ledger.make_alloc(&u->results, (size_t)RL_QUERY_CHUNK * sizeof(RlPathResult)));
+    u->timed_done = false;
+    rc = with_film_ctx(plot, [&](const CallCtx& c) -> int {
+        const float aspect = (float)plot->width / (float)plot->height; // plot_unit.rs:48, as launch_film_photons has it
+        // (the chunks share the scratch: the stream keeps them in order)
+        for (uint64_t done = 0; done < u->n_paths;) {
+            const uint32_t k = (uint32_t)std::min<uint64_t>(u->n_paths - done, RL_QUERY_CHUNK);
+            RL_HIP(hipEventRecord(u->timed[0].start, c.stream));
+            launch_adaptive_samples(c, u, scene, seed, stream, first_path_index, (uint32_t)done, u->samples, u->rays, k);
+            RL_HIP(hipGetLastError());
+            RL_HIP(hipEventRecord(u->timed[0].stop, c.stream));
+            RL_HIP(hipEventRecord(u->timed[1].start, c.stream));
+            const int r = launch_paths(c, scene, primitive_fetch, job, first_path_index + done, u->rays, u->results, k);
+            if (r != RL_OK) return r;
+            RL_HIP(hipEventRecord(u->timed[1].stop, c.stream));
+            g_adaptive_launches[1].fetch_add(1, std::memory_order_relaxed);
+            const int r2 = timed_launch(u->timed[2], c.stream, &g_adaptive_launches[2], [&] {
+                hipLaunchKernelGGL(rl_adaptive_splat_kernel, dim3(grid_for(k, c.cus)), dim3(RL_BLOCK), 0, c.stream, (const RlCameraSample*)u->samples,
+                                   (const RlPathResult*)u->results, (uint64_t)k, (const RlF4*)plot->cie, plot->width, plot->height, aspect, plot->xyz);
+            });
+            if (r2 != RL_OK) return r2;
+            done += k;
+        }
+        return RL_OK;
+    });
+    if (rc == RL_OK) u->timed_done = true;
+    return rc;
+}
+
 // ---- GatherUnit-time exchange across GPUs (gather_unit.rs:49-64 with the plot buffers of G GPUs) ----
 
 namespace {
@@ -3531,6 +3751,23 @@ int rl_debug_error_ms(RlErrorUnit* u, float out[2]) {
     for (int k = 0; k < 2; ++k) {
         out[k] = 0.0f;
         if (!u->timed_done[k]) continue;
+        RL_HIP(hipEventSynchronize(u->timed[k].stop));
+        RL_HIP(hipEventElapsedTime(&out[k], u->timed[k].start, u->timed[k].stop));
+    }
+    return RL_OK;
+}
+int rl_debug_adaptive_launches(uint64_t out[3]) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    for (int k = 0; k < 3; ++k) out[k] = g_adaptive_launches[k].load(std::memory_order_relaxed);
+    return RL_OK;
+}
+int rl_debug_adaptive_ms(RlAdaptiveUnit* u, float out[3]) {
+    if (!u || !out) return fail(RL_E_INVALID, "null argument");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    for (int k = 0; k < 3; ++k) {
+        out[k] = 0.0f;
+        if (!u->timed_done) continue;
         RL_HIP(hipEventSynchronize(u->timed[k].stop));
         RL_HIP(hipEventElapsedTime(&out[k], u->timed[k].start, u->timed[k].stop));
     }

@@ -199,14 +199,11 @@ RL_HD float rl_sf10_ior(float wavelength) {
 
 // ---- camera: trace_unit.rs:151-148, app.rs:327-357, camera.rs:47-108 --------------------------
 
-RL_HD void rl_begin_path(const RlSceneView& sv, float aspect_ratio, uint64_t seed, uint32_t stream, uint64_t path,
-                         RlPath* p) {
-    const RlRngBlock b0 = rl_rng_block(seed, stream, path, 0);
-    const float wavelength = rl_get_wavelength(b0.w[0]);
-    const float x = rl_get_bi_unit(b0.w[1]);
-    const float y = rl_get_bi_unit(b0.w[2]) / aspect_ratio;
-    const float t = rl_get_unit(b0.w[3]);
-
+// The camera of a path whose first block gave the screen position x, y, the camera time t and the wavelength: make_camera(t) and
+// Camera::get_ray, which draws the lens from block 1 of the path.  rl_begin_path is its draws from block 0 and this; a sampler that
+// places x, y by a rule of its own (rl_adaptive.hip.h) calls it with the same t and wavelength.
+RL_HD void rl_camera_path(const RlSceneView& sv, float x, float y, float t, float wavelength, uint64_t seed, uint32_t stream, uint64_t path,
+                          RlPath* p) {
     // make_camera(t)
     const float* crec = (const float*)sv.camera_rec;
     RlCameraDesc cd;
@@ -254,6 +251,16 @@ RL_HD void rl_begin_path(const RlSceneView& sv, float aspect_ratio, uint64_t see
     p->sy = y;
     p->ior = rl_sf10_ior(wavelength);
     p->bounce = 0;
+}
+
+RL_HD void rl_begin_path(const RlSceneView& sv, float aspect_ratio, uint64_t seed, uint32_t stream, uint64_t path,
+                         RlPath* p) {
+    const RlRngBlock b0 = rl_rng_block(seed, stream, path, 0);
+    const float wavelength = rl_get_wavelength(b0.w[0]);
+    const float x = rl_get_bi_unit(b0.w[1]);
+    const float y = rl_get_bi_unit(b0.w[2]) / aspect_ratio;
+    const float t = rl_get_unit(b0.w[3]);
+    rl_camera_path(sv, x, y, t, wavelength, seed, stream, path, p);
 }
 
 // ---- the scan: scene.rs:39-60 over the flat records --------------------------------------------
