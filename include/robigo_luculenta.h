@@ -93,9 +93,11 @@ enum RlBuiltinScene {
 };
 
 /* Where the trace kernel reads the primitive list from. */
-// RL_FETCH_LDS stages as much as fits beside the waves' scratch: the whole scene (up to about 1,300 objects), else its tables
-// (planes, paraboloids, prisms, the cull table) with the spheres and objects read from L2 / HBM, else -- tables beyond ~37 KB,
-// tens of thousands of objects -- nothing.  RL_FETCH_GLOBAL never stages anything.
+// RL_FETCH_LDS stages as much as fits beside the waves' scratch, which leaves 32 KB of the 160 (24 KB where the cull table has a
+// third level, 2 KB less in a blocking render call): the whole scene (random spheres: up to about 670 objects; a prism takes as
+// much as eight spheres), else its tables (planes, paraboloids, prisms, the cull table) with the spheres and objects read from
+// L2 / HBM, else -- tables beyond those 32 or 24 KB: some 80 prisms beside 3,000 spheres, a thousand planes, tens of thousands of
+// objects -- nothing.  RL_FETCH_GLOBAL never stages anything.  (tests/test_scene_extremes.py finds both thresholds and prints them.)
 enum RlPrimitiveFetch {
     RL_FETCH_LDS = 0,   /* primitives + CIE tables staged in LDS by each workgroup */
     RL_FETCH_GLOBAL = 1 /* wave-uniform loads from HBM/L2 through the scalar cache */

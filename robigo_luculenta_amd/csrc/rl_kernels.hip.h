@@ -70,9 +70,13 @@ struct RlSceneLayout {
     uint32_t small_ordered;                    // the paraboloids' objects all precede the planes' and circles' (rl_scan_wave: one compare per candidate)
     uint32_t n_cluster_supers, super_g;        // RlFlatScene: third level of the cull table (0: none); a scene that has one is never staged whole
     // Records [off_planes, off_objects) of the blob are the TABLES -- planes, paraboloids, prisms, the cull table, the camera:
-    // everything a scan reads with wave-uniform addresses or once per (group, ray) / (prism, ray) pair, 10-40 KB whatever the
-    // scene's size.  The spheres in front of them and the per-object arrays behind them grow with the scene: one too large for
-    // LDS stages its tables only (RL_STAGE_TABLES).
+    // everything a scan reads with wave-uniform addresses or once per (group, ray) / (prism, ray) pair.  Their size does not grow
+    // with the spheres' records but with the planes (32 bytes each), paraboloids (48), prisms (325 with their share of the cull
+    // table) and sphere clusters (about 21): 8 KB for the built-in scene, 22 KB for the glass-stress scene's 66 prisms, 16 KB for 6,000 random spheres
+    // and 45 KB for 20,000 -- past the 32 KB that LDS has beside the scratch (24 KB with a third table level) from some 80 prisms
+    // beside 3,000 spheres, or a thousand planes, on.  The spheres in front of them and the
+    // per-object arrays behind them grow with the scene: one too large for LDS stages its tables only (RL_STAGE_TABLES), and one
+    // whose tables are too large stages nothing (RL_STAGE_NONE; rl_api.hip: stage_of).
 };
 enum { RL_STAGE_NONE = 0, RL_STAGE_TABLES = 1, RL_STAGE_ALL = 2 };
 

@@ -150,6 +150,83 @@ def super_bounds(scene, cap=4096):
     return sup[:n], sg.value
 
 
+def bounds(scene, cap=1 << 16):
+    """The level-1 bounds of `scene`'s cull table as ((n, 4) floats {centre, radius^2}, number of cluster bounds in front): the
+    sphere clusters' first, then one per prism record (a dummy prism's radius^2 is -inf)."""
+    L = lib()
+    L.mirror_bounds.restype = C.c_uint32
+    L.mirror_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    out, nc = np.zeros((cap, 4), np.float32), C.c_uint32(0)
+    n = L.mirror_bounds(scene.h, O.ptr(out), cap, C.byref(nc))
+    assert n <= cap
+    return out[:n], nc.value
+
+
+LAYOUT_FIELDS = ("staged_bytes", "blob_bytes", "table_bytes", "n_prism_records", "n_prisms", "n_prism_groups", "prism_cylinders",
+                 "n_planes", "n_parabs", "n_cluster_supers", "n_clusters", "n_direct", "n_bounded_prisms")
+
+
+def layout(scene):
+    """mirror_layout of `scene` as a dict over LAYOUT_FIELDS: RlFlatScene::staged_bytes(), the bytes of the blob rl_scene_create
+    makes of the flat scene and of its tables (the records [off_planes, off_objects)), and the counts the kernel variants and the
+    scan's loops depend on.  n_prisms counts the description's prisms, n_prism_records those and the dummies that fill short groups,
+    n_bounded_prisms the ones whose bound is finite: the count rl_flatten_scene's cylinder switch is made on."""
+    L = lib()
+    L.mirror_layout.argtypes = [C.c_void_p, C.c_void_p]
+    out = np.zeros(len(LAYOUT_FIELDS), np.uint64)
+    L.mirror_layout(scene.h, O.ptr(out))
+    return dict(zip(LAYOUT_FIELDS, (int(v) for v in out)))
+
+
+# ---- the staging rule (rl_api.hip: stage_of), stated once for the tests -----------------------------------------------------------
+
+STAGE_NONE, STAGE_TABLES, STAGE_ALL = 0, 1, 2
+LDS_BYTES = 160 * 1024
+_CONSTANTS = None
+
+
+def launch_constants():
+    """{block, wave_scratch, open_cap} as the product's kernel header states them (RL_TRACE_BLOCK, sizeof(RlWaveScratch) by its
+    static_assert, RL_OPEN_CAP): read from csrc/rl_kernels.hip.h, which only hipcc compiles, so that no figure is repeated here."""
+    global _CONSTANTS
+    if _CONSTANTS is None:
+        import re
+        with open(os.path.join(HERE, "..", "robigo_luculenta_amd", "csrc", "rl_kernels.hip.h")) as f:
+            text = f.read()
+        found = {}
+        for key, pattern in (("block", r"#define RL_TRACE_BLOCK (\d+)"), ("wave_scratch", r"static_assert\(sizeof\(RlWaveScratch\) == (\d+)"),
+                             ("open_cap", r"#define RL_OPEN_CAP (\d+)u")):
+            m = re.findall(pattern, text)
+            assert len(m) == 1, (key, m)
+            found[key] = int(m[0])
+        _CONSTANTS = found
+    return _CONSTANTS
+
+
+def scratch_bytes(lay, open_launch=False):
+    """The LDS a launch asks for beside what it stages: one RlWaveScratch per wave of the workgroup; 512 bytes per wave of ring T
+    where the cull table has a third level (ring_t_bytes); and, in an open launch of the trace kernel, one RlOpenWg (two uint32 per
+    job slot and four more)."""
+    c = launch_constants()
+    waves = c["block"] // 64
+    return waves * c["wave_scratch"] + (waves * 512 if lay["n_cluster_supers"] else 0) + ((2 * c["open_cap"] + 4) * 4 if open_launch else 0)
+
+
+def predicted_stage(lay, lds_fetch=True, open_launch=False):
+    """(stage, LDS bytes the launch asks for) as stage_of decides them for a scene of layout `lay`: under RL_FETCH_LDS the whole blob,
+    rounded up to 512 bytes, if it fits in 160 KB beside the scratch and the cull table has no third level; else the tables, rounded
+    likewise, if they do; else nothing.  Nothing under RL_FETCH_GLOBAL."""
+    scratch = scratch_bytes(lay, open_launch)
+    if not lds_fetch:
+        return STAGE_NONE, scratch
+    whole, tables = (lay["blob_bytes"] + 511) & ~511, (lay["table_bytes"] + 511) & ~511
+    if lay["n_cluster_supers"] == 0 and whole + scratch <= LDS_BYTES:
+        return STAGE_ALL, whole + scratch
+    if tables + scratch <= LDS_BYTES:
+        return STAGE_TABLES, tables + scratch
+    return STAGE_NONE, scratch
+
+
 def axis_z_check(seed, n):
     """rl_paraboloid_t<AXIS_Z> / rl_plane_t<AXIS_Z> against the general forms: (cases, hits compared, differences, cases with a zero n.d / n.o)."""
     L = lib()

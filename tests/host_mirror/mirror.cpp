@@ -597,6 +597,39 @@ extern "C" void mirror_small_counts(void* scene, uint32_t* n_parabs, uint32_t* n
     *n_planes = (uint32_t)(fs.planes.size() / 2);
 }
 
+// The figures the library's staging rule (rl_api.hip: stage_of) is made on, for a description flattened here: out[0] =
+// RlFlatScene::staged_bytes(); out[1] = the bytes of the blob rl_scene_create builds from the same flat scene (RlScene::staged_bytes:
+// every record array, the CIE table, and sphere_obj and sphere_r2 each padded to whole 16-byte records); out[2] = the bytes of its
+// tables, records [off_planes, off_objects) (RlScene::tables_bytes); then the counts the kernel variants and the scan's loops depend
+// on: out[3] = prism records (dummies of short groups included), [4] = the description's prisms among them, [5] = prism groups, [6] = prism_cylinders,
+// [7] = plane and circle records, [8] = paraboloid records, [9] = cluster supers, [10] = clusters, [11] = direct spheres,
+// [12] = prisms with a finite bound, the ones rl_flatten_scene counts for the cylinder switch.
+extern "C" void mirror_layout(void* scene, uint64_t* out) {
+    const RlFlatScene& fs = ((MirrorScene*)scene)->flat;
+    const size_t tables = fs.planes.size() + fs.parabs.size() + fs.prisms.size() + fs.cull_bounds.size() + fs.prism_cyl.size() + fs.camera_rec.size();
+    const size_t so_f4 = (fs.sphere_obj.size() + 3) / 4;
+    uint64_t real = 0, bounded = 0;
+    const uint64_t n_prisms = fs.prisms.size() / RL_PRISM_STRIDE;
+    for (uint64_t i = 0; i < n_prisms; ++i) {
+        const float w = fs.prisms[RL_PRISM_STRIDE * i + 16].w;
+        if (std::isfinite(w) && w > 0.0f) bounded += 1;
+        if (!(w == -INFINITY)) real += 1; // (a dummy's radius^2)
+    }
+    out[0] = fs.staged_bytes();
+    out[1] = (fs.spheres.size() + tables + fs.objects.size() + RL_CIE_SAMPLES + 2 * so_f4) * sizeof(RlF4);
+    out[2] = tables * sizeof(RlF4);
+    out[3] = n_prisms;
+    out[4] = real;
+    out[5] = fs.n_prism_groups;
+    out[6] = fs.prism_cylinders ? 1 : 0;
+    out[7] = fs.planes.size() / 2;
+    out[8] = fs.parabs.size() / 3;
+    out[9] = fs.n_cluster_supers;
+    out[10] = fs.n_clusters;
+    out[11] = fs.n_direct;
+    out[12] = bounded;
+}
+
 extern "C" void mirror_cull_counts(void* scene, uint32_t w, uint32_t h, uint64_t seed, uint32_t stream, uint64_t first, uint64_t n,
                                    uint64_t* counts) {
     const MirrorScene* ms = (MirrorScene*)scene;
