@@ -108,6 +108,11 @@ pub const RL_COMM_ID_BYTES: usize = 128;
 pub enum RlScene {} pub enum RlTraceUnit {} pub enum RlPlotUnit {} pub enum RlGatherUnit {} pub enum RlTonemapUnit {}
 pub enum RlScheduler {} pub enum RlComm {} pub enum RlDenoiseUnit {} pub enum RlSpectralUnit {} pub enum RlErrorUnit {}
 pub enum RlAdaptiveUnit {}
+pub enum RlWavelengthTable {}
+#[repr(C)] #[derive(Copy, Clone)] pub struct RlWavelengthSampling {
+    pub importance: *const f64, pub n_nodes: u32, pub reserved: u32, pub uniform_share: f64,
+}
+pub const RL_WAVELENGTH_BINS: usize = 256;
 
 extern "C" {
     pub fn rl_last_error() -> *const c_char;
@@ -162,6 +167,12 @@ extern "C" {
     pub fn rl_trace_unit_create(device: c_int, id: u32, w: u32, h: u32, n_photons: u32, out: *mut *mut RlTraceUnit) -> c_int;
     pub fn rl_trace_unit_destroy(u: *mut RlTraceUnit) -> c_int;
     pub fn rl_trace_unit_set_fetch(u: *mut RlTraceUnit, primitive_fetch: c_int) -> c_int;   // 0 LDS, 1 global
+    pub fn rl_wavelength_table_create(device: c_int, importance: *const f64, n_nodes: u32, uniform_share: f64,
+                                      out: *mut *mut RlWavelengthTable) -> c_int;
+    pub fn rl_wavelength_table_destroy(table: *mut RlWavelengthTable) -> c_int;
+    pub fn rl_wavelength_table_download(table: *mut RlWavelengthTable, quantiles: *mut f32, weights: *mut f32) -> c_int;   // 257, 256
+    pub fn rl_wavelength_importance_cie1931(out: *mut f64) -> c_int;   // 81
+    pub fn rl_trace_unit_set_wavelengths(u: *mut RlTraceUnit, table: *const RlWavelengthTable) -> c_int;   // null: the uniform draw
     pub fn rl_trace_unit_render(u: *mut RlTraceUnit, scene: *const RlScene, seed: u64, stream: u32, first_path: u64) -> c_int;
     pub fn rl_trace_unit_render_begin(u: *mut RlTraceUnit, scene: *const RlScene, seed: u64, stream: u32, first_path: u64) -> c_int;
     pub fn rl_trace_unit_render_end(u: *mut RlTraceUnit) -> c_int;
@@ -297,6 +308,8 @@ extern "C" {
     // rl_app_run with a stopping rule: render until the estimated relative error is below a target (NULL target: rl_app_run).
     pub fn rl_app_run_to_error(config: *const RlAppConfig, target: *const RlErrorTarget, stats: *mut RlAppStats,
                                error_stats: *mut RlAppErrorStats, rgb_out: *mut u8) -> c_int;
+    pub fn rl_app_run_sampled(config: *const RlAppConfig, target: *const RlErrorTarget, sampling: *const RlWavelengthSampling,
+                              stats: *mut RlAppStats, error_stats: *mut RlAppErrorStats, rgb_out: *mut u8) -> c_int;
     pub fn rl_app_error_tiles(tiles: *mut f64, capacity: u32, n_tiles: *mut u32) -> c_int;
     pub fn rl_app_error_state(sum_y: *mut f64, sum_q: *mut f64, capacity_pixels: u64, n_pixels: *mut u64, observations: *mut u64,
                               paths: *mut u64) -> c_int;

@@ -121,6 +121,7 @@ typedef struct RlDenoiseUnit RlDenoiseUnit;
 typedef struct RlSpectralUnit RlSpectralUnit;
 typedef struct RlErrorUnit RlErrorUnit;
 typedef struct RlAdaptiveUnit RlAdaptiveUnit;
+typedef struct RlWavelengthTable RlWavelengthTable;
 typedef struct RlScheduler RlScheduler;
 typedef struct RlComm RlComm;
 
@@ -496,6 +497,47 @@ int rl_trace_unit_create(int device, uint32_t id, uint32_t width, uint32_t heigh
 int rl_trace_unit_destroy(RlTraceUnit* unit);
 /* Selects RL_FETCH_LDS (default) or RL_FETCH_GLOBAL for subsequent renders. */
 int rl_trace_unit_set_fetch(RlTraceUnit* unit, int primitive_fetch);
+
+/* ---- wavelength importance sampling (not in the reference, which draws every wavelength uniformly: trace_unit.rs:152) ----
+ * A table turns a path's first random word into a wavelength whose density follows an importance, and gives the path the
+ * reciprocal of that density (relative to uniform) as a weight, so the film's expectation is that of the uniform draw.
+ *
+ * The table.  M = RL_WAVELENGTH_BINS = 256.  `importance` is n_nodes doubles at equally spaced wavelengths from 380 to 780 nm
+ * inclusive, 2 <= n_nodes <= 4096 (NULL: uniform); uniform_share = u in (0, 1] is the part of the density that stays uniform.
+ * f64, in exactly this order, never contracted, divides correctly rounded:
+ *   g_k = importance[k] if it is finite and > 0, else 0;  m_j = (g_j + g_{j+1}) * 0.5 for j < n - 1;
+ *   G = the sequential sum of the m_j from +0.0 (an infinite G: RL_E_INVALID);
+ *   d_j = 1 / (n - 1) for a NULL importance or G == 0, else u / (n - 1) + (1 - u) * (m_j / G);
+ *   C_0 = 0, C_{j+1} = C_j + d_j;
+ *   for i = 0 .. M:  T_i = ((double)i / M) * C_{n-1};  j = the largest index <= n - 2 with C_j <= T_i;
+ *                    lambda_i = 380 + (400 / (n - 1)) * (j + (T_i - C_j) / d_j);  Q_i = (float)lambda_i,
+ *                    with Q_0 = 380 and Q_M = 780 set exactly;
+ *   Q must increase strictly, else RL_E_INVALID (the share is too small for f32);
+ *   W_i = (float)(((double)Q_{i+1} - (double)Q_i) * M / 400.0).
+ * The weight is taken from the ROUNDED quantiles: it is exactly the reciprocal of the density the device samples.
+ *
+ * A path.  f32, in this order, never contracted.  w0 = word 0 of the path's RNG block 0, v = w0 >> 8 (the 24 bits the uniform
+ * draw reads), i = v >> 16, f = (float)(v & 0xffff) * 2^-16, lambda = Q[i] + (Q[i+1] - Q[i]) * f.  Every other draw of the
+ * path, and everything made of lambda (the camera's chromatic zoom, the index of refraction), is the uniform path's word for
+ * word.  bin_of(lambda) = the largest i <= M - 1 with Q[i] <= lambda; the path's weight is W[bin_of(lambda)], a function of
+ * lambda alone, and enters once: value = emission * W, one f32 multiply.  RlMappedPhoton::probability carries it, so
+ * rl_plot_unit_plot and rl_spectral_unit_plot of such photons stay unbiased as they are.
+ *
+ * rl_wavelength_table_create checks, each RL_E_INVALID and before any device work, in this order: NULL out; n_nodes outside
+ * 2..4096; a share outside (0, 1] or NaN; the rule's own refusals.  _download: 257 quantiles and 256 weights, either pointer may
+ * be NULL.  rl_wavelength_importance_cie1931: x-bar + y-bar + z-bar of the CIE 1931 observer at its 81 nodes (host only). */
+#define RL_WAVELENGTH_BINS 256
+int rl_wavelength_table_create(int device, const double* importance, uint32_t n_nodes, double uniform_share,
+                               RlWavelengthTable** out);
+int rl_wavelength_table_destroy(RlWavelengthTable* table);
+int rl_wavelength_table_download(RlWavelengthTable* table, float* quantiles, float* weights);
+int rl_wavelength_importance_cie1931(double* out);
+/* Selects the table for subsequent renders of the unit -- every render call: render, _begin, _async, _fused, _fused_sync,
+ * _fused_begin -- as rl_trace_unit_set_fetch selects the fetch mode; NULL restores the reference's uniform draw.  The table must
+ * outlive the renders it was set for.  A table on another device than the unit's, or a call while a render begun on the unit
+ * has not ended: RL_E_STATE.  The table joins the combination under which calls share an open launch (rl_trace_unit_render_begin);
+ * a begun render for a fifth combination takes the plain launch described there, with the table. */
+int rl_trace_unit_set_wavelengths(RlTraceUnit* unit, const RlWavelengthTable* table);
 /* TraceUnit::render(&mut self, &Scene) (trace_unit.rs:151-168): fills the unit's mapped_photons.
  * Photon i of this call is path (first_path_index + i) of RNG stream `stream` under `seed`.
  * Complete on return: mapped_photons may be plotted or downloaded.  Calls made from several threads (the reference's
@@ -1297,6 +1339,23 @@ int rl_app_run_to_error(const RlAppConfig* config, const RlErrorTarget* target, 
 int rl_app_error_tiles(double* tiles, uint32_t capacity, uint32_t* n_tiles);
 int rl_app_error_state(double* sum_y, double* sum_q, uint64_t capacity_pixels, uint64_t* n_pixels, uint64_t* observations,
                        uint64_t* paths);
+
+/* ---- the App with wavelength importance sampling (rl_app_run_sampled) ---- */
+
+typedef struct RlWavelengthSampling {
+    const double* importance; /* n_nodes values from 380 to 780 nm (NULL: uniform), as rl_wavelength_table_create takes them */
+    uint32_t n_nodes;
+    uint32_t reserved;        /* must be 0 */
+    double uniform_share;
+} RlWavelengthSampling;
+
+/* rl_app_run_to_error whose trace units draw their wavelengths by importance: the App creates one table per rank, on the rank's
+ * device, sets it on every trace unit of the rank (rl_trace_unit_set_wavelengths) and destroys it with them.  With a NULL
+ * `sampling` it is rl_app_run_to_error; `target` may be NULL as there.  RlAppConfig keeps its layout.  The sampling's arguments are
+ * checked as rl_wavelength_table_create checks them, after rl_app_run_to_error's own checks and before any device work; a non-zero
+ * reserved is RL_E_INVALID too.  rl_app_error_tiles and rl_app_error_state serve this call as they serve rl_app_run_to_error. */
+int rl_app_run_sampled(const RlAppConfig* config, const RlErrorTarget* target, const RlWavelengthSampling* sampling, RlAppStats* stats,
+                       RlAppErrorStats* error_stats, uint8_t* rgb_out);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,9 @@ int rl_debug_batch_histogram(int device, uint64_t* out);
  * second bound); v = 16 + the low three bits: the variants that stage the scene's tables only (a scene too large for LDS).
  * The parity matrix (tests/test_gpu_parity.py) asserts with it that the variant it means to test is the one that ran. */
 int rl_debug_variant_launches(uint64_t* out);
+/* The same for the instantiations that draw the wavelength from a table (a unit after rl_trace_unit_set_wavelengths), indexed as
+ * rl_debug_variant_launches is; that one does not count them. */
+int rl_debug_wavelength_variant_launches(uint64_t out[24]);
 /* out[v], v = 0..5: launches of instantiation v of the query kernel (rl_scene_intersect*) since the library was loaded;
  * v = 2 * stage + (prisms carry a second bound), stage 0: nothing staged in LDS, 1: the scene's tables, 2: the whole scene. */
 int rl_debug_query_launches(uint64_t* out);

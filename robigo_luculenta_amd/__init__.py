@@ -14,7 +14,8 @@ from ._lib import (RlAppConfig, RlAppStats, RlCameraDesc, RlCameraSample, RlErro
                    RL_PATH_MAX_SEGMENTS_CAP, RL_TASK_MAX_UNITS, RlLightSample, RlDirectStats, RL_LIGHT_SKIPPED, RL_LIGHT_BACKFACING, RL_LIGHT_OCCLUDED,
                    RL_LIGHT_VISIBLE, RlFeatureSample, RlFeatureStats, RL_FEATURE_VOID, RL_FEATURE_EMITTER, RL_FEATURE_DIFFUSE, RL_FEATURE_LIMIT,
                    RL_FEATURE_MAX_SEGMENTS, RlDenoiseParams, RL_DENOISE_ITERATIONS, RL_DENOISE_MAX_ITERATIONS,
-                   RL_SPECTRAL_MAX_NODES, RlErrorStats, RlErrorTarget, RlAppErrorStats, RL_ERROR_TILE, RlAdaptiveStats)
+                   RL_SPECTRAL_MAX_NODES, RlErrorStats, RlErrorTarget, RlAppErrorStats, RL_ERROR_TILE, RlAdaptiveStats,
+                   RlWavelengthSampling)
 
 PHOTON_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("probability", "<f4"), ("wavelength", "<f4")])
 OBJECT_DTYPE = np.dtype([("surface_kind", "<u4"), ("material_kind", "<u4"), ("v0", "<f4", 3), ("v1", "<f4", 3),
@@ -390,6 +391,50 @@ class Scene(_Handle):
         return {"paths": int(stats.paths), "segments": int(stats.segments), "kinds": [int(k) for k in stats.kinds]}
 
 
+WAVELENGTH_BINS = 256
+
+
+def wavelength_importance_cie1931():
+    """rl_wavelength_importance_cie1931: x-bar + y-bar + z-bar of the CIE 1931 observer at its 81 nodes, float64."""
+    out = np.zeros(81, dtype=np.float64)
+    check(lib.rl_wavelength_importance_cie1931(_host_ptr(out)))
+    return out
+
+
+def _wavelength_importance(importance):
+    """An importance as the entry points take it: None, "cie", or values at equally spaced wavelengths from 380 to 780 nm."""
+    if importance is None:
+        return None
+    if isinstance(importance, str):
+        if importance != "cie":
+            raise ValueError("a named wavelength importance must be 'cie'")
+        return wavelength_importance_cie1931()
+    return np.ascontiguousarray(importance, dtype=np.float64).reshape(-1)
+
+
+class WavelengthTable(_Handle):
+    """Wavelength importance sampling (rl_wavelength_table_*): 257 quantiles and 256 weights made of an importance over 380-780 nm.
+    A TraceUnit draws its wavelengths from it after set_wavelengths; the table must outlive those renders."""
+    _destroy = lib.rl_wavelength_table_destroy
+
+    def __init__(self, importance="cie", uniform_share=0.1, n_nodes=None, device=0):
+        """importance: "cie", values at n_nodes equally spaced wavelengths, or None (uniform; n_nodes then defaults to 2)."""
+        super().__init__()
+        g = _wavelength_importance(importance)
+        if n_nodes is None:
+            n_nodes = len(g) if g is not None else 2
+        if g is not None and len(g) != n_nodes:
+            raise ValueError("importance must hold n_nodes values")
+        check(lib.rl_wavelength_table_create(device, _host_ptr(g), n_nodes, uniform_share, C.byref(self._h)))
+        self.device = device
+
+    def download(self):
+        """(quantiles float32[257], weights float32[256]) read back from the device."""
+        q, w = np.zeros(WAVELENGTH_BINS + 1, dtype=np.float32), np.zeros(WAVELENGTH_BINS, dtype=np.float32)
+        check(lib.rl_wavelength_table_download(self._h, _host_ptr(q), _host_ptr(w)))
+        return q, w
+
+
 class TraceUnit(_Handle):
     """trace_unit.rs:51-168."""
     _destroy = lib.rl_trace_unit_destroy
@@ -401,6 +446,11 @@ class TraceUnit(_Handle):
 
     def set_fetch(self, fetch):
         check(lib.rl_trace_unit_set_fetch(self._h, fetch))
+
+    def set_wavelengths(self, table):
+        """rl_trace_unit_set_wavelengths: a WavelengthTable for subsequent renders, or None for the reference's uniform draw."""
+        check(lib.rl_trace_unit_set_wavelengths(self._h, table.handle if table is not None else None))
+        self._wavelengths = table  # (kept alive with the unit)
 
     def render(self, scene, seed=1, stream=0, first_path_index=0):
         check(lib.rl_trace_unit_render(self._h, scene.handle, seed, stream, first_path_index))
@@ -1042,11 +1092,22 @@ class TaskScheduler(_Handle):
 
 def app_run(width, height, max_batches, concurrency=1, device=0, photons_per_batch=NUMBER_OF_PHOTONS, seed=1, stream=0,
             scene=SCENE_DEMO, scene_param=0, tonemap_interval_ms=30000, fused=False, output_ppm=None, checkpoint=None,
-            resume=False, verbose=False, sleep_us=0, first_batch=0, devices=None, blocking_trace=False, threads=0):
+            resume=False, verbose=False, sleep_us=0, first_batch=0, devices=None, blocking_trace=False, threads=0,
+            wavelength_importance=None, wavelength_uniform_share=0.1):
     """App::new + worker loops (app.rs:54-111) until `max_batches` trace tasks are done, on one GPU or, with
     `devices` = a list of device indices (repeats allowed), on one rank per entry with the plot buffers summed
     onto rank 0 at every gather.  `concurrency` sizes the scheduler's pools, `threads` (0 = concurrency) the host worker pool.
+    wavelength_importance ("cie" or values from 380 to 780 nm) makes the trace units draw their wavelengths by importance
+    (rl_app_run_sampled), wavelength_uniform_share of the density staying uniform.
     Returns (rgb image as (H, W, 3) uint8, stats dict)."""
+    if wavelength_importance is not None:
+        rgb, stats, _ = app_run_to_error(width, height, max_batches, None, concurrency=concurrency, device=device, photons_per_batch=photons_per_batch,
+                                         seed=seed, stream=stream, scene=scene, scene_param=scene_param, tonemap_interval_ms=tonemap_interval_ms,
+                                         fused=fused, output_ppm=output_ppm, checkpoint=checkpoint, resume=resume, verbose=verbose,
+                                         sleep_us=sleep_us, first_batch=first_batch, devices=devices, blocking_trace=blocking_trace,
+                                         threads=threads, wavelength_importance=wavelength_importance,
+                                         wavelength_uniform_share=wavelength_uniform_share)
+        return rgb, stats
     dev_arr = (C.c_int * len(devices))(*devices) if devices else None
     cfg = RlAppConfig(width, height, device, concurrency, photons_per_batch, seed, stream, scene, scene_param, max_batches,
                       tonemap_interval_ms, int(fused), output_ppm.encode() if output_ppm else None,
@@ -1067,10 +1128,11 @@ def _app_stats(stats):
 def app_run_to_error(width, height, max_batches, target_error=None, worst_tile_error=0.0, min_observations=0, concurrency=1, device=0,
                      photons_per_batch=NUMBER_OF_PHOTONS, seed=1, stream=0, scene=SCENE_DEMO, scene_param=0, tonemap_interval_ms=30000,
                      fused=False, output_ppm=None, checkpoint=None, resume=False, verbose=False, sleep_us=0, first_batch=0, devices=None,
-                     blocking_trace=False, threads=0, reserved=0):
+                     blocking_trace=False, threads=0, reserved=0, wavelength_importance=None, wavelength_uniform_share=0.1):
     """rl_app_run_to_error: app_run that ends the hand-out of batches once an estimate made at a tonemap (every tonemap_interval_ms)
     has at least min_observations (0 = 16) observations and a relative error <= target_error (and, with a non-zero worst_tile_error,
-    a worst tile <= it); max_batches stays the cap.  target_error=None passes no target: app_run.  Returns (rgb, stats dict, error
+    a worst tile <= it); max_batches stays the cap.  target_error=None passes no target: app_run.  wavelength_importance ("cie" or
+    values from 380 to 780 nm) makes the trace units draw their wavelengths by importance (rl_app_run_sampled).  Returns (rgb, stats dict, error
     dict {at_stop, at_end: rl_error_unit_estimate's stats, reached, estimates, tiles: at_end's (tiles_y, tiles_x, 2) pairs or None})."""
     dev_arr = (C.c_int * len(devices))(*devices) if devices else None
     cfg = RlAppConfig(width, height, device, concurrency, photons_per_batch, seed, stream, scene, scene_param, max_batches,
@@ -1080,7 +1142,12 @@ def app_run_to_error(width, height, max_batches, target_error=None, worst_tile_e
     target = None if target_error is None else C.byref(RlErrorTarget(target_error, worst_tile_error, min_observations, reserved))
     stats, es = RlAppStats(), RlAppErrorStats()
     rgb = np.zeros((height, width, 3), dtype=np.uint8)
-    check(lib.rl_app_run_to_error(C.byref(cfg), target, C.byref(stats), C.byref(es), rgb.ctypes.data_as(C.c_void_p)))
+    g = _wavelength_importance(wavelength_importance)
+    if g is None:
+        check(lib.rl_app_run_to_error(C.byref(cfg), target, C.byref(stats), C.byref(es), rgb.ctypes.data_as(C.c_void_p)))
+    else:
+        sampling = RlWavelengthSampling(g.ctypes.data, len(g), 0, wavelength_uniform_share)
+        check(lib.rl_app_run_sampled(C.byref(cfg), target, C.byref(sampling), C.byref(stats), C.byref(es), rgb.ctypes.data_as(C.c_void_p)))
     n = C.c_uint32(0)
     lib.rl_app_error_tiles(None, 0, C.byref(n))     # (RL_E_INVALID when there are tiles: the count is what is asked for)
     tiles = None
@@ -1123,6 +1190,12 @@ def variant_launches():
     index = 8 * whole scene staged in LDS + 4 * fused + 2 * open launch + 1 * prisms with a second bound; 16 + the low three
     bits for the variants that stage the scene's tables only."""
     return _launch_counters(lib.rl_debug_variant_launches, 24, list)
+
+
+def wavelength_variant_launches():
+    """rl_debug_wavelength_variant_launches: the same for the instantiations that draw the wavelength from a table (a TraceUnit after
+    set_wavelengths), indexed as variant_launches is, which does not count them."""
+    return _launch_counters(lib.rl_debug_wavelength_variant_launches, 24, list)
 
 
 def query_launches():

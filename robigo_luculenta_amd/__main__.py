@@ -71,7 +71,22 @@ def parse_args(argv=None):
                          "(render_adaptive_to_error over the unit API, not the App worker pool)")
     ap.add_argument("--uniform-share", metavar="F", type=float, default=None,
                     help="with --adaptive: the share of a batch's paths spread by area, 0 < F <= 1 (default 0.25)")
+    ap.add_argument("--wavelength-importance", choices=["cie"], default=None,
+                    help="draw each path's wavelength by importance instead of uniformly from 380-780 nm, and weight it accordingly: "
+                         "'cie' follows the sum of the CIE 1931 observer's three curves (the App modes and --spectral's re-render)")
+    ap.add_argument("--wavelength-uniform-share", metavar="F", type=float, default=None,
+                    help="with --wavelength-importance: the share of the density that stays uniform, 0 < F <= 1 (default 0.1)")
     a = ap.parse_args(argv)
+    if a.wavelength_uniform_share is not None and a.wavelength_importance is None:
+        ap.error("--wavelength-uniform-share needs --wavelength-importance")
+    if a.wavelength_uniform_share is not None and not 0 < a.wavelength_uniform_share <= 1:
+        ap.error("--wavelength-uniform-share must be a number in (0, 1]")
+    if a.wavelength_importance is not None:
+        for given, flag in ((a.direct, "--direct"), (a.adaptive, "--adaptive")):
+            if given:
+                ap.error("--wavelength-importance cannot be combined with %s: that renderer draws its own wavelengths" % flag)
+        if a.wavelength_uniform_share is None:
+            a.wavelength_uniform_share = 0.1
     if a.adaptive and a.target_error is None:
         ap.error("--adaptive needs --target-error: the samples follow the estimate the target is held to")
     if a.uniform_share is not None and not a.adaptive:
@@ -207,9 +222,12 @@ def render_spectral(a):
     """--spectral PATH: the batches x photons_per_batch paths of stream 0 once more, un-fused -- TraceUnit.render in runs of at most
     2^22 paths, SpectralUnit.plot of each -- and the cube saved with numpy.save.  Returns the cube, float32 (nodes, height, width)."""
     import numpy as np
-    from . import Scene, SpectralUnit, TraceUnit
+    from . import Scene, SpectralUnit, TraceUnit, WavelengthTable
     scene = Scene.builtin(SCENE_DEMO if a.scene == "demo" else SCENE_GLASS_STRESS, device=a.device)
     film = SpectralUnit(a.width, a.height, a.spectral_nodes, device=a.device)
+    table = None
+    if a.wavelength_importance is not None:       # the image's paths: the same table, so the same wavelengths and weights
+        table = WavelengthTable(a.wavelength_importance, a.wavelength_uniform_share, device=a.device)
     total = a.batches * a.photons_per_batch
     run = max(1, min(total, 1 << 22))
     traces = {}
@@ -217,6 +235,7 @@ def render_spectral(a):
         n = min(run, total - first)
         if n not in traces:
             traces[n] = TraceUnit(0, a.width, a.height, n_photons=n, device=a.device)
+            traces[n].set_wavelengths(table)
         traces[n].render(scene, seed=a.seed, stream=0, first_path_index=first)
         film.plot([traces[n]])
     cube = film.download()
@@ -321,6 +340,8 @@ def main(argv=None):
     common = dict(concurrency=a.concurrency, device=a.device, seed=a.seed, photons_per_batch=a.photons_per_batch,
                   scene=SCENE_DEMO if a.scene == "demo" else SCENE_GLASS_STRESS, fused=not a.unfused,
                   output_ppm=a.output, checkpoint=checkpoint, resume=a.resume, verbose=not a.quiet)
+    if a.wavelength_importance is not None:
+        common.update(wavelength_importance=a.wavelength_importance, wavelength_uniform_share=a.wavelength_uniform_share)
     if a.target_error is not None or a.error_map is not None:
         # without a target the rule is 0, which no noisy render meets: the run goes to the cap and estimates at its end
         rgb, st, err = app_run_to_error(a.width, a.height, a.batches, target_error=a.target_error or 0.0,

@@ -137,6 +137,10 @@ class RlErrorTarget(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class RlWavelengthSampling(C.Structure):
+    _fields_ = [("importance", C.c_void_p), ("n_nodes", C.c_uint32), ("reserved", C.c_uint32), ("uniform_share", C.c_double)]
+
+
 class RlAppErrorStats(C.Structure):
     _fields_ = [("at_stop", RlErrorStats), ("at_end", RlErrorStats), ("reached", C.c_uint32), ("estimates", C.c_uint32)]
 
@@ -196,6 +200,11 @@ SIGNATURES = {
     "rl_trace_unit_create": (_i, [_i, _u32, _u32, _u32, _u32, _pp]),
     "rl_trace_unit_destroy": (_i, [_vp]),
     "rl_trace_unit_set_fetch": (_i, [_vp, _i]),
+    "rl_trace_unit_set_wavelengths": (_i, [_vp, _vp]),
+    "rl_wavelength_table_create": (_i, [_i, _vp, _u32, C.c_double, _pp]),
+    "rl_wavelength_table_destroy": (_i, [_vp]),
+    "rl_wavelength_table_download": (_i, [_vp, _vp, _vp]),
+    "rl_wavelength_importance_cie1931": (_i, [_vp]),
     "rl_trace_unit_render": (_i, [_vp, _vp, _u64, _u32, _u64]),
     "rl_trace_unit_render_begin": (_i, [_vp, _vp, _u64, _u32, _u64]),
     "rl_trace_unit_render_end": (_i, [_vp]),
@@ -284,6 +293,8 @@ SIGNATURES = {
     "rl_scheduler_performance": (_i, [_vp, C.POINTER(_f), C.POINTER(_f)]),
     "rl_app_run": (_i, [C.POINTER(RlAppConfig), C.POINTER(RlAppStats), _vp]),
     "rl_app_run_to_error": (_i, [C.POINTER(RlAppConfig), C.POINTER(RlErrorTarget), C.POINTER(RlAppStats), C.POINTER(RlAppErrorStats), _vp]),
+    "rl_app_run_sampled": (_i, [C.POINTER(RlAppConfig), C.POINTER(RlErrorTarget), C.POINTER(RlWavelengthSampling), C.POINTER(RlAppStats),
+                                C.POINTER(RlAppErrorStats), _vp]),
     "rl_app_error_tiles": (_i, [_vp, _u32, C.POINTER(_u32)]),
     "rl_app_error_state": (_i, [_vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
 }
@@ -294,6 +305,7 @@ DEBUG_SIGNATURES = {
     "rl_debug_app_rank_plan": (_i, [_i, _vp, _u32, _vp, _vp, _vp, C.POINTER(_u32)]),
     "rl_debug_batch_histogram": (_i, [_i, _vp]),
     "rl_debug_variant_launches": (_i, [_vp]),
+    "rl_debug_wavelength_variant_launches": (_i, [_vp]),
     "rl_debug_query_launches": (_i, [_vp]),
     "rl_debug_occlusion_launches": (_i, [_vp]),
     "rl_debug_path_launches": (_i, [_vp]),

@@ -384,9 +384,19 @@ struct Ticket {
 };
 }
 
+// rl_wavelength_table_create: the table of rl_wavelength.h on a device, and the host's copy of it.
+struct RlWavelengthTable {
+    int device;
+    uint64_t id;   // never 0, never reused: the open launches' key (an address may be, by the next table)
+    Ledger ledger; // table
+    float* table;  // RL_WAVELENGTH_TABLE_FLOATS floats: the quantiles, then the weights
+    float host[RL_WAVELENGTH_TABLE_FLOATS];
+};
+
 struct RlTraceUnit {
     int device;
     uint32_t id, width, height, n_photons;
+    const RlWavelengthTable* wavelengths; // rl_trace_unit_set_wavelengths: the caller's, null = the reference's uniform draw
     RlMappedPhoton* photons;
     unsigned long long* queue; // 3 counters, see rl_trace_kernel
     hipStream_t stream;
@@ -543,6 +553,25 @@ TraceKernel trace_kernel_variant(int stage, bool fused, bool open, bool cyl) {
     };
     return table[index];
 }
+// The same for a unit with a wavelength table (rl_trace_unit_set_wavelengths): the WL instantiations, which take the table as one
+// more argument, counted on their own (rl_debug_wavelength_variant_launches; same index).
+typedef void (*TraceKernelWl)(const RlF4*, RlSceneLayout, RlTraceJob, RlMappedPhoton*, float*, unsigned long long*, const RlJobEntry*,
+                              RlOpenDev*, RlOpenCtl*, const float*);
+std::atomic<uint64_t> g_wavelength_variant_launches[24];
+TraceKernelWl trace_kernel_variant_wl(int stage, bool fused, bool open, bool cyl) {
+    const int low = (fused ? 4 : 0) | (open ? 2 : 0) | (cyl ? 1 : 0);
+    const int index = stage == RL_STAGE_TABLES ? 16 + low : (stage == RL_STAGE_ALL ? 8 : 0) | low;
+    g_wavelength_variant_launches[index].fetch_add(1, std::memory_order_relaxed);
+    static const TraceKernelWl table[24] = {
+        rl_wl_trace_kernel<RL_STAGE_NONE, false, false>, rl_wl_trace_kernel<RL_STAGE_NONE, false, true>, rl_wl_trace_open_kernel<RL_STAGE_NONE, false, false>, rl_wl_trace_open_kernel<RL_STAGE_NONE, false, true>,
+        rl_wl_trace_kernel<RL_STAGE_NONE, true, false>, rl_wl_trace_kernel<RL_STAGE_NONE, true, true>, rl_wl_trace_open_kernel<RL_STAGE_NONE, true, false>, rl_wl_trace_open_kernel<RL_STAGE_NONE, true, true>,
+        rl_wl_trace_kernel<RL_STAGE_ALL, false, false>, rl_wl_trace_kernel<RL_STAGE_ALL, false, true>, rl_wl_trace_open_kernel<RL_STAGE_ALL, false, false>, rl_wl_trace_open_kernel<RL_STAGE_ALL, false, true>,
+        rl_wl_trace_kernel<RL_STAGE_ALL, true, false>, rl_wl_trace_kernel<RL_STAGE_ALL, true, true>, rl_wl_trace_open_kernel<RL_STAGE_ALL, true, false>, rl_wl_trace_open_kernel<RL_STAGE_ALL, true, true>,
+        rl_wl_trace_kernel<RL_STAGE_TABLES, false, false>, rl_wl_trace_kernel<RL_STAGE_TABLES, false, true>, rl_wl_trace_open_kernel<RL_STAGE_TABLES, false, false>, rl_wl_trace_open_kernel<RL_STAGE_TABLES, false, true>,
+        rl_wl_trace_kernel<RL_STAGE_TABLES, true, false>, rl_wl_trace_kernel<RL_STAGE_TABLES, true, true>, rl_wl_trace_open_kernel<RL_STAGE_TABLES, true, false>, rl_wl_trace_open_kernel<RL_STAGE_TABLES, true, true>,
+    };
+    return table[index];
+}
 // Ring T of rl_scan_wave: 512 bytes per wave in front of the scratch blocks, for scenes whose cull table has a third level.
 size_t ring_t_bytes(const RlScene* scene) { return scene->lay.n_cluster_supers != 0u ? (size_t)(RL_TRACE_BLOCK / 64) * 512u : 0u; }
 // What a launch stages in LDS beside `scratch_bytes` of per-wave scratch: the whole scene where it fits, its tables where
@@ -605,17 +634,20 @@ int launch_trace(RlTraceUnit* u, const RlScene* scene, RlMappedPhoton* photons, 
     const int stage = stage_of(scene, u->fetch, scratch_bytes, &blob_bytes);
     const bool fused = plot != nullptr;
     const bool cyl = scene->lay.prism_cylinders != 0u;
-    auto kernel = trace_kernel_variant(stage, fused, false, cyl);
+    const float* wl = u->wavelengths ? u->wavelengths->table : nullptr;
+    const TraceKernel plain = wl ? nullptr : trace_kernel_variant(stage, fused, false, cyl);
+    const TraceKernelWl sampled = wl ? trace_kernel_variant_wl(stage, fused, false, cyl) : nullptr;
+    const void* kernel = wl ? (const void*)sampled : (const void*)plain;
     const size_t dyn = scratch_bytes + blob_bytes;
-    if (u->tuned_per_cu == 0 || u->tuned_dyn != dyn || u->tuned_kernel != (const void*)kernel) { // once per (unit, scene size, variant)
+    if (u->tuned_per_cu == 0 || u->tuned_dyn != dyn || u->tuned_kernel != kernel) { // once per (unit, scene size, variant)
         // The limit is a property of the function, shared by every unit: always raise it to the whole LDS.
-        RL_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        RL_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         int per_cu = 1;
         RL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, RL_TRACE_BLOCK, dyn));
         u->tuned_per_cu = per_cu < 1 ? 1 : per_cu;
         if (getenv("RL_DEBUG_LAUNCH")) fprintf(stderr, "rl: trace launch: %d workgroup(s) of %d threads per CU, %zu bytes of LDS each, stage %d\n", per_cu, RL_TRACE_BLOCK, dyn, stage);
         u->tuned_dyn = dyn;
-        u->tuned_kernel = (const void*)kernel; // (the instantiation itself, not some of its template arguments -- `cyl` was not among them)
+        u->tuned_kernel = kernel; // (the instantiation itself, not some of its template arguments -- `cyl` was not among them)
     }
     uint64_t blocks = (uint64_t)u->cu_count * (uint64_t)u->tuned_per_cu;
     const uint64_t needed = (n_paths + RL_TRACE_BLOCK - 1) / RL_TRACE_BLOCK;
@@ -633,8 +665,12 @@ int launch_trace(RlTraceUnit* u, const RlScene* scene, RlMappedPhoton* photons, 
         }
         RL_HIP(hipMemsetAsync(u->queue, 0, sizeof(unsigned long long), u->stream));
         return timed_launch(ep, u->stream, &u->launches, [&] {
-            hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(RL_TRACE_BLOCK), dyn, u->stream, scene->blob, scene->lay, job, photons,
-                               plot, u->queue, (const RlJobEntry*)nullptr, (RlOpenDev*)nullptr, (RlOpenCtl*)nullptr);
+            if (wl)
+                hipLaunchKernelGGL(sampled, dim3((unsigned)blocks), dim3(RL_TRACE_BLOCK), dyn, u->stream, scene->blob, scene->lay, job, photons,
+                                   plot, u->queue, (const RlJobEntry*)nullptr, (RlOpenDev*)nullptr, (RlOpenCtl*)nullptr, wl);
+            else
+                hipLaunchKernelGGL(plain, dim3((unsigned)blocks), dim3(RL_TRACE_BLOCK), dyn, u->stream, scene->blob, scene->lay, job, photons,
+                                   plot, u->queue, (const RlJobEntry*)nullptr, (RlOpenDev*)nullptr, (RlOpenCtl*)nullptr);
         });
     }();
     if (rc != RL_OK) {
@@ -1624,6 +1660,68 @@ int rl_trace_unit_set_fetch(RlTraceUnit* u, int primitive_fetch) {
     return RL_OK;
 }
 
+// ---- wavelength importance sampling (rl_wavelength.h) ---------------------------------------------
+
+int rl_wavelength_importance_cie1931(double* out) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    rl_wavelength_cie_importance(out);
+    return RL_OK;
+}
+
+// The checks of rl_wavelength_table_create behind its null-output check, in the header's order, and the table itself (513 floats).
+// Host arithmetic only.  Internal (not in the C header): rl_app.cpp checks an RlWavelengthSampling with it before any device work.
+extern "C" int rl_internal_wavelength_rule(const double* importance, uint32_t n_nodes, double uniform_share, float* table) {
+    if (n_nodes < 2u || n_nodes > RL_WAVELENGTH_MAX_NODES) return fail(RL_E_INVALID, "wavelength table: n_nodes must be 2 .. 4096");
+    if (!(uniform_share > 0.0 && uniform_share <= 1.0)) return fail(RL_E_INVALID, "wavelength table: uniform_share must be in (0, 1]");
+    switch (rl_wavelength_table_rule(importance, n_nodes, uniform_share, table)) {
+    case RL_WAVELENGTH_OK: return RL_OK;
+    case RL_WAVELENGTH_OVERFLOW: return fail(RL_E_INVALID, "wavelength table: the sum of the importance overflows");
+    default: return fail(RL_E_INVALID, "wavelength table: the quantiles do not increase in f32 (uniform_share is too small for this importance)");
+    }
+}
+
+int rl_wavelength_table_create(int device, const double* importance, uint32_t n_nodes, double uniform_share, RlWavelengthTable** out) {
+    if (!out) return fail(RL_E_INVALID, "null output handle");
+    *out = nullptr;
+    RlWavelengthTable* t = new (std::nothrow) RlWavelengthTable();
+    if (!t) return fail(RL_E_INVALID, "out of host memory");
+    int rc = rl_internal_wavelength_rule(importance, n_nodes, uniform_share, t->host);
+    if (rc == RL_OK) rc = use_device(device);
+    if (rc != RL_OK) {
+        delete t;
+        return rc;
+    }
+    static std::atomic<uint64_t> next_id{1};
+    t->device = device;
+    t->id = next_id.fetch_add(1, std::memory_order_relaxed);
+    t->ledger.alloc(&t->table, sizeof t->host, t->host);
+    return unit_created("wavelength table allocation", t, rl_wavelength_table_destroy, out);
+}
+
+int rl_wavelength_table_destroy(RlWavelengthTable* t) {
+    if (!t) return RL_OK;
+    (void)hipSetDevice(t->device);
+    t->ledger.release();
+    delete t;
+    return RL_OK;
+}
+
+int rl_wavelength_table_download(RlWavelengthTable* t, float* quantiles, float* weights) {
+    if (!t) return fail(RL_E_INVALID, "null wavelength table");
+    const int rc = use_device(t->device);
+    if (rc != RL_OK) return rc;
+    return download(nullptr, {{t->table, quantiles, (RL_WAVELENGTH_BINS + 1) * sizeof(float)},
+                              {t->table + (RL_WAVELENGTH_BINS + 1), weights, RL_WAVELENGTH_BINS * sizeof(float)}});
+}
+
+int rl_trace_unit_set_wavelengths(RlTraceUnit* u, const RlWavelengthTable* table) {
+    if (!u) return fail(RL_E_INVALID, "null trace unit");
+    if (table && table->device != u->device) return fail(RL_E_STATE, "wavelength table and trace unit live on different devices");
+    if (u->ticket.pending) return fail(RL_E_STATE, "the trace unit has a render that was begun and not ended");
+    u->wavelengths = table;
+    return RL_OK;
+}
+
 int rl_trace_unit_render_async(RlTraceUnit* u, const RlScene* scene, uint64_t seed, uint32_t stream, uint64_t first_path_index) {
     if (!u || !scene) return fail(RL_E_INVALID, "null handle");
     int rc = use_device(u->device);
@@ -1663,6 +1761,7 @@ struct Session {
     uint32_t stream_id = 0, width = 0, height = 0;
     int fetch = 0;
     bool fused = false;
+    uint64_t wavelengths = 0; // the id of the units' wavelength table (0: none): calls with another one do not join
     // who the running kernel works for: (a unit's counters, paths of its call) per job; its run time is split by paths
     std::vector<std::pair<std::shared_ptr<UnitCounters>, uint64_t>> shares;
 };
@@ -1760,6 +1859,7 @@ int session_start(DeviceSessions* d, Session& x, RlTraceUnit* u, const RlScene* 
     x.height = u->height;
     x.fetch = u->fetch;
     x.fused = fused;
+    x.wavelengths = u->wavelengths ? u->wavelengths->id : 0u;
     RlTraceJob job;
     job.width = u->width;
     job.height = u->height;
@@ -1776,14 +1876,17 @@ int session_start(DeviceSessions* d, Session& x, RlTraceUnit* u, const RlScene* 
     const size_t scratch_bytes = (RL_TRACE_BLOCK / 64) * sizeof(RlWaveScratch) + sizeof(RlOpenWg) + ring_t_bytes(scene);
     size_t blob_bytes = 0;
     const int stage = stage_of(scene, u->fetch, scratch_bytes, &blob_bytes);
-    auto kernel = trace_kernel_variant(stage, fused, true, scene->lay.prism_cylinders != 0u);
+    const float* wl = u->wavelengths ? u->wavelengths->table : nullptr;
+    const TraceKernel plain = wl ? nullptr : trace_kernel_variant(stage, fused, true, scene->lay.prism_cylinders != 0u);
+    const TraceKernelWl sampled = wl ? trace_kernel_variant_wl(stage, fused, true, scene->lay.prism_cylinders != 0u) : nullptr;
+    const void* kernel = wl ? (const void*)sampled : (const void*)plain;
     const size_t dyn = scratch_bytes + blob_bytes;
-    if (x.tuned_kernel != (const void*)kernel || x.tuned_dyn != dyn) { // once per (slot, variant, scene size)
-        RL_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if (x.tuned_kernel != kernel || x.tuned_dyn != dyn) { // once per (slot, variant, scene size)
+        RL_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         int n = 1;
         RL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, RL_TRACE_BLOCK, dyn));
         x.tuned_per_cu = n < 1 ? 1 : n;
-        x.tuned_kernel = (const void*)kernel;
+        x.tuned_kernel = kernel;
         x.tuned_dyn = dyn;
     }
     const int per_cu = x.tuned_per_cu;
@@ -1796,8 +1899,12 @@ int session_start(DeviceSessions* d, Session& x, RlTraceUnit* u, const RlScene* 
     RL_HIP(hipMemsetAsync(x.od, 0, sizeof(RlOpenDev), x.stream));
     RL_HIP(hipMemsetAsync(x.counters, 0, 3 * sizeof(unsigned long long), x.stream));
     RL_HIP(hipEventRecord(x.start, x.stream));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(u->cu_count * per_cu)), dim3(RL_TRACE_BLOCK), dyn, x.stream, scene->blob, scene->lay, job,
-                       (RlMappedPhoton*)nullptr, (float*)nullptr, x.counters, (const RlJobEntry*)x.od->jobs, x.od, x.ctl_dev);
+    if (wl)
+        hipLaunchKernelGGL(sampled, dim3((unsigned)(u->cu_count * per_cu)), dim3(RL_TRACE_BLOCK), dyn, x.stream, scene->blob, scene->lay, job,
+                           (RlMappedPhoton*)nullptr, (float*)nullptr, x.counters, (const RlJobEntry*)x.od->jobs, x.od, x.ctl_dev, wl);
+    else
+        hipLaunchKernelGGL(plain, dim3((unsigned)(u->cu_count * per_cu)), dim3(RL_TRACE_BLOCK), dyn, x.stream, scene->blob, scene->lay, job,
+                           (RlMappedPhoton*)nullptr, (float*)nullptr, x.counters, (const RlJobEntry*)x.od->jobs, x.od, x.ctl_dev);
     RL_HIP(hipGetLastError());
     RL_HIP(hipEventRecord(x.stop, x.stream));
     x.launched = true;
@@ -1888,7 +1995,7 @@ int session_begin(RlTraceUnit* u, const RlScene* scene, RlPlotUnit* plot, uint64
         for (;;) {
             for (Session& x : d->s) // a running kernel that takes this call?
                 if (x.open && x.n < RL_OPEN_CAP && x.scene == scene && x.seed == seed && x.stream_id == stream_id && x.width == u->width &&
-                    x.height == u->height && x.fetch == u->fetch && x.fused == (plot != nullptr)) {
+                    x.height == u->height && x.fetch == u->fetch && x.fused == (plot != nullptr) && x.wavelengths == (u->wavelengths ? u->wavelengths->id : 0u)) {
                     k = session_append(x, e);
                     if (k >= 0) mine = &x, x.waiters += 1, x.shares.emplace_back(u->counters, n_paths);
                     else x.open = false;
@@ -1912,7 +2019,7 @@ int session_begin(RlTraceUnit* u, const RlScene* scene, RlPlotUnit* plot, uint64
             for (Session& x : d->s)
                 if (x.open && x.n >= RL_OPEN_CAP) x.open = false, retry = true;
             if (retry) continue;
-            // Every slot is taken by another (scene, seed, stream, size, fetch, fused) combination.  A slot nobody waits
+            // Every slot is taken by another (scene, seed, stream, size, fetch, fused, wavelength table) combination.  A slot nobody waits
             // on frees itself (its kernel closes after a grace period), but one that carries begun renders stays until
             // they are ended -- possibly by this very thread (a fifth combination begun without ending an
             // earlier one used to spin here for ever).  If all of them do, the call gets a launch of its own instead.
@@ -3692,6 +3799,12 @@ int rl_debug_batch_histogram(int device, uint64_t* out) {
 int rl_debug_variant_launches(uint64_t* out) {
     if (!out) return fail(RL_E_INVALID, "null argument");
     for (int k = 0; k < 24; ++k) out[k] = g_variant_launches[k].load(std::memory_order_relaxed);
+    return RL_OK;
+}
+
+int rl_debug_wavelength_variant_launches(uint64_t out[24]) {
+    if (!out) return fail(RL_E_INVALID, "null argument");
+    for (int k = 0; k < 24; ++k) out[k] = g_wavelength_variant_launches[k].load(std::memory_order_relaxed);
     return RL_OK;
 }
 

@@ -34,6 +34,7 @@
 #include "../../include/robigo_luculenta.h"
 
 void rl_internal_set_last_error(const std::string& msg); // rl_api.hip
+extern "C" int rl_internal_wavelength_rule(const double* importance, uint32_t n_nodes, double uniform_share, float* table); // rl_api.hip
 
 namespace {
 
@@ -42,6 +43,7 @@ struct Rank { // one GPU (or one RNG stream of a GPU that is listed twice)
     int leader = 0;            // first rank on the same device
     RlScene* scene = nullptr;
     RlComm* comm = nullptr;    // set on device leaders when there is more than one distinct device
+    RlWavelengthTable* wavelengths = nullptr; // rl_app_run_sampled: set on every trace unit of the rank
     std::vector<RlTraceUnit*> trace_units;
     std::vector<RlPlotUnit*> plot_units;
 };
@@ -534,6 +536,11 @@ extern "C" int rl_app_error_state(double* sum_y, double* sum_q, uint64_t capacit
 
 extern "C" int rl_app_run_to_error(const RlAppConfig* config, const RlErrorTarget* target, RlAppStats* stats, RlAppErrorStats* error_stats,
                                    uint8_t* rgb_out) {
+    return rl_app_run_sampled(config, target, nullptr, stats, error_stats, rgb_out);
+}
+
+extern "C" int rl_app_run_sampled(const RlAppConfig* config, const RlErrorTarget* target, const RlWavelengthSampling* sampling, RlAppStats* stats,
+                                  RlAppErrorStats* error_stats, uint8_t* rgb_out) {
     g_last_error_tiles.clear();
     g_last_error_planes.clear();
     g_last_error_observations = g_last_error_paths = 0;
@@ -556,6 +563,15 @@ extern "C" int rl_app_run_to_error(const RlAppConfig* config, const RlErrorTarge
     if (target && (!(target->relative_error >= 0.0) || !(target->worst_tile_error >= 0.0) || target->reserved != 0)) {
         rl_internal_set_last_error("rl_app_run_to_error: the target's relative_error and worst_tile_error must be >= 0 (not NaN) and its reserved field 0");
         return RL_E_INVALID;
+    }
+    if (sampling) { // (the table itself is made per rank below: this run of the rule only refuses)
+        std::vector<float> table(2 * RL_WAVELENGTH_BINS + 1);
+        if (sampling->reserved != 0) {
+            rl_internal_set_last_error("rl_app_run_sampled: the sampling's reserved field must be 0");
+            return RL_E_INVALID;
+        }
+        const int checked = rl_internal_wavelength_rule(sampling->importance, sampling->n_nodes, sampling->uniform_share, table.data());
+        if (checked != RL_OK) return checked;
     }
     AppState a;
     a.cfg = config;
@@ -600,10 +616,13 @@ extern "C" int rl_app_run_to_error(const RlAppConfig* config, const RlErrorTarge
         desc.objects = objects.data();
         desc.camera = camera;
         rc = rl_scene_create(&desc, k.device, &k.scene); // Arc::new(App::set_up_scene()), app.rs:63: one copy per rank
+        if (rc == RL_OK && sampling)
+            rc = rl_wavelength_table_create(k.device, sampling->importance, sampling->n_nodes, sampling->uniform_share, &k.wavelengths);
         for (uint32_t i = 0; i < n_trace && rc == RL_OK; ++i) {
             RlTraceUnit* u = nullptr;
             rc = rl_trace_unit_create(k.device, i, config->width, config->height, a.photons, &u);
             if (u) k.trace_units.push_back(u);
+            if (rc == RL_OK && k.wavelengths) rc = rl_trace_unit_set_wavelengths(u, k.wavelengths);
         }
         for (uint32_t i = 0; i < n_plot && rc == RL_OK; ++i) {
             RlPlotUnit* u = nullptr;
@@ -716,6 +735,7 @@ extern "C" int rl_app_run_to_error(const RlAppConfig* config, const RlErrorTarge
     for (Rank& k : a.ranks) {
         for (RlTraceUnit* u : k.trace_units) rl_trace_unit_destroy(u);
         for (RlPlotUnit* u : k.plot_units) rl_plot_unit_destroy(u);
+        rl_wavelength_table_destroy(k.wavelengths); // (behind the units it was set on and the plot units their fused renders belong to)
         rl_scene_destroy(k.scene);
     }
     rl_gather_unit_destroy(a.gather);

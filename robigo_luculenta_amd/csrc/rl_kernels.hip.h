@@ -39,6 +39,7 @@
 
 #include "rl_cie1931.h"
 #include "rl_core.h"
+#include "rl_wavelength.h"
 
 #define RL_BLOCK 256        // streaming kernels (plot, gather, tonemap)
 #ifndef RL_TRACE_BLOCK
@@ -1241,9 +1242,14 @@ __device__ __forceinline__ RlStagedScene rl_stage_scene(const RlF4* __restrict__
 // plain launch -- every bulk launch -- carries none of the bookkeeping (measured 1 % on the fused kernel).
 // CYL: the scene's prisms carry a second bound (RlFlatScene::prism_cylinders) -- a compile-time switch so that scenes
 // without it run exactly the code they ran before it existed.
-template <int STAGE, bool FUSED, bool OPEN, bool CYL>
+// WL: the wavelength of a path is drawn from the table `wl` (rl_wavelength.h: 513 floats in global memory, no LDS -- the kernel has
+// none to spare) and its emission carries the table's weight.  A compile-time switch in the same sense as the others: the
+// instantiations without it are the ones they were before it existed, instruction for instruction (profiles/wavelength_isa_diff.txt).
+// The fetch is a vector load: the bin differs from lane to lane, and the table's 2 KB stay in the CU's vector cache.
+template <int STAGE, bool FUSED, bool OPEN, bool CYL, bool WL = false>
 __device__ __forceinline__ void rl_trace_body(const RlF4* __restrict__ scene, const RlSceneLayout& lay, const RlTraceJob& job, RlMappedPhoton* __restrict__ photons,
-                                              float* __restrict__ plot, unsigned long long* __restrict__ queue, const RlJobEntry* jobs, RlOpenDev* od, RlOpenCtl* ctl) {
+                                              float* __restrict__ plot, unsigned long long* __restrict__ queue, const RlJobEntry* jobs, RlOpenDev* od, RlOpenCtl* ctl,
+                                              const float* __restrict__ wl = nullptr) {
     // (rl_stage_scene's statements, kept as text: called from here it changed the instructions of 16 of the 24 trace bodies and
     // gave one of them 8 bytes of scratch -- measured on the commit after 69f31a2, profiles/refactor_isa_diff.txt)
     extern __shared__ __attribute__((aligned(512))) RlF4 smem[]; // (512: the ring pushes OR slot offsets into a wave's scratch address, RL_RING_SLOT)
@@ -1433,10 +1439,11 @@ __device__ __forceinline__ void rl_trace_body(const RlF4* __restrict__ scene, co
                 }
                 const RlRngBlock b0 = rl_rng_block(job.seed, job.stream, first + idx, 0);
                 RlMappedPhoton ph;
-                ph.wavelength = rl_get_wavelength(b0.w[0]);
+                ph.wavelength = WL ? rl_wavelength_draw(wl, b0.w[0]) : rl_get_wavelength(b0.w[0]);
                 ph.x = rl_get_bi_unit(b0.w[1]);
                 ph.y = rl_get_bi_unit(b0.w[2]) / job.aspect_ratio;
                 value = rl_emission(sv, emit_get(3, slot), ph.wavelength, OPEN ? (tagged & 0xffffffu) : tagged);
+                if (WL) value = value * rl_wavelength_weight(wl, ph.wavelength);
                 ph.probability = value;
                 if (OPEN) { // write-through: the reader is a kernel launched while this one still runs
                     uint32_t* dst = (uint32_t*)&dst_base[idx];
@@ -1457,7 +1464,8 @@ __device__ __forceinline__ void rl_trace_body(const RlF4* __restrict__ scene, co
             if (OPEN) ((RlLdsU32*)ws->ring_b)[lane] = tagged;
             float* target = plot;
             if (OPEN) target = (float*)jobs[tagged >> 24].target;
-            const float value = rl_emission(sv, emit_get(3, slot), wavelength, OPEN ? (tagged & 0xffffffu) : tagged);
+            float value = rl_emission(sv, emit_get(3, slot), wavelength, OPEN ? (tagged & 0xffffffu) : tagged);
+            if (WL) value = value * rl_wavelength_weight(wl, wavelength); // (the queue kept the wavelength, not the bin: the weight is a function of it)
             if (value != 0.0f) { // adding +0 is the identity
                 const RlF3 cie = rl_mul(rl_tristimulus(sv.cie, wavelength), value);
                 uint32_t width = job.width, height = job.height; // opaque: `width - 1` etc. are re-derived here instead of living in
@@ -1639,7 +1647,11 @@ __device__ __forceinline__ void rl_trace_body(const RlF4* __restrict__ scene, co
                 const uint64_t path_index = stash_path0 + lane;
                 RlPath fresh = p;
                 RL_T0(t_cam);
-                if (valid) rl_begin_path(sv, job.aspect_ratio, job.seed, job.stream, path_index, &fresh);
+                if (WL) {
+                    if (valid) rl_begin_path_wl(sv, job.aspect_ratio, job.seed, job.stream, path_index, wl, &fresh);
+                } else {
+                    if (valid) rl_begin_path(sv, job.aspect_ratio, job.seed, job.stream, path_index, &fresh);
+                }
                 RL_T1(RL_ST_T_CAMERA, t_cam);
                 rl_wave_sync();
                 stash[0 * 64 + lane] = fresh.origin.x;
@@ -1882,6 +1894,22 @@ __global__ __launch_bounds__(RL_TRACE_BLOCK, RL_TRACE_WPS) __attribute__((amdgpu
                                                                                                             unsigned long long* __restrict__ queue, const RlJobEntry* jobs,
                                                                                                             RlOpenDev* od, RlOpenCtl* ctl) {
     rl_trace_body<STAGE, FUSED, true, CYL>(scene, lay, job, photons, plot, queue, jobs, od, ctl);
+}
+// The same two with the wavelength table (rl_trace_unit_set_wavelengths): kernels of their own, since the table is one more argument.
+// Same register caps as their siblings.
+template <int STAGE, bool FUSED, bool CYL>
+__global__ __launch_bounds__(RL_TRACE_BLOCK, RL_TRACE_WPS) __attribute__((amdgpu_num_vgpr(RL_TRACE_VGPRS / 2))) void rl_wl_trace_kernel(const RlF4* __restrict__ scene, RlSceneLayout lay, RlTraceJob job,
+                                                                                                       RlMappedPhoton* __restrict__ photons, float* __restrict__ plot,
+                                                                                                       unsigned long long* __restrict__ queue, const RlJobEntry* jobs,
+                                                                                                       RlOpenDev* od, RlOpenCtl* ctl, const float* __restrict__ wl) {
+    rl_trace_body<STAGE, FUSED, false, CYL, true>(scene, lay, job, photons, plot, queue, jobs, od, ctl, wl);
+}
+template <int STAGE, bool FUSED, bool CYL>
+__global__ __launch_bounds__(RL_TRACE_BLOCK, RL_TRACE_WPS) __attribute__((amdgpu_num_vgpr(RL_TRACE_VGPRS_OPEN / 2))) void rl_wl_trace_open_kernel(const RlF4* __restrict__ scene, RlSceneLayout lay, RlTraceJob job,
+                                                                                                            RlMappedPhoton* __restrict__ photons, float* __restrict__ plot,
+                                                                                                            unsigned long long* __restrict__ queue, const RlJobEntry* jobs,
+                                                                                                            RlOpenDev* od, RlOpenCtl* ctl, const float* __restrict__ wl) {
+    rl_trace_body<STAGE, FUSED, true, CYL, true>(scene, lay, job, photons, plot, queue, jobs, od, ctl, wl);
 }
 
 // PlotUnit::plot (plot_unit.rs:87-95) for the un-fused path: one photon per thread.

@@ -5,7 +5,8 @@
     tools/kernel_isa_diff.py a.s b.s
 
 Per kernel symbol (every .amdhsa_kernel of either file, mangled or not): identical, or the number of instruction lines that differ
-out of the total, after dropping comments, directives and blank lines and renumbering the .LBB labels in order of appearance; and
+out of the total, after dropping comments, directives and blank lines and renumbering the .LBB labels, and the .Lpost_getpc labels of
+long branches (numbered through the whole file, so a kernel added in front moves them), in order of appearance; and
 the metadata figures (VGPRs, SGPRs, spilled SGPRs, scratch bytes) of both side by side.  Exit status 0 whatever it finds: it
 reports, it does not judge.  No GPU needed."""
 import difflib
@@ -26,9 +27,9 @@ def kernels(path):
                 continue
             lines.append(line)
         for line in lines:   # labels numbered by first appearance, definition or use
-            for lab in re.findall(r"\.LBB\d+_\d+", line):
+            for lab in re.findall(r"\.LBB\d+_\d+|\.Lpost_getpc\d+", line):
                 labels.setdefault(lab, ".L%d" % len(labels))
-        lines = [re.sub(r"\.LBB\d+_\d+", lambda m: labels[m.group(0)], l) for l in lines]
+        lines = [re.sub(r"\.LBB\d+_\d+|\.Lpost_getpc\d+", lambda m: labels[m.group(0)], l) for l in lines]
         meta = re.search(r"^\s+\.name:\s+%s\n(.*?)^\s+\.wavefront_size" % re.escape(name), text, re.S | re.M).group(1)
         figure = lambda key: int(re.search(r"\.%s:\s+(\d+)" % key, meta).group(1))
         out[name] = (lines, (figure("vgpr_count"), figure("sgpr_count"), figure("sgpr_spill_count"), figure("private_segment_fixed_size")))
