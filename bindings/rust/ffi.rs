@@ -71,10 +71,12 @@ pub const RL_DENOISE_ITERATIONS: u32 = 5;
 pub const RL_DENOISE_MAX_ITERATIONS: u32 = 6;
 pub const RL_SPECTRAL_MAX_NODES: u32 = 401;
 pub const RL_ERROR_TILE: u32 = 16;
+pub const RL_ROBUST_NEXT: u32 = 0xffff_ffff;
 
 pub const RL_MAX_PIXELS: usize = 2147483647;
 pub const RL_TASK_MAX_UNITS: usize = 256;
 pub const RL_COMM_ID_BYTES: usize = 128;
+pub const RL_ROBUST_MAX_BUCKETS: usize = 32;
 #[repr(C)] #[derive(Copy, Clone)] pub struct RlTask {            // enum Task by value, task_scheduler.rs:26-41
     pub kind: u32,      // 0 Sleep, 1 Trace, 2 Plot, 3 Gather, 4 Tonemap
     pub unit: u32, pub n_units: u32, pub units: [u32; RL_TASK_MAX_UNITS],
@@ -94,6 +96,11 @@ pub const RL_COMM_ID_BYTES: usize = 128;
     pub observations: u64, pub paths: u64, pub tiles_x: u32, pub tiles_y: u32, pub worst_tile_x: u32, pub worst_tile_y: u32,
     pub sum_y: f64, pub sum_se: f64, pub relative_error: f64, pub worst_tile_error: f64,
 }
+#[repr(C)] #[derive(Copy, Clone, Default)] pub struct RlRobustParams { pub gain: f64, pub max_trim: u32, pub reserved: u32 } // 16 bytes
+#[repr(C)] #[derive(Copy, Clone, Default)] pub struct RlRobustStats {
+    pub observations: u64, pub paths: u64, pub buckets: u32, pub largest_trim: u32,
+    pub trimmed_pixels: u64, pub trimmed_buckets: u64, pub untrimmable_pixels: u64,
+}
 #[repr(C)] #[derive(Copy, Clone, Default)] pub struct RlErrorTarget {
     pub relative_error: f64, pub worst_tile_error: f64, pub min_observations: u32, pub reserved: u32,
 }
@@ -108,6 +115,7 @@ pub const RL_COMM_ID_BYTES: usize = 128;
 pub enum RlScene {} pub enum RlTraceUnit {} pub enum RlPlotUnit {} pub enum RlGatherUnit {} pub enum RlTonemapUnit {}
 pub enum RlScheduler {} pub enum RlComm {} pub enum RlDenoiseUnit {} pub enum RlSpectralUnit {} pub enum RlErrorUnit {}
 pub enum RlAdaptiveUnit {}
+pub enum RlRobustUnit {}
 pub enum RlWavelengthTable {}
 #[repr(C)] #[derive(Copy, Clone)] pub struct RlWavelengthSampling {
     pub importance: *const f64, pub n_nodes: u32, pub reserved: u32, pub uniform_share: f64,
@@ -258,6 +266,15 @@ extern "C" {
     pub fn rl_error_unit_estimate(unit: *mut RlErrorUnit, stats: *mut RlErrorStats, se: *mut f32, tiles: *mut f64) -> c_int;
     pub fn rl_error_unit_download(unit: *mut RlErrorUnit, sum_y: *mut f64, sum_q: *mut f64, observations: *mut u64, paths: *mut u64) -> c_int;
     pub fn rl_error_unit_upload(unit: *mut RlErrorUnit, sum_y: *const f64, sum_q: *const f64, observations: u64, paths: u64) -> c_int;
+    pub fn rl_robust_params_default(out: *mut RlRobustParams) -> c_int;
+    pub fn rl_robust_unit_create(device: c_int, width: u32, height: u32, n_buckets: u32, out: *mut *mut RlRobustUnit) -> c_int;
+    pub fn rl_robust_unit_destroy(unit: *mut RlRobustUnit) -> c_int;
+    pub fn rl_robust_unit_clear(unit: *mut RlRobustUnit) -> c_int;
+    pub fn rl_robust_unit_observe(unit: *mut RlRobustUnit, plot: *mut RlPlotUnit, n_paths: u64, bucket: u32) -> c_int;
+    pub fn rl_robust_unit_resolve(unit: *mut RlRobustUnit, params: *const RlRobustParams, dst: *mut RlGatherUnit, stats: *mut RlRobustStats,
+                                  trim: *mut u8) -> c_int;
+    pub fn rl_robust_unit_download(unit: *mut RlRobustUnit, sums: *mut f64, bucket_paths: *mut u64, observations: *mut u64) -> c_int;
+    pub fn rl_robust_unit_upload(unit: *mut RlRobustUnit, sums: *const f64, bucket_paths: *const u64, observations: u64) -> c_int;
     pub fn rl_adaptive_unit_create(device: c_int, width: u32, height: u32, out: *mut *mut RlAdaptiveUnit) -> c_int;
     pub fn rl_adaptive_unit_destroy(unit: *mut RlAdaptiveUnit) -> c_int;
     pub fn rl_adaptive_unit_plan(unit: *mut RlAdaptiveUnit, importance: *const f64, uniform_share: f64, n_paths: u64,

@@ -120,6 +120,7 @@ typedef struct RlTonemapUnit RlTonemapUnit;
 typedef struct RlDenoiseUnit RlDenoiseUnit;
 typedef struct RlSpectralUnit RlSpectralUnit;
 typedef struct RlErrorUnit RlErrorUnit;
+typedef struct RlRobustUnit RlRobustUnit;
 typedef struct RlAdaptiveUnit RlAdaptiveUnit;
 typedef struct RlWavelengthTable RlWavelengthTable;
 typedef struct RlScheduler RlScheduler;
@@ -1051,6 +1052,88 @@ int rl_error_unit_observe(RlErrorUnit* unit, RlPlotUnit* plot, uint64_t n_paths)
 int rl_error_unit_estimate(RlErrorUnit* unit, RlErrorStats* stats, float* se, double* tiles);
 int rl_error_unit_download(RlErrorUnit* unit, double* sum_y, double* sum_q, uint64_t* observations, uint64_t* paths);
 int rl_error_unit_upload(RlErrorUnit* unit, const double* sum_y, const double* sum_q, uint64_t observations, uint64_t paths);
+
+/* ---- robust film: M sub-films combined by a Gini-trimmed median of means (rl_robust_unit_*) ---- */
+
+#define RL_ROBUST_MAX_BUCKETS 32
+#define RL_ROBUST_NEXT 0xffffffffu
+
+/* A robust unit removes outliers -- fireflies: rare paths whose contribution is hundreds of times a pixel's mean -- from an
+ * accumulated image.  It keeps M = n_buckets independent sub-films ("buckets") instead of one: it is shown every plot buffer just
+ * before the buffer is gathered (rl_robust_unit_observe, the error unit's protocol; the caller gathers afterwards) and adds it to
+ * one bucket.  rl_robust_unit_resolve combines the buckets per pixel by a median of means whose trim follows the inequality of the
+ * M bucket means, measured by their Gini coefficient (Buisine et al. 2021, "Firefly removal in Monte Carlo rendering with adaptive
+ * Median of meaNs"): equal buckets are averaged, one bucket far above the others is dropped together with the lowest one.  The
+ * result goes to a gather unit, as the denoiser's and the spectral projection's do.
+ *   State.  On the device M x 3 planes of width x height doubles in rows, all +0 at first: plane j * 3 + c holds component c (X, Y,
+ *     Z) of bucket j's sum S[j][c].  sums[(j * 3 + c) * n_pixels + p] is the host layout of download and upload and part of the
+ *     ABI.  On the host n[j], the paths of bucket j (u64), and k, the number of observations.  24 M bytes per pixel.
+ *   The arithmetic.  f64 as stated, in exactly this order, never contracted; the division correctly rounded.
+ *   rl_robust_unit_observe(unit, plot, n_paths, bucket).  j = bucket, or k mod M for RL_ROBUST_NEXT.  Per pixel and component:
+ *     S[j][c] = S[j][c] + (double)p[c]; the plot buffer is only read and left exactly as it was.  On the host: n[j] += n_paths;
+ *     k += 1.  No special cases for negative or non-finite values.  Checked in this order: a NULL unit or plot, or n_paths == 0, is
+ *     RL_E_INVALID; bucket >= M and != RL_ROBUST_NEXT is RL_E_INVALID; n[j] or the total N overflowing 64 bits is RL_E_INVALID; a
+ *     plot unit of another size or device is RL_E_STATE, and nothing is written.  Ordering is rl_error_unit_observe's: a fused
+ *     render begun into the plot unit is ended first; the kernel waits through an event for everything queued on the plot unit's
+ *     stream and runs on the robust unit's own stream; the plot unit's stream then waits for the kernel, so a later clear or gather
+ *     cannot overtake the read.  The call does not synchronise the host.  The caller owes independence: each observation is a plot
+ *     buffer of paths that no other bucket's observations contain.
+ *   rl_robust_unit_resolve(unit, params, dst, stats, trim).  Checked in this order: a NULL unit, params or dst is RL_E_INVALID;
+ *     params->gain NaN or negative is RL_E_INVALID (+infinity is legal); any n[j] == 0 is RL_E_STATE (every bucket needs an
+ *     observation); a dst of another size or device is RL_E_STATE, and nothing is written.  With N = sum_j n[j], per pixel:
+ *       1. m[j][c] = S[j][c] / (double)n[j].
+ *       2. The key of bucket j is m[j][1], its Y.
+ *       3. The buckets are ranked by (key, j) ascending: rank(j) = the number of i with key[i] < key[j], or key[i] == key[j] and
+ *          i < j.  (r) is the bucket of rank r.
+ *       4. If any key is not finite or is < 0 the pixel is untrimmable: c = 0, it counts in untrimmable_pixels, the ranks are not
+ *          used and the sums of 6 run in bucket order j = 0 .. M - 1.
+ *       5. Otherwise T = sum_r key(r) and W = sum_r (double)(2 r - M + 1) * key(r), each summed sequentially from +0.0 for
+ *          r = 0 .. M - 1 (the integer arithmetic first, then the conversion).  If !(T > 0): c = 0, counted in untrimmable_pixels
+ *          too.  Else G = W / ((double)M * T) -- the Gini coefficient of the keys --, v = ((gain * G) * (double)M) * 0.5 and
+ *          cmax = min(max_trim, (M - 1) / 2) in integer division; c = 0 if !(v >= 0), c = cmax if v >= (double)cmax, otherwise
+ *          c = (uint32_t)floor(v).
+ *       6. Per component, A = sum of m(r)[c] for r = c .. M - c - 1, sequentially from +0.0 in rank order.  The ranks of Y order
+ *          all three components: a pixel keeps whole buckets, so its colour stays that of real samples.
+ *       7. dst's tristimulus gets (float)((A / (double)(M - 2 c)) * (double)N); dst's compensation gets +0, as after
+ *          rl_spectral_unit_project.  dst's previous contents are replaced.
+ *     So gain = 0, max_trim = 0 or M equal means give the plain pooled mean of the bucket means times N -- for equal n[j] the sum a
+ *     gather unit would hold, up to rounding --, and gain = +infinity with any inequality gives the median bucket for odd M and the
+ *     two middle buckets for even M.  Where c > 0 the film is no longer unbiased: a skewed pixel distribution is pulled towards
+ *     its median.
+ *     `trim` may be NULL; otherwise width x height bytes of host memory, c per pixel in rows.  `stats` may be NULL; its counts are
+ *     exact (a host reduction of the trim bytes): the same on every run.  Ordering is rl_spectral_unit_project's: the call waits on
+ *     the device for what is queued on dst's stream and on the unit, runs on dst's stream and returns with dst complete.
+ *     Everything it produces is exact: the same bits on every run, and the bits of the CPU restatement tests/_robust_oracle.py.
+ *   rl_robust_unit_download / _upload move the planes in the host layout above, the M values n[j] and k; any of download's outputs
+ *     may be NULL; upload needs `sums` and `bucket_paths` (a NULL unit or either is RL_E_INVALID), takes any contents of the planes,
+ *     NaN included, and refuses an `observations` below the number of non-zero bucket_paths entries and a total N that overflows
+ *     64 bits (RL_E_INVALID, before any device work).  They wait for what is queued on the unit.
+ *   rl_robust_unit_create refuses a NULL `out`, a zero size, width * height > RL_MAX_PIXELS and n_buckets < 3 or
+ *     > RL_ROBUST_MAX_BUCKETS (RL_E_INVALID, in this order, before any device work; the handle is left NULL).
+ *     rl_robust_unit_clear restores the initial state (queued on the unit).
+ *   rl_robust_params_default: gain 1.0, max_trim 0xffffffff (no limit besides (M - 1) / 2), reserved 0.
+ *   One user per robust unit at a time. */
+typedef struct RlRobustParams {
+    double gain;       /* scales the trim: c = floor(gain * G * M / 2), at most cmax */
+    uint32_t max_trim; /* an upper limit of c */
+    uint32_t reserved; /* 0 */
+} RlRobustParams;
+typedef struct RlRobustStats {
+    uint64_t observations, paths;    /* k, N */
+    uint32_t buckets, largest_trim;  /* M, the largest c */
+    uint64_t trimmed_pixels;         /* pixels with c > 0 */
+    uint64_t trimmed_buckets;        /* the sum of 2 c over the pixels */
+    uint64_t untrimmable_pixels;
+} RlRobustStats;
+
+int rl_robust_params_default(RlRobustParams* out);
+int rl_robust_unit_create(int device, uint32_t width, uint32_t height, uint32_t n_buckets, RlRobustUnit** out);
+int rl_robust_unit_destroy(RlRobustUnit* unit);
+int rl_robust_unit_clear(RlRobustUnit* unit);
+int rl_robust_unit_observe(RlRobustUnit* unit, RlPlotUnit* plot, uint64_t n_paths, uint32_t bucket);
+int rl_robust_unit_resolve(RlRobustUnit* unit, const RlRobustParams* params, RlGatherUnit* dst, RlRobustStats* stats, uint8_t* trim);
+int rl_robust_unit_download(RlRobustUnit* unit, double* sums, uint64_t* bucket_paths, uint64_t* observations);
+int rl_robust_unit_upload(RlRobustUnit* unit, const double* sums, const uint64_t* bucket_paths, uint64_t observations);
 
 /* ---- adaptive sampling: camera samples drawn tile by tile from an importance map (rl_adaptive_unit_*) ---- */
 

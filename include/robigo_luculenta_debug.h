@@ -95,6 +95,12 @@ int rl_debug_error_launches(uint64_t out[2]);
 /* Device time in milliseconds, from events around the launch: out[0] the unit's last observe launch, out[1] its last estimate
  * launch; 0 before the first.  Waits for the launch.  tools/error_bench.py. */
 int rl_debug_error_ms(RlErrorUnit* unit, float out[2]);
+/* out[0]: launches of rl_robust_observe_kernel (one per rl_robust_unit_observe), out[1]: launches of rl_robust_resolve_kernel (one per
+ * rl_robust_unit_resolve) since the library was loaded. */
+int rl_debug_robust_launches(uint64_t out[2]);
+/* Device time in milliseconds, from events around the launch: out[0] the unit's last observe launch, out[1] the resolve launch of
+ * its last completed rl_robust_unit_resolve; 0 before the first.  Waits for the launch.  tools/robust_bench.py. */
+int rl_debug_robust_ms(RlRobustUnit* unit, float out[2]);
 /* out[0]: launches of rl_adaptive_samples_kernel (one per chunk of rl_adaptive_unit_samples* and of rl_plot_unit_render_adaptive),
  * out[1]: path kernel launches made by rl_plot_unit_render_adaptive (counted in rl_debug_path_launches too), out[2]: launches of
  * rl_adaptive_splat_kernel, since the library was loaded. */

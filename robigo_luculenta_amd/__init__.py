@@ -15,7 +15,7 @@ from ._lib import (RlAppConfig, RlAppStats, RlCameraDesc, RlCameraSample, RlErro
                    RL_LIGHT_VISIBLE, RlFeatureSample, RlFeatureStats, RL_FEATURE_VOID, RL_FEATURE_EMITTER, RL_FEATURE_DIFFUSE, RL_FEATURE_LIMIT,
                    RL_FEATURE_MAX_SEGMENTS, RlDenoiseParams, RL_DENOISE_ITERATIONS, RL_DENOISE_MAX_ITERATIONS,
                    RL_SPECTRAL_MAX_NODES, RlErrorStats, RlErrorTarget, RlAppErrorStats, RL_ERROR_TILE, RlAdaptiveStats,
-                   RlWavelengthSampling)
+                   RlWavelengthSampling, RlRobustParams, RlRobustStats, RL_ROBUST_MAX_BUCKETS, RL_ROBUST_NEXT)
 
 PHOTON_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("probability", "<f4"), ("wavelength", "<f4")])
 OBJECT_DTYPE = np.dtype([("surface_kind", "<u4"), ("material_kind", "<u4"), ("v0", "<f4", 3), ("v1", "<f4", 3),
@@ -957,6 +957,52 @@ def error_tile_rel(tiles):
         return (pairs[:, 0] / np.where(pairs[:, 1] > m, pairs[:, 1], m)).reshape(np.asarray(tiles).shape[:-1])
 
 
+class RobustUnit(_Handle):
+    """The robust film (rl_robust_unit_*): n_buckets sub-films of f64 XYZ sums over the plot buffers shown to the unit just before
+    they are gathered, combined per pixel by a median of means whose trim follows the Gini coefficient of the bucket means."""
+    _destroy = lib.rl_robust_unit_destroy
+
+    def __init__(self, width, height, n_buckets=15, device=0):
+        super().__init__()
+        check(lib.rl_robust_unit_create(device, width, height, n_buckets, C.byref(self._h)))
+        self.width, self.height, self.n_buckets, self.device = width, height, n_buckets, device
+
+    def clear(self):
+        check(lib.rl_robust_unit_clear(self._h))
+
+    def observe(self, plot_unit, n_paths, bucket=None):
+        """rl_robust_unit_observe: the plot unit's buffer, the sum over n_paths paths no other bucket has seen, is added to `bucket`
+        (None: RL_ROBUST_NEXT, the buckets in turn).  The buffer is left as it was: gather it afterwards.  Does not wait on the host."""
+        check(lib.rl_robust_unit_observe(self._h, plot_unit.handle, n_paths, RL_ROBUST_NEXT if bucket is None else bucket))
+
+    def resolve(self, dst, gain=1.0, max_trim=0xFFFFFFFF, trim=False):
+        """rl_robust_unit_resolve into the gather unit `dst`: the stats as a dict, or (stats, trim as (height, width) uint8) with
+        trim=True."""
+        params, stats = RlRobustParams(gain, max_trim, 0), RlRobustStats()
+        trim_out = np.zeros((self.height, self.width), dtype=np.uint8) if trim else None
+        check(lib.rl_robust_unit_resolve(self._h, C.byref(params), dst.handle, C.byref(stats), _host_ptr(trim_out)))
+        out = {name: getattr(stats, name) for name, _ in RlRobustStats._fields_}
+        return (out, trim_out) if trim else out
+
+    def download(self):
+        """(sums as (n_buckets, 3, height, width) float64, bucket_paths as (n_buckets,) uint64, k)."""
+        sums = np.zeros((self.n_buckets, 3, self.height, self.width), dtype=np.float64)
+        paths, k = np.zeros(self.n_buckets, dtype=np.uint64), C.c_uint64(0)
+        check(lib.rl_robust_unit_download(self._h, _host_ptr(sums), _host_ptr(paths), C.byref(k)))
+        return sums, paths, k.value
+
+    def upload(self, sums, bucket_paths, observations):
+        s = np.ascontiguousarray(sums, dtype=np.float64).reshape(self.n_buckets, 3, self.height, self.width)
+        n = np.ascontiguousarray(bucket_paths, dtype=np.uint64).reshape(self.n_buckets)
+        check(lib.rl_robust_unit_upload(self._h, _host_ptr(s), _host_ptr(n), observations))
+
+    def launch_ms(self):
+        """Device milliseconds of (the last observe launch, the last resolve launch) of this unit (rl_debug_robust_ms)."""
+        out = (C.c_float * 2)()
+        check(lib.rl_debug_robust_ms(self._h, out))
+        return tuple(out)
+
+
 class AdaptiveUnit(_Handle):
     """Adaptive sampling (rl_adaptive_unit_*): a plan of how many of a batch's camera paths start in each 16 x 16 tile of the film
     and the weight their splats carry, so that the film's expectation is the uniform sampler's."""
@@ -1288,6 +1334,12 @@ def error_launches():
     """(launches of the error unit's observe kernel, launches of its estimate kernel) since the library was loaded
     (rl_debug_error_launches)."""
     return _launch_counters(lib.rl_debug_error_launches, 2, tuple)
+
+
+def robust_launches():
+    """(launches of the robust unit's observe kernel, launches of its resolve kernel) since the library was loaded
+    (rl_debug_robust_launches)."""
+    return _launch_counters(lib.rl_debug_robust_launches, 2, tuple)
 
 
 def adaptive_launches():

@@ -9,7 +9,9 @@ With --spectral PATH the same paths are rendered once more into a spectral film 
 With --target-error E the run ends once the estimated relative error of the image (rl_app_run_to_error) is at most E; --batches stays
 the cap.  With --error-map PATH the per-tile relative error of the last estimate is written as a grey image.
 With --adaptive as well the batches are rendered over the unit API by render_adaptive_to_error: from --min-observations on, every batch's
-camera samples are drawn tile by tile from the running error map (AdaptiveUnit), --uniform-share of them spread by area."""
+camera samples are drawn tile by tile from the running error map (AdaptiveUnit), --uniform-share of them spread by area.
+With --robust PATH every batch also goes into one of the --robust-buckets sub-films of a RobustUnit (with --direct inside its batch
+loop, otherwise batch by batch over the unit API), and their Gini-trimmed median of means, fireflies removed, is tonemapped to PATH."""
 import argparse
 import os
 import struct
@@ -76,7 +78,38 @@ def parse_args(argv=None):
                          "'cie' follows the sum of the CIE 1931 observer's three curves (the App modes and --spectral's re-render)")
     ap.add_argument("--wavelength-uniform-share", metavar="F", type=float, default=None,
                     help="with --wavelength-importance: the share of the density that stays uniform, 0 < F <= 1 (default 0.1)")
+    ap.add_argument("--robust", metavar="PATH", default=None,
+                    help="keep the batches in the buckets of a robust film (RobustUnit) as well and write its image, fireflies removed by "
+                         "a Gini-trimmed median of means, to PATH (*.png or *.ppm); --output is what it is without this option")
+    ap.add_argument("--robust-buckets", metavar="M", type=int, default=None,
+                    help="with --robust: the number of buckets, 3 .. 32 (default 15); the batches go to them in turn")
+    ap.add_argument("--robust-gain", metavar="G", type=float, default=None,
+                    help="with --robust: scales the number of buckets trimmed at each end, G >= 0 (default 1; 0 trims nothing)")
     a = ap.parse_args(argv)
+    for given, flag in ((a.robust_buckets is not None, "--robust-buckets"), (a.robust_gain is not None, "--robust-gain")):
+        if given and a.robust is None:
+            ap.error("%s needs --robust PATH" % flag)
+    if a.robust is not None:
+        for given, flag in ((a.adaptive, "--adaptive"), (a.resume, "--resume"), (a.unfused, "--unfused"),
+                            (a.concurrency is not None, "--concurrency"), (a.spectral is not None, "--spectral")):
+            if given:
+                ap.error("%s cannot be combined with --robust: the robust mode renders batch by batch over the unit API, every batch "
+                         "into one bucket" % flag)
+        if a.robust_buckets is None:
+            a.robust_buckets = 15
+        if not 3 <= a.robust_buckets <= 32:
+            ap.error("--robust-buckets must be in 3 .. 32")
+        if a.batches < a.robust_buckets:
+            ap.error("--robust needs --batches of at least --robust-buckets (default 15): every bucket needs a batch")
+        if a.robust_gain is None:
+            a.robust_gain = 1.0
+        if not a.robust_gain >= 0:
+            ap.error("--robust-gain must be a number >= 0")
+        for given, flag in ((a.target_error is not None, "--target-error"), (a.error_map is not None, "--error-map"),
+                            (a.wavelength_importance is not None, "--wavelength-importance")):
+            if given:
+                ap.error("%s cannot be combined with --robust: that is the App worker pool's, and the robust mode renders over the "
+                         "unit API" % flag)
     if a.wavelength_uniform_share is not None and a.wavelength_importance is None:
         ap.error("--wavelength-uniform-share needs --wavelength-importance")
     if a.wavelength_uniform_share is not None and not 0 < a.wavelength_uniform_share <= 1:
@@ -155,17 +188,20 @@ def render_direct(a):
     """--direct: batch b is paths [b * photons_per_batch, (b + 1) * photons_per_batch) of stream 0, one render_direct call into a
     plot unit and one GatherUnit.accumulate each; one tonemap at the end.  With --denoise-variance an ErrorUnit observes each batch's
     plot buffer before it is gathered.  Returns (rgb, totals, the gather unit, the error unit or None)."""
-    from . import ErrorUnit, GatherUnit, PlotUnit, Scene, TonemapUnit
+    from . import ErrorUnit, GatherUnit, PlotUnit, RobustUnit, Scene, TonemapUnit
     scene = Scene.builtin(SCENE_DEMO if a.scene == "demo" else SCENE_GLASS_STRESS, device=a.device)
     plot = PlotUnit(0, a.width, a.height, device=a.device)
     gather = GatherUnit(a.width, a.height, device=a.device)
     error = ErrorUnit(a.width, a.height, device=a.device) if a.denoise_variance else None
+    robust = RobustUnit(a.width, a.height, a.robust_buckets, device=a.device) if a.robust is not None else None
     total = {}
     t0 = time.perf_counter()
     for b in range(a.batches):
         stats = plot.render_direct(scene, a.seed, 0, b * a.photons_per_batch, a.photons_per_batch, max_segments=a.max_segments or 0)
         if error is not None:
             error.observe(plot, a.photons_per_batch)
+        if robust is not None:
+            robust.observe(plot, a.photons_per_batch)
         gather.accumulate(plot)
         for k, v in stats.items():
             total[k] = total.get(k, 0) + v
@@ -181,7 +217,52 @@ def render_direct(a):
     print("direct light: %s" % ", ".join("%s %d" % kv for kv in total.items()))
     print("%d batches, %.1f Mpaths, %.1f Mrays and %.1f M shadow rays in %.2f s; wrote %s"
           % (a.batches, total.get("paths", 0) / 1e6, total.get("segments", 0) / 1e6, total.get("shadow_rays", 0) / 1e6, seconds, a.output))
+    if robust is not None:
+        resolve_robust(a, robust)
     return rgb, total, gather, error
+
+
+def resolve_robust(a, robust):
+    """--robust PATH: the robust unit that observed every batch resolved into a gather unit of its own, tonemapped as the image was,
+    written to PATH; prints the stats line.  Returns (rgb, stats)."""
+    from . import GatherUnit, TonemapUnit
+    film = GatherUnit(a.width, a.height, device=a.device)
+    stats = robust.resolve(film, gain=a.robust_gain)
+    tonemap = TonemapUnit(a.width, a.height, device=a.device)
+    tonemap.tonemap(film)
+    rgb = tonemap.rgb_buffer
+    write_image(a.robust, rgb, a.width, a.height)
+    print("robust film: %d buckets, gain %g, %d observations of %d paths; %d pixels trimmed (%d buckets, at most %d at each end), "
+          "%d untrimmable; wrote %s"
+          % (stats["buckets"], a.robust_gain, stats["observations"], stats["paths"], stats["trimmed_pixels"], stats["trimmed_buckets"],
+             stats["largest_trim"], stats["untrimmable_pixels"], a.robust))
+    return rgb, stats
+
+
+def render_robust(a):
+    """--robust without --direct: batch b is paths [b * photons_per_batch, (b + 1) * photons_per_batch) of stream 0, one fused
+    synchronous render into a plot unit, shown to the robust unit and then gathered; one tonemap at the end, then the robust film.
+    Returns (rgb, the gather unit, the robust film's stats)."""
+    from . import GatherUnit, PlotUnit, RobustUnit, Scene, TonemapUnit, TraceUnit
+    scene = Scene.builtin(SCENE_DEMO if a.scene == "demo" else SCENE_GLASS_STRESS, device=a.device)
+    trace = TraceUnit(0, a.width, a.height, n_photons=64, device=a.device)
+    plot = PlotUnit(0, a.width, a.height, device=a.device)
+    gather = GatherUnit(a.width, a.height, device=a.device)
+    robust = RobustUnit(a.width, a.height, a.robust_buckets, device=a.device)
+    t0 = time.perf_counter()
+    for b in range(a.batches):
+        trace.render_fused_sync(scene, plot, a.photons_per_batch, seed=a.seed, stream=0, first_path_index=b * a.photons_per_batch)
+        robust.observe(plot, a.photons_per_batch)
+        gather.accumulate(plot)
+    tonemap = TonemapUnit(a.width, a.height, device=a.device)
+    tonemap.tonemap(gather)
+    rgb = tonemap.rgb_buffer
+    seconds = time.perf_counter() - t0
+    write_image(a.output, rgb, a.width, a.height)
+    if a.checkpoint:
+        gather.save(a.checkpoint)
+    print("%d batches, %.1f Mpaths in %.2f s; wrote %s" % (a.batches, a.batches * a.photons_per_batch / 1e6, seconds, a.output))
+    return rgb, gather, resolve_robust(a, robust)[1]
 
 
 def render_features(a):
@@ -327,8 +408,8 @@ def main(argv=None):
             if a.denoise is not None:
                 denoise(a, image, guides, error)
         return
-    if a.adaptive:
-        image = render_adaptive(a)[3]
+    if a.adaptive or a.robust is not None:
+        image = render_adaptive(a)[3] if a.adaptive else render_robust(a)[1]
         if a.features is not None:
             guides = render_features(a)[2]
             if a.denoise is not None:

@@ -121,6 +121,19 @@ RL_SPECTRAL_MAX_NODES = 401
 RL_ERROR_TILE = 16
 
 
+RL_ROBUST_MAX_BUCKETS = 32
+RL_ROBUST_NEXT = 0xFFFFFFFF
+
+
+class RlRobustParams(C.Structure):
+    _fields_ = [("gain", C.c_double), ("max_trim", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RlRobustStats(C.Structure):
+    _fields_ = [("observations", C.c_uint64), ("paths", C.c_uint64), ("buckets", C.c_uint32), ("largest_trim", C.c_uint32),
+                ("trimmed_pixels", C.c_uint64), ("trimmed_buckets", C.c_uint64), ("untrimmable_pixels", C.c_uint64)]
+
+
 class RlErrorStats(C.Structure):
     _fields_ = [("observations", C.c_uint64), ("paths", C.c_uint64), ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32),
                 ("worst_tile_x", C.c_uint32), ("worst_tile_y", C.c_uint32), ("sum_y", C.c_double), ("sum_se", C.c_double),
@@ -268,6 +281,14 @@ SIGNATURES = {
     "rl_error_unit_estimate": (_i, [_vp, C.POINTER(RlErrorStats), _vp, _vp]),
     "rl_error_unit_download": (_i, [_vp, _vp, _vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "rl_error_unit_upload": (_i, [_vp, _vp, _vp, _u64, _u64]),
+    "rl_robust_params_default": (_i, [C.POINTER(RlRobustParams)]),
+    "rl_robust_unit_create": (_i, [_i, _u32, _u32, _u32, _pp]),
+    "rl_robust_unit_destroy": (_i, [_vp]),
+    "rl_robust_unit_clear": (_i, [_vp]),
+    "rl_robust_unit_observe": (_i, [_vp, _vp, _u64, _u32]),
+    "rl_robust_unit_resolve": (_i, [_vp, C.POINTER(RlRobustParams), _vp, C.POINTER(RlRobustStats), _vp]),
+    "rl_robust_unit_download": (_i, [_vp, _vp, _vp, C.POINTER(_u64)]),
+    "rl_robust_unit_upload": (_i, [_vp, _vp, _vp, _u64]),
     "rl_adaptive_unit_create": (_i, [_i, _u32, _u32, _pp]),
     "rl_adaptive_unit_destroy": (_i, [_vp]),
     "rl_adaptive_unit_plan": (_i, [_vp, _vp, C.c_double, _u64, C.POINTER(RlAdaptiveStats)]),
@@ -324,6 +345,8 @@ DEBUG_SIGNATURES = {
     "rl_debug_spectral_ms": (_i, [_vp, _vp]),
     "rl_debug_error_launches": (_i, [_vp]),
     "rl_debug_error_ms": (_i, [_vp, _vp]),
+    "rl_debug_robust_launches": (_i, [_vp]),
+    "rl_debug_robust_ms": (_i, [_vp, _vp]),
     "rl_debug_adaptive_launches": (_i, [_vp]),
     "rl_debug_adaptive_ms": (_i, [_vp, _vp]),
     "rl_debug_gather_accumulate_ms": (_i, [_vp, _vp, C.POINTER(C.c_float)]),

@@ -58,6 +58,7 @@
 #include "rl_denoise.hip.h"
 #include "rl_spectral.hip.h"
 #include "rl_error.hip.h"
+#include "rl_robust.hip.h"
 #include "rl_adaptive.hip.h"
 #include "rl_scene.h"
 
@@ -121,6 +122,7 @@ const char* unit_name(const RlTonemapUnit*) { return "tonemap unit"; }
 const char* unit_name(const RlDenoiseUnit*) { return "denoise unit"; }
 const char* unit_name(const RlSpectralUnit*) { return "spectral unit"; }
 const char* unit_name(const RlErrorUnit*) { return "error unit"; }
+const char* unit_name(const RlRobustUnit*) { return "robust unit"; }
 const char* unit_name(const RlAdaptiveUnit*) { return "adaptive unit"; }
 template <class Given, class Owner>
 int match_check(const Given* given, const Owner* owner) {
@@ -496,6 +498,22 @@ struct RlErrorUnit {
     Ledger ledger;
 };
 
+struct RlRobustUnit {
+    int device;
+    uint32_t width, height, n_buckets;
+    uint64_t stride;       // doubles from one plane to the next: the pixel count rounded up to even (rl_robust.hip.h)
+    double* sums;          // n_buckets x 3 planes: component c of bucket j at (j * 3 + c) * stride
+    uint8_t* trim;         // the resolve's per-pixel c, bit 7 = untrimmable: width x height bytes
+    uint64_t bucket_paths[RL_ROBUST_MAX_BUCKETS]; // n[j]
+    uint64_t observations; // k
+    hipStream_t stream;    // clears and observes
+    hipEvent_t observed;   // recorded on `stream` after an observe kernel: the plot unit's stream waits for it
+    hipEvent_t ready;      // recorded on `stream` when a resolve takes the planes
+    EventPair timed[2];    // around the last observe launch and the last resolve launch (rl_debug_robust_ms)
+    bool timed_done[2];    // ... recorded at least once (observe), of a call that completed (resolve)
+    Ledger ledger;
+};
+
 struct RlAdaptiveUnit {
     int device;
     uint32_t width, height, tiles_x, tiles_y;
@@ -518,6 +536,13 @@ struct RlAdaptiveUnit {
 static_assert(offsetof(RlAdaptiveUnit, width) == 4 && offsetof(RlAdaptiveUnit, height) == 8 && offsetof(RlAdaptiveUnit, planned) == 20 &&
                   offsetof(RlAdaptiveUnit, n_paths) == 24,
               "tests/test_adaptive_abi.py: test_a_stand_in_with_a_plan_is_checked_for_its_range_size_and_device");
+
+// tests/test_robust_abi.py does the same for a robust unit, and for the device and size of the plot and gather units it is handed.
+static_assert(offsetof(RlRobustUnit, width) == 4 && offsetof(RlRobustUnit, height) == 8 && offsetof(RlRobustUnit, n_buckets) == 12 &&
+                  offsetof(RlRobustUnit, bucket_paths) == 40 && offsetof(RlRobustUnit, observations) == 40 + 8 * RL_ROBUST_MAX_BUCKETS &&
+                  offsetof(RlPlotUnit, width) == 8 && offsetof(RlPlotUnit, height) == 12 && offsetof(RlGatherUnit, width) == 4 &&
+                  offsetof(RlGatherUnit, height) == 8,
+              "tests/test_robust_abi.py: test_a_stand_in_handle_is_checked_in_the_stated_order");
 
 // One rank of an RCCL communicator (rl_comm_*).
 struct RlComm {
@@ -3320,6 +3345,192 @@ int rl_error_unit_upload(RlErrorUnit* u, const double* sum_y, const double* sum_
     return RL_OK;
 }
 
+// ---- RobustUnit (rl_robust.hip.h) ----------------------------------------------------------------
+
+namespace {
+std::atomic<uint64_t> g_robust_launches[2]; // rl_debug_robust_launches: observe launches, resolve launches
+
+size_t robust_planes_bytes(const RlRobustUnit* u) { return (size_t)u->n_buckets * 3 * u->stride * sizeof(double); }
+
+// The sum of the buckets' path counts; false if it overflows 64 bits.
+bool robust_total(const uint64_t* bucket_paths, uint32_t n_buckets, uint64_t* total) {
+    uint64_t n = 0;
+    for (uint32_t j = 0; j < n_buckets; ++j) {
+        if (n + bucket_paths[j] < n) return false;
+        n += bucket_paths[j];
+    }
+    *total = n;
+    return true;
+}
+}
+
+int rl_robust_params_default(RlRobustParams* out) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    out->gain = 1.0;
+    out->max_trim = 0xffffffffu;
+    out->reserved = 0;
+    return RL_OK;
+}
+
+int rl_robust_unit_create(int device, uint32_t width, uint32_t height, uint32_t n_buckets, RlRobustUnit** out) {
+    if (!out) return fail(RL_E_INVALID, "null output handle");
+    *out = nullptr;
+    if (width == 0 || height == 0) return fail(RL_E_INVALID, "zero-sized robust unit");
+    int rc = check_image_size("robust unit", width, height);
+    if (rc != RL_OK) return rc;
+    if (n_buckets < 3 || n_buckets > RL_ROBUST_MAX_BUCKETS)
+        return fail(RL_E_INVALID, "robust unit: n_buckets " + std::to_string(n_buckets) + " outside 3 .. RL_ROBUST_MAX_BUCKETS = " +
+                                      std::to_string(RL_ROBUST_MAX_BUCKETS));
+    RlRobustUnit* u = nullptr;
+    if ((rc = unit_new("robust unit", device, width, height, n_buckets, out, &u)) != RL_OK) return rc;
+    u->n_buckets = n_buckets;
+    const size_t n_pixels = (size_t)width * height;
+    u->stride = (n_pixels + 1) & ~(uint64_t)1;
+    u->ledger.alloc_zeroed(&u->sums, robust_planes_bytes(u));
+    u->ledger.alloc(&u->trim, n_pixels);
+    u->ledger.stream(&u->stream);
+    u->ledger.event(&u->observed);
+    u->ledger.event(&u->ready);
+    for (EventPair& ep : u->timed) u->ledger.pair(&ep);
+    return unit_created("robust unit allocation", u, rl_robust_unit_destroy, out);
+}
+
+int rl_robust_unit_destroy(RlRobustUnit* u) {
+    if (!u) return RL_OK;
+    (void)hipSetDevice(u->device);
+    u->ledger.release();
+    delete u;
+    return RL_OK;
+}
+
+int rl_robust_unit_clear(RlRobustUnit* u) {
+    if (!u) return fail(RL_E_INVALID, "null robust unit");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    RL_HIP(hipMemsetAsync(u->sums, 0, robust_planes_bytes(u), u->stream));
+    for (uint64_t& n : u->bucket_paths) n = 0;
+    u->observations = 0;
+    return RL_OK;
+}
+
+int rl_robust_unit_observe(RlRobustUnit* u, RlPlotUnit* plot, uint64_t n_paths, uint32_t bucket) {
+    if (!u || !plot) return fail(RL_E_INVALID, "rl_robust_unit_observe: null robust unit or plot unit");
+    if (n_paths == 0) return fail(RL_E_INVALID, "rl_robust_unit_observe: n_paths is 0: an observation is the sum over at least one path");
+    if (bucket >= u->n_buckets && bucket != RL_ROBUST_NEXT)
+        return fail(RL_E_INVALID, "rl_robust_unit_observe: bucket " + std::to_string(bucket) + " of " + std::to_string(u->n_buckets) +
+                                      " (RL_ROBUST_NEXT takes them in turn)");
+    const uint32_t j = bucket == RL_ROBUST_NEXT ? (uint32_t)(u->observations % u->n_buckets) : bucket;
+    uint64_t total = 0;
+    if (u->bucket_paths[j] + n_paths < u->bucket_paths[j] || !robust_total(u->bucket_paths, u->n_buckets, &total) || total + n_paths < total)
+        return fail(RL_E_INVALID, "rl_robust_unit_observe: the number of paths of a bucket or their total N overflows 64 bits");
+    int cus = 256;
+    int rc = match_check(plot, u);
+    if (rc == RL_OK) rc = enter_device(u->device, &cus);
+    if (rc != RL_OK) return rc;
+    if ((rc = plot_settle(plot)) != RL_OK) return rc; // a fused render begun into this buffer ends first
+    const uint64_t n_pixels = (uint64_t)u->width * u->height;
+    if ((rc = hand_over(plot->ready, plot->stream, u->stream)) != RL_OK) return rc; // everything plotted / splatted / reduced into the buffer so far
+    rc = timed_launch(u->timed[0], u->stream, &g_robust_launches[0], [&] {
+        hipLaunchKernelGGL(rl_robust_observe_kernel, dim3(grid_for(n_pixels / 2 + 1, cus)), dim3(RL_BLOCK), 0, u->stream,
+                           u->sums + (uint64_t)j * 3 * u->stride, (const float*)plot->xyz, n_pixels, u->stride);
+    });
+    if (rc != RL_OK) return rc;
+    u->timed_done[0] = true; // recorded: rl_debug_robust_ms waits for the launch itself
+    if ((rc = hand_over(u->observed, u->stream, plot->stream)) != RL_OK) return rc; // a later clear or gather of the buffer must not overtake the read
+    u->observations += 1;
+    u->bucket_paths[j] += n_paths;
+    return RL_OK;
+}
+
+int rl_robust_unit_resolve(RlRobustUnit* u, const RlRobustParams* params, RlGatherUnit* dst, RlRobustStats* stats, uint8_t* trim) {
+    if (!u || !params || !dst) return fail(RL_E_INVALID, "rl_robust_unit_resolve: null robust unit, params or dst");
+    if (!(params->gain >= 0.0)) return fail(RL_E_INVALID, "rl_robust_unit_resolve: gain is negative or not a number");
+    for (uint32_t j = 0; j < u->n_buckets; ++j)
+        if (u->bucket_paths[j] == 0)
+            return fail(RL_E_STATE, "rl_robust_unit_resolve: bucket " + std::to_string(j) + " holds no paths: every bucket needs an observation");
+    int cus = 256;
+    int rc = match_check(dst, u);
+    if (rc == RL_OK) rc = enter_device(u->device, &cus);
+    if (rc != RL_OK) return rc;
+    const uint64_t n_pixels = (uint64_t)u->width * u->height;
+    const uint32_t M = u->n_buckets, cmax = std::min(params->max_trim, (M - 1u) / 2u);
+    uint64_t total = 0;
+    if (!robust_total(u->bucket_paths, M, &total)) return fail(RL_E_STATE, "rl_robust_unit_resolve: the number of paths N overflows 64 bits");
+    RlRobustCounts counts;
+    for (uint32_t j = 0; j < RL_ROBUST_MAX_BUCKETS; ++j) counts.n[j] = j < M ? (double)u->bucket_paths[j] : 1.0;
+    // one wave per workgroup (rl_robust.hip.h); as many lanes in flight as grid_for gives a streaming kernel
+    const uint64_t blocks = std::min<uint64_t>((n_pixels + RL_ROBUST_LANES - 1) / RL_ROBUST_LANES, (uint64_t)cus * 8 * (RL_BLOCK / RL_ROBUST_LANES));
+    const size_t lds = (size_t)M * RL_ROBUST_LANES * (3 * sizeof(double) + 1);
+    std::vector<uint8_t> bytes((stats || trim) ? (size_t)n_pixels : 0);
+    hipStream_t stream = dst->stream;
+    u->timed_done[1] = false; // readable again once the call has completed
+    // (the copy writes `bytes` and the kernel reads the unit's planes: neither outlives the call, also after a failure)
+    rc = drained(stream, [&]() -> int {
+        int r = hand_over(u->ready, u->stream, stream); // everything queued on the unit: clears and observations
+        if (r != RL_OK) return r;
+        r = timed_launch(u->timed[1], stream, &g_robust_launches[1], [&] {
+            hipLaunchKernelGGL(rl_robust_resolve_kernel, dim3((unsigned)blocks), dim3(RL_ROBUST_LANES), lds, stream, (const double*)u->sums, u->stride,
+                               n_pixels, M, counts, (double)total, params->gain, cmax, dst->acc, u->trim);
+        });
+        if (r != RL_OK) return r;
+        RL_HIP(hipMemsetAsync(dst->comp, 0, (size_t)n_pixels * 3 * sizeof(float), stream));
+        if (!bytes.empty()) RL_HIP(hipMemcpyAsync(bytes.data(), u->trim, (size_t)n_pixels, hipMemcpyDeviceToHost, stream));
+        return RL_OK;
+    }());
+    if (rc != RL_OK) return rc;
+    u->timed_done[1] = true;
+    if (stats) {
+        std::memset(stats, 0, sizeof *stats);
+        stats->observations = u->observations;
+        stats->paths = total;
+        stats->buckets = M;
+        for (const uint8_t b : bytes) {
+            const uint32_t c = b & 0x7fu;
+            stats->largest_trim = std::max(stats->largest_trim, c);
+            stats->trimmed_pixels += c > 0 ? 1 : 0;
+            stats->trimmed_buckets += 2 * c;
+            stats->untrimmable_pixels += b >> 7;
+        }
+    }
+    if (trim)
+        for (size_t p = 0; p < bytes.size(); ++p) trim[p] = bytes[p] & 0x7fu;
+    return RL_OK;
+}
+
+int rl_robust_unit_download(RlRobustUnit* u, double* sums, uint64_t* bucket_paths, uint64_t* observations) {
+    if (!u) return fail(RL_E_INVALID, "null robust unit");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    const size_t n_pixels = (size_t)u->width * u->height;
+    RL_HIP(hipStreamSynchronize(u->stream));
+    if (sums)
+        for (size_t k = 0; k < (size_t)u->n_buckets * 3; ++k) // plane by plane: the device's planes are an even number of doubles apart
+            RL_HIP(hipMemcpy(sums + k * n_pixels, u->sums + k * u->stride, n_pixels * sizeof(double), hipMemcpyDeviceToHost));
+    if (bucket_paths) std::memcpy(bucket_paths, u->bucket_paths, u->n_buckets * sizeof(uint64_t));
+    if (observations) *observations = u->observations;
+    return RL_OK;
+}
+
+int rl_robust_unit_upload(RlRobustUnit* u, const double* sums, const uint64_t* bucket_paths, uint64_t observations) {
+    if (!u || !sums || !bucket_paths) return fail(RL_E_INVALID, "rl_robust_unit_upload: null robust unit, sums or bucket_paths");
+    uint64_t filled = 0, total = 0;
+    for (uint32_t j = 0; j < u->n_buckets; ++j) filled += bucket_paths[j] != 0 ? 1 : 0;
+    if (observations < filled)
+        return fail(RL_E_INVALID, "rl_robust_unit_upload: " + std::to_string(observations) + " observations cannot have filled " + std::to_string(filled) +
+                                      " buckets");
+    if (!robust_total(bucket_paths, u->n_buckets, &total)) return fail(RL_E_INVALID, "rl_robust_unit_upload: the number of paths N overflows 64 bits");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    const size_t n_pixels = (size_t)u->width * u->height;
+    RL_HIP(hipStreamSynchronize(u->stream));
+    for (size_t k = 0; k < (size_t)u->n_buckets * 3; ++k)
+        RL_HIP(hipMemcpy(u->sums + k * u->stride, sums + k * n_pixels, n_pixels * sizeof(double), hipMemcpyHostToDevice));
+    RL_HIP(hipStreamSynchronize(nullptr)); // (the null stream only: a resident open trace kernel of another unit is not waited for)
+    for (uint32_t j = 0; j < RL_ROBUST_MAX_BUCKETS; ++j) u->bucket_paths[j] = j < u->n_buckets ? bucket_paths[j] : 0;
+    u->observations = observations;
+    return RL_OK;
+}
+
 // ---- AdaptiveUnit (rl_adaptive_plan.h, rl_adaptive.hip.h) ----------------------------------------
 
 namespace {
@@ -3858,6 +4069,23 @@ int rl_debug_error_launches(uint64_t out[2]) {
     return RL_OK;
 }
 int rl_debug_error_ms(RlErrorUnit* u, float out[2]) {
+    if (!u || !out) return fail(RL_E_INVALID, "null argument");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    for (int k = 0; k < 2; ++k) {
+        out[k] = 0.0f;
+        if (!u->timed_done[k]) continue;
+        RL_HIP(hipEventSynchronize(u->timed[k].stop));
+        RL_HIP(hipEventElapsedTime(&out[k], u->timed[k].start, u->timed[k].stop));
+    }
+    return RL_OK;
+}
+int rl_debug_robust_launches(uint64_t out[2]) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    for (int k = 0; k < 2; ++k) out[k] = g_robust_launches[k].load(std::memory_order_relaxed);
+    return RL_OK;
+}
+int rl_debug_robust_ms(RlRobustUnit* u, float out[2]) {
     if (!u || !out) return fail(RL_E_INVALID, "null argument");
     int rc = use_device(u->device);
     if (rc != RL_OK) return rc;
