@@ -273,6 +273,8 @@ extern "C" {
     pub fn rl_robust_unit_observe(unit: *mut RlRobustUnit, plot: *mut RlPlotUnit, n_paths: u64, bucket: u32) -> c_int;
     pub fn rl_robust_unit_resolve(unit: *mut RlRobustUnit, params: *const RlRobustParams, dst: *mut RlGatherUnit, stats: *mut RlRobustStats,
                                   trim: *mut u8) -> c_int;
+    pub fn rl_robust_unit_estimate(unit: *mut RlRobustUnit, params: *const RlRobustParams, stats: *mut RlErrorStats, se: *mut f32,
+                                   tiles: *mut f64, trim: *mut u8) -> c_int;
     pub fn rl_robust_unit_download(unit: *mut RlRobustUnit, sums: *mut f64, bucket_paths: *mut u64, observations: *mut u64) -> c_int;
     pub fn rl_robust_unit_upload(unit: *mut RlRobustUnit, sums: *const f64, bucket_paths: *const u64, observations: u64) -> c_int;
     pub fn rl_adaptive_unit_create(device: c_int, width: u32, height: u32, out: *mut *mut RlAdaptiveUnit) -> c_int;

@@ -1104,6 +1104,40 @@ int rl_error_unit_upload(RlErrorUnit* unit, const double* sum_y, const double* s
  *     exact (a host reduction of the trim bytes): the same on every run.  Ordering is rl_spectral_unit_project's: the call waits on
  *     the device for what is queued on dst's stream and on the unit, runs on dst's stream and returns with dst complete.
  *     Everything it produces is exact: the same bits on every run, and the bits of the CPU restatement tests/_robust_oracle.py.
+ *   rl_robust_unit_estimate(unit, params, stats, se, tiles, trim).  How noisy the film is that rl_robust_unit_resolve writes with
+ *     the same params: the standard error of its Y, per pixel and per tile, in rl_error_unit_estimate's output format, so that the
+ *     tile map, a target-error stopping rule and rl_adaptive_unit_plan take it as they take that call's.  The M buckets are M
+ *     estimates of the pixel; the standard error of their trimmed mean is the winsorized sum of squares over K (K - 1), K the
+ *     number of kept buckets (Tukey and McLaughlin 1963), so a firefly that the resolve trims stops inflating the estimate.
+ *     Luminance only, from the Y planes alone.  Checked in this order: a NULL unit, params or stats is RL_E_INVALID; params->gain
+ *     NaN or negative is RL_E_INVALID (+infinity is legal); any n[j] == 0 is RL_E_STATE; nothing is written and nothing launched.
+ *     All arithmetic is f64 in exactly this order, never contracted, the division correctly rounded; one f64 -> f32 conversion and
+ *     one rl_sqrtf.  With N = sum_j n[j] and k observations, per pixel:
+ *       1. key[j] = S[j][1] / (double)n[j].  The ranks, the untrimmable rule, T, W, G and v are the resolve's steps 2 to 5, word for
+ *          word, but for the cap: cmax = min(max_trim, (M - 2) / 2) in integer division, so that at least two buckets are kept --
+ *          for odd M at full trim one less than the resolve's cap; M = 3 never trims.
+ *       2. With c the trim and K = M - 2 c: lo = key(c), hi = key(M - c - 1), and A = sum of key(r) for r = c .. M - c - 1,
+ *          sequentially from +0.0 in rank order.  An untrimmable pixel has c = 0 and bucket order, as in the resolve.
+ *       3. B = (double)c * lo + A;  B = B + (double)c * hi;  mw = B / (double)M: the winsorized mean.
+ *       4. D from +0.0: for r = c .. M - c - 1 in order e = key(r) - mw; D = D + e * e.  Then el = lo - mw;
+ *          D = D + (double)c * (el * el);  eh = hi - mw;  D = D + (double)c * (eh * eh).
+ *       5. var = D / (double)(K * (K - 1)), the integer product first.
+ *       6. f = (A / (double)K) * (double)N -- the Y the resolve writes, before its conversion, wherever its c is this c --;
+ *          v = (var * (double)N) * (double)N;  se = rl_sqrtf((float)v);  ay = fabs(f).  No special cases: a NaN stays a NaN, an
+ *          overflow becomes +infinity.
+ *       7. The RL_ERROR_TILE tiles are rl_error_unit_estimate's tree over (double)se and over ay, bit for bit (strides 128 .. 1,
+ *          +0.0 outside the image), and the host part is that call's: sum_se, sum_y, relative_error, the worst tile.
+ *          stats->observations = k and stats->paths = N.
+ *       8. trim[p] = c, with bit 7 set for an untrimmable pixel.
+ *     The estimate treats the bucket means as equally weighted draws, as the resolve does: with unequal n[j] it is an
+ *     approximation.  For gain 0, equal n[j] and one observation per bucket, v equals rl_error_unit_estimate's d N / (k - 1)
+ *     algebraically.  The trim is chosen from the same keys whose spread is then measured: the estimate is calibrated for a fixed c
+ *     (tests/test_robust_error.py), and by how much a Gini-chosen c biases it is not measured.
+ *     `se` may be NULL; otherwise width x height floats of host memory, in rows.  `tiles` may be NULL; otherwise
+ *     tiles_y * tiles_x * 2 doubles, {t_se, t_y} per tile in raster order.  `trim` may be NULL; otherwise width x height bytes.
+ *     Ordering is rl_error_unit_estimate's: the call runs on the unit's stream behind what is queued on the unit and returns with a
+ *     host synchronisation; the unit's state is only read.  The result is exact: the same bits on every run, and the bits of the CPU
+ *     restatement tests/_robust_error_oracle.py.
  *   rl_robust_unit_download / _upload move the planes in the host layout above, the M values n[j] and k; any of download's outputs
  *     may be NULL; upload needs `sums` and `bucket_paths` (a NULL unit or either is RL_E_INVALID), takes any contents of the planes,
  *     NaN included, and refuses an `observations` below the number of non-zero bucket_paths entries and a total N that overflows
@@ -1132,6 +1166,7 @@ int rl_robust_unit_destroy(RlRobustUnit* unit);
 int rl_robust_unit_clear(RlRobustUnit* unit);
 int rl_robust_unit_observe(RlRobustUnit* unit, RlPlotUnit* plot, uint64_t n_paths, uint32_t bucket);
 int rl_robust_unit_resolve(RlRobustUnit* unit, const RlRobustParams* params, RlGatherUnit* dst, RlRobustStats* stats, uint8_t* trim);
+int rl_robust_unit_estimate(RlRobustUnit* unit, const RlRobustParams* params, RlErrorStats* stats, float* se, double* tiles, uint8_t* trim);
 int rl_robust_unit_download(RlRobustUnit* unit, double* sums, uint64_t* bucket_paths, uint64_t* observations);
 int rl_robust_unit_upload(RlRobustUnit* unit, const double* sums, const uint64_t* bucket_paths, uint64_t observations);
 

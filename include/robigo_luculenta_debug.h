@@ -101,6 +101,12 @@ int rl_debug_robust_launches(uint64_t out[2]);
 /* Device time in milliseconds, from events around the launch: out[0] the unit's last observe launch, out[1] the resolve launch of
  * its last completed rl_robust_unit_resolve; 0 before the first.  Waits for the launch.  tools/robust_bench.py. */
 int rl_debug_robust_ms(RlRobustUnit* unit, float out[2]);
+/* Launches of rl_robust_estimate_kernel (one per rl_robust_unit_estimate) since the library was loaded.  A counter of its own:
+ * rl_debug_robust_launches keeps its two elements. */
+int rl_debug_robust_estimate_launches(uint64_t* out);
+/* Device time in milliseconds, from events around the launch, of the unit's last estimate launch; 0 before the first.  Waits for
+ * the launch.  tools/robust_error_bench.py. */
+int rl_debug_robust_estimate_ms(RlRobustUnit* unit, float* out);
 /* out[0]: launches of rl_adaptive_samples_kernel (one per chunk of rl_adaptive_unit_samples* and of rl_plot_unit_render_adaptive),
  * out[1]: path kernel launches made by rl_plot_unit_render_adaptive (counted in rl_debug_path_launches too), out[2]: launches of
  * rl_adaptive_splat_kernel, since the library was loaded. */

@@ -984,6 +984,24 @@ class RobustUnit(_Handle):
         out = {name: getattr(stats, name) for name, _ in RlRobustStats._fields_}
         return (out, trim_out) if trim else out
 
+    def estimate(self, gain=1.0, max_trim=0xFFFFFFFF, se=True, trim=False):
+        """rl_robust_unit_estimate, the standard error of the film that resolve() writes with the same gain and max_trim, in
+        ErrorUnit.estimate's shapes: (stats dict, se as (height, width) float32 or None, tiles as (tiles_y, tiles_x, 2) float64
+        {t_se, t_y}), and with trim=True a fourth element, (height, width) uint8: c, bit 7 set for an untrimmable pixel."""
+        params, stats = RlRobustParams(gain, max_trim, 0), RlErrorStats()
+        se_out = np.zeros((self.height, self.width), dtype=np.float32) if se else None
+        tiles_out = np.zeros((-(-self.height // RL_ERROR_TILE), -(-self.width // RL_ERROR_TILE), 2), dtype=np.float64)
+        trim_out = np.zeros((self.height, self.width), dtype=np.uint8) if trim else None
+        check(lib.rl_robust_unit_estimate(self._h, C.byref(params), C.byref(stats), _host_ptr(se_out), _host_ptr(tiles_out), _host_ptr(trim_out)))
+        out = (_error_stats(stats), se_out, tiles_out)
+        return out + (trim_out,) if trim else out
+
+    def estimate_ms(self):
+        """Device milliseconds of the last estimate launch of this unit (rl_debug_robust_estimate_ms)."""
+        out = C.c_float(0)
+        check(lib.rl_debug_robust_estimate_ms(self._h, C.byref(out)))
+        return out.value
+
     def download(self):
         """(sums as (n_buckets, 3, height, width) float64, bucket_paths as (n_buckets,) uint64, k)."""
         sums = np.zeros((self.n_buckets, 3, self.height, self.width), dtype=np.float64)
@@ -1079,6 +1097,34 @@ def render_adaptive_to_error(scene, plot, gather, error, adaptive, n_paths_per_b
         if batch + 1 < max(2, min_observations):
             continue
         stats, _, tiles = error.estimate(se=False)
+        if stats["relative_error"] <= target_error:
+            return batch + 1, stats, tiles
+        if adaptive_sampling and batch + 1 < max_batches:
+            adaptive.plan_from_error_tiles(tiles, uniform_share, n_paths_per_batch)
+    return max_batches, stats, tiles
+
+
+def render_robust_to_error(scene, plot, gather, robust, adaptive, n_paths_per_batch, max_batches, target_error, gain=1.0,
+                           max_trim=0xFFFFFFFF, uniform_share=0.25, min_observations=0, seed=1, stream=0, first_path_index=0,
+                           fetch=FETCH_LDS, max_segments=0, adaptive_sampling=True):
+    """render_adaptive_to_error's loop on the robust film: each batch is shown to `robust` (the buckets in turn) and accumulated into
+    `gather`, until rl_robust_unit_estimate's relative_error -- the noise of the film that robust.resolve writes with this gain and
+    max_trim -- is at most target_error or max_batches are made.  The first estimate comes after max(M, min_observations)
+    batches, M = robust.n_buckets: every bucket needs one.  Until then the plans are uniform; from then on every batch is planned
+    from the estimate's tile map, which a trimmed firefly no longer inflates.  adaptive_sampling=False keeps the uniform plan
+    throughout.  `robust` must be empty (RobustUnit.clear).  Returns (batches made, the last estimate's stats, its tiles)."""
+    first = max(robust.n_buckets, min_observations)
+    if max_batches < first:
+        raise ValueError("max_batches leaves no room for one batch per bucket and min_observations")
+    stats = tiles = None
+    adaptive.plan(None, uniform_share, n_paths_per_batch)
+    for batch in range(max_batches):
+        plot.render_adaptive(adaptive, scene, seed, stream, first_path_index + batch * n_paths_per_batch, fetch=fetch, max_segments=max_segments)
+        robust.observe(plot, n_paths_per_batch)
+        gather.accumulate(plot)       # (and clears the plot unit)
+        if batch + 1 < first:
+            continue
+        stats, _, tiles = robust.estimate(gain, max_trim, se=False)
         if stats["relative_error"] <= target_error:
             return batch + 1, stats, tiles
         if adaptive_sampling and batch + 1 < max_batches:
@@ -1340,6 +1386,13 @@ def robust_launches():
     """(launches of the robust unit's observe kernel, launches of its resolve kernel) since the library was loaded
     (rl_debug_robust_launches)."""
     return _launch_counters(lib.rl_debug_robust_launches, 2, tuple)
+
+
+def robust_estimate_launches():
+    """Launches of the robust unit's estimate kernel since the library was loaded (rl_debug_robust_estimate_launches)."""
+    out = C.c_uint64(0)
+    check(lib.rl_debug_robust_estimate_launches(C.byref(out)))
+    return out.value
 
 
 def adaptive_launches():

@@ -11,7 +11,9 @@ the cap.  With --error-map PATH the per-tile relative error of the last estimate
 With --adaptive as well the batches are rendered over the unit API by render_adaptive_to_error: from --min-observations on, every batch's
 camera samples are drawn tile by tile from the running error map (AdaptiveUnit), --uniform-share of them spread by area.
 With --robust PATH every batch also goes into one of the --robust-buckets sub-films of a RobustUnit (with --direct inside its batch
-loop, otherwise batch by batch over the unit API), and their Gini-trimmed median of means, fireflies removed, is tonemapped to PATH."""
+loop, otherwise batch by batch over the unit API), and their Gini-trimmed median of means, fireflies removed, is tonemapped to PATH.
+With --robust-target-error E as well that loop ends once the robust film's own noise estimate (RobustUnit.estimate) is at most E, with
+--robust-adaptive the batches are render_robust_to_error's, drawn from that estimate's tile map, and --robust-error-map PATH writes it."""
 import argparse
 import os
 import struct
@@ -85,10 +87,32 @@ def parse_args(argv=None):
                     help="with --robust: the number of buckets, 3 .. 32 (default 15); the batches go to them in turn")
     ap.add_argument("--robust-gain", metavar="G", type=float, default=None,
                     help="with --robust: scales the number of buckets trimmed at each end, G >= 0 (default 1; 0 trims nothing)")
+    ap.add_argument("--robust-target-error", metavar="E", type=float, default=None,
+                    help="with --robust: end the run once the estimated relative error of the robust film (RobustUnit.estimate, which a "
+                         "trimmed firefly does not inflate) is at most E, looked at after every batch once each bucket has one; "
+                         "--batches stays the cap")
+    ap.add_argument("--robust-adaptive", action="store_true",
+                    help="with --robust-target-error: draw each batch's camera samples tile by tile from the robust estimate's error map "
+                         "(render_robust_to_error)")
+    ap.add_argument("--robust-error-map", metavar="PATH", default=None,
+                    help="with --robust: write the per-tile relative error of the last robust estimate as a grey image, the worst "
+                         "16 x 16 tile white, to PATH (*.png or *.ppm); without --robust-target-error the run estimates once at the end")
     a = ap.parse_args(argv)
-    for given, flag in ((a.robust_buckets is not None, "--robust-buckets"), (a.robust_gain is not None, "--robust-gain")):
+    for given, flag in ((a.robust_buckets is not None, "--robust-buckets"), (a.robust_gain is not None, "--robust-gain"),
+                        (a.robust_target_error is not None, "--robust-target-error"), (a.robust_adaptive, "--robust-adaptive"),
+                        (a.robust_error_map is not None, "--robust-error-map")):
         if given and a.robust is None:
             ap.error("%s needs --robust PATH" % flag)
+    if a.robust_adaptive and a.robust_target_error is None:
+        ap.error("--robust-adaptive needs --robust-target-error: the samples follow the estimate the target is held to")
+    if a.robust_target_error is not None and not a.robust_target_error >= 0:
+        ap.error("--robust-target-error must be a number >= 0")
+    for given, flag in ((a.robust_target_error is not None, "--robust-target-error"), (a.robust_adaptive, "--robust-adaptive"),
+                        (a.robust_error_map is not None, "--robust-error-map")):
+        if given and a.direct:
+            ap.error("%s cannot be combined with --direct: the robust estimate drives the camera-path batch loop" % flag)
+    if a.robust_adaptive and not 0 < a.photons_per_batch < 1 << 32:
+        ap.error("--robust-adaptive needs --photons-per-batch in 1 .. 2^32 - 1: a plan's size")
     if a.robust is not None:
         for given, flag in ((a.adaptive, "--adaptive"), (a.resume, "--resume"), (a.unfused, "--unfused"),
                             (a.concurrency is not None, "--concurrency"), (a.spectral is not None, "--spectral")):
@@ -242,18 +266,36 @@ def resolve_robust(a, robust):
 def render_robust(a):
     """--robust without --direct: batch b is paths [b * photons_per_batch, (b + 1) * photons_per_batch) of stream 0, one fused
     synchronous render into a plot unit, shown to the robust unit and then gathered; one tonemap at the end, then the robust film.
+    With --robust-target-error E the run ends once RobustUnit.estimate's relative_error -- the noise of the robust film, which a
+    trimmed firefly does not inflate -- is at most E, looked at after every batch from the M-th on; the batches are the same fused
+    renders, so --output is what --batches of that many gives without the option.  With --robust-adaptive as well the batches are
+    render_robust_to_error's: every batch's camera samples follow the estimate's tile map.  With --robust-error-map PATH the last
+    estimate's per-tile relative error is written as a grey image (without a target: one estimate at the end).
     Returns (rgb, the gather unit, the robust film's stats)."""
-    from . import GatherUnit, PlotUnit, RobustUnit, Scene, TonemapUnit, TraceUnit
+    from . import AdaptiveUnit, GatherUnit, PlotUnit, RobustUnit, Scene, TonemapUnit, TraceUnit, render_robust_to_error
     scene = Scene.builtin(SCENE_DEMO if a.scene == "demo" else SCENE_GLASS_STRESS, device=a.device)
-    trace = TraceUnit(0, a.width, a.height, n_photons=64, device=a.device)
     plot = PlotUnit(0, a.width, a.height, device=a.device)
     gather = GatherUnit(a.width, a.height, device=a.device)
     robust = RobustUnit(a.width, a.height, a.robust_buckets, device=a.device)
+    made, estimate, tiles = a.batches, None, None
     t0 = time.perf_counter()
-    for b in range(a.batches):
-        trace.render_fused_sync(scene, plot, a.photons_per_batch, seed=a.seed, stream=0, first_path_index=b * a.photons_per_batch)
-        robust.observe(plot, a.photons_per_batch)
-        gather.accumulate(plot)
+    if a.robust_adaptive:
+        adaptive = AdaptiveUnit(a.width, a.height, device=a.device)
+        made, estimate, tiles = render_robust_to_error(scene, plot, gather, robust, adaptive, a.photons_per_batch, a.batches,
+                                                       a.robust_target_error, gain=a.robust_gain, seed=a.seed)
+    else:
+        trace = TraceUnit(0, a.width, a.height, n_photons=64, device=a.device)
+        for b in range(a.batches):
+            trace.render_fused_sync(scene, plot, a.photons_per_batch, seed=a.seed, stream=0, first_path_index=b * a.photons_per_batch)
+            robust.observe(plot, a.photons_per_batch)
+            gather.accumulate(plot)
+            if a.robust_target_error is not None and b + 1 >= a.robust_buckets:
+                estimate, _, tiles = robust.estimate(a.robust_gain, se=False)
+                if estimate["relative_error"] <= a.robust_target_error:
+                    made = b + 1
+                    break
+        if estimate is None and a.robust_error_map is not None:
+            estimate, _, tiles = robust.estimate(a.robust_gain, se=False)
     tonemap = TonemapUnit(a.width, a.height, device=a.device)
     tonemap.tonemap(gather)
     rgb = tonemap.rgb_buffer
@@ -261,7 +303,14 @@ def render_robust(a):
     write_image(a.output, rgb, a.width, a.height)
     if a.checkpoint:
         gather.save(a.checkpoint)
-    print("%d batches, %.1f Mpaths in %.2f s; wrote %s" % (a.batches, a.batches * a.photons_per_batch / 1e6, seconds, a.output))
+    print("%d batches, %.1f Mpaths in %.2f s; wrote %s" % (made, made * a.photons_per_batch / 1e6, seconds, a.output))
+    if estimate is not None:
+        target = "no target"
+        if a.robust_target_error is not None:
+            target = "target %g %s" % (a.robust_target_error, "reached" if estimate["relative_error"] <= a.robust_target_error else "not reached")
+        print("robust estimate: %d of %d batches, relative_error %.6g, %s" % (made, a.batches, estimate["relative_error"], target))
+        if a.robust_error_map is not None:
+            write_error_map(a, a.robust_error_map, tiles)
     return rgb, gather, resolve_robust(a, robust)[1]
 
 
@@ -342,13 +391,21 @@ def report_error(a, st, err):
         print("after the last gather: relative_error %.6g from %d observations" % (err["at_end"]["relative_error"], err["at_end"]["observations"]))
     if a.error_map is None:
         return None
-    rel = error_tile_rel(err["tiles"])
+    return write_error_map(a, a.error_map, err["tiles"])
+
+
+def write_error_map(a, path, tiles):
+    """An estimate's (tiles_y, tiles_x, 2) tile pairs as a grey image at `path`: per tile rel = t_se / max(t_y, mean t_y)
+    (error_tile_rel), grey = rel over the worst tile's, every pixel of a tile alike."""
+    import numpy as np
+    from . import RL_ERROR_TILE, error_tile_rel
+    rel = error_tile_rel(tiles)
     finite = rel[np.isfinite(rel)]
     worst = float(finite.max()) if finite.size and finite.max() > 0 else 1.0
     grey = np.clip(np.where(np.isfinite(rel), rel, worst) / worst * 255.0 + 0.5, 0, 255).astype(np.uint8)
     grey = np.repeat(np.repeat(grey, RL_ERROR_TILE, axis=0), RL_ERROR_TILE, axis=1)[:a.height, :a.width]
-    write_image(a.error_map, np.repeat(grey.reshape(-1, 1), 3, axis=1), a.width, a.height)
-    print("error map: wrote %s" % a.error_map)
+    write_image(path, np.repeat(grey.reshape(-1, 1), 3, axis=1), a.width, a.height)
+    print("error map: wrote %s" % path)
     return grey
 
 

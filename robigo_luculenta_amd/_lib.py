@@ -287,6 +287,7 @@ SIGNATURES = {
     "rl_robust_unit_clear": (_i, [_vp]),
     "rl_robust_unit_observe": (_i, [_vp, _vp, _u64, _u32]),
     "rl_robust_unit_resolve": (_i, [_vp, C.POINTER(RlRobustParams), _vp, C.POINTER(RlRobustStats), _vp]),
+    "rl_robust_unit_estimate": (_i, [_vp, C.POINTER(RlRobustParams), C.POINTER(RlErrorStats), _vp, _vp, _vp]),
     "rl_robust_unit_download": (_i, [_vp, _vp, _vp, C.POINTER(_u64)]),
     "rl_robust_unit_upload": (_i, [_vp, _vp, _vp, _u64]),
     "rl_adaptive_unit_create": (_i, [_i, _u32, _u32, _pp]),
@@ -347,6 +348,8 @@ DEBUG_SIGNATURES = {
     "rl_debug_error_ms": (_i, [_vp, _vp]),
     "rl_debug_robust_launches": (_i, [_vp]),
     "rl_debug_robust_ms": (_i, [_vp, _vp]),
+    "rl_debug_robust_estimate_launches": (_i, [C.POINTER(_u64)]),
+    "rl_debug_robust_estimate_ms": (_i, [_vp, C.POINTER(C.c_float)]),
     "rl_debug_adaptive_launches": (_i, [_vp]),
     "rl_debug_adaptive_ms": (_i, [_vp, _vp]),
     "rl_debug_gather_accumulate_ms": (_i, [_vp, _vp, C.POINTER(C.c_float)]),

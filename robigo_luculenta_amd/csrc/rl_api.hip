@@ -503,7 +503,7 @@ struct RlRobustUnit {
     uint32_t width, height, n_buckets;
     uint64_t stride;       // doubles from one plane to the next: the pixel count rounded up to even (rl_robust.hip.h)
     double* sums;          // n_buckets x 3 planes: component c of bucket j at (j * 3 + c) * stride
-    uint8_t* trim;         // the resolve's per-pixel c, bit 7 = untrimmable: width x height bytes
+    uint8_t* trim;         // the last resolve's or estimate's per-pixel c, bit 7 = untrimmable: width x height bytes
     uint64_t bucket_paths[RL_ROBUST_MAX_BUCKETS]; // n[j]
     uint64_t observations; // k
     hipStream_t stream;    // clears and observes
@@ -511,6 +511,11 @@ struct RlRobustUnit {
     hipEvent_t ready;      // recorded on `stream` when a resolve takes the planes
     EventPair timed[2];    // around the last observe launch and the last resolve launch (rl_debug_robust_ms)
     bool timed_done[2];    // ... recorded at least once (observe), of a call that completed (resolve)
+    uint32_t tiles_x, tiles_y; // the estimate's RL_ERROR_TILE tiles
+    float* se;             // the estimate's per-pixel result, width x height floats
+    double* tiles;         // the estimate's {t_se, t_y} per tile, tiles in raster order
+    EventPair timed_estimate;  // around the last estimate launch (rl_debug_robust_estimate_ms)
+    bool timed_estimate_done;  // ... recorded at least once
     Ledger ledger;
 };
 
@@ -3213,6 +3218,36 @@ int rl_spectral_observer_cie1931(uint32_t n_nodes, float* out) {
 
 namespace {
 std::atomic<uint64_t> g_error_launches[2]; // rl_debug_error_launches: observe launches, estimate launches
+
+// The host part of an estimate (rl_error_unit_estimate, rl_robust_unit_estimate): RlErrorStats from the tiles' {t_se, t_y} pairs,
+// every sum sequential in f64 in tile raster order, as the header states it.
+void error_host_stats(const std::vector<double>& pairs, uint32_t tiles_x, uint32_t tiles_y, uint64_t observations, uint64_t paths,
+                      RlErrorStats* stats) {
+    const size_t n_tiles = (size_t)tiles_x * tiles_y;
+    std::memset(stats, 0, sizeof *stats);
+    stats->observations = observations;
+    stats->paths = paths;
+    stats->tiles_x = tiles_x;
+    stats->tiles_y = tiles_y;
+    double sum_se = 0.0, sum_y = 0.0;
+    for (size_t i = 0; i < n_tiles; ++i) {
+        sum_se = sum_se + pairs[2 * i];
+        sum_y = sum_y + pairs[2 * i + 1];
+    }
+    stats->sum_se = sum_se;
+    stats->sum_y = sum_y;
+    stats->relative_error = sum_se / sum_y;
+    const double m = sum_y / (double)n_tiles;
+    for (size_t i = 0; i < n_tiles; ++i) {
+        const double t_se = pairs[2 * i], t_y = pairs[2 * i + 1];
+        const double rel = t_se / (t_y > m ? t_y : m);
+        if (i == 0 || rel > stats->worst_tile_error) {
+            stats->worst_tile_error = rel;
+            stats->worst_tile_x = (uint32_t)(i % tiles_x);
+            stats->worst_tile_y = (uint32_t)(i / tiles_x);
+        }
+    }
+}
 }
 
 int rl_error_unit_create(int device, uint32_t width, uint32_t height, RlErrorUnit** out) {
@@ -3296,29 +3331,7 @@ int rl_error_unit_estimate(RlErrorUnit* u, RlErrorStats* stats, float* se, doubl
         return RL_OK;
     }());
     if (rc != RL_OK) return rc;
-    std::memset(stats, 0, sizeof *stats);
-    stats->observations = u->observations;
-    stats->paths = u->paths;
-    stats->tiles_x = u->tiles_x;
-    stats->tiles_y = u->tiles_y;
-    double sum_se = 0.0, sum_y = 0.0;
-    for (size_t i = 0; i < n_tiles; ++i) {
-        sum_se = sum_se + pairs[2 * i];
-        sum_y = sum_y + pairs[2 * i + 1];
-    }
-    stats->sum_se = sum_se;
-    stats->sum_y = sum_y;
-    stats->relative_error = sum_se / sum_y;
-    const double m = sum_y / (double)n_tiles;
-    for (size_t i = 0; i < n_tiles; ++i) {
-        const double t_se = pairs[2 * i], t_y = pairs[2 * i + 1];
-        const double rel = t_se / (t_y > m ? t_y : m);
-        if (i == 0 || rel > stats->worst_tile_error) {
-            stats->worst_tile_error = rel;
-            stats->worst_tile_x = (uint32_t)(i % u->tiles_x);
-            stats->worst_tile_y = (uint32_t)(i / u->tiles_x);
-        }
-    }
+    error_host_stats(pairs, u->tiles_x, u->tiles_y, u->observations, u->paths, stats);
     if (tiles) std::memcpy(tiles, pairs.data(), pairs.size() * sizeof(double));
     return RL_OK;
 }
@@ -3349,6 +3362,7 @@ int rl_error_unit_upload(RlErrorUnit* u, const double* sum_y, const double* sum_
 
 namespace {
 std::atomic<uint64_t> g_robust_launches[2]; // rl_debug_robust_launches: observe launches, resolve launches
+std::atomic<uint64_t> g_robust_estimate_launches; // rl_debug_robust_estimate_launches
 
 size_t robust_planes_bytes(const RlRobustUnit* u) { return (size_t)u->n_buckets * 3 * u->stride * sizeof(double); }
 
@@ -3388,10 +3402,15 @@ int rl_robust_unit_create(int device, uint32_t width, uint32_t height, uint32_t 
     u->stride = (n_pixels + 1) & ~(uint64_t)1;
     u->ledger.alloc_zeroed(&u->sums, robust_planes_bytes(u));
     u->ledger.alloc(&u->trim, n_pixels);
+    u->tiles_x = (width + RL_ERROR_TILE - 1u) / RL_ERROR_TILE;
+    u->tiles_y = (height + RL_ERROR_TILE - 1u) / RL_ERROR_TILE;
+    u->ledger.alloc(&u->se, n_pixels * sizeof(float));
+    u->ledger.alloc(&u->tiles, (size_t)u->tiles_x * u->tiles_y * 2 * sizeof(double));
     u->ledger.stream(&u->stream);
     u->ledger.event(&u->observed);
     u->ledger.event(&u->ready);
     for (EventPair& ep : u->timed) u->ledger.pair(&ep);
+    u->ledger.pair(&u->timed_estimate);
     return unit_created("robust unit allocation", u, rl_robust_unit_destroy, out);
 }
 
@@ -3494,6 +3513,41 @@ int rl_robust_unit_resolve(RlRobustUnit* u, const RlRobustParams* params, RlGath
     }
     if (trim)
         for (size_t p = 0; p < bytes.size(); ++p) trim[p] = bytes[p] & 0x7fu;
+    return RL_OK;
+}
+
+int rl_robust_unit_estimate(RlRobustUnit* u, const RlRobustParams* params, RlErrorStats* stats, float* se, double* tiles, uint8_t* trim) {
+    if (!u || !params || !stats) return fail(RL_E_INVALID, "rl_robust_unit_estimate: null robust unit, params or stats");
+    if (!(params->gain >= 0.0)) return fail(RL_E_INVALID, "rl_robust_unit_estimate: gain is negative or not a number");
+    for (uint32_t j = 0; j < u->n_buckets; ++j)
+        if (u->bucket_paths[j] == 0)
+            return fail(RL_E_STATE, "rl_robust_unit_estimate: bucket " + std::to_string(j) + " holds no paths: every bucket needs an observation");
+    const uint32_t M = u->n_buckets, cmax = std::min(params->max_trim, (M - 2u) / 2u); // at least two buckets are kept
+    uint64_t total = 0;
+    if (!robust_total(u->bucket_paths, M, &total)) return fail(RL_E_STATE, "rl_robust_unit_estimate: the number of paths N overflows 64 bits");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    const size_t n_pixels = (size_t)u->width * u->height, n_tiles = (size_t)u->tiles_x * u->tiles_y;
+    RlRobustCounts counts;
+    for (uint32_t j = 0; j < RL_ROBUST_MAX_BUCKETS; ++j) counts.n[j] = j < M ? (double)u->bucket_paths[j] : 1.0;
+    const size_t lds = (size_t)M * RL_ERROR_TILE_PIXELS * (sizeof(double) + 1); // the keys and the rank bytes (rl_robust.hip.h)
+    std::vector<double> pairs(2 * n_tiles);
+    // (the copies write `pairs` and the caller's `se` and `trim`: none may be written after the call, also after a failure)
+    rc = drained(u->stream, [&]() -> int {
+        const int r = timed_launch(u->timed_estimate, u->stream, &g_robust_estimate_launches, [&] {
+            hipLaunchKernelGGL(rl_robust_estimate_kernel, dim3((unsigned)n_tiles), dim3(RL_ERROR_TILE_PIXELS), lds, u->stream, (const double*)u->sums,
+                               u->stride, u->width, u->height, u->tiles_x, M, counts, (double)total, params->gain, cmax, u->se, u->tiles, u->trim);
+        });
+        if (r != RL_OK) return r;
+        u->timed_estimate_done = true; // recorded: rl_debug_robust_estimate_ms waits for the launch itself
+        RL_HIP(hipMemcpyAsync(pairs.data(), u->tiles, pairs.size() * sizeof(double), hipMemcpyDeviceToHost, u->stream));
+        if (se) RL_HIP(hipMemcpyAsync(se, u->se, n_pixels * sizeof(float), hipMemcpyDeviceToHost, u->stream));
+        if (trim) RL_HIP(hipMemcpyAsync(trim, u->trim, n_pixels, hipMemcpyDeviceToHost, u->stream));
+        return RL_OK;
+    }());
+    if (rc != RL_OK) return rc;
+    error_host_stats(pairs, u->tiles_x, u->tiles_y, u->observations, total, stats);
+    if (tiles) std::memcpy(tiles, pairs.data(), pairs.size() * sizeof(double));
     return RL_OK;
 }
 
@@ -4095,6 +4149,21 @@ int rl_debug_robust_ms(RlRobustUnit* u, float out[2]) {
         RL_HIP(hipEventSynchronize(u->timed[k].stop));
         RL_HIP(hipEventElapsedTime(&out[k], u->timed[k].start, u->timed[k].stop));
     }
+    return RL_OK;
+}
+int rl_debug_robust_estimate_launches(uint64_t* out) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    *out = g_robust_estimate_launches.load(std::memory_order_relaxed);
+    return RL_OK;
+}
+int rl_debug_robust_estimate_ms(RlRobustUnit* u, float* out) {
+    if (!u || !out) return fail(RL_E_INVALID, "null argument");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    *out = 0.0f;
+    if (!u->timed_estimate_done) return RL_OK;
+    RL_HIP(hipEventSynchronize(u->timed_estimate.stop));
+    RL_HIP(hipEventElapsedTime(out, u->timed_estimate.start, u->timed_estimate.stop));
     return RL_OK;
 }
 int rl_debug_adaptive_launches(uint64_t out[3]) {

@@ -45,32 +45,15 @@ __global__ __launch_bounds__(RL_BLOCK) __attribute__((amdgpu_num_vgpr(16))) void
     }
 }
 
-// The estimate: one workgroup per tile, thread t on the tile's pixel (t % 16, t / 16), so t is the tile raster index of the tree.
-// A thread outside the image contributes +0.0 to both trees and writes nothing.  The trees: every thread's pair goes to LDS; the
-// strides 128 and 64 cross waves and are added from LDS between barriers; wave 0 then holds v[0 .. 63] in registers, one per lane,
-// and the strides 32 .. 1 are cross-lane moves (lane i reads lane i + stride and adds it onto its own: the lanes below `stride` hold
-// exactly v[i] + v[i + stride]; what the lanes above it hold is never read again).  Same additions, same order, same bits as the
-// stated tree.  LDS: the two 256-double arrays, 4,096 bytes.  `ratio` is (double)N / (double)(k - 1), divided on the host.
-__global__ __launch_bounds__(RL_ERROR_TILE_PIXELS) void rl_error_estimate_kernel(const double* __restrict__ sum_y, const double* __restrict__ sum_q,
-                                                                                  uint32_t width, uint32_t height, uint32_t tiles_x, double n_total, double ratio,
-                                                                                  float* __restrict__ se_out, double* __restrict__ tiles) {
-    __shared__ double tree_se[RL_ERROR_TILE_PIXELS];
-    __shared__ double tree_y[RL_ERROR_TILE_PIXELS];
-    const uint32_t t = threadIdx.x;
-    const uint32_t tile = blockIdx.x; // tiles in raster order, one workgroup each
-    const uint32_t x = (tile % tiles_x) * RL_ERROR_TILE + (t % RL_ERROR_TILE), y = (tile / tiles_x) * RL_ERROR_TILE + (t / RL_ERROR_TILE);
-    double vse = 0.0, vy = 0.0;
-    if (x < width && y < height) {
-        const uint64_t p = (uint64_t)y * width + x;
-        const double s = sum_y[p], q = sum_q[p];
-        double d = q - (s * s) / n_total;
-        d = d < 0.0 ? 0.0 : d;
-        const double v = d * ratio;
-        const float se = rl_sqrtf((float)v);
-        se_out[p] = se;
-        vse = (double)se;
-        vy = fabs(s);
-    }
+// The two trees of a tile, for a workgroup of 256 threads of which thread t holds the pair (vse, vy) of tile raster index t: every
+// thread's pair goes to LDS (tree_se, tree_y: 256 doubles each); the strides 128 and 64 cross waves and are added from LDS between
+// barriers; wave 0 then holds v[0 .. 63] in registers, one per lane, and the strides 32 .. 1 are cross-lane moves (lane i reads lane
+// i + stride and adds it onto its own: the lanes below `stride` hold exactly v[i] + v[i + stride]; what the lanes above it hold is
+// never read again).  Same additions, same order, same bits as the stated tree.  Thread 0 writes the tile's pair; the waves 1 .. 3
+// leave at the second barrier, so the call is the last thing its kernel does.  Shared with rl_robust_estimate_kernel
+// (rl_robust.hip.h).
+__device__ __forceinline__ void rl_error_tile_trees(double* tree_se, double* tree_y, uint32_t t, uint32_t tile, double vse, double vy,
+                                                    double* __restrict__ tiles) {
     tree_se[t] = vse;
     tree_y[t] = vy;
     __syncthreads();
@@ -93,4 +76,30 @@ __global__ __launch_bounds__(RL_ERROR_TILE_PIXELS) void rl_error_estimate_kernel
         tiles[2 * (uint64_t)tile] = vse;
         tiles[2 * (uint64_t)tile + 1] = vy;
     }
+}
+
+// The estimate: one workgroup per tile, thread t on the tile's pixel (t % 16, t / 16), so t is the tile raster index of the tree.
+// A thread outside the image contributes +0.0 to both trees and writes nothing.  The trees are rl_error_tile_trees'.  LDS: the two
+// 256-double arrays, 4,096 bytes.  `ratio` is (double)N / (double)(k - 1), divided on the host.
+__global__ __launch_bounds__(RL_ERROR_TILE_PIXELS) void rl_error_estimate_kernel(const double* __restrict__ sum_y, const double* __restrict__ sum_q,
+                                                                                  uint32_t width, uint32_t height, uint32_t tiles_x, double n_total, double ratio,
+                                                                                  float* __restrict__ se_out, double* __restrict__ tiles) {
+    __shared__ double tree_se[RL_ERROR_TILE_PIXELS];
+    __shared__ double tree_y[RL_ERROR_TILE_PIXELS];
+    const uint32_t t = threadIdx.x;
+    const uint32_t tile = blockIdx.x; // tiles in raster order, one workgroup each
+    const uint32_t x = (tile % tiles_x) * RL_ERROR_TILE + (t % RL_ERROR_TILE), y = (tile / tiles_x) * RL_ERROR_TILE + (t / RL_ERROR_TILE);
+    double vse = 0.0, vy = 0.0;
+    if (x < width && y < height) {
+        const uint64_t p = (uint64_t)y * width + x;
+        const double s = sum_y[p], q = sum_q[p];
+        double d = q - (s * s) / n_total;
+        d = d < 0.0 ? 0.0 : d;
+        const double v = d * ratio;
+        const float se = rl_sqrtf((float)v);
+        se_out[p] = se;
+        vse = (double)se;
+        vy = fabs(s);
+    }
+    rl_error_tile_trees(tree_se, tree_y, t, tile, vse, vy, tiles);
 }

@@ -2,7 +2,9 @@
 // the unit, and their combination per pixel by a median of means whose trim follows the Gini coefficient of the M bucket means
 // (Buisine et al. 2021).  The arithmetic is the contract stated in include/robigo_luculenta.h: f64 in the stated order, no
 // contraction; add, multiply, the correctly rounded divide, comparisons and the f64 -> f32 conversion only, so the CPU restatement
-// (tests/_robust_oracle.py) is held bit for bit.  Included by rl_api.hip; needs nothing of the scene or the ray kernels.
+// (tests/_robust_oracle.py) is held bit for bit.  Included by rl_api.hip; needs nothing of the scene or the ray kernels.  The
+// estimate kernel at the end adds rl_sqrtf (rl_math.h) and the error unit's tile trees (rl_error.hip.h, included before this file);
+// its restatement is tests/_robust_error_oracle.py.
 #pragma once
 
 // The device layout: plane (j * 3 + c) -- component c of bucket j -- starts at double `(j * 3 + c) * stride`, stride = the pixel
@@ -120,4 +122,91 @@ __global__ __launch_bounds__(RL_ROBUST_LANES) void rl_robust_resolve_kernel(cons
         }
         trim[p] = (uint8_t)(c | (untrimmable ? 0x80u : 0u));
     }
+}
+
+// The estimate (rl_robust_unit_estimate): the standard error of the trimmed film's Y from the M bucket means -- the winsorized sum
+// of squares over K (K - 1), K = M - 2 c kept buckets -- per pixel and, through rl_error_tile_trees, per RL_ERROR_TILE tile in the
+// error unit's output format.  One 256-thread workgroup per tile, thread t on the tile's pixel (t % 16, t / 16) as in
+// rl_error_estimate_kernel.  Only the Y planes are read, a third of the resolve's traffic.  The keys of a thread sit in LDS as
+// key[j][t] and the rank permutation as bytes perm[r][t]: a thread touches its own column only, so there is nothing to conflict and,
+// until the trees, nothing to synchronise.  M * 256 * 9 bytes: 34,560 B at M = 15 (four workgroups per CU), 73,728 B at M = 32
+// (two); the 4 KB of the two trees reuse the first 512 doubles after a barrier (M >= 3: 6,912 B at least).  The ranking and the
+// trim are the resolve's forty lines once more, with the keys alone and the estimate's cap: shared code would have to leave
+// rl_robust_resolve_kernel instruction-identical, and its one-wave layout (a stride of 64, three means per bucket) differs in every
+// address.  No register is indexed dynamically: no scratch.  A thread outside the image skips the pixel and adds +0.0 to both trees.
+__global__ __launch_bounds__(RL_ERROR_TILE_PIXELS) void rl_robust_estimate_kernel(const double* __restrict__ sums, uint64_t stride, uint32_t width,
+                                                                                   uint32_t height, uint32_t tiles_x, uint32_t m_buckets,
+                                                                                   RlRobustCounts counts, double n_total, double gain, uint32_t cmax,
+                                                                                   float* __restrict__ se_out, double* __restrict__ tiles,
+                                                                                   uint8_t* __restrict__ trim) {
+    extern __shared__ double rl_robust_lds[];
+    const uint32_t t = threadIdx.x, M = m_buckets;
+    const uint32_t tile = blockIdx.x; // tiles in raster order, one workgroup each
+    const uint32_t x = (tile % tiles_x) * RL_ERROR_TILE + (t % RL_ERROR_TILE), y = (tile / tiles_x) * RL_ERROR_TILE + (t / RL_ERROR_TILE);
+    double* key = rl_robust_lds + t;                                                          // key[j * 256]
+    uint8_t* perm = (uint8_t*)(rl_robust_lds + (size_t)M * RL_ERROR_TILE_PIXELS) + t;         // perm[r * 256]
+    const double md = (double)M;
+    double vse = 0.0, vy = 0.0;
+    if (x < width && y < height) {
+        const uint64_t p = (uint64_t)y * width + x;
+        bool untrimmable = false;
+        for (uint32_t j = 0; j < M; ++j) {
+            const double k = sums[((uint64_t)j * 3 + 1) * stride + p] / counts.n[j];
+            key[(size_t)j * RL_ERROR_TILE_PIXELS] = k;
+            untrimmable = untrimmable || !(k >= 0.0) || k == (double)INFINITY; // not finite, or < 0
+        }
+        for (uint32_t j = 0; j < M; ++j) {
+            const double kj = key[(size_t)j * RL_ERROR_TILE_PIXELS];
+            uint32_t rank = 0;
+            for (uint32_t i = 0; i < M; ++i) {
+                const double ki = key[(size_t)i * RL_ERROR_TILE_PIXELS];
+                rank += (ki < kj || (ki == kj && i < j)) ? 1u : 0u;
+            }
+            perm[(size_t)(untrimmable ? j : rank) * RL_ERROR_TILE_PIXELS] = (uint8_t)j; // (an untrimmable pixel: bucket order)
+        }
+        uint32_t c = 0;
+        if (!untrimmable) {
+            double ts = 0.0, w = 0.0;
+            for (uint32_t r = 0; r < M; ++r) {
+                const double k = key[(size_t)perm[(size_t)r * RL_ERROR_TILE_PIXELS] * RL_ERROR_TILE_PIXELS];
+                ts = ts + k;
+                w = w + (double)(2 * (int)r - (int)M + 1) * k;
+            }
+            if (!(ts > 0.0)) {
+                untrimmable = true;
+            } else {
+                const double g = w / (md * ts);
+                const double v = ((gain * g) * md) * 0.5;
+                c = !(v >= 0.0) ? 0u : (v >= (double)cmax ? cmax : (uint32_t)v); // (0 <= v < cmax: the conversion truncates = floor)
+            }
+        }
+        const uint32_t K = M - 2 * c;
+        const double cd = (double)c;
+        const double lo = key[(size_t)perm[(size_t)c * RL_ERROR_TILE_PIXELS] * RL_ERROR_TILE_PIXELS];
+        const double hi = key[(size_t)perm[(size_t)(M - c - 1) * RL_ERROR_TILE_PIXELS] * RL_ERROR_TILE_PIXELS];
+        double a = 0.0;
+        for (uint32_t r = c; r < M - c; ++r) a = a + key[(size_t)perm[(size_t)r * RL_ERROR_TILE_PIXELS] * RL_ERROR_TILE_PIXELS];
+        double b = cd * lo + a;
+        b = b + cd * hi;
+        const double mw = b / md; // the winsorized mean
+        double d = 0.0;
+        for (uint32_t r = c; r < M - c; ++r) {
+            const double e = key[(size_t)perm[(size_t)r * RL_ERROR_TILE_PIXELS] * RL_ERROR_TILE_PIXELS] - mw;
+            d = d + e * e;
+        }
+        const double el = lo - mw;
+        d = d + cd * (el * el);
+        const double eh = hi - mw;
+        d = d + cd * (eh * eh);
+        const double var = d / (double)(K * (K - 1u));
+        const double f = (a / (double)K) * n_total;
+        const double v = (var * n_total) * n_total;
+        const float se = rl_sqrtf((float)v);
+        se_out[p] = se;
+        trim[p] = (uint8_t)(c | (untrimmable ? 0x80u : 0u));
+        vse = (double)se;
+        vy = fabs(f);
+    }
+    __syncthreads(); // every thread is done with its column: the trees take the first 4 KB
+    rl_error_tile_trees(rl_robust_lds, rl_robust_lds + RL_ERROR_TILE_PIXELS, t, tile, vse, vy, tiles);
 }
