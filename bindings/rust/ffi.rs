@@ -71,6 +71,8 @@ pub const RL_DENOISE_ITERATIONS: u32 = 5;
 pub const RL_DENOISE_MAX_ITERATIONS: u32 = 6;
 pub const RL_SPECTRAL_MAX_NODES: u32 = 401;
 pub const RL_ERROR_TILE: u32 = 16;
+pub const RL_RELIGHT_MAX_GROUPS: u32 = 16;
+pub const RL_RELIGHT_DROP: u8 = 0xff;
 pub const RL_ROBUST_NEXT: u32 = 0xffff_ffff;
 
 pub const RL_MAX_PIXELS: usize = 2147483647;
@@ -116,6 +118,7 @@ pub enum RlScene {} pub enum RlTraceUnit {} pub enum RlPlotUnit {} pub enum RlGa
 pub enum RlScheduler {} pub enum RlComm {} pub enum RlDenoiseUnit {} pub enum RlSpectralUnit {} pub enum RlErrorUnit {}
 pub enum RlAdaptiveUnit {}
 pub enum RlRobustUnit {}
+pub enum RlRelightUnit {}
 pub enum RlWavelengthTable {}
 #[repr(C)] #[derive(Copy, Clone)] pub struct RlWavelengthSampling {
     pub importance: *const f64, pub n_nodes: u32, pub reserved: u32, pub uniform_share: f64,
@@ -257,6 +260,17 @@ extern "C" {
     pub fn rl_spectral_unit_upload(unit: *mut RlSpectralUnit, input: *const f32) -> c_int;
     pub fn rl_spectral_unit_project(unit: *mut RlSpectralUnit, matrix: *const f32, dst: *mut RlGatherUnit) -> c_int;
     pub fn rl_spectral_observer_cie1931(n_nodes: u32, out: *mut f32) -> c_int;
+    pub fn rl_relight_unit_create(device: c_int, width: u32, height: u32, n_nodes: u32, n_groups: u32, out: *mut *mut RlRelightUnit) -> c_int;
+    pub fn rl_relight_unit_destroy(unit: *mut RlRelightUnit) -> c_int;
+    pub fn rl_relight_unit_clear(unit: *mut RlRelightUnit) -> c_int;
+    pub fn rl_relight_unit_set_groups(unit: *mut RlRelightUnit, groups: *const u8, n_objects: u32) -> c_int;
+    pub fn rl_relight_unit_plot_results(unit: *mut RlRelightUnit, samples: *const RlCameraSample, results: *const RlPathResult, n: u64) -> c_int;
+    pub fn rl_relight_unit_plot_results_device(unit: *mut RlRelightUnit, device_samples: *const RlCameraSample, device_results: *const RlPathResult, n: u64) -> c_int;
+    pub fn rl_relight_unit_render(unit: *mut RlRelightUnit, scene: *const RlScene, primitive_fetch: c_int, seed: u64, stream: u32, first_path_index: u64, n_paths: u64, max_segments: u32) -> c_int;
+    pub fn rl_relight_unit_download(unit: *mut RlRelightUnit, out: *mut f32) -> c_int;
+    pub fn rl_relight_unit_upload(unit: *mut RlRelightUnit, input: *const f32) -> c_int;
+    pub fn rl_relight_unit_mix(unit: *mut RlRelightUnit, gains: *const f32, matrix: *const f32, dst: *mut RlGatherUnit) -> c_int;
+    pub fn rl_relight_gains_black_body(n_nodes: u32, kelvins_from: f32, intensity_from: f32, kelvins_to: f32, intensity_to: f32, out: *mut f32) -> c_int;
 
     // The noise estimate: f64 sums of Y and Y^2 / n over the plot buffers shown to the unit; the standard error per pixel and tile.
     pub fn rl_error_unit_create(device: c_int, width: u32, height: u32, out: *mut *mut RlErrorUnit) -> c_int;

@@ -119,6 +119,7 @@ typedef struct RlGatherUnit RlGatherUnit;
 typedef struct RlTonemapUnit RlTonemapUnit;
 typedef struct RlDenoiseUnit RlDenoiseUnit;
 typedef struct RlSpectralUnit RlSpectralUnit;
+typedef struct RlRelightUnit RlRelightUnit;
 typedef struct RlErrorUnit RlErrorUnit;
 typedef struct RlRobustUnit RlRobustUnit;
 typedef struct RlAdaptiveUnit RlAdaptiveUnit;
@@ -993,6 +994,78 @@ int rl_spectral_unit_download(RlSpectralUnit* unit, float* out);
 int rl_spectral_unit_upload(RlSpectralUnit* unit, const float* in);
 int rl_spectral_unit_project(RlSpectralUnit* unit, const float* matrix, RlGatherUnit* dst);
 int rl_spectral_observer_cie1931(uint32_t n_nodes, float* out);
+
+/* ---- relight film: photons kept by wavelength and by light, re-mixed without a re-trace (rl_relight_unit_*) ---- */
+
+#define RL_RELIGHT_MAX_GROUPS 16
+#define RL_RELIGHT_DROP 0xff
+
+/* A relight unit is a film of n_groups * n_nodes planes of width x height floats: n_groups spectral cubes, one per group of
+ * lights.  Plane q = g * n_nodes + b holds node b of group g (group-major, then node-major: part of the ABI of download and
+ * upload).  The node model is the spectral film's: spacing = 400.0f / (float)(n_nodes - 1), node b at 380.0f + (float)b * spacing.
+ *   Why it is exact.  render_ray multiplies the emission in as the last factor of a path's value (trace_unit.rs:99-101): geometry,
+ *   bounces and roulette never see it, and RlPathResult::object names the emitter.  So another temperature or intensity of a black
+ *   body changes the value of a finished path that ended on it by get_intensity'(wavelength) / get_intensity(wavelength)
+ *   (material.rs:92-104) and nothing else.  Keep the photons by emitter, and a light is dimmed, warmed or shown alone by a gain per
+ *   (group, node) applied in the mix: rl_relight_gains_black_body gives that ratio at the nodes.  What is not exact is the node
+ *   model: the gain is interpolated linearly between nodes, as the observer is.
+ *   rl_relight_unit_create.  Checked in this order before any device work, each failure RL_E_INVALID with a message: a NULL `out`;
+ *   a zero width or height; n_nodes outside 2 .. RL_SPECTRAL_MAX_NODES; n_groups outside 1 .. RL_RELIGHT_MAX_GROUPS;
+ *   width * height * n_nodes * n_groups > RL_MAX_PIXELS (computed in 64 bits).  The film is zeroed.  rl_relight_unit_clear zeroes
+ *   it again (queued on the unit; everything below is ordered after it).
+ *   rl_relight_unit_set_groups.  groups[o] is the group of object o of the scene's description, n_objects entries: each below
+ *   n_groups, or RL_RELIGHT_DROP (paths that end on that object are left out).  Any other entry is RL_E_INVALID and the unit keeps
+ *   the table it had; so is a NULL unit or table and n_objects == 0.  A unit starts without a table, and the calls that need one
+ *   return RL_E_STATE until it has one.  The call returns when the table is on the device.
+ *   The routed splat (rl_relight_unit_plot_results / _device) of sample i with result r = results[i].  All f32, in this order, never
+ *   contracted.  Skipped if r.value == 0; if samples[i].x or .y is NaN or infinite; if samples[i].ray.wavelength is NaN or
+ *   infinite; if r.object >= n_objects (RL_OBJECT_NONE is such a value); if groups[r.object] == RL_RELIGHT_DROP.  Otherwise it is
+ *   rl_spectral_unit_plot_photons' splat of the photon {x, y, r.value, wavelength} -- the same f, fl, r, lo, hi, the same decisions
+ *   on fl as a float, the same four weights, at most eight f32 atomics -- into the cube of group g = groups[r.object]: plane
+ *   g * n_nodes + node.  No content of the buffers makes the kernel touch memory outside the film.  r.end and r.segments are not read.
+ *   Checked in this order before any device work: a NULL unit, or NULL samples or results with n > 0 (RL_E_INVALID); a unit without
+ *   a table (RL_E_STATE).  n = 0 then does nothing and launches nothing.  The host form stages in chunks of 2^20 records, the
+ *   _device form takes device pointers on the unit's device and refuses pageable host memory (RL_E_INVALID), as
+ *   rl_scene_render_rays_device does.  The splats are in the film on return.
+ *   rl_relight_unit_render.  Paths first_path_index .. first_path_index + n_paths - 1 of RNG stream `stream` under `seed`, in chunks
+ *   of at most 2^20 in scratch the unit owns (taken at the first such call): rl_scene_camera_rays_device's samples of those indices
+ *   for the unit's width x height; their rays traced by the path kernel as rl_scene_render_rays_device traces them (the same
+ *   launch, the same results bit for bit); the routed splat.  Checked in this order: a NULL unit, a NULL scene, an unknown fetch
+ *   mode, max_segments > RL_PATH_MAX_SEGMENTS_CAP (RL_E_INVALID); a unit without a table (RL_E_STATE); path indices that reach
+ *   2^64 - 1 (RL_E_INVALID); a table whose n_objects is not the scene's object count, or unit and scene on different devices
+ *   (RL_E_STATE).  n_paths = 0 then does nothing.  The call orders against open launches as rl_scene_render_rays does and returns
+ *   when the splats are in the film.
+ *   rl_relight_unit_download / _upload move the whole film, n_groups * n_nodes * width * height floats, planes in the order above,
+ *   each plane rows of `width`.
+ *   rl_relight_unit_mix.  gains is host memory, n_groups x n_nodes floats (NULL: all 1); matrix is host memory, n_nodes x 3 floats,
+ *   an observer as rl_spectral_unit_project takes it.  The host forms c[3 q + k] = gains[q] * matrix[3 b + k] for q = g * n_nodes + b,
+ *   one f32 multiply (gains == NULL: matrix[3 b + k] itself).  Per pixel p and component k the device computes acc = 0.0f; for
+ *   q = 0 .. n_groups * n_nodes - 1 in order acc = acc + c[3 q + k] * film[q * n_pixels + p], multiply and add separate, no special
+ *   case for non-finite values.  dst's tristimulus buffer gets acc and its compensation buffer is all +0; the film is left as it
+ *   was.  This is rl_spectral_unit_project's arithmetic on the composed matrix.  A NULL unit, matrix or dst is RL_E_INVALID; a dst
+ *   of another size or device is RL_E_STATE, and nothing is written.  Ordering is rl_spectral_unit_project's.
+ *   rl_relight_gains_black_body(n_nodes, kelvins_from, intensity_from, kelvins_to, intensity_to, out) writes n_nodes floats:
+ *   out[b] = I_to(l_b) / I_from(l_b), l_b node b's wavelength, I(l) = (float)rl_boltzmann((double)l, (double)kelvins) *
+ *   rl_black_body_normalisation(kelvins, intensity) -- the library's get_intensity -- and the divide in f32; a node whose I_from is 0
+ *   gets gain 0 (that light deposited nothing there).  Host arithmetic only: callable without a GPU.  A NULL `out`, an n_nodes
+ *   outside 2 .. RL_SPECTRAL_MAX_NODES, or a kelvins or intensity that is not finite and greater than 0 is RL_E_INVALID.
+ *   Determinism.  The film differs between runs only by the order of its atomics, as the spectral film does; the mix is exact given
+ *   the film: the same bits on every run, and the bits of the CPU restatement tests/_relight_oracle.py.
+ *   One user per relight unit at a time. */
+int rl_relight_unit_create(int device, uint32_t width, uint32_t height, uint32_t n_nodes, uint32_t n_groups, RlRelightUnit** out);
+int rl_relight_unit_destroy(RlRelightUnit* unit);
+int rl_relight_unit_clear(RlRelightUnit* unit);
+int rl_relight_unit_set_groups(RlRelightUnit* unit, const uint8_t* groups, uint32_t n_objects);
+int rl_relight_unit_plot_results(RlRelightUnit* unit, const RlCameraSample* samples, const RlPathResult* results, uint64_t n);
+int rl_relight_unit_plot_results_device(RlRelightUnit* unit, const RlCameraSample* device_samples, const RlPathResult* device_results,
+                                        uint64_t n);
+int rl_relight_unit_render(RlRelightUnit* unit, const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream,
+                           uint64_t first_path_index, uint64_t n_paths, uint32_t max_segments);
+int rl_relight_unit_download(RlRelightUnit* unit, float* out);
+int rl_relight_unit_upload(RlRelightUnit* unit, const float* in);
+int rl_relight_unit_mix(RlRelightUnit* unit, const float* gains, const float* matrix, RlGatherUnit* dst);
+int rl_relight_gains_black_body(uint32_t n_nodes, float kelvins_from, float intensity_from, float kelvins_to, float intensity_to,
+                                float* out);
 
 /* ---- noise estimate: the standard error of the accumulated luminance (rl_error_unit_*) ---- */
 

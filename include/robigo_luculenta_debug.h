@@ -89,6 +89,15 @@ int rl_debug_spectral_launches(uint64_t out[2]);
  * (rl_spectral_unit_plot, _plot_photons, _plot_photons_device), out[1] the projection launch of its last completed
  * rl_spectral_unit_project; 0 before the first.  tools/spectral_bench.py. */
 int rl_debug_spectral_ms(RlSpectralUnit* unit, float out[2]);
+/* out[0]: launches of rl_relight_splat_kernel (one per chunk of rl_relight_unit_plot_results and of rl_relight_unit_render, one per
+ * rl_relight_unit_plot_results_device), out[1]: path kernel launches made by rl_relight_unit_render (one per chunk; counted in
+ * rl_debug_path_launches too), out[2]: launches of the mix (rl_spectral_project_kernel on the composed matrix, one per
+ * rl_relight_unit_mix; not counted in rl_debug_spectral_launches), since the library was loaded. */
+int rl_debug_relight_launches(uint64_t out[3]);
+/* Device time in milliseconds, from events around the launch: out[0] the last splat launch of the unit's last completed splat or
+ * render call, out[1] the path launch of the last chunk of its last completed rl_relight_unit_render, out[2] the mix launch of
+ * its last completed rl_relight_unit_mix; 0 before the first.  tools/relight_bench.py. */
+int rl_debug_relight_ms(RlRelightUnit* unit, float out[3]);
 /* out[0]: launches of rl_error_observe_kernel (one per rl_error_unit_observe), out[1]: launches of rl_error_estimate_kernel (one per
  * rl_error_unit_estimate) since the library was loaded. */
 int rl_debug_error_launches(uint64_t out[2]);

@@ -15,7 +15,8 @@ from ._lib import (RlAppConfig, RlAppStats, RlCameraDesc, RlCameraSample, RlErro
                    RL_LIGHT_VISIBLE, RlFeatureSample, RlFeatureStats, RL_FEATURE_VOID, RL_FEATURE_EMITTER, RL_FEATURE_DIFFUSE, RL_FEATURE_LIMIT,
                    RL_FEATURE_MAX_SEGMENTS, RlDenoiseParams, RL_DENOISE_ITERATIONS, RL_DENOISE_MAX_ITERATIONS,
                    RL_SPECTRAL_MAX_NODES, RlErrorStats, RlErrorTarget, RlAppErrorStats, RL_ERROR_TILE, RlAdaptiveStats,
-                   RlWavelengthSampling, RlRobustParams, RlRobustStats, RL_ROBUST_MAX_BUCKETS, RL_ROBUST_NEXT)
+                   RlWavelengthSampling, RlRobustParams, RlRobustStats, RL_ROBUST_MAX_BUCKETS, RL_ROBUST_NEXT,
+                   RL_RELIGHT_MAX_GROUPS, RL_RELIGHT_DROP)
 
 PHOTON_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("probability", "<f4"), ("wavelength", "<f4")])
 OBJECT_DTYPE = np.dtype([("surface_kind", "<u4"), ("material_kind", "<u4"), ("v0", "<f4", 3), ("v1", "<f4", 3),
@@ -893,6 +894,97 @@ class SpectralUnit(_Handle):
         return tuple(out)
 
 
+MATERIAL_BLACK_BODY = 0  # RL_MATERIAL_BLACK_BODY: kelvins = m[0], intensity = m[1]
+
+
+def relight_gains_black_body(n_nodes, kelvins_from, intensity_from, kelvins_to, intensity_to):
+    """rl_relight_gains_black_body: (n_nodes,) float32, what a finished path that ended on a black body of (kelvins_from,
+    intensity_from) is multiplied by when that light becomes (kelvins_to, intensity_to), at each node's wavelength.  Host
+    arithmetic: needs no device."""
+    out = np.zeros(max(int(n_nodes), 0), dtype=np.float32)
+    check(lib.rl_relight_gains_black_body(n_nodes, kelvins_from, intensity_from, kelvins_to, intensity_to, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def relight_groups(objects, n_groups):
+    """The table RelightUnit.set_groups takes for an OBJECT_DTYPE array: black bodies get groups 0, 1, ... in scan order, those
+    beyond n_groups - 1 share the last group; every other object gets RL_RELIGHT_DROP.  (objects,) uint8."""
+    if not 1 <= n_groups <= RL_RELIGHT_MAX_GROUPS:
+        raise ValueError("n_groups must be 1 .. RL_RELIGHT_MAX_GROUPS = %d" % RL_RELIGHT_MAX_GROUPS)
+    lights = np.asarray(objects)["material_kind"] == MATERIAL_BLACK_BODY
+    table = np.full(len(lights), RL_RELIGHT_DROP, dtype=np.uint8)
+    table[lights] = np.minimum(np.arange(int(lights.sum())), n_groups - 1)
+    return table
+
+
+class RelightUnit(_Handle):
+    """A film that keeps photons by wavelength and by light: n_groups cubes of n_nodes planes of width x height floats
+    (rl_relight_unit_*), filled by a routed splat of traced camera samples and mixed into a gather unit under per-(group, node)
+    gains and any (n_nodes, 3) observer, without a re-trace."""
+    _destroy = lib.rl_relight_unit_destroy
+
+    def __init__(self, width, height, n_nodes=81, n_groups=1, device=0):
+        super().__init__()
+        check(lib.rl_relight_unit_create(device, width, height, n_nodes, n_groups, C.byref(self._h)))
+        self.width, self.height, self.n_nodes, self.n_groups, self.device = width, height, n_nodes, n_groups, device
+
+    def set_groups(self, groups):
+        """rl_relight_unit_set_groups: one byte per object of the scene's description, a group below n_groups or RL_RELIGHT_DROP
+        (relight_groups makes one)."""
+        groups = np.ascontiguousarray(groups, dtype=np.uint8)
+        check(lib.rl_relight_unit_set_groups(self._h, groups.ctypes.data_as(C.c_void_p), len(groups)))
+
+    def plot_results(self, samples, results):
+        """(n,) CAMERA_SAMPLE_DTYPE and (n,) PATH_RESULT_DTYPE arrays of the caller's (rl_relight_unit_plot_results), or two device
+        buffers on the unit's device with data_ptr() (e.g. torch tensors; rl_relight_unit_plot_results_device: as many records as
+        `samples` holds whole, `results` with room for as many): each path's value goes into the cube of the light it ended on,
+        complete on return."""
+        if hasattr(samples, "data_ptr"):
+            n = _record_count(samples, CAMERA_SAMPLE_DTYPE, "samples must hold whole 48-byte records and results as many 16-byte ones",
+                              (results, PATH_RESULT_DTYPE.itemsize))
+            check(lib.rl_relight_unit_plot_results_device(self._h, C.c_void_p(samples.data_ptr()), C.c_void_p(results.data_ptr()), n))
+            return
+        samples = np.ascontiguousarray(samples, dtype=CAMERA_SAMPLE_DTYPE)
+        results = np.ascontiguousarray(results, dtype=PATH_RESULT_DTYPE)
+        if len(samples) != len(results):
+            raise ValueError("samples and results differ in length")
+        check(lib.rl_relight_unit_plot_results(self._h, samples.ctypes.data_as(C.c_void_p), results.ctypes.data_as(C.c_void_p), len(samples)))
+
+    def render(self, scene, seed, stream, first, n_paths, fetch=FETCH_LDS, max_segments=0):
+        """rl_relight_unit_render: paths first .. first + n_paths - 1 of (seed, stream) -- camera samples, the path kernel, the
+        routed splat -- in the film on return."""
+        check(lib.rl_relight_unit_render(self._h, scene.handle, fetch, seed, stream, first, n_paths, max_segments))
+
+    def clear(self):
+        check(lib.rl_relight_unit_clear(self._h))
+
+    def download(self):
+        """The film: (n_groups, n_nodes, height, width) float32."""
+        out = np.zeros((self.n_groups, self.n_nodes, self.height, self.width), dtype=np.float32)
+        check(lib.rl_relight_unit_download(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def upload(self, film):
+        film = np.ascontiguousarray(film, dtype=np.float32).reshape(self.n_groups, self.n_nodes, self.height, self.width)
+        check(lib.rl_relight_unit_upload(self._h, film.ctypes.data_as(C.c_void_p)))
+
+    def mix(self, gains, matrix, dst):
+        """rl_relight_unit_mix: gather unit `dst` = the cubes under the (n_groups, n_nodes) `gains` (None: all 1) and the
+        (n_nodes, 3) `matrix`, complete on return; its compensation buffer is zeroed, the film is left as it was.  Returns dst."""
+        matrix = np.ascontiguousarray(matrix, dtype=np.float32).reshape(self.n_nodes, 3)
+        if gains is not None:
+            gains = np.ascontiguousarray(gains, dtype=np.float32).reshape(self.n_groups, self.n_nodes)
+        check(lib.rl_relight_unit_mix(self._h, _host_ptr(gains), matrix.ctypes.data_as(C.c_void_p), dst.handle))
+        return dst
+
+    def launch_ms(self):
+        """Device milliseconds of (the last splat launch, the last render's last path launch, the last mix launch) of this unit
+        (rl_debug_relight_ms)."""
+        out = (C.c_float * 3)()
+        check(lib.rl_debug_relight_ms(self._h, out))
+        return tuple(out)
+
+
 def _error_stats(stats):
     return {name: getattr(stats, name) for name, _ in RlErrorStats._fields_}
 
@@ -1367,6 +1459,12 @@ def spectral_launches():
     """(launches of the spectral film's splat kernel, launches of its projection kernel) since the library was loaded
     (rl_debug_spectral_launches)."""
     return _launch_counters(lib.rl_debug_spectral_launches, 2, tuple)
+
+
+def relight_launches():
+    """(launches of the relight film's routed splat kernel, path kernel launches of RelightUnit.render, launches of its mix) since
+    the library was loaded (rl_debug_relight_launches)."""
+    return _launch_counters(lib.rl_debug_relight_launches, 3, tuple)
 
 
 def gather_accumulate_ms(gather, plot_unit):

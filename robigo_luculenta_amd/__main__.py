@@ -6,6 +6,8 @@ With --denoise PATH as well the image is filtered over those guides on the devic
 With --denoise-variance as well the filter's colour term is the noise estimate's variance (DenoiseUnit.denoise_variance): it backs off
 as the image converges, which the plain filter does not.
 With --spectral PATH the same paths are rendered once more into a spectral film (SpectralUnit) and the cube is saved as PATH (.npy).
+With --relight PATH the same paths are rendered once more into a relight film (RelightUnit), one cube per light, saved as PATH (.npy);
+with --light G:KELVINS[:INTENSITY] as well light G is re-balanced in the mix and the relit image written beside the cubes, without a re-trace.
 With --target-error E the run ends once the estimated relative error of the image (rl_app_run_to_error) is at most E; --batches stays
 the cap.  With --error-map PATH the per-tile relative error of the last estimate is written as a grey image.
 With --adaptive as well the batches are rendered over the unit API by render_adaptive_to_error: from --min-observations on, every batch's
@@ -62,6 +64,13 @@ def parse_args(argv=None):
                          "float32 (nodes, height, width), to PATH with numpy.save (*.npy)")
     ap.add_argument("--spectral-nodes", metavar="K", type=int, default=81,
                     help="with --spectral: nodes from 380 to 780 nm (default 81, the CIE table's own)")
+    ap.add_argument("--relight", metavar="PATH", default=None,
+                    help="after the image, render the same paths into a relight film (RelightUnit.render): one cube of --spectral-nodes "
+                         "nodes per black body of the scene (relight_groups; at most 16), saved as float32 (groups, nodes, height, width) "
+                         "to PATH with numpy.save (*.npy)")
+    ap.add_argument("--light", metavar="G:KELVINS[:INTENSITY]", action="append", default=None,
+                    help="with --relight, repeatable: give the light of group G another temperature (and intensity; default: the scene's) "
+                         "and write the mix under the CIE observer, tonemapped, to PATH with its suffix replaced by .png")
     ap.add_argument("--target-error", metavar="E", type=float, default=None,
                     help="end the run once the estimated relative error of the image, sum of the pixels' standard errors over the sum "
                          "of their luminance, is at most E (looked at every %d ms); --batches stays the cap" % TARGET_TONEMAP_INTERVAL_MS)
@@ -171,6 +180,25 @@ def parse_args(argv=None):
             ap.error("%s cannot be combined with --direct: the estimate is made by the App worker pool" % flag)
     if a.spectral is not None and a.direct:
         ap.error("--spectral cannot be combined with --direct: the direct renderer writes no photons")
+    if a.light is not None and a.relight is None:
+        ap.error("--light needs --relight PATH")
+    if a.relight is not None:
+        for given, flag in ((a.direct, "--direct"), (a.adaptive, "--adaptive"), (a.robust is not None, "--robust"),
+                            (a.wavelength_importance is not None, "--wavelength-importance")):
+            if given:
+                ap.error("--relight cannot be combined with %s: the relight film re-renders the camera paths of the plain image" % flag)
+        lights = []
+        for text in a.light or []:
+            parts = text.split(":")
+            try:
+                group, kelvins = int(parts[0]), float(parts[1])
+                intensity = float(parts[2]) if len(parts) == 3 else None
+                if len(parts) not in (2, 3) or group < 0 or not 0 < kelvins < float("inf") or (intensity is not None and not 0 < intensity < float("inf")):
+                    raise ValueError(text)
+            except (ValueError, IndexError):
+                ap.error("--light takes G:KELVINS[:INTENSITY], G >= 0 and the numbers finite and greater than 0, not %r" % text)
+            lights.append((group, kelvins, intensity))
+        a.light = lights
     if a.denoise is not None and a.features is None:
         ap.error("--denoise needs --features: the filter is guided by the albedo, normal and depth films")
     if a.denoise_variance:
@@ -375,6 +403,42 @@ def render_spectral(a):
     return cube
 
 
+def render_relight(a):
+    """--relight PATH: the batches x photons_per_batch paths of stream 0 once more by RelightUnit.render, one group per black body
+    (relight_groups), and the cubes saved with numpy.save; with --light the mix under those gains and the CIE observer, tonemapped,
+    beside them.  Returns the cubes, float32 (groups, nodes, height, width)."""
+    import numpy as np
+    from . import (MATERIAL_BLACK_BODY, RL_RELIGHT_MAX_GROUPS, GatherUnit, RelightUnit, Scene, TonemapUnit, builtin_scene_desc,
+                   relight_gains_black_body, relight_groups, spectral_observer_cie1931)
+    objs, cam = builtin_scene_desc(SCENE_DEMO if a.scene == "demo" else SCENE_GLASS_STRESS)
+    scene = Scene(objs, cam, device=a.device)
+    lights = np.nonzero(objs["material_kind"] == MATERIAL_BLACK_BODY)[0]
+    n_groups = max(1, min(len(lights), RL_RELIGHT_MAX_GROUPS))
+    table = relight_groups(objs, n_groups)
+    for group, _, _ in a.light:
+        if group >= n_groups or not (table == group).any():
+            raise SystemExit("--light %d: the scene's lights make groups 0 .. %d" % (group, min(len(lights), n_groups) - 1))
+    film = RelightUnit(a.width, a.height, a.spectral_nodes, n_groups, device=a.device)
+    film.set_groups(table)
+    total = a.batches * a.photons_per_batch
+    film.render(scene, a.seed, 0, 0, total)
+    cubes = film.download()
+    with open(a.relight, "wb") as f:      # (numpy.save would append .npy to a name that lacks it)
+        np.save(f, cubes)
+    print("relight film: %d groups of %d nodes, %d paths; wrote %s" % (n_groups, a.spectral_nodes, total, a.relight))
+    if a.light:
+        gains = np.ones((n_groups, a.spectral_nodes), np.float32)
+        for group, kelvins, intensity in a.light:
+            m = objs["m"][np.nonzero(table == group)[0][0]]     # (the first light of the group: its own kelvins and intensity)
+            gains[group] = relight_gains_black_body(a.spectral_nodes, float(m[0]), float(m[1]), kelvins, float(m[1]) if intensity is None else intensity)
+        gather, tonemap = GatherUnit(a.width, a.height, device=a.device), TonemapUnit(a.width, a.height, device=a.device)
+        tonemap.tonemap(film.mix(gains, spectral_observer_cie1931(a.spectral_nodes), gather))
+        path = os.path.splitext(a.relight)[0] + ".png"
+        write_image(path, tonemap.rgb_buffer, a.width, a.height)
+        print("relit: %s; wrote %s" % (", ".join("group %d at %g K" % (g, k) for g, k, _ in a.light), path))
+    return cubes
+
+
 def report_error(a, st, err):
     """The estimate's line, and --error-map: per tile rel = t_se / max(t_y, mean t_y) (error_tile_rel), grey = rel over the worst
     tile's, every pixel of a tile alike."""
@@ -510,6 +574,8 @@ def main(argv=None):
             denoise(a, image, guides, error)
     if a.spectral is not None:
         render_spectral(a)
+    if a.relight is not None:
+        render_relight(a)
     if scratch:
         scratch.cleanup()
 

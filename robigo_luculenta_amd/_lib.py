@@ -118,6 +118,8 @@ class RlDenoiseParams(C.Structure):
 
 
 RL_SPECTRAL_MAX_NODES = 401
+RL_RELIGHT_MAX_GROUPS = 16
+RL_RELIGHT_DROP = 0xFF
 RL_ERROR_TILE = 16
 
 
@@ -274,6 +276,17 @@ SIGNATURES = {
     "rl_spectral_unit_upload": (_i, [_vp, _vp]),
     "rl_spectral_unit_project": (_i, [_vp, _vp, _vp]),
     "rl_spectral_observer_cie1931": (_i, [_u32, _vp]),
+    "rl_relight_unit_create": (_i, [_i, _u32, _u32, _u32, _u32, _pp]),
+    "rl_relight_unit_destroy": (_i, [_vp]),
+    "rl_relight_unit_clear": (_i, [_vp]),
+    "rl_relight_unit_set_groups": (_i, [_vp, _u8p, _u32]),
+    "rl_relight_unit_plot_results": (_i, [_vp, _vp, _vp, _u64]),
+    "rl_relight_unit_plot_results_device": (_i, [_vp, _vp, _vp, _u64]),
+    "rl_relight_unit_render": (_i, [_vp, _vp, _i, _u64, _u32, _u64, _u64, _u32]),
+    "rl_relight_unit_download": (_i, [_vp, _vp]),
+    "rl_relight_unit_upload": (_i, [_vp, _vp]),
+    "rl_relight_unit_mix": (_i, [_vp, _vp, _vp, _vp]),
+    "rl_relight_gains_black_body": (_i, [_u32, _f, _f, _f, _f, _vp]),
     "rl_error_unit_create": (_i, [_i, _u32, _u32, _pp]),
     "rl_error_unit_destroy": (_i, [_vp]),
     "rl_error_unit_clear": (_i, [_vp]),
@@ -344,6 +357,8 @@ DEBUG_SIGNATURES = {
     "rl_debug_denoise_variance_ms": (_i, [_vp, C.POINTER(C.c_float)]),
     "rl_debug_spectral_launches": (_i, [_vp]),
     "rl_debug_spectral_ms": (_i, [_vp, _vp]),
+    "rl_debug_relight_launches": (_i, [_vp]),
+    "rl_debug_relight_ms": (_i, [_vp, _vp]),
     "rl_debug_error_launches": (_i, [_vp]),
     "rl_debug_error_ms": (_i, [_vp, _vp]),
     "rl_debug_robust_launches": (_i, [_vp]),

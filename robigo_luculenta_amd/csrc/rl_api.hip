@@ -57,6 +57,7 @@
 #include "rl_features.hip.h"
 #include "rl_denoise.hip.h"
 #include "rl_spectral.hip.h"
+#include "rl_relight.hip.h"
 #include "rl_error.hip.h"
 #include "rl_robust.hip.h"
 #include "rl_adaptive.hip.h"
@@ -121,6 +122,7 @@ const char* unit_name(const RlGatherUnit*) { return "gather unit"; }
 const char* unit_name(const RlTonemapUnit*) { return "tonemap unit"; }
 const char* unit_name(const RlDenoiseUnit*) { return "denoise unit"; }
 const char* unit_name(const RlSpectralUnit*) { return "spectral unit"; }
+const char* unit_name(const RlRelightUnit*) { return "relight unit"; }
 const char* unit_name(const RlErrorUnit*) { return "error unit"; }
 const char* unit_name(const RlRobustUnit*) { return "robust unit"; }
 const char* unit_name(const RlAdaptiveUnit*) { return "adaptive unit"; }
@@ -482,6 +484,26 @@ struct RlSpectralUnit {
     Ledger ledger;
 };
 
+struct RlRelightUnit {
+    int device;
+    uint32_t width, height, n_nodes, n_groups;
+    uint32_t n_objects;     // of the table on the device; 0: no table yet (rl_relight_unit_set_groups)
+    float spacing;          // 400.0f / (float)(n_nodes - 1), the spectral film's
+    float* film;            // n_groups * n_nodes planes of width x height floats: plane g * n_nodes + b
+    float* matrix;          // the composed (n_groups * n_nodes) x 3 matrix of the mix in flight
+    uint8_t* groups;        // the table: one byte per object, room for groups_room of them
+    uint32_t groups_room;
+    // rl_relight_unit_render's scratch, taken at the first such call (null before it): RL_QUERY_CHUNK records each
+    RlCameraSample* samples;
+    RlSpectralRay* rays;
+    RlPathResult* results;
+    hipStream_t stream;     // clears, splats and renders; every splat and render call returns with it drained
+    hipEvent_t ready;       // recorded on `stream` when a mix takes the film
+    EventPair timed[3];     // around the last splat launch, the last path launch of a render and the last mix launch (rl_debug_relight_ms)
+    bool timed_done[3];     // ... of a call that completed
+    Ledger ledger;
+};
+
 struct RlErrorUnit {
     int device;
     uint32_t width, height, tiles_x, tiles_y;
@@ -548,6 +570,11 @@ static_assert(offsetof(RlRobustUnit, width) == 4 && offsetof(RlRobustUnit, heigh
                   offsetof(RlPlotUnit, width) == 8 && offsetof(RlPlotUnit, height) == 12 && offsetof(RlGatherUnit, width) == 4 &&
                   offsetof(RlGatherUnit, height) == 8,
               "tests/test_robust_abi.py: test_a_stand_in_handle_is_checked_in_the_stated_order");
+
+// tests/test_relight_abi.py does the same for a relight unit.
+static_assert(offsetof(RlRelightUnit, width) == 4 && offsetof(RlRelightUnit, height) == 8 && offsetof(RlRelightUnit, n_nodes) == 12 &&
+                  offsetof(RlRelightUnit, n_groups) == 16 && offsetof(RlRelightUnit, n_objects) == 20,
+              "tests/test_relight_abi.py: test_a_stand_in_handle_is_checked_in_the_stated_order");
 
 // One rank of an RCCL communicator (rl_comm_*).
 struct RlComm {
@@ -3214,6 +3241,240 @@ int rl_spectral_observer_cie1931(uint32_t n_nodes, float* out) {
     return RL_OK;
 }
 
+// ---- RelightUnit (rl_relight.hip.h) ----------------------------------------------------------------
+
+namespace {
+std::atomic<uint64_t> g_relight_launches[3]; // rl_debug_relight_launches: splat launches, path launches, mix launches
+
+size_t relight_planes(const RlRelightUnit* u) { return (size_t)u->n_groups * u->n_nodes; }
+size_t relight_film_bytes(const RlRelightUnit* u) { return (size_t)u->width * u->height * relight_planes(u) * sizeof(float); }
+
+// The routed splat for device arrays samples, results [0, n) (n > 0; the unit has a table) on `stream`.
+int launch_relight_splat(RlRelightUnit* u, hipStream_t stream, int cus, const RlCameraSample* samples, const RlPathResult* results, uint64_t n) {
+    const float aspect = (float)u->width / (float)u->height; // plot_unit.rs:48, as launch_spectral_photons has it
+    u->timed_done[0] = false; // readable again once the call has completed (relight_drained)
+    return timed_launch(u->timed[0], stream, &g_relight_launches[0], [&] {
+        hipLaunchKernelGGL(rl_relight_splat_kernel, dim3(grid_for(n, cus)), dim3(RL_BLOCK), 0, stream, samples, results, n, (const uint8_t*)u->groups,
+                           u->n_objects, u->width, u->height, u->n_nodes, u->n_groups, u->spacing, aspect, u->film);
+    });
+}
+
+// As spectral_drained: a splat or render call queues everything on the unit's stream, which has drained when the call returns.
+int relight_drained(RlRelightUnit* u, int rc) {
+    if ((rc = drained(u->stream, rc)) == RL_OK) u->timed_done[0] = true;
+    return rc;
+}
+
+// What the two forms of rl_relight_unit_plot_results check before any device work, in the header's order.
+int relight_results_check(const RlRelightUnit* u, const void* samples, const void* results, uint64_t n) {
+    if (!u) return fail(RL_E_INVALID, "null relight unit");
+    if (n > 0 && (!samples || !results)) return fail(RL_E_INVALID, "null sample or result buffer");
+    if (u->n_objects == 0u) return fail(RL_E_STATE, "the relight unit has no table: call rl_relight_unit_set_groups first");
+    return RL_OK;
+}
+
+bool relight_positive(float v) { return v > 0.0f && v < INFINITY; }
+} // namespace
+
+int rl_relight_unit_create(int device, uint32_t width, uint32_t height, uint32_t n_nodes, uint32_t n_groups, RlRelightUnit** out) {
+    if (!out) return fail(RL_E_INVALID, "null output handle");
+    *out = nullptr;
+    if (width == 0 || height == 0) return fail(RL_E_INVALID, "zero-sized relight unit");
+    int rc = spectral_nodes_check("relight unit", n_nodes);
+    if (rc != RL_OK) return rc;
+    if (n_groups < 1u || n_groups > RL_RELIGHT_MAX_GROUPS)
+        return fail(RL_E_INVALID, "relight unit: n_groups " + std::to_string(n_groups) + " outside 1 .. RL_RELIGHT_MAX_GROUPS = " +
+                                      std::to_string(RL_RELIGHT_MAX_GROUPS));
+    const uint64_t n_pixels = (uint64_t)width * height; // (below 2^64; times the planes, at most 16 * 401, only once it is known to be below 2^31)
+    if (n_pixels > RL_MAX_PIXELS || n_pixels * n_nodes * n_groups > RL_MAX_PIXELS)
+        return fail(RL_E_INVALID, "relight unit: " + std::to_string(width) + " x " + std::to_string(height) + " pixels x " + std::to_string(n_nodes) +
+                                      " nodes x " + std::to_string(n_groups) + " groups exceed RL_MAX_PIXELS = 2^31 - 1");
+    rc = use_device(device);
+    if (rc != RL_OK) return rc;
+    RlRelightUnit* u = new (std::nothrow) RlRelightUnit();
+    if (!u) return fail(RL_E_INVALID, "out of host memory");
+    u->device = device;
+    u->width = width;
+    u->height = height;
+    u->n_nodes = n_nodes;
+    u->n_groups = n_groups;
+    u->spacing = spectral_spacing(n_nodes);
+    u->ledger.alloc_zeroed(&u->film, relight_film_bytes(u));
+    u->ledger.alloc(&u->matrix, relight_planes(u) * 3 * sizeof(float));
+    u->ledger.stream(&u->stream);
+    u->ledger.event(&u->ready);
+    for (EventPair& ep : u->timed) u->ledger.pair(&ep);
+    return unit_created("relight unit allocation", u, rl_relight_unit_destroy, out);
+}
+
+int rl_relight_unit_destroy(RlRelightUnit* u) {
+    if (!u) return RL_OK;
+    (void)hipSetDevice(u->device);
+    u->ledger.release();
+    delete u;
+    return RL_OK;
+}
+
+int rl_relight_unit_clear(RlRelightUnit* u) {
+    if (!u) return fail(RL_E_INVALID, "null relight unit");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    RL_HIP(hipMemsetAsync(u->film, 0, relight_film_bytes(u), u->stream));
+    return RL_OK;
+}
+
+int rl_relight_unit_set_groups(RlRelightUnit* u, const uint8_t* groups, uint32_t n_objects) {
+    if (!u || !groups) return fail(RL_E_INVALID, "rl_relight_unit_set_groups: null relight unit or table");
+    if (n_objects == 0u) return fail(RL_E_INVALID, "rl_relight_unit_set_groups: n_objects is 0");
+    for (uint32_t o = 0; o < n_objects; ++o)
+        if (groups[o] >= u->n_groups && groups[o] != RL_RELIGHT_DROP)
+            return fail(RL_E_INVALID, "rl_relight_unit_set_groups: object " + std::to_string(o) + " has group " + std::to_string(groups[o]) +
+                                          ", which is neither below n_groups = " + std::to_string(u->n_groups) + " nor RL_RELIGHT_DROP");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    if (n_objects > u->groups_room) {
+        // (a table that outgrows its buffer gets one of at least twice the size; the ledger keeps the old one until the unit goes)
+        uint64_t room = 1024;
+        while (room < n_objects) room *= 2;
+        uint8_t* grown = nullptr;
+        RL_HIP(u->ledger.make_alloc(&grown, (size_t)room));
+        u->groups = grown;
+        u->groups_room = (uint32_t)std::min<uint64_t>(room, 0xffffffffull);
+    }
+    u->n_objects = 0u; // (a failed copy leaves no table)
+    if ((rc = upload(u->stream, {{u->groups, groups, (size_t)n_objects}})) != RL_OK) return rc;
+    u->n_objects = n_objects;
+    return RL_OK;
+}
+
+int rl_relight_unit_plot_results(RlRelightUnit* u, const RlCameraSample* samples, const RlPathResult* results, uint64_t n) {
+    const int rc = relight_results_check(u, samples, results, n);
+    if (rc != RL_OK || n == 0) return rc;
+    return with_call_ctx(u->device, "relight unit", nullptr, DeviceArrays{}, [&](const CallCtx& q) -> int {
+        const CallCtx c{q.q, u->stream, q.cus};
+        return relight_drained(u, staged_chunks(c, n, {staged_in(STAGING_HITS, samples, sizeof(RlCameraSample)), staged_in(STAGING_RAYS, results, sizeof(RlPathResult))},
+                                                [&](uint64_t, uint64_t k) -> int {
+            return launch_relight_splat(u, c.stream, c.cus, (const RlCameraSample*)c.q->staging[STAGING_HITS], (const RlPathResult*)c.q->staging[STAGING_RAYS], k);
+        }));
+    });
+}
+
+int rl_relight_unit_plot_results_device(RlRelightUnit* u, const RlCameraSample* device_samples, const RlPathResult* device_results, uint64_t n) {
+    const int rc = relight_results_check(u, device_samples, device_results, n);
+    if (rc != RL_OK || n == 0) return rc;
+    return with_call_ctx(u->device, "relight unit", nullptr, {"rl_relight_unit_plot_results_device", "rl_relight_unit_plot_results", {device_samples, device_results}},
+                         [&](const CallCtx& q) -> int { return relight_drained(u, launch_relight_splat(u, u->stream, q.cus, device_samples, device_results, n)); });
+}
+
+int rl_relight_unit_render(RlRelightUnit* u, const RlScene* scene, int primitive_fetch, uint64_t seed, uint32_t stream, uint64_t first_path_index,
+                           uint64_t n_paths, uint32_t max_segments) {
+    PathJob job{seed, stream, 0u};
+    if (!u) return fail(RL_E_INVALID, "null relight unit");
+    if (!scene) return fail(RL_E_INVALID, "null scene");
+    if (fetch_check(primitive_fetch) != RL_OK || max_segments_resolve(max_segments, &job.max_segments) != RL_OK) return RL_E_INVALID;
+    if (u->n_objects == 0u) return fail(RL_E_STATE, "the relight unit has no table: call rl_relight_unit_set_groups first");
+    if (path_range_check(first_path_index, n_paths) != RL_OK) return RL_E_INVALID;
+    if (u->n_objects != scene->lay.n_objects)
+        return fail(RL_E_STATE, "the relight unit's table has " + std::to_string(u->n_objects) + " objects and the scene " + std::to_string(scene->lay.n_objects));
+    if (scene->device != u->device) return fail(RL_E_STATE, "scene and relight unit live on different devices");
+    if (n_paths == 0) return RL_OK;
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    if (!u->samples) RL_HIP(u->ledger.make_alloc(&u->samples, (size_t)RL_QUERY_CHUNK * sizeof(RlCameraSample)));
+    if (!u->rays) RL_HIP(u->ledger.make_alloc(&u->rays, (size_t)RL_QUERY_CHUNK * sizeof(RlSpectralRay)));
+    if (!u->results) RL_HIP(u->ledger.make_alloc(&u->results, (size_t)RL_QUERY_CHUNK * sizeof(RlPathResult)));
+    u->timed_done[1] = false;
+    rc = with_call_ctx(u->device, "relight unit", nullptr, DeviceArrays{}, [&](const CallCtx& q) -> int {
+        const CallCtx c{q.q, u->stream, q.cus}; // (the context lends its queue counter; its own stream stays idle)
+        return relight_drained(u, [&]() -> int {
+            // (the chunks share the scratch: the stream keeps them in order)
+            for (uint64_t done = 0; done < n_paths;) {
+                const uint32_t k = (uint32_t)std::min<uint64_t>(n_paths - done, RL_QUERY_CHUNK);
+                int r = launch_camera(c, scene, u->width, u->height, seed, stream, first_path_index + done, u->samples, k);
+                if (r != RL_OK) return r;
+                hipLaunchKernelGGL(rl_relight_rays_kernel, dim3(grid_for(k, c.cus)), dim3(RL_BLOCK), 0, c.stream, (const RlCameraSample*)u->samples, u->rays,
+                                   (uint64_t)k);
+                RL_HIP(hipGetLastError());
+                RL_HIP(hipEventRecord(u->timed[1].start, c.stream));
+                if ((r = launch_paths(c, scene, primitive_fetch, job, first_path_index + done, u->rays, u->results, k)) != RL_OK) return r;
+                RL_HIP(hipEventRecord(u->timed[1].stop, c.stream));
+                g_relight_launches[1].fetch_add(1, std::memory_order_relaxed);
+                if ((r = launch_relight_splat(u, c.stream, c.cus, u->samples, u->results, k)) != RL_OK) return r;
+                done += k;
+            }
+            return RL_OK;
+        }());
+    });
+    if (rc == RL_OK) u->timed_done[1] = true;
+    return rc;
+}
+
+int rl_relight_unit_download(RlRelightUnit* u, float* out) {
+    if (!u || !out) return fail(RL_E_INVALID, "null argument");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    return download(u->stream, {{u->film, out, relight_film_bytes(u)}});
+}
+
+int rl_relight_unit_upload(RlRelightUnit* u, const float* in) {
+    if (!u || !in) return fail(RL_E_INVALID, "null argument");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    return upload(u->stream, {{u->film, in, relight_film_bytes(u)}});
+}
+
+int rl_relight_unit_mix(RlRelightUnit* u, const float* gains, const float* matrix, RlGatherUnit* dst) {
+    if (!u || !matrix || !dst) return fail(RL_E_INVALID, "rl_relight_unit_mix: null relight unit, matrix or dst");
+    int cus = 256;
+    int rc = match_check(dst, u);
+    if (rc == RL_OK) rc = enter_device(u->device, &cus);
+    if (rc != RL_OK) return rc;
+    // The composed matrix: row q = g * n_nodes + b is row b of the observer times that plane's gain, one f32 multiply each.
+    const uint32_t planes = (uint32_t)relight_planes(u);
+    std::vector<float> composed((size_t)planes * 3);
+    for (uint32_t q = 0; q < planes; ++q)
+        for (uint32_t k = 0; k < 3u; ++k) {
+            const float m = matrix[3u * (q % u->n_nodes) + k];
+            composed[3u * q + k] = gains ? gains[q] * m : m;
+        }
+    const uint64_t n_pixels = (uint64_t)u->width * u->height;
+    hipStream_t stream = dst->stream;
+    // (the copy reads `composed` and the kernel the unit's buffers: neither outlives the call, also after a failure)
+    rc = drained(stream, [&]() -> int {
+        int r = hand_over(u->ready, u->stream, stream); // everything queued on the film (a clear; the splats have drained)
+        if (r != RL_OK) return r;
+        RL_HIP(hipMemcpyAsync(u->matrix, composed.data(), composed.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+        u->timed_done[2] = false; // readable again once the call has completed
+        // rl_spectral_project_kernel as it is: the cubes are one film of n_groups * n_nodes planes under the composed matrix
+        r = timed_launch(u->timed[2], stream, &g_relight_launches[2], [&] {
+            hipLaunchKernelGGL(rl_spectral_project_kernel, dim3(grid_for(n_pixels, cus)), dim3(RL_BLOCK), 0, stream, (const float*)u->film,
+                               (const float*)u->matrix, n_pixels, planes, dst->acc);
+        });
+        if (r != RL_OK) return r;
+        RL_HIP(hipMemsetAsync(dst->comp, 0, (size_t)n_pixels * 3 * sizeof(float), stream));
+        return RL_OK;
+    }());
+    if (rc == RL_OK) u->timed_done[2] = true;
+    return rc;
+}
+
+int rl_relight_gains_black_body(uint32_t n_nodes, float kelvins_from, float intensity_from, float kelvins_to, float intensity_to, float* out) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    const int rc = spectral_nodes_check("rl_relight_gains_black_body", n_nodes);
+    if (rc != RL_OK) return rc;
+    if (!relight_positive(kelvins_from) || !relight_positive(intensity_from) || !relight_positive(kelvins_to) || !relight_positive(intensity_to))
+        return fail(RL_E_INVALID, "rl_relight_gains_black_body: kelvins and intensity must be finite and greater than 0");
+    const float norm_from = rl_black_body_normalisation(kelvins_from, intensity_from), norm_to = rl_black_body_normalisation(kelvins_to, intensity_to);
+    const float spacing = spectral_spacing(n_nodes);
+    for (uint32_t b = 0; b < n_nodes; ++b) {
+        const float l = 380.0f + (float)b * spacing;
+        const float from = (float)rl_boltzmann((double)l, (double)kelvins_from) * norm_from; // get_intensity, material.rs:101-105
+        const float to = (float)rl_boltzmann((double)l, (double)kelvins_to) * norm_to;
+        out[b] = from == 0.0f ? 0.0f : to / from; // (a light that deposited nothing at this node)
+    }
+    return RL_OK;
+}
+
 // ---- ErrorUnit (rl_error.hip.h) ------------------------------------------------------------------
 
 namespace {
@@ -4112,6 +4373,21 @@ int rl_debug_spectral_ms(RlSpectralUnit* u, float out[2]) {
     int rc = use_device(u->device);
     if (rc != RL_OK) return rc;
     for (int k = 0; k < 2; ++k) {
+        out[k] = 0.0f;
+        if (u->timed_done[k]) RL_HIP(hipEventElapsedTime(&out[k], u->timed[k].start, u->timed[k].stop));
+    }
+    return RL_OK;
+}
+int rl_debug_relight_launches(uint64_t out[3]) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    for (int k = 0; k < 3; ++k) out[k] = g_relight_launches[k].load(std::memory_order_relaxed);
+    return RL_OK;
+}
+int rl_debug_relight_ms(RlRelightUnit* u, float out[3]) {
+    if (!u || !out) return fail(RL_E_INVALID, "null argument");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    for (int k = 0; k < 3; ++k) {
         out[k] = 0.0f;
         if (u->timed_done[k]) RL_HIP(hipEventElapsedTime(&out[k], u->timed[k].start, u->timed[k].stop));
     }
