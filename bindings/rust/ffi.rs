@@ -70,6 +70,7 @@ pub const RL_STEP_NO_ROULETTE: u32 = 1;
 pub const RL_DENOISE_ITERATIONS: u32 = 5;
 pub const RL_DENOISE_MAX_ITERATIONS: u32 = 6;
 pub const RL_SPECTRAL_MAX_NODES: u32 = 401;
+pub const RL_GLARE_MAX_TAPS: u32 = 65;
 pub const RL_ERROR_TILE: u32 = 16;
 pub const RL_RELIGHT_MAX_GROUPS: u32 = 16;
 pub const RL_RELIGHT_DROP: u8 = 0xff;
@@ -118,7 +119,7 @@ pub enum RlScene {} pub enum RlTraceUnit {} pub enum RlPlotUnit {} pub enum RlGa
 pub enum RlScheduler {} pub enum RlComm {} pub enum RlDenoiseUnit {} pub enum RlSpectralUnit {} pub enum RlErrorUnit {}
 pub enum RlAdaptiveUnit {}
 pub enum RlRobustUnit {}
-pub enum RlRelightUnit {}
+pub enum RlRelightUnit {} pub enum RlGlareUnit {}
 pub enum RlWavelengthTable {}
 #[repr(C)] #[derive(Copy, Clone)] pub struct RlWavelengthSampling {
     pub importance: *const f64, pub n_nodes: u32, pub reserved: u32, pub uniform_share: f64,
@@ -260,6 +261,13 @@ extern "C" {
     pub fn rl_spectral_unit_upload(unit: *mut RlSpectralUnit, input: *const f32) -> c_int;
     pub fn rl_spectral_unit_project(unit: *mut RlSpectralUnit, matrix: *const f32, dst: *mut RlGatherUnit) -> c_int;
     pub fn rl_spectral_observer_cie1931(n_nodes: u32, out: *mut f32) -> c_int;
+    // Spectral glare: one taps x taps gather table per node applied to a spectral unit's film and projected in the same launch.
+    pub fn rl_glare_unit_create(device: c_int, width: u32, height: u32, n_nodes: u32, taps: u32, out: *mut *mut RlGlareUnit) -> c_int;
+    pub fn rl_glare_unit_destroy(unit: *mut RlGlareUnit) -> c_int;
+    pub fn rl_glare_unit_set_kernels(unit: *mut RlGlareUnit, tables: *const f32) -> c_int;
+    pub fn rl_glare_unit_apply(unit: *mut RlGlareUnit, film: *mut RlSpectralUnit, matrix: *const f32, dst: *mut RlGatherUnit) -> c_int;
+    pub fn rl_glare_psf_veil(taps: u32, r0: f64, out: *mut f32) -> c_int;
+    pub fn rl_glare_kernels_scaled(psf: *const f32, psf_taps: u32, lambda0: f64, n_nodes: u32, strength: f64, taps: u32, out: *mut f32) -> c_int;
     pub fn rl_relight_unit_create(device: c_int, width: u32, height: u32, n_nodes: u32, n_groups: u32, out: *mut *mut RlRelightUnit) -> c_int;
     pub fn rl_relight_unit_destroy(unit: *mut RlRelightUnit) -> c_int;
     pub fn rl_relight_unit_clear(unit: *mut RlRelightUnit) -> c_int;

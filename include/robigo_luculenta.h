@@ -119,6 +119,7 @@ typedef struct RlGatherUnit RlGatherUnit;
 typedef struct RlTonemapUnit RlTonemapUnit;
 typedef struct RlDenoiseUnit RlDenoiseUnit;
 typedef struct RlSpectralUnit RlSpectralUnit;
+typedef struct RlGlareUnit RlGlareUnit;
 typedef struct RlRelightUnit RlRelightUnit;
 typedef struct RlErrorUnit RlErrorUnit;
 typedef struct RlRobustUnit RlRobustUnit;
@@ -994,6 +995,77 @@ int rl_spectral_unit_download(RlSpectralUnit* unit, float* out);
 int rl_spectral_unit_upload(RlSpectralUnit* unit, const float* in);
 int rl_spectral_unit_project(RlSpectralUnit* unit, const float* matrix, RlGatherUnit* dst);
 int rl_spectral_observer_cie1931(uint32_t n_nodes, float* out);
+
+/* ---- spectral glare: a wavelength-scaled point-spread convolution of the spectral film (rl_glare_unit_*) ---- */
+
+#define RL_GLARE_MAX_TAPS 65
+
+/* A glare unit holds one K x K gather table per spectral node (K = `taps`, odd, 1 .. RL_GLARE_MAX_TAPS; R = (K - 1) / 2) and
+ * applies them to a spectral unit's film: bloom, veiling glare, the diffraction pattern of an aperture -- point-spread functions
+ * whose size grows linearly with wavelength, which is what gives a glare halo its coloured fringe (red outside, blue inside) and
+ * what a blur of an XYZ image cannot reproduce.  rl_glare_unit_apply convolves every plane with its node's table, projects the
+ * result under a caller-supplied n_nodes x 3 matrix (as rl_spectral_unit_project takes it) in the same launch and writes a gather
+ * unit, so rl_tonemap_unit_tonemap, rl_gather_unit_save, _download and the denoisers work on the result unchanged.  The convolved
+ * cube never exists in memory.  The chain is: rl_spectral_unit_plot; rl_glare_unit_set_kernels; rl_glare_unit_apply; tonemap.
+ *   The cap of 65 taps is part of the ABI: at that size a 64 x 16 output tile with its halo is 40 KB of on-chip memory, so more
+ *   than one workgroup still fits on a compute unit.  Wider point-spread functions want another method and another contract.
+ *   The arithmetic of apply.  All f32, in exactly this order, a separate multiply and add, never contracted.  For pixel (x, y) and
+ *   component c of 3:
+ *       acc_c = 0.0f
+ *       for b = 0 .. n_nodes - 1:
+ *           g = 0.0f
+ *           for j = 0 .. K - 1:
+ *               r = 0.0f
+ *               for i = 0 .. K - 1:
+ *                   (qx, qy) = (x + i - R, y + j - R)
+ *                   if (qx, qy) is inside the film:  r = r + tables[b][j][i] * film[b][qy][qx]
+ *               g = g + r
+ *           acc_c = acc_c + matrix[b * 3 + c] * g
+ *       dst.tristimulus[(y * width + x) * 3 + c] = acc_c
+ *     A tap outside the film adds nothing -- no clamp, no mirror: light from outside the frame is unknown.  No special cases for
+ *     non-finite values.  dst's compensation buffer is all +0, as after rl_spectral_unit_project.  The film and the tables are left
+ *     as they were.  The two-level sum (row sums, then the sum of rows) keeps the rounding error at O(K) ulps instead of O(K^2).
+ *     With K = 1 and every table entry 1.0f, apply writes the bits of rl_spectral_unit_project for any finite film.
+ *   rl_glare_unit_create.  Checked in this order before any device work, each failure RL_E_INVALID with a message: a NULL `out`;
+ *   a zero width or height; n_nodes outside 2 .. RL_SPECTRAL_MAX_NODES; taps even, zero or above RL_GLARE_MAX_TAPS;
+ *   width * height * n_nodes > RL_MAX_PIXELS (computed in 64 bits).  A unit starts without tables.
+ *   rl_glare_unit_set_kernels.  `tables` is host memory, n_nodes * taps * taps floats: table b, row j, entry i at
+ *   (b * taps + j) * taps + i; entry (j, i) weighs the film at (x + i - R, y + j - R), a gather.  A NULL unit or NULL tables is
+ *   RL_E_INVALID.  The tables are read as given, non-finite entries included, copied to the device and queued on the unit; they may
+ *   be set again.
+ *   rl_glare_unit_apply.  Checked in this order: a NULL unit, film, matrix or dst is RL_E_INVALID; a unit without tables is
+ *   RL_E_STATE; a film of another width, height, n_nodes or device is RL_E_STATE; a dst of another size or device is RL_E_STATE.
+ *   Nothing is written on failure.  `matrix` is host memory, n_nodes x 3 floats, read as given.  Ordering is the projection's: the
+ *   call waits on the device for everything queued on dst's stream, on the film and on the unit's tables, runs on dst's stream
+ *   and returns when dst is complete.
+ *   rl_glare_psf_veil(taps, r0, out) writes a taps x taps table, a veiling-glare point-spread function: entry (j, i) with
+ *   d2 = (i - R)^2 + (j - R)^2 is 1 / (q * sqrt(q)), q = 1 + d2 / (r0 * r0), computed in f64 in that order and rounded to f32.  The
+ *   table is not normalised.  Checked in this order: a NULL `out`; taps not odd in 1 .. RL_GLARE_MAX_TAPS; an r0 that is not finite
+ *   and greater than 0 (RL_E_INVALID).
+ *   rl_glare_kernels_scaled(psf, psf_taps, lambda0, n_nodes, strength, taps, out) turns one base point-spread function -- psf_taps
+ *   x psf_taps floats, row-major, centre at R_in = (psf_taps - 1) / 2, sampled at pixel pitch for wavelength lambda0 (nm) -- into
+ *   the n_nodes gather tables of set_kernels.  All f64 with add, subtract, multiply, divide and floor only, in this order; node b:
+ *   lambda = 380 + b * (400 / (n_nodes - 1)); s = lambda / lambda0; for entry (j, i): u = -(i - R) / s + R_in, v = -(j - R) / s +
+ *   R_in (the point flip makes a gather table out of a scatter function: an impulse at q produces the function centred on q,
+ *   unflipped); iu = floor(u), fu = u - iu, likewise for v; w = ((1 - fu) * p00 + fu * p10) * (1 - fv) + ((1 - fu) * p01 + fu * p11)
+ *   * fv, where pab = psf[iv + b][iu + a] and 0 outside the base table.  S = the sum of w over the table in row-major order with
+ *   one accumulator; t = strength * (w / S), the centre entry gets + (1 - strength); out = (float)t.  So every node's table sums to 1
+ *   up to rounding: glare moves energy, it adds none.  For s > 1 the scaled function is cut at the table's edge BEFORE it is
+ *   normalised: what a wider table would have spread further stays inside.  RL_E_INVALID before anything is written: a NULL psf
+ *   or out; psf_taps not odd in 1 .. 257; a lambda0 that is not finite and greater than 0; n_nodes outside 2 ..
+ *   RL_SPECTRAL_MAX_NODES; a strength outside [0, 1]; taps not odd in 1 .. RL_GLARE_MAX_TAPS; a psf entry that is not finite and
+ *   >= 0; a node whose S is not > 0 (the function gives it nothing).
+ *   Both helpers are host arithmetic only: callable without a GPU.
+ *   Determinism.  apply is exact given the film, the tables and the matrix: the same bits on every run, and the bits of the CPU
+ *   restatement tests/_glare_oracle.py; so are the two helpers.
+ *   One user per glare unit at a time. */
+int rl_glare_unit_create(int device, uint32_t width, uint32_t height, uint32_t n_nodes, uint32_t taps, RlGlareUnit** out);
+int rl_glare_unit_destroy(RlGlareUnit* unit);
+int rl_glare_unit_set_kernels(RlGlareUnit* unit, const float* tables);
+int rl_glare_unit_apply(RlGlareUnit* unit, RlSpectralUnit* film, const float* matrix, RlGatherUnit* dst);
+int rl_glare_psf_veil(uint32_t taps, double r0, float* out);
+int rl_glare_kernels_scaled(const float* psf, uint32_t psf_taps, double lambda0, uint32_t n_nodes, double strength, uint32_t taps,
+                            float* out);
 
 /* ---- relight film: photons kept by wavelength and by light, re-mixed without a re-trace (rl_relight_unit_*) ---- */
 

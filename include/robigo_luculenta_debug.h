@@ -89,6 +89,11 @@ int rl_debug_spectral_launches(uint64_t out[2]);
  * (rl_spectral_unit_plot, _plot_photons, _plot_photons_device), out[1] the projection launch of its last completed
  * rl_spectral_unit_project; 0 before the first.  tools/spectral_bench.py. */
 int rl_debug_spectral_ms(RlSpectralUnit* unit, float out[2]);
+/* Launches of rl_glare_kernel (one per rl_glare_unit_apply, either form of the kernel) since the library was loaded. */
+int rl_debug_glare_launches(uint64_t* out);
+/* Device time in milliseconds, from events around the launch, of the unit's last completed rl_glare_unit_apply; 0 before the
+ * first.  tools/glare_bench.py. */
+int rl_debug_glare_ms(RlGlareUnit* unit, float* ms);
 /* out[0]: launches of rl_relight_splat_kernel (one per chunk of rl_relight_unit_plot_results and of rl_relight_unit_render, one per
  * rl_relight_unit_plot_results_device), out[1]: path kernel launches made by rl_relight_unit_render (one per chunk; counted in
  * rl_debug_path_launches too), out[2]: launches of the mix (rl_spectral_project_kernel on the composed matrix, one per

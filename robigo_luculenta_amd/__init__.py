@@ -16,7 +16,7 @@ from ._lib import (RlAppConfig, RlAppStats, RlCameraDesc, RlCameraSample, RlErro
                    RL_FEATURE_MAX_SEGMENTS, RlDenoiseParams, RL_DENOISE_ITERATIONS, RL_DENOISE_MAX_ITERATIONS,
                    RL_SPECTRAL_MAX_NODES, RlErrorStats, RlErrorTarget, RlAppErrorStats, RL_ERROR_TILE, RlAdaptiveStats,
                    RlWavelengthSampling, RlRobustParams, RlRobustStats, RL_ROBUST_MAX_BUCKETS, RL_ROBUST_NEXT,
-                   RL_RELIGHT_MAX_GROUPS, RL_RELIGHT_DROP)
+                   RL_RELIGHT_MAX_GROUPS, RL_RELIGHT_DROP, RL_GLARE_MAX_TAPS)
 
 PHOTON_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("probability", "<f4"), ("wavelength", "<f4")])
 OBJECT_DTYPE = np.dtype([("surface_kind", "<u4"), ("material_kind", "<u4"), ("v0", "<f4", 3), ("v1", "<f4", 3),
@@ -894,6 +894,59 @@ class SpectralUnit(_Handle):
         return tuple(out)
 
 
+def glare_psf_veil(taps, r0):
+    """rl_glare_psf_veil: the (taps, taps) float32 veiling-glare point-spread function 1 / (q * sqrt(q)), q = 1 + d^2 / r0^2, d the
+    distance from the centre in pixels; not normalised.  Host arithmetic: needs no device."""
+    out = np.zeros((max(int(taps), 0), max(int(taps), 0)), dtype=np.float32)
+    check(lib.rl_glare_psf_veil(taps, float(r0), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def glare_kernels_scaled(psf, lambda0, n_nodes, strength, taps):
+    """rl_glare_kernels_scaled: the (n_nodes, taps, taps) float32 gather tables of GlareUnit.set_kernels from one square base
+    point-spread function `psf` (odd side, sampled at pixel pitch for wavelength lambda0 nm): node b's is the function scaled by
+    lambda_b / lambda0, point-flipped, normalised to sum 1 and mixed with a delta, strength * table + (1 - strength) at the centre.
+    Host arithmetic: needs no device."""
+    psf = np.ascontiguousarray(psf, dtype=np.float32)
+    if psf.ndim != 2 or psf.shape[0] != psf.shape[1]:
+        raise ValueError("glare_kernels_scaled: psf must be a square 2-d array, not %r" % (psf.shape,))
+    out = np.zeros((max(int(n_nodes), 0), max(int(taps), 0), max(int(taps), 0)), dtype=np.float32)
+    check(lib.rl_glare_kernels_scaled(psf.ctypes.data_as(C.c_void_p), psf.shape[0], float(lambda0), n_nodes, float(strength), taps,
+                                      out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+class GlareUnit(_Handle):
+    """One (taps, taps) gather table per spectral node, applied to a spectral unit's film and projected into a gather unit in one
+    launch (rl_glare_unit_*): bloom, veiling glare, an aperture's diffraction pattern, each growing with wavelength."""
+    _destroy = lib.rl_glare_unit_destroy
+
+    def __init__(self, width, height, n_nodes, taps, device=0):
+        super().__init__()
+        check(lib.rl_glare_unit_create(device, width, height, n_nodes, taps, C.byref(self._h)))
+        self.width, self.height, self.n_nodes, self.taps, self.device = width, height, n_nodes, taps, device
+
+    def set_kernels(self, tables):
+        """rl_glare_unit_set_kernels: (n_nodes, taps, taps) float32, entry [b, j, i] weighs node b of the film at (x + i - R,
+        y + j - R); on the device on return.  May be set again."""
+        tables = np.ascontiguousarray(tables, dtype=np.float32).reshape(self.n_nodes, self.taps, self.taps)
+        check(lib.rl_glare_unit_set_kernels(self._h, tables.ctypes.data_as(C.c_void_p)))
+
+    def apply(self, film, matrix, gather):
+        """rl_glare_unit_apply: gather unit `gather` = spectral unit `film` convolved plane by plane with the tables and projected
+        under the (n_nodes, 3) `matrix`, complete on return; its compensation buffer is zeroed, the film is left as it was.
+        Returns gather."""
+        matrix = np.ascontiguousarray(matrix, dtype=np.float32).reshape(self.n_nodes, 3)
+        check(lib.rl_glare_unit_apply(self._h, film.handle, matrix.ctypes.data_as(C.c_void_p), gather.handle))
+        return gather
+
+    def launch_ms(self):
+        """Device milliseconds of the last apply's launch (rl_debug_glare_ms)."""
+        ms = C.c_float(0)
+        check(lib.rl_debug_glare_ms(self._h, C.byref(ms)))
+        return ms.value
+
+
 MATERIAL_BLACK_BODY = 0  # RL_MATERIAL_BLACK_BODY: kelvins = m[0], intensity = m[1]
 
 
@@ -1459,6 +1512,13 @@ def spectral_launches():
     """(launches of the spectral film's splat kernel, launches of its projection kernel) since the library was loaded
     (rl_debug_spectral_launches)."""
     return _launch_counters(lib.rl_debug_spectral_launches, 2, tuple)
+
+
+def glare_launches():
+    """Launches of the glare kernel (GlareUnit.apply) since the library was loaded (rl_debug_glare_launches)."""
+    out = C.c_uint64(0)
+    check(lib.rl_debug_glare_launches(C.byref(out)))
+    return out.value
 
 
 def relight_launches():

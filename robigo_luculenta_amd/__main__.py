@@ -6,6 +6,8 @@ With --denoise PATH as well the image is filtered over those guides on the devic
 With --denoise-variance as well the filter's colour term is the noise estimate's variance (DenoiseUnit.denoise_variance): it backs off
 as the image converges, which the plain filter does not.
 With --spectral PATH the same paths are rendered once more into a spectral film (SpectralUnit) and the cube is saved as PATH (.npy).
+With --glare PATH the same paths are rendered into a spectral film as for --spectral, a wavelength-scaled point-spread function
+(--glare-psf FILE.npy, or the veil of --glare-r0) is applied to it under the CIE observer (GlareUnit.apply) and the tonemapped image written to PATH.
 With --relight PATH the same paths are rendered once more into a relight film (RelightUnit), one cube per light, saved as PATH (.npy);
 with --light G:KELVINS[:INTENSITY] as well light G is re-balanced in the mix and the relit image written beside the cubes, without a re-trace.
 With --target-error E the run ends once the estimated relative error of the image (rl_app_run_to_error) is at most E; --batches stays
@@ -64,6 +66,21 @@ def parse_args(argv=None):
                          "float32 (nodes, height, width), to PATH with numpy.save (*.npy)")
     ap.add_argument("--spectral-nodes", metavar="K", type=int, default=81,
                     help="with --spectral: nodes from 380 to 780 nm (default 81, the CIE table's own)")
+    ap.add_argument("--glare", metavar="PATH", default=None,
+                    help="after the image, render the same paths un-fused into a spectral film of --spectral-nodes nodes, apply a "
+                         "wavelength-scaled point-spread function under the CIE observer (GlareUnit.apply) and write the tonemapped "
+                         "image to PATH (*.png or *.ppm)")
+    ap.add_argument("--glare-psf", metavar="FILE.npy", default=None,
+                    help="with --glare: the base point-spread function, a square float array of odd side (at most 257) sampled at "
+                         "pixel pitch for --glare-lambda0 (default: the veil of --glare-r0)")
+    ap.add_argument("--glare-r0", metavar="PX", type=float, default=None,
+                    help="with --glare: the veil 1 / (1 + d^2 / PX^2)^1.5 as the base function (default 2)")
+    ap.add_argument("--glare-strength", metavar="A", type=float, default=None,
+                    help="with --glare: the share of a pixel's light that the function spreads, 0 .. 1 (default 0.3)")
+    ap.add_argument("--glare-taps", metavar="K", type=int, default=None,
+                    help="with --glare: the side of the per-node tables, odd, 1 .. 65 (default 33)")
+    ap.add_argument("--glare-lambda0", metavar="NM", type=float, default=None,
+                    help="with --glare: the wavelength the base function is sampled for (default 550)")
     ap.add_argument("--relight", metavar="PATH", default=None,
                     help="after the image, render the same paths into a relight film (RelightUnit.render): one cube of --spectral-nodes "
                          "nodes per black body of the scene (relight_groups; at most 16), saved as float32 (groups, nodes, height, width) "
@@ -180,6 +197,26 @@ def parse_args(argv=None):
             ap.error("%s cannot be combined with --direct: the estimate is made by the App worker pool" % flag)
     if a.spectral is not None and a.direct:
         ap.error("--spectral cannot be combined with --direct: the direct renderer writes no photons")
+    for given, flag in ((a.glare_psf is not None, "--glare-psf"), (a.glare_r0 is not None, "--glare-r0"),
+                        (a.glare_strength is not None, "--glare-strength"), (a.glare_taps is not None, "--glare-taps"),
+                        (a.glare_lambda0 is not None, "--glare-lambda0")):
+        if given and a.glare is None:
+            ap.error("%s needs --glare PATH" % flag)
+    if a.glare is not None:
+        if a.direct:
+            ap.error("--glare cannot be combined with --direct: the direct renderer writes no photons")
+        if a.glare_psf is not None and a.glare_r0 is not None:
+            ap.error("--glare-psf and --glare-r0 both name the base function: give one")
+        a.glare_r0 = 2.0 if a.glare_r0 is None else a.glare_r0
+        a.glare_strength = 0.3 if a.glare_strength is None else a.glare_strength
+        a.glare_taps = 33 if a.glare_taps is None else a.glare_taps
+        a.glare_lambda0 = 550.0 if a.glare_lambda0 is None else a.glare_lambda0
+        if not 0 < a.glare_r0 < float("inf") or not 0 < a.glare_lambda0 < float("inf"):
+            ap.error("--glare-r0 and --glare-lambda0 must be finite and greater than 0")
+        if not 0 <= a.glare_strength <= 1:
+            ap.error("--glare-strength must be in 0 .. 1")
+        if not (1 <= a.glare_taps <= 65 and a.glare_taps % 2 == 1):
+            ap.error("--glare-taps must be odd and in 1 .. 65")
     if a.light is not None and a.relight is None:
         ap.error("--light needs --relight PATH")
     if a.relight is not None:
@@ -376,10 +413,9 @@ def render_features(a):
     return films, total, gathers
 
 
-def render_spectral(a):
-    """--spectral PATH: the batches x photons_per_batch paths of stream 0 once more, un-fused -- TraceUnit.render in runs of at most
-    2^22 paths, SpectralUnit.plot of each -- and the cube saved with numpy.save.  Returns the cube, float32 (nodes, height, width)."""
-    import numpy as np
+def spectral_film(a):
+    """The batches x photons_per_batch paths of stream 0 once more, un-fused -- TraceUnit.render in runs of at most 2^22 paths,
+    SpectralUnit.plot of each.  Returns the spectral unit (--spectral and --glare)."""
     from . import Scene, SpectralUnit, TraceUnit, WavelengthTable
     scene = Scene.builtin(SCENE_DEMO if a.scene == "demo" else SCENE_GLASS_STRESS, device=a.device)
     film = SpectralUnit(a.width, a.height, a.spectral_nodes, device=a.device)
@@ -396,11 +432,43 @@ def render_spectral(a):
             traces[n].set_wavelengths(table)
         traces[n].render(scene, seed=a.seed, stream=0, first_path_index=first)
         film.plot([traces[n]])
+    return film
+
+
+def render_spectral(a, film):
+    """--spectral PATH: the cube of spectral_film(a) saved with numpy.save.  Returns the cube, float32 (nodes, height, width)."""
+    import numpy as np
+    total = a.batches * a.photons_per_batch
     cube = film.download()
     with open(a.spectral, "wb") as f:     # (numpy.save would append .npy to a name that lacks it)
         np.save(f, cube)
     print("spectral film: %d nodes, %d paths; wrote %s" % (a.spectral_nodes, total, a.spectral))
     return cube
+
+
+def render_glare(a, film):
+    """--glare PATH: the film of spectral_film(a) under the tables of glare_kernels_scaled -- the base function of --glare-psf or the
+    veil of --glare-r0 on 2 * taps - 1 samples, so that the longest wavelength's table is still cut by the table and not by the base --
+    and the CIE observer, tonemapped to PATH.  Returns the gather unit that holds the glared XYZ image."""
+    import numpy as np
+    from . import GatherUnit, GlareUnit, TonemapUnit, glare_kernels_scaled, glare_psf_veil, spectral_observer_cie1931
+    if a.glare_psf is not None:
+        psf = np.load(a.glare_psf)
+    else:
+        side = 2 * a.glare_taps - 1     # (the veil itself is written up to 65 taps; a wider base is the same formula in numpy)
+        d = np.arange(side, dtype=np.float64) - (side - 1) // 2
+        q = 1.0 + (d[None, :] ** 2 + d[:, None] ** 2) / (a.glare_r0 * a.glare_r0)
+        psf = glare_psf_veil(side, a.glare_r0) if side <= 65 else (1.0 / (q * np.sqrt(q))).astype(np.float32)
+    tables = glare_kernels_scaled(psf, a.glare_lambda0, a.spectral_nodes, a.glare_strength, a.glare_taps)
+    glare = GlareUnit(a.width, a.height, a.spectral_nodes, a.glare_taps, device=a.device)
+    glare.set_kernels(tables)
+    gather, tonemap = GatherUnit(a.width, a.height, device=a.device), TonemapUnit(a.width, a.height, device=a.device)
+    tonemap.tonemap(glare.apply(film, spectral_observer_cie1931(a.spectral_nodes), gather))
+    write_image(a.glare, tonemap.rgb_buffer, a.width, a.height)
+    print("glare: %d taps on %d nodes, strength %g, %s at %g nm, %.3f ms; wrote %s"
+          % (a.glare_taps, a.spectral_nodes, a.glare_strength, a.glare_psf or "veil r0 = %g px" % a.glare_r0, a.glare_lambda0, glare.launch_ms(),
+             a.glare))
+    return gather
 
 
 def render_relight(a):
@@ -572,8 +640,12 @@ def main(argv=None):
                 error = ErrorUnit(a.width, a.height, device=a.device)
                 error.upload(s, q, k, n)
             denoise(a, image, guides, error)
-    if a.spectral is not None:
-        render_spectral(a)
+    if a.spectral is not None or a.glare is not None:
+        film = spectral_film(a)
+        if a.spectral is not None:
+            render_spectral(a, film)
+        if a.glare is not None:
+            render_glare(a, film)
     if a.relight is not None:
         render_relight(a)
     if scratch:

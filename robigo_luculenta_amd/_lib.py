@@ -118,6 +118,7 @@ class RlDenoiseParams(C.Structure):
 
 
 RL_SPECTRAL_MAX_NODES = 401
+RL_GLARE_MAX_TAPS = 65
 RL_RELIGHT_MAX_GROUPS = 16
 RL_RELIGHT_DROP = 0xFF
 RL_ERROR_TILE = 16
@@ -276,6 +277,12 @@ SIGNATURES = {
     "rl_spectral_unit_upload": (_i, [_vp, _vp]),
     "rl_spectral_unit_project": (_i, [_vp, _vp, _vp]),
     "rl_spectral_observer_cie1931": (_i, [_u32, _vp]),
+    "rl_glare_unit_create": (_i, [_i, _u32, _u32, _u32, _u32, _pp]),
+    "rl_glare_unit_destroy": (_i, [_vp]),
+    "rl_glare_unit_set_kernels": (_i, [_vp, _vp]),
+    "rl_glare_unit_apply": (_i, [_vp, _vp, _vp, _vp]),
+    "rl_glare_psf_veil": (_i, [_u32, C.c_double, _vp]),
+    "rl_glare_kernels_scaled": (_i, [_vp, _u32, C.c_double, _u32, C.c_double, _u32, _vp]),
     "rl_relight_unit_create": (_i, [_i, _u32, _u32, _u32, _u32, _pp]),
     "rl_relight_unit_destroy": (_i, [_vp]),
     "rl_relight_unit_clear": (_i, [_vp]),
@@ -357,6 +364,8 @@ DEBUG_SIGNATURES = {
     "rl_debug_denoise_variance_ms": (_i, [_vp, C.POINTER(C.c_float)]),
     "rl_debug_spectral_launches": (_i, [_vp]),
     "rl_debug_spectral_ms": (_i, [_vp, _vp]),
+    "rl_debug_glare_launches": (_i, [_vp]),
+    "rl_debug_glare_ms": (_i, [_vp, _vp]),
     "rl_debug_relight_launches": (_i, [_vp]),
     "rl_debug_relight_ms": (_i, [_vp, _vp]),
     "rl_debug_error_launches": (_i, [_vp]),

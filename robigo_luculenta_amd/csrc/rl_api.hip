@@ -58,6 +58,7 @@
 #include "rl_denoise.hip.h"
 #include "rl_spectral.hip.h"
 #include "rl_relight.hip.h"
+#include "rl_glare.hip.h"
 #include "rl_error.hip.h"
 #include "rl_robust.hip.h"
 #include "rl_adaptive.hip.h"
@@ -123,6 +124,7 @@ const char* unit_name(const RlTonemapUnit*) { return "tonemap unit"; }
 const char* unit_name(const RlDenoiseUnit*) { return "denoise unit"; }
 const char* unit_name(const RlSpectralUnit*) { return "spectral unit"; }
 const char* unit_name(const RlRelightUnit*) { return "relight unit"; }
+const char* unit_name(const RlGlareUnit*) { return "glare unit"; }
 const char* unit_name(const RlErrorUnit*) { return "error unit"; }
 const char* unit_name(const RlRobustUnit*) { return "robust unit"; }
 const char* unit_name(const RlAdaptiveUnit*) { return "adaptive unit"; }
@@ -503,6 +505,26 @@ struct RlRelightUnit {
     bool timed_done[3];     // ... of a call that completed
     Ledger ledger;
 };
+
+struct RlGlareUnit {
+    int device;
+    uint32_t width, height, n_nodes, taps;
+    uint32_t has_tables; // rl_glare_unit_set_kernels has put tables on the device
+    bool exact_skip;     // ... with a NaN or an infinity among them: the kernel form that skips a tap outside the film
+    float* tables;       // n_nodes tables of taps x taps floats, node-major
+    float* matrix;       // the n_nodes x 3 matrix of the apply in flight
+    hipStream_t stream;  // the table copies
+    hipEvent_t ready;    // recorded on `stream` when an apply takes the tables
+    EventPair timed;     // around the last apply's launch (rl_debug_glare_ms)
+    bool timed_done;     // ... of a call that completed
+    Ledger ledger;
+};
+
+// tests/test_glare.py writes a stand-in handle's first fields at these offsets (the checks that read a handle before any device
+// work): a field that moves must move there too.
+static_assert(offsetof(RlGlareUnit, width) == 4 && offsetof(RlGlareUnit, height) == 8 && offsetof(RlGlareUnit, n_nodes) == 12 &&
+                  offsetof(RlGlareUnit, taps) == 16 && offsetof(RlGlareUnit, has_tables) == 20 && offsetof(RlSpectralUnit, n_nodes) == 12,
+              "tests/test_glare.py: test_apply_checks_a_stand_in_handle_in_the_stated_order");
 
 struct RlErrorUnit {
     int device;
@@ -3241,6 +3263,177 @@ int rl_spectral_observer_cie1931(uint32_t n_nodes, float* out) {
     return RL_OK;
 }
 
+// ---- GlareUnit (rl_glare.hip.h) --------------------------------------------------------------------
+
+namespace {
+std::atomic<uint64_t> g_glare_launches; // rl_debug_glare_launches: launches of rl_glare_kernel, either form
+
+int glare_taps_check(const char* what, uint32_t taps) {
+    if ((taps & 1u) && taps <= RL_GLARE_MAX_TAPS) return RL_OK;
+    return fail(RL_E_INVALID, std::string(what) + ": taps " + std::to_string(taps) + " is not odd and in 1 .. RL_GLARE_MAX_TAPS = " +
+                                  std::to_string(RL_GLARE_MAX_TAPS));
+}
+bool glare_finite(double v) { return std::fabs(v) < (double)INFINITY; }
+} // namespace
+
+int rl_glare_unit_create(int device, uint32_t width, uint32_t height, uint32_t n_nodes, uint32_t taps, RlGlareUnit** out) {
+    if (!out) return fail(RL_E_INVALID, "null output handle");
+    *out = nullptr;
+    if (width == 0 || height == 0) return fail(RL_E_INVALID, "zero-sized glare unit");
+    int rc = spectral_nodes_check("glare unit", n_nodes);
+    if (rc == RL_OK) rc = glare_taps_check("glare unit", taps);
+    if (rc != RL_OK) return rc;
+    const uint64_t n_pixels = (uint64_t)width * height; // (below 2^64; times n_nodes only once it is known to be below 2^31)
+    if (n_pixels > RL_MAX_PIXELS || n_pixels * n_nodes > RL_MAX_PIXELS)
+        return fail(RL_E_INVALID, "glare unit: " + std::to_string(width) + " x " + std::to_string(height) + " pixels x " + std::to_string(n_nodes) +
+                                      " nodes exceed RL_MAX_PIXELS = 2^31 - 1");
+    rc = use_device(device);
+    if (rc != RL_OK) return rc;
+    RlGlareUnit* u = new (std::nothrow) RlGlareUnit();
+    if (!u) return fail(RL_E_INVALID, "out of host memory");
+    u->device = device;
+    u->width = width;
+    u->height = height;
+    u->n_nodes = n_nodes;
+    u->taps = taps;
+    u->ledger.alloc(&u->tables, (size_t)n_nodes * taps * taps * sizeof(float));
+    u->ledger.alloc(&u->matrix, (size_t)n_nodes * 3 * sizeof(float));
+    u->ledger.stream(&u->stream);
+    u->ledger.event(&u->ready);
+    u->ledger.pair(&u->timed);
+    return unit_created("glare unit allocation", u, rl_glare_unit_destroy, out);
+}
+
+int rl_glare_unit_destroy(RlGlareUnit* u) {
+    if (!u) return RL_OK;
+    (void)hipSetDevice(u->device);
+    u->ledger.release();
+    delete u;
+    return RL_OK;
+}
+
+int rl_glare_unit_set_kernels(RlGlareUnit* u, const float* tables) {
+    if (!u || !tables) return fail(RL_E_INVALID, "rl_glare_unit_set_kernels: null glare unit or tables");
+    const int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    const size_t n = (size_t)u->n_nodes * u->taps * u->taps;
+    bool finite = true;
+    for (size_t k = 0; k < n && finite; ++k) finite = std::fabs(tables[k]) < INFINITY;
+    // (the copy reads the caller's tables: it has run when the call returns, also after a failure)
+    const int copied = drained(u->stream, [&]() -> int {
+        RL_HIP(hipMemcpyAsync(u->tables, tables, n * sizeof(float), hipMemcpyHostToDevice, u->stream));
+        return RL_OK;
+    }());
+    if (copied != RL_OK) return copied;
+    u->exact_skip = !finite;
+    u->has_tables = 1u;
+    return RL_OK;
+}
+
+int rl_glare_unit_apply(RlGlareUnit* u, RlSpectralUnit* film, const float* matrix, RlGatherUnit* dst) {
+    if (!u || !film || !matrix || !dst) return fail(RL_E_INVALID, "rl_glare_unit_apply: null glare unit, film, matrix or dst");
+    if (!u->has_tables) return fail(RL_E_STATE, "the glare unit has no tables: call rl_glare_unit_set_kernels first");
+    int cus = 256;
+    int rc = match_check(film, u);
+    if (rc == RL_OK && film->n_nodes != u->n_nodes)
+        rc = fail(RL_E_STATE, "spectral unit does not match the glare unit: " + std::to_string(film->n_nodes) + " nodes against " +
+                                  std::to_string(u->n_nodes));
+    if (rc == RL_OK) rc = match_check(dst, u);
+    if (rc == RL_OK) rc = enter_device(u->device, &cus);
+    if (rc != RL_OK) return rc;
+    const uint64_t n_pixels = (uint64_t)u->width * u->height;
+    const uint32_t tiles_x = (u->width + RL_GLARE_TILE_X - 1u) / RL_GLARE_TILE_X; // (at most 2^25 and 2^27: the sums cannot wrap)
+    const uint32_t tiles_y = (u->height + RL_GLARE_TILE_Y - 1u) / RL_GLARE_TILE_Y;
+    const uint64_t n_tiles = (uint64_t)tiles_x * tiles_y;                          // (at most ~2^31 / 1024 + 2^27 + 2^25)
+    const unsigned grid = (unsigned)std::min<uint64_t>(n_tiles, RL_GLARE_MAX_GRID);
+    const size_t lds = (size_t)rl_glare_lds_floats(u->taps) * sizeof(float);
+    hipStream_t stream = dst->stream;
+    // (the copy reads the caller's matrix and the kernel the units' buffers: neither outlives the call, also after a failure)
+    rc = drained(stream, [&]() -> int {
+        int r = hand_over(film->ready, film->stream, stream); // everything queued on the film (a clear; the splats have drained)
+        if (r == RL_OK) r = hand_over(u->ready, u->stream, stream); // ... and on the unit: its tables
+        if (r != RL_OK) return r;
+        RL_HIP(hipMemcpyAsync(u->matrix, matrix, (size_t)u->n_nodes * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
+        u->timed_done = false; // readable again once the call has completed
+        r = timed_launch(u->timed, stream, &g_glare_launches, [&] {
+            if (u->exact_skip)
+                hipLaunchKernelGGL(rl_glare_kernel<true>, dim3(grid), dim3(RL_GLARE_BLOCK), lds, stream, (const float*)film->film, (const float*)u->tables,
+                                   (const float*)u->matrix, u->width, u->height, u->n_nodes, u->taps, tiles_x, (uint32_t)n_tiles, dst->acc);
+            else
+                hipLaunchKernelGGL(rl_glare_kernel<false>, dim3(grid), dim3(RL_GLARE_BLOCK), lds, stream, (const float*)film->film, (const float*)u->tables,
+                                   (const float*)u->matrix, u->width, u->height, u->n_nodes, u->taps, tiles_x, (uint32_t)n_tiles, dst->acc);
+        });
+        if (r != RL_OK) return r;
+        RL_HIP(hipMemsetAsync(dst->comp, 0, (size_t)n_pixels * 3 * sizeof(float), stream));
+        return RL_OK;
+    }());
+    if (rc == RL_OK) u->timed_done = true;
+    return rc;
+}
+
+int rl_glare_psf_veil(uint32_t taps, double r0, float* out) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    const int rc = glare_taps_check("rl_glare_psf_veil", taps);
+    if (rc != RL_OK) return rc;
+    if (!(glare_finite(r0) && r0 > 0.0)) return fail(RL_E_INVALID, "rl_glare_psf_veil: r0 is not finite and greater than 0");
+    const int radius = (int)(taps >> 1);
+    for (int j = 0; j < (int)taps; ++j)
+        for (int i = 0; i < (int)taps; ++i) {
+            const double d2 = (double)((i - radius) * (i - radius) + (j - radius) * (j - radius));
+            const double q = 1.0 + d2 / (r0 * r0);
+            out[(size_t)j * taps + i] = (float)(1.0 / (q * std::sqrt(q)));
+        }
+    return RL_OK;
+}
+
+int rl_glare_kernels_scaled(const float* psf, uint32_t psf_taps, double lambda0, uint32_t n_nodes, double strength, uint32_t taps, float* out) {
+    if (!psf || !out) return fail(RL_E_INVALID, "rl_glare_kernels_scaled: null psf or output");
+    if (!(psf_taps & 1u) || psf_taps > 257u)
+        return fail(RL_E_INVALID, "rl_glare_kernels_scaled: psf_taps " + std::to_string(psf_taps) + " is not odd and in 1 .. 257");
+    if (!(glare_finite(lambda0) && lambda0 > 0.0)) return fail(RL_E_INVALID, "rl_glare_kernels_scaled: lambda0 is not finite and greater than 0");
+    int rc = spectral_nodes_check("rl_glare_kernels_scaled", n_nodes);
+    if (rc != RL_OK) return rc;
+    if (!(strength >= 0.0 && strength <= 1.0)) return fail(RL_E_INVALID, "rl_glare_kernels_scaled: strength is outside 0 .. 1");
+    if ((rc = glare_taps_check("rl_glare_kernels_scaled", taps)) != RL_OK) return rc;
+    for (size_t k = 0; k < (size_t)psf_taps * psf_taps; ++k)
+        if (!(psf[k] >= 0.0f && psf[k] < INFINITY))
+            return fail(RL_E_INVALID, "rl_glare_kernels_scaled: psf entry " + std::to_string(k) + " is not finite and at least 0");
+    const double size = (double)psf_taps, radius_in = (double)(psf_taps >> 1);
+    const int radius = (int)(taps >> 1);
+    // p = 0 outside the base table; whether (ix, iy) is inside is decided on the doubles, before any conversion to int
+    auto at = [&](double ix, double iy) -> double {
+        if (!(ix >= 0.0 && ix < size && iy >= 0.0 && iy < size)) return 0.0;
+        return (double)psf[(size_t)iy * psf_taps + (size_t)ix];
+    };
+    std::vector<double> w((size_t)taps * taps);
+    std::vector<float> result((size_t)n_nodes * taps * taps);
+    for (uint32_t b = 0; b < n_nodes; ++b) {
+        const double lambda = 380.0 + (double)b * (400.0 / (double)(n_nodes - 1u));
+        const double s = lambda / lambda0;
+        double sum = 0.0;
+        for (int j = 0; j < (int)taps; ++j)
+            for (int i = 0; i < (int)taps; ++i) {
+                const double pu = -(double)(i - radius) / s + radius_in, pv = -(double)(j - radius) / s + radius_in;
+                const double iu = std::floor(pu), iv = std::floor(pv);
+                const double fu = pu - iu, fv = pv - iv;
+                const double p00 = at(iu, iv), p10 = at(iu + 1.0, iv), p01 = at(iu, iv + 1.0), p11 = at(iu + 1.0, iv + 1.0);
+                const double v = ((1.0 - fu) * p00 + fu * p10) * (1.0 - fv) + ((1.0 - fu) * p01 + fu * p11) * fv;
+                w[(size_t)j * taps + i] = v;
+                sum = sum + v;
+            }
+        if (!(sum > 0.0))
+            return fail(RL_E_INVALID, "rl_glare_kernels_scaled: the psf gives node " + std::to_string(b) + " nothing (the sum of its table is not > 0)");
+        for (int j = 0; j < (int)taps; ++j)
+            for (int i = 0; i < (int)taps; ++i) {
+                double t = strength * (w[(size_t)j * taps + i] / sum);
+                if (i == radius && j == radius) t = t + (1.0 - strength);
+                result[((size_t)b * taps + j) * taps + i] = (float)t;
+            }
+    }
+    std::memcpy(out, result.data(), result.size() * sizeof(float));
+    return RL_OK;
+}
+
 // ---- RelightUnit (rl_relight.hip.h) ----------------------------------------------------------------
 
 namespace {
@@ -4376,6 +4569,19 @@ int rl_debug_spectral_ms(RlSpectralUnit* u, float out[2]) {
         out[k] = 0.0f;
         if (u->timed_done[k]) RL_HIP(hipEventElapsedTime(&out[k], u->timed[k].start, u->timed[k].stop));
     }
+    return RL_OK;
+}
+int rl_debug_glare_launches(uint64_t* out) {
+    if (!out) return fail(RL_E_INVALID, "null output");
+    *out = g_glare_launches.load(std::memory_order_relaxed);
+    return RL_OK;
+}
+int rl_debug_glare_ms(RlGlareUnit* u, float* ms) {
+    if (!u || !ms) return fail(RL_E_INVALID, "null argument");
+    int rc = use_device(u->device);
+    if (rc != RL_OK) return rc;
+    *ms = 0.0f;
+    if (u->timed_done) RL_HIP(hipEventElapsedTime(ms, u->timed.start, u->timed.stop));
     return RL_OK;
 }
 int rl_debug_relight_launches(uint64_t out[3]) {
